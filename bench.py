@@ -27,6 +27,11 @@ fresh child (`--leg graph`, own rendezvous port, a deadline).  If that optional 
 dies with its own non-zero status and the supervisor prints the eager line with "graph_leg": {"status": "abandoned",
 "reason": ...}; nothing in a GPU-touched process turns a fault into status 0.  ITCV_DDP_GRAPH=0 skips the attempt.
 
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy: the losses the step returned
+(float64) and the model it trained in place, "model.<state_dict key>" (float32; integer buffers as float64), with a fixed
+seeded sample of the largest tensors' elements so that the dump stays under 64 MB.  Inputs, initial weights and noise are
+seeded, so two builds run with the same arguments can be compared output for output.
+
 Extra objects on the line:
   roofline      dominant kernel (an implicit-GEMM conv on the matrix cores): algorithmic FLOP of its launches / their
                 HIP-event durations, measured live on the launch stream; peak = dense MFMA peak of the arithmetic
@@ -43,6 +48,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 for p in (os.path.join(ROOT, "intro-tc-vae_amd"), ROOT):
@@ -69,6 +76,7 @@ PEAK_HBM_GBS = 8000.0                # HBM3E spec (MI355X_MICROARCH.md: 8 TB/s; 
 DTYPE = {"fp32": "f32", "bf16x3": "f32 in/out/accumulate, conv products on split-bf16 MFMA (bf16x3)",
          "bf16x6": "f32 in/out/accumulate, conv products on split-bf16 MFMA (bf16x6, fp32-class)",
          "f16x3": "f32 in/out/accumulate, conv products on split-fp16 MFMA (two scaled fp16 planes, 3 products, fp32-class)"}
+DUMP_STATE_BYTES = 56 << 20          # model state in a --dump-outputs directory; the losses come on top (64 MB in all)
 
 
 class _DS:
@@ -152,6 +160,34 @@ def make_solver(wl, math, dev):
                            HP["beta_neg"], HP["gamma_r"], dev, math != "fp32", None, clip=HP["clip"])
     solver.conv_math = math
     return solver
+
+
+def step_outputs(last, model):
+    """name -> host array of what one train_step hands its caller: the returned losses and the model state it updated.
+    Every state tensor gets an equal share of DUMP_STATE_BYTES (water-filled: what the small ones leave goes to the
+    rest); a larger tensor is replaced by the elements at a fixed seeded set of flat indices, the same in every run."""
+    out = {k: np.array(v, dtype=np.float64) for k, v in last.items() if v is not None}
+    state = {k: v.detach().reshape(-1) for k, v in model.state_dict().items()}
+    cap, left = None, DUMP_STATE_BYTES // 4
+    for i, n in enumerate(sorted(v.numel() for v in state.values())):
+        share = left // (len(state) - i)
+        if n > share:
+            cap = share
+            break
+        left -= n
+    for k, v in state.items():
+        if cap is not None and v.numel() > cap:
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            v = v[idx.to(v.device)]
+        out["model." + k] = v.cpu().numpy().astype(np.float32 if v.is_floating_point() else np.float64)
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    log(f"wrote {len(arrays)} arrays ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MiB) to {d}")
 
 
 def _pmc(cfg_name, math):
@@ -287,6 +323,8 @@ def measure(wl, math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=
         elapsed = time.perf_counter() - t0
         if rank == 0:
             log(f"[{math}] eager, events off: {args.steps} steps in {elapsed:.3f} s")
+    # the host-fed leg below trains on: what the timed path computed is taken here
+    outputs = step_outputs(last, solver.model) if args.dump_outputs and math == args.math and rank == 0 else None
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -323,7 +361,7 @@ def measure(wl, math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=
     where = (", immediately before the timed hipGraph-replay steps" if use_graph else
              ", immediately before the timed eager steps" if ddp_on else " (the timed region)")
     return dict(solver=solver, batches=batches, elapsed=elapsed, eager_elapsed=eager_elapsed, last=last, h2d=h2d,
-                roofline=roofline_of(records, math, args.steps, eager_elapsed, where, args.config))
+                outputs=outputs, roofline=roofline_of(records, math, args.steps, eager_elapsed, where, args.config))
 
 
 def main():
@@ -346,7 +384,12 @@ def main():
     ap.add_argument("--leg", choices=["eager", "graph"], default=None,
                     help="(internal, N>1) run ONE leg of the data-parallel measurement in this process; without it an N>1 "
                          "invocation supervises the two legs as child processes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the losses and the trained model state of the timed path's last "
+                         "step as DIR/<name>.npy (at most 64 MB; a fixed seeded sample of the largest tensors)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     wl = CONFIGS[args.config]
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -360,7 +403,7 @@ def main():
     force_ddp = world == 1 and os.environ.get("ITCV_BENCH_FORCE_DDP", "0") == "1"
     if ((world > 1 or force_ddp) and args.leg is None and not args.no_graph and backend == "nccl"
             and os.environ.get("ITCV_DDP_GRAPH", "try") == "try"):
-        return _supervise_legs(rank)             # this process never initialises the GPU
+        return _supervise_legs(rank, args.dump_outputs)     # this process never initialises the GPU
     if backend != "nccl":
         local_rank %= max(torch.cuda.device_count(), 1)
     torch.cuda.set_device(local_rank)
@@ -400,6 +443,8 @@ def main():
     B = wl["batch"]
     m = measure(wl, args.math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=not ddp_on)
     solver, batches, elapsed, eager_elapsed, last = m["solver"], m["batches"], m["elapsed"], m["eager_elapsed"], m["last"]
+    if m["outputs"] is not None:
+        write_outputs(args.dump_outputs, m.pop("outputs"))
 
     images = B * world * args.steps
     value = images / elapsed
@@ -492,24 +537,34 @@ def _graph_leg(wl, args, dev, rank, world, sync):
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        solver.train_step(batches[i % len(batches)], args.warmup + i)
+        last = solver.train_step(batches[i % len(batches)], args.warmup + i)
     sync()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     if rank == 0:
         log(f"graph (data-parallel): {args.steps} steps in {float(t):.3f} s")
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, step_outputs(last, solver.model))
         print(json.dumps({"graph_elapsed_s": float(t), "steps": args.steps}), flush=True)
     dist.barrier()
     dist.destroy_process_group()
 
 
-def _supervise_legs(rank):
+def _supervise_legs(rank, dump_dir):
     """N>1 (or the one-rank rig ITCV_BENCH_FORCE_DDP=1): run the two legs as child processes of this one, which never
     initialises the GPU.  Leg 1 (eager) IS the measurement: if it fails, so does this process, with the child's status.
     Leg 2 (captured) is optional: whatever happens to its process -- exception, abort() in RCCL's watchdog thread, a
-    rank stuck in a collective until the deadline -- rank 0 reports the finished eager line with the reason."""
+    rank stuck in a collective until the deadline -- rank 0 reports the finished eager line with the reason.
+    With --dump-outputs the captured leg writes into a directory of its own, whose arrays replace the eager leg's only
+    if the captured leg is the one reported."""
+    import shutil
     import subprocess
+    import tempfile
     me = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]
+    graph_dir = None
+    if dump_dir:
+        os.makedirs(dump_dir, exist_ok=True)
+        graph_dir = tempfile.mkdtemp(prefix=".graph_leg_", dir=dump_dir)
     a = subprocess.run(me + ["--leg", "eager"], stdout=subprocess.PIPE, text=True)
     lines = [ln for ln in a.stdout.splitlines() if ln.startswith("{")]
     if a.returncode != 0 or (rank == 0 and not lines):
@@ -527,7 +582,8 @@ def _supervise_legs(rank):
     deadline = float(os.environ.get("ITCV_BENCH_GRAPH_DEADLINE", "240"))
     status, reason, g_elapsed = "abandoned", None, None
     try:
-        b = subprocess.run(me + ["--leg", "graph"], stdout=subprocess.PIPE, text=True, env=env, timeout=deadline)
+        b = subprocess.run(me + ["--leg", "graph"] + (["--dump-outputs", graph_dir] if graph_dir else []),
+                           stdout=subprocess.PIPE, text=True, env=env, timeout=deadline)
         glines = [ln for ln in b.stdout.splitlines() if ln.startswith("{")]
         if b.returncode == 0 and (rank != 0 or glines):
             status = "ok"
@@ -539,6 +595,8 @@ def _supervise_legs(rank):
     except subprocess.TimeoutExpired:
         reason = f"no result within {deadline:.0f} s (process killed)"
     if rank != 0:
+        if graph_dir:
+            shutil.rmtree(graph_dir, ignore_errors=True)
         return
     if status == "ok":
         steps, images = out["steps"], out["config"]["global_batch"] * out["steps"]
@@ -550,9 +608,13 @@ def _supervise_legs(rank):
             out.update(value=round(value, 2), ms_per_step=out["graph_ms_per_step"],
                        execution="hipGraph replay (whole data-parallel step, RCCL collectives included, = one graph per rank)",
                        whole_step_tflops=round(out["whole_step_tflops"] * value / eager_value, 2))
+            for f in os.listdir(graph_dir) if graph_dir else ():
+                os.replace(os.path.join(graph_dir, f), os.path.join(dump_dir, f))
     else:
         log(f"captured data-parallel leg abandoned ({reason}); reporting the eager measurement")
         out["graph_leg"] = {"status": "abandoned", "reason": reason, "deadline_s": deadline}
+    if graph_dir:
+        shutil.rmtree(graph_dir, ignore_errors=True)
     print(json.dumps(out), flush=True)
 
 
