@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define ITCV_ABI_VERSION 3
+#define ITCV_ABI_VERSION 4
 
 /* ---- library ------------------------------------------------------------------------- */
 int itcv_abi_version(void);
@@ -420,6 +420,32 @@ int itcv_adam_step(float* p, const float* g, float* m, float* v, size_t n, float
  * memory, so that a captured launch (hipGraph replay) advances the bias correction */
 int itcv_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1,
                        float beta2, float eps, int* step_dev, void* stream);
+/* Fused torch.optim updates (train.py:140-144 picks the class from the run config) over one flat fp32 buffer of n
+ * elements (n % 4 == 0, every pointer 16-byte aligned): the single-tensor arithmetic of torch/optim/{adam,sgd,adagrad,
+ * rmsprop}.py in torch's order.  Each reads the 0-based count of completed steps from step_dev (bias corrections,
+ * Adagrad's lr decay, SGD's first-step momentum buffer) and increments it, so captured launches advance it.
+ * `live` (may be NULL) holds one byte per 4 elements: 0 marks elements of a parameter that never receives a gradient
+ * (torch skips such a parameter: no weight decay, no state); those elements of p and of every state buffer are left
+ * untouched.  Hyper-parameters are the Python floats of the param group; flags are ITCV_OPT_* bits. */
+#define ITCV_OPT_MAXIMIZE 0x1
+#define ITCV_OPT_NESTEROV 0x2     /* SGD */
+#define ITCV_OPT_AMSGRAD 0x4      /* Adam */
+#define ITCV_OPT_DECOUPLED_WD 0x8 /* Adam: AdamW / decoupled_weight_decay=True */
+#define ITCV_OPT_CENTERED 0x10    /* RMSprop */
+/* Adam / AdamW with weight decay, amsgrad (max_exp_avg_sq, else may be NULL) and/or maximize */
+int itcv_adamx_step_dev(float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* max_exp_avg_sq,
+                        const unsigned char* live, size_t n, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, int flags, int* step_dev, void* stream);
+/* SGD; momentum_buffer may be NULL when momentum == 0 (on the first step it becomes a copy of the gradient) */
+int itcv_sgd_step_dev(float* p, const float* g, float* momentum_buffer, const unsigned char* live, size_t n, double lr,
+                      double momentum, double dampening, double weight_decay, int flags, int* step_dev, void* stream);
+/* Adagrad: clr = lr / (1 + (step - 1) * lr_decay); `sum` starts at initial_accumulator_value (set by the caller) */
+int itcv_adagrad_step_dev(float* p, const float* g, float* sum, const unsigned char* live, size_t n, double lr,
+                          double lr_decay, double weight_decay, double eps, int flags, int* step_dev, void* stream);
+/* RMSprop; momentum_buffer only when momentum > 0, grad_avg only when ITCV_OPT_CENTERED (else may be NULL) */
+int itcv_rmsprop_step_dev(float* p, const float* g, float* square_avg, float* momentum_buffer, float* grad_avg,
+                          const unsigned char* live, size_t n, double lr, double alpha, double eps,
+                          double weight_decay, double momentum, int flags, int* step_dev, void* stream);
 int itcv_fill(float* x, size_t n, float value, void* stream);
 /* Input pipeline (dataset.py:219-224 transforms.RandomHorizontalFlip, moved behind the host -> device copy):
  * y[b] = x[b] mirrored along W where flip[b] != 0, else x[b]; x, y are [B][rows_per_image][W] (rows = C*H), x != y. */

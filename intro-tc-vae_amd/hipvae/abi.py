@@ -19,7 +19,7 @@ PKG_ROOT = os.path.dirname(_HERE)
 # ITCV_LIB: load another build of the same library (the -DITCV_DIAG diagnostic build of `make diag`, tools/abl.sh)
 LIB_PATH = os.environ.get("ITCV_LIB") or os.path.join(PKG_ROOT, "lib", "libitcv_hip.so")
 CSRC = os.path.join(PKG_ROOT, "csrc")
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 p, i32, i64, sz, f32, f64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t,
                              ctypes.c_float, ctypes.c_double)
@@ -142,6 +142,10 @@ SIGNATURES = {
     "itcv_scale_by_dev": (i32, [p, sz, p, p]),
     "itcv_adam_step": (i32, [p, p, p, p, sz, f32, f32, f32, f32, i32, p]),
     "itcv_adam_step_dev": (i32, [p, p, p, p, sz, f32, f32, f32, f32, p, p]),
+    "itcv_adamx_step_dev": (i32, [p] * 6 + [sz] + [f64] * 5 + [i32, p, p]),
+    "itcv_sgd_step_dev": (i32, [p] * 4 + [sz] + [f64] * 4 + [i32, p, p]),
+    "itcv_adagrad_step_dev": (i32, [p] * 4 + [sz] + [f64] * 4 + [i32, p, p]),
+    "itcv_rmsprop_step_dev": (i32, [p] * 6 + [sz] + [f64] * 5 + [i32, p, p]),
     "itcv_fill": (i32, [p, sz, f32, p]),
     "itcv_hflip": (i32, [p, p, p, i32, i32, i32, p]),
 }
@@ -149,6 +153,7 @@ SIGNATURES = {
 TC_VAR_FROM_ROW, TC_EPS_DENSITY, TC_WEIGHTED = 1, 2, 4
 TC_LIVE = TC_VAR_FROM_ROW | TC_EPS_DENSITY
 LOSS_TYPES = {"mse": 0, "l1": 1, "bce": 2}
+OPT_MAXIMIZE, OPT_NESTEROV, OPT_AMSGRAD, OPT_DECOUPLED_WD, OPT_CENTERED = 0x1, 0x2, 0x4, 0x8, 0x10
 
 
 class HipExtensionError(RuntimeError):

@@ -196,6 +196,15 @@ class ConvolutionalBlock(nn.Module):
                         grad_mode=HF.conv_grad_mode(self.conv2, B, H, W))
 
 
+def grad_free_parameters(module):
+    """Parameters of ``module`` that the reference's forward never reaches, so torch leaves their ``.grad`` None and its
+    optimisers skip them (no weight decay, no state): every ``ConvolutionalBlock.conv_expand`` (models.py:15-26,51-54).
+    The flat gradient buffers (hipvae/flat.py) give them a zero gradient instead, and the fused updates leave them
+    untouched."""
+    return [p for m in module.modules() if isinstance(m, ConvolutionalBlock) and m.conv_expand is not None
+            for p in m.conv_expand.parameters()]
+
+
 class ResidualBlock(nn.Module):
     """models.py:57-115: conv-BN-LReLU-conv-BN, + (1x1-expanded) input, LReLU.  BN eps 1e-5."""
 

@@ -2,7 +2,7 @@
 (/root/reference/solvers/vae.py:26-136), running the step on HIP kernels.
 
 Shared machinery for all four solvers lives here: flat gradient buffers, the fused
-clip-norm + Adam tail, the single end-of-step host read-back and the data-parallel hooks.
+clip-norm + optimiser tail, the single end-of-step host read-back and the data-parallel hooks.
 """
 from typing import Optional
 
@@ -11,7 +11,8 @@ from torch import Tensor
 
 from hipvae import ddp
 from hipvae.functional import LinCombFn, conv_math_scope, deferred_wgrad_reduces, direct_grad_accumulation
-from hipvae.flat import FlatGroup, clip_grad_norm, plain_adam_hparams
+from hipvae.flat import FlatGroup, clip_grad_norm, fused_update
+from models import grad_free_parameters
 from ops import kl_divergence, reconstruction_loss
 from utils import SingletonWriter
 
@@ -95,8 +96,9 @@ class VAESolver:
         g = self._flat.get(part)
         if g is None or not g.owns(params):
             # ownership lost (model.to() / .float() / load_state_dict(assign=True) after the first step): the new group
-            # inherits the Adam moments and step count instead of restarting them
-            g = self._flat[part] = FlatGroup(params, inherit=g)
+            # inherits the optimiser state and step count instead of restarting them
+            g = self._flat[part] = FlatGroup(params, inherit=g,
+                                             grad_free=grad_free_parameters(getattr(self.model, part)))
         return g
 
     def _set_trainable(self, encoder: bool, decoder: bool):
@@ -132,13 +134,13 @@ class VAESolver:
 
     def _step(self, part):
         opt = self.optimizer_e if part == "encoder" else self.optimizer_d
-        hp = plain_adam_hparams(opt)
-        if hp is None:
-            opt.step()                       # non-Adam optimiser supplied by the caller: torch's own update
+        spec = fused_update(opt)
+        if spec is None:
+            opt.step()                       # an optimiser config without a fused update: torch's own
         else:
             g = self._group(part)
-            g.bind_optimizer(opt)            # moments visible in (and adopted from) opt.state / state_dict()
-            g.adam_step(*hp)
+            g.bind_optimizer(opt, spec)      # state visible in (and adopted from) opt.state / state_dict()
+            g.fused_step(spec)
 
     # ---- step execution: eager, or one hipGraph replay -----------------------------------------
     def enable_graph(self, flag: bool = True):
@@ -152,12 +154,16 @@ class VAESolver:
         self._graphs, self._graph_warm = {}, {}
         return self
 
-    def _graph_ok(self):
+    def _graph_ok(self, specs=None):
+        """``specs``: (fused_update(optimizer_e), fused_update(optimizer_d)) when the caller has them already."""
         import ops
-        return (getattr(self, "_graph_on", False) and self.writer is None
+        if not (getattr(self, "_graph_on", False) and self.writer is None
                 and (ddp.get() is None or ddp.graph_capturable())
-                and ops._noise["queue"] is None and ops._noise["mode"] == "device"
-                and plain_adam_hparams(self.optimizer_e) is not None and plain_adam_hparams(self.optimizer_d) is not None)
+                and ops._noise["queue"] is None and ops._noise["mode"] == "device"):
+            return False
+        if specs is None:
+            specs = (fused_update(self.optimizer_e), fused_update(self.optimizer_d))
+        return specs[0] is not None and specs[1] is not None
 
     def _run(self, real: Tensor) -> Tensor:
         """Runs ``_device_step`` eagerly or through the captured graph; returns the device stats vector."""
@@ -165,12 +171,13 @@ class VAESolver:
             return self._run_scoped(real)
 
     def _run_scoped(self, real: Tensor) -> Tensor:
-        if not self._graph_ok():
+        specs = (fused_update(self.optimizer_e), fused_update(self.optimizer_d)) if getattr(self, "_graph_on", False) \
+            else None
+        if not self._graph_ok(specs):
             return self._device_step(real)
-        # lr / betas / eps are scalar kernel arguments frozen into a captured graph: they are part of its key, so a
-        # scheduler or manual decay of param_groups[0]["lr"] re-captures instead of being silently ignored
-        key = (tuple(real.shape), real.dtype, self.conv_math, plain_adam_hparams(self.optimizer_e),
-               plain_adam_hparams(self.optimizer_d))
+        # the optimiser hyper-parameters are scalar kernel arguments frozen into a captured graph: the update specs are
+        # part of its key, so a scheduler or manual decay of param_groups[0]["lr"] re-captures instead of being ignored
+        key = (tuple(real.shape), real.dtype, self.conv_math) + specs
         from hipvae.functional import bump_weight_epoch
         graphs = self.__dict__.setdefault("_graphs", {})
         ent = graphs.get(key)
