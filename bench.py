@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec of one IntroTCSovler.train_step (Soft-Intro beta-TC-VAE step:
 5 encoder + 8 decoder forwards, 2 backwards, 2 Adam updates) on synthetic batches resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--math bf16x3|bf16x6|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--math bf16x3|bf16x6|fp32] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,8 +12,18 @@ Workloads (BASELINE.json configs; conv architecture, Adam lr 2e-4, clip 100, N =
     c3            128x128x3, z=256, channels (64,128,256,512,512),     128 images per GPU
     c5            256x256x3, z=512, channels (64,128,256,512,512,512), 32 images per GPU  (--gpus 8: global batch 256)
 fp32 tensors throughout; the conv products run in the mode --math selects (default f16x3 = what the reference's
-use_amp=True config maps to: fp32-class accuracy on the fp16 matrix cores).  At N=1 on c2 the line also carries
-"modes": the same measurement in exact fp32 (the reference's own precision), bf16x3 and bf16x6, made in the same process.
+use_amp=True config maps to: fp32-class accuracy on the fp16 matrix cores).  With --full, at N=1 on c2 the line also
+carries "modes": the same measurement in exact fp32 (the reference's own precision), bf16x3 and bf16x6, made in the same
+process.
+
+A plain run does what the headline figure needs: it sets up, runs the W warm-up steps, K eager steps (the state the timed
+steps start from), the capture, the K timed steps, writes --dump-outputs and prints the line.  --full measures the rest:
+a HIP-event pair around every implicit-GEMM launch of the eager steps ("roofline", "eager_ms_per_step"), the host-fed
+rate ("host_fed"), "modes" and the CPU oracle ("cpu_baseline", "gpu_over_cpu"); --no-modes / --no-cpu-baseline drop
+those two from a --full run.  Where the eager steps are themselves the timed region (--no-graph at N=1) their events
+stay on in a plain run too, so that ms_per_step measures what it always has; the line then carries "roofline" as well.
+"last_step" holds the losses of the last step the process ran: in a plain run the last timed step (the losses that
+--dump-outputs writes), in a --full run at N=1 the last step of the host-fed leg.
 
 One process per GPU; N>1 shards the batch (weak scaling) with a flat RCCL all-reduce of the trained half's gradients
 per phase and an all-gather of mu for the full-batch TC estimator; BatchNorm statistics are per rank (throughput
@@ -32,13 +42,14 @@ dies with its own non-zero status and the supervisor prints the eager line with 
 seeded sample of the largest tensors' elements so that the dump stays under 64 MB.  Inputs, initial weights and noise are
 seeded, so two builds run with the same arguments can be compared output for output.
 
-Extra objects on the line:
+Extra objects on a --full line:
   roofline      dominant kernel (an implicit-GEMM conv on the matrix cores): algorithmic FLOP of its launches / their
                 HIP-event durations, measured live on the launch stream; peak = dense MFMA peak of the arithmetic
                 (2500/3 TFLOP/s for f16x3 and bf16x3, 2500/6 for bf16x6, 157.3 for fp32; MI355X_MICROARCH.md); traffic = HBM
                 bytes per launch from the committed rocprofv3 --pmc passes, only while the kernel sources are unchanged.
   cpu_baseline  the CPU oracle (oracle/, a PyTorch-CPU port pinned to the reference by golden vectors) timed on the
                 host cores: 1 warm-up + 3 timed steps (BASELINE.md protocol) on a bounded batch of the same workload.
+  host_fed      the same K steps with every batch starting in pageable host memory (N=1).
 """
 import argparse
 import contextlib
@@ -276,8 +287,9 @@ def roofline_of(records, math, steps, eager_elapsed, where, cfg_name="c2"):
     return out
 
 
-def measure(wl, math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=False):
-    """Warm-up, roofline leg (K eager steps with per-launch events), timed leg.  Returns a dict of raw results."""
+def measure(wl, math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=False, profile=True):
+    """Warm-up, K eager steps (the roofline leg when ``profile``: per-launch events), timed leg.  Returns a dict of raw
+    results; "roofline" is None without ``profile``."""
     from hipvae import functional as HF
     solver = make_solver(wl, math, dev)
     B, S = wl["batch"], wl["cfg"]["image_size"]
@@ -289,17 +301,18 @@ def measure(wl, math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=
         if rank == 0:
             log(f"[{math}] warm-up step {i}: {last}")
     sync()
-    # ---- roofline leg: K eager steps with a HIP-event pair around every implicit-GEMM launch ----
-    HF.LaunchProfile.begin()
+    # ---- K eager steps; the roofline leg when profiled: a HIP-event pair around every implicit-GEMM launch ----
+    if profile:
+        HF.LaunchProfile.begin()
     t0 = time.perf_counter()
     for i in range(args.steps):
         last = solver.train_step(batches[i % len(batches)], args.warmup + i)
     sync()
     eager_elapsed = time.perf_counter() - t0
-    records = HF.LaunchProfile.end()
+    records = HF.LaunchProfile.end() if profile else None
     elapsed = eager_elapsed
     if rank == 0:
-        log(f"[{math}] eager: {args.steps} steps in {eager_elapsed:.3f} s (events on)")
+        log(f"[{math}] eager: {args.steps} steps in {eager_elapsed:.3f} s (events {'on' if profile else 'off'})")
     if use_graph:
         # ---- timed region proper: the same K steps as hipGraph replays (one submission per step) ----
         solver.enable_graph()
@@ -360,8 +373,9 @@ def measure(wl, math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=
             log(f"[{math}] host-fed: {args.steps} steps in {t_h2d:.3f} s")
     where = (", immediately before the timed hipGraph-replay steps" if use_graph else
              ", immediately before the timed eager steps" if ddp_on else " (the timed region)")
+    roofline = roofline_of(records, math, args.steps, eager_elapsed, where, args.config) if profile else None
     return dict(solver=solver, batches=batches, elapsed=elapsed, eager_elapsed=eager_elapsed, last=last, h2d=h2d,
-                outputs=outputs, roofline=roofline_of(records, math, args.steps, eager_elapsed, where, args.config))
+                outputs=outputs, roofline=roofline)
 
 
 def main():
@@ -371,9 +385,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="workload: c2 = the metric's configuration (c4 when --gpus 8); c3 / c5 = BASELINE configs[2] / [4]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-launch events over the eager steps "
+                         "('roofline'), the host-fed rate, the other arithmetics ('modes', N=1 on c2) and the CPU oracle")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle baseline")
     ap.add_argument("--no-modes", action="store_true",
-                    help="N=1, c2: skip the additional fp32 / bf16x6 measurements (the 'modes' object)")
+                    help="--full, N=1, c2: skip the additional fp32 / bf16x6 measurements (the 'modes' object)")
     ap.add_argument("--sync-bn", action="store_true",
                     help="N>1: all-reduce BatchNorm moments (full-batch parity mode); default is per-rank statistics")
     ap.add_argument("--math", choices=["f16x3", "bf16x3", "bf16x6", "fp32"], default="f16x3",
@@ -441,7 +458,10 @@ def main():
     ddp_on = ddp.get() is not None
     use_graph = not args.no_graph and (not ddp_on or ddp.graph_capturable())
     B = wl["batch"]
-    m = measure(wl, args.math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=not ddp_on)
+    # the eager steps' events: --full, or where those steps are the timed region (ms_per_step as it has always been)
+    profile = args.full or not (use_graph or ddp_on)
+    m = measure(wl, args.math, dev, args, rank, world, sync, use_graph, ddp_on, with_h2d=args.full and not ddp_on,
+                profile=profile)
     solver, batches, elapsed, eager_elapsed, last = m["solver"], m["batches"], m["elapsed"], m["eager_elapsed"], m["last"]
     if m["outputs"] is not None:
         write_outputs(args.dump_outputs, m.pop("outputs"))
@@ -460,12 +480,13 @@ def main():
                    "parallelism": f"dp{world}" if world > 1 else ("single, dp code path forced (one-rank RCCL group)" if force_ddp else "single"),
                    "sync_bn": bool(ddp_on and args.sync_bn)},
         "execution": "hipGraph replay (whole step = one graph)" if use_graph else "eager launches",
-        "eager_ms_per_step": round(eager_elapsed / args.steps * 1e3, 3),
         "step_tflop": round(wl["gflop"] * B * world * 1e-3, 3),
         "whole_step_tflops": round(value * wl["gflop"] * 1e-3 / world, 2),
         "last_step": last,
-        "roofline": m["roofline"],
     }
+    if profile:
+        out["eager_ms_per_step"] = round(eager_elapsed / args.steps * 1e3, 3)
+        out["roofline"] = m["roofline"]
     if m["h2d"] is not None:
         out["host_fed"] = m["h2d"]
     if ddp_on:
@@ -473,7 +494,7 @@ def main():
                             "reason": "ITCV_DDP_GRAPH=" + os.environ.get("ITCV_DDP_GRAPH", "") + (" / --no-graph" if args.no_graph else "")
                             + (" / backend " + backend if backend != "nccl" else "")}
     # ---- N=1 on the metric's workload: the same measurement in the reference's own precision (and bf16x6) ----------
-    if world == 1 and not ddp_on and args.config == "c2" and not args.no_modes:
+    if args.full and world == 1 and not ddp_on and args.config == "c2" and not args.no_modes:
         del solver, batches, m
         torch.cuda.empty_cache()
         out["modes"] = {}
@@ -491,7 +512,7 @@ def main():
             del mm
             torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl)
             out["gpu_over_cpu"] = round(value / out["cpu_baseline"]["value"], 1)
         print(json.dumps(out), flush=True)

@@ -1,32 +1,34 @@
 #!/bin/bash
 # Round evidence on the GPU box: per workload the two --pmc passes (HBM bytes per launch), the kernel-trace summary and
-# the bench line.  Run as: gpurun -- 'bash tools/evidence.sh'; then copy gpurun_out/ev/r03_* into profiles/.
+# the bench line (bench.py --full throughout).  Run as: bash tools/evidence.sh OUTDIR (relative to the repository
+# root); then copy OUTDIR/r03_* into profiles/.
 # The PMC passes run WITHOUT any trace domain beside the kernel trace (gpurun refuses other combinations).
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/ev
+EV=${1:?usage: bash tools/evidence.sh OUTDIR}
+mkdir -p "$EV"
 MATH=${MATH:-f16x3}
 PMC_ARGS=""
 for c in c2 c3 c5; do
-  ARGS="--config $c --math $MATH --steps 2 --warmup 1 --no-graph --no-modes --no-cpu-baseline"
-  timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/ev/pmc_fetch_$c -o f -- python3 bench.py $ARGS > gpurun_out/ev/pmc_fetch_$c.json 2> gpurun_out/ev/pmc_fetch_$c.err
-  timeout -k 10 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/ev/pmc_write_$c -o w -- python3 bench.py $ARGS > gpurun_out/ev/pmc_write_$c.json 2> gpurun_out/ev/pmc_write_$c.err
-  PMC_ARGS="$PMC_ARGS $c $(find gpurun_out/ev/pmc_fetch_$c -name '*counter_collection.csv') $(find gpurun_out/ev/pmc_write_$c -name '*counter_collection.csv')"
+  ARGS="--config $c --math $MATH --steps 2 --warmup 1 --no-graph --no-modes --no-cpu-baseline --full"
+  timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $EV/pmc_fetch_$c -o f -- python3 bench.py $ARGS > $EV/pmc_fetch_$c.json 2> $EV/pmc_fetch_$c.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $EV/pmc_write_$c -o w -- python3 bench.py $ARGS > $EV/pmc_write_$c.json 2> $EV/pmc_write_$c.err
+  PMC_ARGS="$PMC_ARGS $c $(find $EV/pmc_fetch_$c -name '*counter_collection.csv') $(find $EV/pmc_write_$c -name '*counter_collection.csv')"
   echo "pmc $c done"
 done
-python tools/pmc_summary.py $MATH $PMC_ARGS > gpurun_out/ev/r03_pmc_traffic.json 2> gpurun_out/ev/pmc_summary.log
-cp gpurun_out/ev/r03_pmc_traffic.json profiles/r03_pmc_traffic.json
-rm -rf gpurun_out/ev/pmc_fetch_c* gpurun_out/ev/pmc_write_c*
+python tools/pmc_summary.py $MATH $PMC_ARGS > $EV/r03_pmc_traffic.json 2> $EV/pmc_summary.log
+cp $EV/r03_pmc_traffic.json profiles/r03_pmc_traffic.json
+rm -rf $EV/pmc_fetch_c* $EV/pmc_write_c*
 for c in c2 c3 c5; do
   S="--steps 20 --warmup 5"; [ $c != c2 ] && S="--steps 6 --warmup 3"
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d gpurun_out/ev/prof_$c -o p -- python3 bench.py --config $c --no-cpu-baseline --no-modes $S > gpurun_out/ev/prof_$c.json 2> gpurun_out/ev/prof_$c.err
-  python tools/rocpd_stats.py gpurun_out/ev/prof_$c/p_results.db > gpurun_out/ev/r03_${c}_kernel_stats.csv 2> gpurun_out/ev/prof_${c}_span.txt
-  rm -rf gpurun_out/ev/prof_$c
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $EV/prof_$c -o p -- python3 bench.py --config $c --no-cpu-baseline --no-modes --full $S > $EV/prof_$c.json 2> $EV/prof_$c.err
+  python tools/rocpd_stats.py $EV/prof_$c/p_results.db > $EV/r03_${c}_kernel_stats.csv 2> $EV/prof_${c}_span.txt
+  rm -rf $EV/prof_$c
   echo "prof $c done"
 done
-timeout -k 10 900 python bench.py > gpurun_out/ev/r03_bench_c2.json 2> gpurun_out/ev/bench_c2.err
+timeout -k 10 900 python bench.py --full > $EV/r03_bench_c2.json 2> $EV/bench_c2.err
 echo "bench c2 done"
-timeout -k 10 600 python bench.py --config c3 --no-modes > gpurun_out/ev/r03_bench_c3.json 2> gpurun_out/ev/bench_c3.err
+timeout -k 10 600 python bench.py --config c3 --no-modes --full > $EV/r03_bench_c3.json 2> $EV/bench_c3.err
 echo "bench c3 done"
-timeout -k 10 600 python bench.py --config c5 --no-modes > gpurun_out/ev/r03_bench_c5.json 2> gpurun_out/ev/bench_c5.err
+timeout -k 10 600 python bench.py --config c5 --no-modes --full > $EV/r03_bench_c5.json 2> $EV/bench_c5.err
 echo "bench c5 done"

@@ -56,7 +56,7 @@ def collect(path, counter):
 
 def summarise(fpath, wpath, math, cfg):
     fetch, write = collect(fpath, "FETCH_SIZE"), collect(wpath, "WRITE_SIZE")
-    out = {"math": math, "command": f"bench.py --config {cfg} --math {math} --steps 2 --warmup 1 --no-graph --no-modes --no-cpu-baseline",
+    out = {"math": math, "command": f"bench.py --config {cfg} --math {math} --steps 2 --warmup 1 --no-graph --no-modes --no-cpu-baseline --full",
            "kernels": {}}
     for k in sorted(set(fetch) | set(write)):
         fv, wv = fetch.get(k, []), write.get(k, [])

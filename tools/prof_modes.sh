@@ -1,10 +1,13 @@
 #!/bin/bash
-# rocprofv3 kernel-trace summaries of the c2 step per conv arithmetic (gpurun -- 'bash tools/prof_modes.sh f16x3 bf16x3')
+# rocprofv3 kernel-trace summaries of the c2 step per conv arithmetic (bench.py --full):
+#   bash tools/prof_modes.sh OUTDIR f16x3 bf16x3   (OUTDIR relative to the repository root)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out/pm
+PM=${1:?usage: bash tools/prof_modes.sh OUTDIR MATH...}
+shift
+mkdir -p "$PM"
 for m in "$@"; do
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/pm/prof_$m -o p -- python3 bench.py --math $m --no-cpu-baseline --no-modes --steps 20 --warmup 3 > gpurun_out/pm/bench_$m.json 2> gpurun_out/pm/bench_$m.err || exit 1
-  python tools/rocpd_stats.py gpurun_out/pm/prof_$m/p_results.db > gpurun_out/pm/kernel_stats_$m.csv 2> gpurun_out/pm/span_$m.txt
-  rm -rf gpurun_out/pm/prof_$m
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $PM/prof_$m -o p -- python3 bench.py --math $m --no-cpu-baseline --no-modes --full --steps 20 --warmup 3 > $PM/bench_$m.json 2> $PM/bench_$m.err || exit 1
+  python tools/rocpd_stats.py $PM/prof_$m/p_results.db > $PM/kernel_stats_$m.csv 2> $PM/span_$m.txt
+  rm -rf $PM/prof_$m
   echo "prof $m done"
 done
