@@ -347,6 +347,29 @@ int itcv_tc_kl_bwd(const float* g, const float* z, const float* mu_all, const fl
                    const float* lse, const float* sjoint, float* dz, float* dmu_all, float* dlogvar, int Bl, int Bt,
                    int row_offset, int D, int64_t dataset_size, float coef_tc, float coef_kl, int reduction, void* ws,
                    size_t ws_bytes, void* stream);
+/* The full beta-TC decomposition of solvers/tc.py:91-144 (_compute_kl_loss_full) as a trainable loss, with weights:
+ *   r_j = alpha (logqcx_j - logqz_j) + beta (logqz_j - prodm_j) + gamma (prodm_j - logpz_j)   (the reference: alpha = gamma = 1)
+ * with the ops.py:24-29 density (no variance floor), the variance of COMPONENT i (logvar.unsqueeze(0)) and the stratified
+ * sampler (ops.py:32-49,104-115); logqcx_j / logpz_j: ops.py:24-29 at (mu_j, logvar_j) / (0, 0), summed over l.
+ *   rows j: z[Bl][D] (global row row_offset + j);  cols i: mu_all / logvar_all [Bt][D] with row stride ld >= D (ld = 2D
+ *   reads the two halves of one packed [Bt][2D] all-gather in place).  This rank's own means and variances are rows
+ *   row_offset .. row_offset+Bl-1 of the column operands.
+ * out[Bl] (reduction 0 none) or out[1] (1 sum, 2 mean) of r_j; rows[Bl]: scratch of the reduced forms; comps[3][Bl]
+ * (may be NULL): the per-sample (mi, tc, dwkl).  prodm / logqz / lse / sjoint as itcv_tc_fwd; ivar[Bt][D] = exp(-logvar_all),
+ * the coefficients the forward used.  Workspace: itcv_tc_full_fwd_workspace.  3 launches at most.
+ * _bwd: g is [Bl] (none) or [1]; dz[Bl][D] (rows), dmu_all / dlogvar_all [Bt][D] with row stride ld (columns: the partial
+ * over this rank's rows, plus the d/dmu, d/dlogvar of logqcx on this rank's own rows).  Workspace: itcv_tc_full_bwd_workspace.
+ * 2 launches, fixed summation orders (bitwise reproducible). */
+size_t itcv_tc_full_fwd_workspace(int Bl, int Bt, int D);
+int itcv_tc_full_fwd(const float* z, const float* mu_all, const float* logvar_all, int ld, float* out, float* rows,
+                     float* comps, float* prodm, float* logqz, float* lse, float* sjoint, float* ivar, int Bl, int Bt,
+                     int row_offset, int D, int64_t dataset_size, float alpha, float beta, float gamma, int reduction,
+                     void* ws, size_t ws_bytes, void* stream);
+size_t itcv_tc_full_bwd_workspace(int Bl, int Bt);
+int itcv_tc_full_bwd(const float* g, const float* z, const float* mu_all, const float* logvar_all, int ld,
+                     const float* logqz, const float* lse, const float* sjoint, const float* ivar, float* dz, float* dmu_all,
+                     float* dlogvar_all, int Bl, int Bt, int row_offset, int D, int64_t dataset_size, float alpha,
+                     float beta, float gamma, int reduction, void* ws, size_t ws_bytes, void* stream);
 /* ops.kl_divergence with its reduction and the hook's `beta *` (ops.py:136-163, solvers/vae.py:63-77) in one launch:
  * reduction 0: out[B] = scale * kl_j; 1 / 2: out[1] = scale * sum_j kl_j [/ B]; _bwd for g of that shape. */
 int itcv_kl_loss_fwd(const float* logvar, const float* mu, float* out, int B, int D, int reduction, float scale, void* stream);

@@ -77,7 +77,8 @@ template <int DL, bool VROW, bool EPS, bool MWS>
 __global__ __launch_bounds__(256) void tc_fwd_part_kernel(const float* __restrict__ z, const float* __restrict__ mu_all,
                                                           const float* __restrict__ logvar, float* __restrict__ pmax,
                                                           float* __restrict__ psum, float* __restrict__ sjoint, int Bt,
-                                                          int row_offset, int D, int nch, TcConst c) {
+                                                          int row_offset, int D, int nch, TcConst c, int ldm,
+                                                          float* __restrict__ ivar) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* mu_s = sm;                                   // [kTcIC][D]
   float* A_s = mu_s + kTcIC * D;                      // [kTcIC][D]  (!VROW only)
@@ -87,9 +88,17 @@ __global__ __launch_bounds__(256) void tc_fwd_part_kernel(const float* __restric
   const int j = blockIdx.x, ch = blockIdx.y, jg = row_offset + j;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int i0 = ch * kTcIC, rows = min(kTcIC, Bt - i0);
-  for (int e = tid; e < rows * D; e += 256) {
-    mu_s[e] = mu_all[(size_t)i0 * D + e];
-    if (!VROW) dens_coef<EPS>(logvar[(size_t)i0 * D + e], A_s[e], B_s[e]);
+  if (VROW || ldm == D) {                             // the live path (VROW) always has dense rows
+    for (int e = tid; e < rows * D; e += 256) {
+      mu_s[e] = mu_all[(size_t)i0 * D + e];
+      if (!VROW) dens_coef<EPS>(logvar[(size_t)i0 * D + e], A_s[e], B_s[e]);
+    }
+  } else {                                            // column operands with a row stride (a packed [Bt][2D] gather)
+    for (int e = tid; e < rows * D; e += 256) {
+      const int r = e / D, l = e - r * D;
+      mu_s[e] = mu_all[(size_t)(i0 + r) * ldm + l];
+      if (!VROW) dens_coef<EPS>(logvar[(size_t)(i0 + r) * ldm + l], A_s[e], B_s[e]);
+    }
   }
   float zj[DL], Aj[DL], Bj[DL];
 #pragma unroll
@@ -102,6 +111,9 @@ __global__ __launch_bounds__(256) void tc_fwd_part_kernel(const float* __restric
     }
   }
   __syncthreads();
+  // the per-(column, l) inverse variance of the column-variance form, kept for its backward (written once, by row 0)
+  if (!VROW && ivar && j == 0)
+    for (int e = tid; e < rows * D; e += 256) ivar[(size_t)i0 * D + e] = B_s[e];
   float v[kTcRW][DL];
 #pragma unroll
   for (int r = 0; r < kTcRW; ++r) {
@@ -164,11 +176,29 @@ struct TcKlOut {
   float coef_tc, coef_kl;
 };
 
+// Full decomposition tail (solvers/tc.py:91-144, with weights): with `rows` set the block also evaluates
+// logqcx_j = sum_l max(lp(z_j; mu_j, lv_j), -50) and logpz_j = sum_l max(lp(z_j; 0, 0), -50) (ops.py:24-29; mu_d / lv_d:
+// this rank's rows of the column operands, row stride ld) and writes
+// rows[j] = a (logqcx - logqz) + b (logqz - prodm) + g (prodm - logpz), and the three terms to comps[0|1|2][Bl] if set.
+struct TcFullOut {
+  const float* z;
+  const float* mu_d;
+  const float* lv_d;
+  float* rows;
+  float* comps;
+  int ld, Bl;
+  float a, b, g;
+};
+
+// diagonal log densities of the full form for one (j, l): max(lp(z; mu, lv), -50) and max(lp(z; 0, 0), -50)
+__device__ __forceinline__ float diag_lp(float zz, float m, float lv) { return logdens<false>(zz - m, lv); }
+__device__ __forceinline__ float prior_lp(float zz) { return logdens<false>(zz, 0.f); }
+
 template <bool MWS>
 __global__ __launch_bounds__(256) void tc_fwd_finish_kernel(const float* __restrict__ pmax, const float* __restrict__ psum,
                                                             const float* __restrict__ sjoint, float* __restrict__ prodm,
                                                             float* __restrict__ logqz, float* __restrict__ lse, int Bt, int D,
-                                                            int nch, TcConst c, TcKlOut kk) {
+                                                            int nch, TcConst c, TcKlOut kk, TcFullOut ff) {
   __shared__ float red[4];
   const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   float prod_acc = 0.f;
@@ -204,11 +234,27 @@ __global__ __launch_bounds__(256) void tc_fwd_finish_kernel(const float* __restr
     }
     klj = -0.5f * block_sum(a, red);
   }
+  float lcx = 0.f, lpz = 0.f;
+  if (ff.rows) {
+    float a = 0.f, b = 0.f;
+    for (int l = tid; l < D; l += 256) {
+      const float zz = ff.z[(size_t)j * D + l];
+      a += fmaxf(diag_lp(zz, ff.mu_d[(size_t)j * ff.ld + l], ff.lv_d[(size_t)j * ff.ld + l]), kFloor);
+      b += fmaxf(prior_lp(zz), kFloor);
+    }
+    lcx = block_sum(a, red);
+    lpz = block_sum(b, red);
+  }
   if (tid == 0) {
     const float lq = mx + logf(se) - (MWS ? c.log_bn : 0.f);
     logqz[j] = lq;
     prodm[j] = pm;
     if (kk.rows) kk.rows[j] = kk.coef_tc * (lq - pm) + kk.coef_kl * klj;
+    if (ff.rows) {
+      const float mi = lcx - lq, tc = lq - pm, dw = pm - lpz;
+      ff.rows[j] = ff.a * mi + ff.b * tc + ff.g * dw;
+      if (ff.comps) ff.comps[j] = mi, ff.comps[ff.Bl + j] = tc, ff.comps[2 * ff.Bl + j] = dw;
+    }
   }
 }
 
@@ -304,6 +350,95 @@ __global__ __launch_bounds__(256) void tc_bwd_cols_kernel(
     // the analytic KL's d/dmu = mu for this rank's own rows (column i is local row i - row_offset)
     if (tg.coef_kl != 0.f && i >= row_offset && i < row_offset + Bl) v += tg.coef_kl * tc_g(tg, i - row_offset) * mi;
     dmu_all[(size_t)i * D + l] = v;
+  }
+}
+
+// ---- backward of sum_j g[j] * r_j, the full decomposition (solvers/tc.py:91-144: ops.py:24-29 density, variance of
+// column i, stratified sampler) ---------------------------------------------------------------------------------------
+//   r_j = a (logqcx_j - logqz_j) + b (logqz_j - prodm_j) + c (prodm_j - logpz_j);  with cq = (b - a) g_j, cp = (c - b) g_j
+//   G[j,i,l] = [lp >= -50] * (cq exp(S[j,i] - logqz_j) + cp exp(logW[j,i] + lp - lse[j,l])),   iv = exp(-lv[i,l])
+//   dz[j,l]  = -sum_i G d iv  + a g_j [lpd >= -50] (-d_jj iv_jj) + c g_j [lpz >= -50] z_jl      (diagonal terms)
+//   dmu[i,l] =  sum_j G d iv  + a g_i' [lpd >= -50] d iv                         (i' = i - row_offset, local rows only)
+//   dlv[i,l] = -1/2 sum_j G (1 - d^2 iv) - 1/2 a g_i' [lpd >= -50] (1 - d^2 iv)
+// iv comes from the forward (`ivar`, the coefficients its partials kernel used); fixed summation orders, no atomics.
+struct TcFullGrad {
+  const float* g;
+  int bcast;
+  float a, cq, cp, c;   // a, b - a, c - b, c, each times the reduction's 1/B
+};
+__device__ __forceinline__ float tcf_g(const TcFullGrad& t, int j) { return t.bcast ? t.g[0] : t.g[j]; }
+
+__global__ __launch_bounds__(256) void tc_full_bwd_rows_kernel(
+    TcFullGrad tg, const float* __restrict__ z, const float* __restrict__ mu_all, const float* __restrict__ lv_all, int ld,
+    const float* __restrict__ ivar, const float* __restrict__ logqz, const float* __restrict__ lse,
+    const float* __restrict__ sjoint, float* __restrict__ wq, float* __restrict__ dz, int Bt, int row_offset, int D,
+    TcConst c) {
+  __shared__ float raz[4][64];
+  const int j = blockIdx.x, jg = row_offset + j, l = blockIdx.y * 64 + (threadIdx.x & 63);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const bool act = l < D;
+  const float gr = tcf_g(tg, j), cq = tg.cq * gr, cp = tg.cp * gr, lq = logqz[j];
+  const float zj = act ? z[(size_t)j * D + l] : 0.f, ls = act ? lse[(size_t)j * D + l] : 0.f;
+  float az = 0.f;
+#pragma unroll 4
+  for (int i = wid; i < Bt; i += 4) {                  // wave-uniform i: sjoint / log_iw are scalar work
+    const float liw = log_iw(c, jg, i);
+    const float q = cq * expf(sjoint[(size_t)j * Bt + i] - lq);
+    if (blockIdx.y == 0 && lane == 0) wq[(size_t)j * Bt + i] = q;
+    if (act) {
+      const float d = zj - mu_all[(size_t)i * ld + l], iv = ivar[(size_t)i * D + l];
+      const float lp = -0.5f * (lv_all[(size_t)i * ld + l] + d * d * iv) - kHalfLog2Pi;
+      if (lp >= kFloor) az -= (q + cp * expf(lp + liw - ls)) * d * iv;
+    }
+  }
+  raz[wid][lane] = az;
+  __syncthreads();
+  if (wid == 0 && act) {
+    float v = (raz[0][lane] + raz[1][lane]) + (raz[2][lane] + raz[3][lane]);
+    const float m = mu_all[(size_t)jg * ld + l], lv = lv_all[(size_t)jg * ld + l], d = zj - m;
+    if (diag_lp(zj, m, lv) >= kFloor) v += tg.a * gr * (-d * expf(-lv));
+    if (prior_lp(zj) >= kFloor) v += tg.c * gr * zj;
+    dz[(size_t)j * D + l] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void tc_full_bwd_cols_kernel(
+    TcFullGrad tg, const float* __restrict__ z, const float* __restrict__ mu_all, const float* __restrict__ lv_all, int ld,
+    const float* __restrict__ ivar, const float* __restrict__ lse, const float* __restrict__ wq,
+    float* __restrict__ dmu_all, float* __restrict__ dlv_all, int Bl, int Bt, int row_offset, int D, TcConst c) {
+  __shared__ float ram[4][64], rav[4][64];
+  const int i = blockIdx.x, l = blockIdx.y * 64 + (threadIdx.x & 63);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const bool act = l < D;
+  const float mi = act ? mu_all[(size_t)i * ld + l] : 0.f, lvi = act ? lv_all[(size_t)i * ld + l] : 0.f;
+  const float iv = act ? ivar[(size_t)i * D + l] : 0.f;
+  float am = 0.f, av = 0.f;
+#pragma unroll 2
+  for (int j = wid; j < Bl; j += 4) {
+    const float cp = tg.cp * tcf_g(tg, j), q = wq[(size_t)j * Bt + i], liw = log_iw(c, row_offset + j, i);
+    if (act) {
+      const float d = z[(size_t)j * D + l] - mi;
+      const float lp = -0.5f * (lvi + d * d * iv) - kHalfLog2Pi;
+      if (lp >= kFloor) {
+        const float G = q + cp * expf(lp + liw - lse[(size_t)j * D + l]);
+        am += G * d * iv;
+        av += G * (1.f - d * d * iv);
+      }
+    }
+  }
+  ram[wid][lane] = am, rav[wid][lane] = av;
+  __syncthreads();
+  if (wid == 0 && act) {
+    float vm = (ram[0][lane] + ram[1][lane]) + (ram[2][lane] + ram[3][lane]);
+    float vl = -0.5f * ((rav[0][lane] + rav[1][lane]) + (rav[2][lane] + rav[3][lane]));
+    // log q(z_i|x_i) of this rank's own rows: column i is local row i - row_offset
+    if (i >= row_offset && i < row_offset + Bl) {
+      const int jl = i - row_offset;
+      const float zz = z[(size_t)jl * D + l], d = zz - mi, e = expf(-lvi), ga = tg.a * tcf_g(tg, jl);
+      if (diag_lp(zz, mi, lvi) >= kFloor) vm += ga * d * e, vl += ga * (-0.5f) * (1.f - d * d * e);
+    }
+    dmu_all[(size_t)i * ld + l] = vm;
+    dlv_all[(size_t)i * ld + l] = vl;
   }
 }
 
@@ -579,10 +714,12 @@ size_t itcv_tc_fwd_workspace(int Bl, int Bt, int D) {
 }  // extern "C"
 static int tc_fwd_impl(const float* z, const float* mu_all, const float* logvar, float* prodm, float* logqz, float* lse,
                        float* sjoint, int Bl, int Bt, int row_offset, int D, int64_t dataset_size, int flags, void* ws,
-                       size_t ws_bytes, const TcKlOut& kk, void* stream) {
+                       size_t ws_bytes, const TcKlOut& kk, void* stream, int ldm = 0, float* ivar = nullptr,
+                       const TcFullOut& ff = TcFullOut{}) {
   ITCV_REQUIRE(z && mu_all && logvar && prodm && logqz && lse && sjoint && Bl > 0 && D > 0, "itcv_tc_fwd");
   ITCV_REQUIRE(row_offset >= 0 && row_offset + Bl <= Bt, "itcv_tc_fwd(rows must lie inside the global batch)");
   if (D > 64 * kTcDLMax) return fail("%s: latent size %lld > 512 is not supported", "itcv_tc_fwd", D);
+  if (ldm == 0) ldm = D;
   TcConst c;
   if (int e = make_const("itcv_tc_fwd", Bt, dataset_size, &c)) return e;
   const int nch = tc_chunks(Bt);
@@ -600,7 +737,7 @@ static int tc_fwd_impl(const float* z, const float* mu_all, const float* logvar,
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tc_fwd_part_kernel<DL, V, E, W>),                 \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
     hipLaunchKernelGGL((tc_fwd_part_kernel<DL, V, E, W>), grid, block, lds, st, z, mu_all, logvar, pmax, psum,   \
-                       sjoint, Bt, row_offset, D, nch, c);                                                      \
+                       sjoint, Bt, row_offset, D, nch, c, ldm, ivar);                                           \
   } while (0)
 #define ITCV_TC_DL(V, E, W)                \
   do {                                     \
@@ -621,9 +758,9 @@ static int tc_fwd_impl(const float* z, const float* mu_all, const float* logvar,
 #undef ITCV_TC_PART
   ITCV_CHECK_LAUNCH("itcv_tc_fwd(partials)");
   if (mws)
-    hipLaunchKernelGGL(tc_fwd_finish_kernel<true>, dim3(Bl), block, 0, st, pmax, psum, sjoint, prodm, logqz, lse, Bt, D, nch, c, kk);
+    hipLaunchKernelGGL(tc_fwd_finish_kernel<true>, dim3(Bl), block, 0, st, pmax, psum, sjoint, prodm, logqz, lse, Bt, D, nch, c, kk, ff);
   else
-    hipLaunchKernelGGL(tc_fwd_finish_kernel<false>, dim3(Bl), block, 0, st, pmax, psum, sjoint, prodm, logqz, lse, Bt, D, nch, c, kk);
+    hipLaunchKernelGGL(tc_fwd_finish_kernel<false>, dim3(Bl), block, 0, st, pmax, psum, sjoint, prodm, logqz, lse, Bt, D, nch, c, kk, ff);
   ITCV_CHECK_LAUNCH("itcv_tc_fwd(finish)");
   return 0;
 }
@@ -691,6 +828,67 @@ int itcv_tc_kl_bwd(const float* g, const float* z, const float* mu_all, const fl
   const float r = reduction == 2 ? 1.f / (float)Bl : 1.f;
   return tc_bwd_impl(TcGrad{g, reduction ? 1 : 0, coef_tc * r, coef_kl * r}, z, mu_all, logvar, logqz, lse, sjoint, dz, dmu_all,
                      dlogvar, Bl, Bt, row_offset, D, dataset_size, ITCV_TC_LIVE, ws, ws_bytes, stream);
+}
+
+size_t itcv_tc_full_fwd_workspace(int Bl, int Bt, int D) { return itcv_tc_fwd_workspace(Bl, Bt, D); }
+size_t itcv_tc_full_bwd_workspace(int Bl, int Bt) { return itcv_tc_bwd_workspace(Bl, Bt); }
+
+// host-side checks shared by the full form's forward and backward (nothing is launched on a failure)
+static int tc_full_check(const char* name, bool ptrs, int Bl, int Bt, int row_offset, int D, int ld, int reduction) {
+  if (!ptrs) return fail("%s: a required pointer is NULL", name);
+  if (Bl <= 0 || D <= 0) return fail("%s: Bl = %lld and D = %lld must be positive", name, Bl, D);
+  if (D > 64 * kTcDLMax) return fail("%s: latent size %lld > 512 is not supported", name, D);
+  if (row_offset < 0 || row_offset + Bl > Bt)
+    return fail("%s: rows must lie inside the global batch (row_offset = %lld, Bt = %lld)", name, row_offset, Bt);
+  if (ld < D) return fail("%s: row stride %lld of mu_all / logvar_all is below D = %lld", name, ld, D);
+  if (reduction < 0 || reduction > 2) return fail("%s: reduction %lld is not 0 (none), 1 (sum) or 2 (mean)", name, reduction);
+  return 0;
+}
+
+int itcv_tc_full_fwd(const float* z, const float* mu_all, const float* logvar_all, int ld, float* out, float* rows,
+                     float* comps, float* prodm, float* logqz, float* lse, float* sjoint, float* ivar, int Bl, int Bt,
+                     int row_offset, int D, int64_t dataset_size, float alpha, float beta, float gamma, int reduction,
+                     void* ws, size_t ws_bytes, void* stream) {
+  if (int e = tc_full_check("itcv_tc_full_fwd",
+                            z && mu_all && logvar_all && out && (reduction == 0 || rows) && prodm && logqz && lse && sjoint &&
+                                ivar && ws,
+                            Bl, Bt, row_offset, D, ld, reduction))
+    return e;
+  const size_t off = (size_t)row_offset * ld;
+  const TcFullOut ff{z, mu_all + off, logvar_all + off, reduction == 0 ? out : rows, comps, ld, Bl, alpha, beta, gamma};
+  if (int e = tc_fwd_impl(z, mu_all, logvar_all, prodm, logqz, lse, sjoint, Bl, Bt, row_offset, D, dataset_size, 0, ws,
+                          ws_bytes, TcKlOut{nullptr, nullptr, nullptr, 0.f, 0.f}, stream, ld, ivar, ff))
+    return e;
+  if (reduction) {
+    hipLaunchKernelGGL(rows_reduce_kernel, dim3(1), dim3(256), 0, S(stream), rows, out, Bl, reduction == 2 ? 1 : 0, 1.f);
+    ITCV_CHECK_LAUNCH("itcv_tc_full_fwd(reduce)");
+  }
+  return 0;
+}
+
+int itcv_tc_full_bwd(const float* g, const float* z, const float* mu_all, const float* logvar_all, int ld,
+                     const float* logqz, const float* lse, const float* sjoint, const float* ivar, float* dz, float* dmu_all,
+                     float* dlogvar_all, int Bl, int Bt, int row_offset, int D, int64_t dataset_size, float alpha,
+                     float beta, float gamma, int reduction, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = tc_full_check("itcv_tc_full_bwd",
+                            g && z && mu_all && logvar_all && logqz && lse && sjoint && ivar && dz && dmu_all && dlogvar_all,
+                            Bl, Bt, row_offset, D, ld, reduction))
+    return e;
+  ITCV_REQUIRE(ws && ws_bytes >= itcv_tc_full_bwd_workspace(Bl, Bt), "itcv_tc_full_bwd(workspace)");
+  TcConst c;
+  if (int e = make_const("itcv_tc_full_bwd", Bt, dataset_size, &c)) return e;
+  const float r = reduction == 2 ? 1.f / (float)Bl : 1.f;
+  const TcFullGrad tg{g, reduction ? 1 : 0, alpha * r, (beta - alpha) * r, (gamma - beta) * r, gamma * r};
+  float* wq = static_cast<float*>(ws);
+  hipStream_t st = S(stream);
+  const int lch = cdiv(D, 64);
+  hipLaunchKernelGGL(tc_full_bwd_rows_kernel, dim3(Bl, lch), dim3(256), 0, st, tg, z, mu_all, logvar_all, ld, ivar, logqz,
+                     lse, sjoint, wq, dz, Bt, row_offset, D, c);
+  ITCV_CHECK_LAUNCH("itcv_tc_full_bwd(rows)");
+  hipLaunchKernelGGL(tc_full_bwd_cols_kernel, dim3(Bt, lch), dim3(256), 0, st, tg, z, mu_all, logvar_all, ld, ivar, lse, wq,
+                     dmu_all, dlogvar_all, Bl, Bt, row_offset, D, c);
+  ITCV_CHECK_LAUNCH("itcv_tc_full_bwd(cols)");
+  return 0;
 }
 
 int itcv_kl_loss_fwd(const float* logvar, const float* mu, float* out, int B, int D, int reduction, float scale, void* stream) {

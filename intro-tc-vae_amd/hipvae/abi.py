@@ -119,6 +119,10 @@ SIGNATURES = {
     "itcv_tc_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, i32, i32, i32, i32, i64, i32, p, sz, p]),
     "itcv_tc_kl_fwd": (i32, [p] * 9 + [i32, i32, i32, i32, i64, f32, f32, i32, p, sz, p]),
     "itcv_tc_kl_bwd": (i32, [p] * 10 + [i32, i32, i32, i32, i64, f32, f32, i32, p, sz, p]),
+    "itcv_tc_full_fwd_workspace": (sz, [i32, i32, i32]),
+    "itcv_tc_full_fwd": (i32, [p, p, p, i32] + [p] * 8 + [i32, i32, i32, i32, i64, f32, f32, f32, i32, p, sz, p]),
+    "itcv_tc_full_bwd_workspace": (sz, [i32, i32]),
+    "itcv_tc_full_bwd": (i32, [p, p, p, p, i32] + [p] * 7 + [i32, i32, i32, i32, i64, f32, f32, f32, i32, p, sz, p]),
     "itcv_kl_loss_fwd": (i32, [p, p, p, i32, i32, i32, f32, p]),
     "itcv_kl_loss_bwd": (i32, [p, p, p, p, p, i32, i32, i32, f32, p]),
     "itcv_diag_logdensity_rows": (i32, [p, p, p, p, p, i32, i32, p]),

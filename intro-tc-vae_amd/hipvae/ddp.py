@@ -6,7 +6,9 @@ full-batch reference step is exactly:
   1. gradient averaging of the half being trained (one flat all-reduce per phase);
   2. the means of the WHOLE global batch for the TC estimator (all-gather of mu [B_loc,D] ->
      [B_glob,D]; its adjoint is a reduce-scatter of dmu) -- logvar stays local because of the
-     reference's transposed-variance indexing (ops.py:81);
+     reference's transposed-variance indexing (ops.py:81).  The full decomposition loss
+     (solvers/tc.py:91-144) takes the variance of component i, so it gathers mu and logvar packed
+     as one [B_loc,2D] tensor: still one collective each way;
   3. full-batch BatchNorm statistics (Sync-BN: all-reduce of per-channel fp64 moments).
 Everything else (reconstruction, KL, exp-ELBO terms) is per-sample.
 """
@@ -85,6 +87,40 @@ class _AllGatherRows(Function):
 def all_gather_rows(x):
     c = get()
     return x if c is None else _AllGatherRows.apply(x, c.group)
+
+
+class _AllGatherPacked(Function):
+    """(mu, logvar) [B_loc, D] each -> the two halves of ONE all-gathered [B_glob, 2D] tensor (rank-major rows): one
+    collective for both.  Backward: one reduce-scatter(sum) of the packed gradient (in place when the consumer returns
+    the two gradients as the halves of one [B_glob, 2D] tensor, as hipvae.functional.TcFullFn does)."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, group):
+        ctx.group = group
+        D = mu.shape[1]
+        packed = torch.cat([mu, logvar], dim=1)
+        out = _AllGatherRows.forward(ctx, packed, group)
+        return out[:, :D], out[:, D:]
+
+    @staticmethod
+    def backward(ctx, g_mu, g_lv):
+        D = g_mu.shape[1] if g_mu is not None else g_lv.shape[1]
+        g_mu = torch.zeros_like(g_lv) if g_mu is None else g_mu
+        g_lv = torch.zeros_like(g_mu) if g_lv is None else g_lv
+        if (g_mu.stride() == g_lv.stride() == (2 * D, 1)
+                and g_lv.data_ptr() == g_mu.data_ptr() + D * g_mu.element_size()):
+            g = g_mu.as_strided((g_mu.shape[0], 2 * D), (2 * D, 1))
+        else:
+            g = torch.cat([g_mu, g_lv], dim=1)
+        gl, _ = _AllGatherRows.backward(ctx, g)
+        return gl[:, :D], gl[:, D:], None
+
+
+def all_gather_mu_logvar(mu, logvar):
+    """(mu_all, logvar_all) of the whole global batch for the full decomposition loss: one all-gather of the packed
+    [B_loc, 2D] pair (halves of one [B_glob, 2D] tensor).  Single rank: (mu, logvar) themselves, no copy."""
+    c = get()
+    return (mu, logvar) if c is None else _AllGatherPacked.apply(mu, logvar, c.group)
 
 
 def row_offset(local_rows):

@@ -1126,6 +1126,79 @@ class TcKlFn(Function):
         return dz, dmu, dlv, None, None, None, None, None
 
 
+def _packed_pair(a, b):
+    """Row stride shared by two [Bt, D] column operands: D for two dense tensors, 2D for the two halves of one dense
+    [Bt, 2D] tensor (a packed all-gather, read in place); None for any other layout."""
+    Bt, D = a.shape
+    if a.is_contiguous() and b.is_contiguous():
+        return D
+    if (a.stride() == b.stride() == (2 * D, 1) and b.data_ptr() == a.data_ptr() + D * a.element_size()
+            and a.dtype == b.dtype == F32):
+        return 2 * D
+    return None
+
+
+class TcFullFn(Function):
+    """Per sample alpha*(logqcx - logqz) + beta*(logqz - prodm) + gamma*(prodm - logpz): the full decomposition loss of
+    solvers/tc.py:91-144 (ops.py:24-29 density, variance of component i, stratified sampler) with the reduction,
+    fused into the estimator's launches (forward: partials, finish [, reduce]; backward: rows, columns).  ``mu_all`` /
+    ``logvar_all``: [Bt, D] column operands, two dense tensors or the halves of one packed [Bt, 2D] tensor (their
+    gradients then come back as the halves of one packed tensor too).  Second output: the per-sample (mi, tc, dwkl)
+    [3, Bl], no gradient."""
+
+    @staticmethod
+    def forward(ctx, z, mu_all, logvar_all, dataset_size, row_offset, alpha, beta, gamma, reduction):
+        z = _f32c(z)
+        if not (mu_all.is_cuda and logvar_all.is_cuda):
+            raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+        ld = _packed_pair(mu_all, logvar_all)
+        if ld is None or ld == mu_all.shape[1]:
+            mu_all, logvar_all = _f32c(mu_all), _f32c(logvar_all)
+            ld = mu_all.shape[1]
+        Bl, D = z.shape
+        Bt = mu_all.shape[0]
+        if tuple(mu_all.shape) != (Bt, D) or tuple(logvar_all.shape) != (Bt, D):
+            raise ValueError(f"mu_all / logvar_all must be [Bt, {D}] (got {tuple(mu_all.shape)}, {tuple(logvar_all.shape)})")
+        dev = z.device
+        out = torch.empty((Bl,) if reduction == 0 else (), dtype=F32, device=dev)
+        rows = torch.empty((Bl,), dtype=F32, device=dev) if reduction else None
+        comps = torch.empty((3, Bl), dtype=F32, device=dev)
+        prodm = torch.empty((Bl,), dtype=F32, device=dev)
+        logqz = torch.empty((Bl,), dtype=F32, device=dev)
+        lse = torch.empty((Bl, D), dtype=F32, device=dev)
+        sjoint = torch.empty((Bl, Bt), dtype=F32, device=dev)
+        ivar = torch.empty((Bt, D), dtype=F32, device=dev)
+        nws = lib.itcv_tc_full_fwd_workspace(Bl, Bt, D)
+        ws = _ws(nws, dev)
+        call("itcv_tc_full_fwd", ptr(z), mu_all.data_ptr(), logvar_all.data_ptr(), ld, ptr(out), ptr(rows), ptr(comps),
+             ptr(prodm), ptr(logqz), ptr(lse), ptr(sjoint), ptr(ivar), Bl, Bt, int(row_offset), D, int(dataset_size),
+             float(alpha), float(beta), float(gamma), reduction, ptr(ws), nws, stream())
+        ctx.save_for_backward(z, mu_all, logvar_all, logqz, lse, sjoint, ivar)
+        ctx.cfg = (int(dataset_size), int(row_offset), float(alpha), float(beta), float(gamma), reduction, ld)
+        ctx.mark_non_differentiable(comps)
+        return out, comps
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_comps):
+        z, mu_all, logvar_all, logqz, lse, sjoint, ivar = ctx.saved_tensors
+        n, off, a, b, c, reduction, ld = ctx.cfg
+        Bl, D = z.shape
+        Bt = mu_all.shape[0]
+        dz = torch.empty_like(z)
+        if ld == D:
+            dmu, dlv = torch.empty((Bt, D), dtype=F32, device=z.device), torch.empty((Bt, D), dtype=F32, device=z.device)
+        else:                               # one packed [Bt, 2D] gradient: the gather's adjoint reduce-scatters it in place
+            dpk = torch.empty((Bt, 2 * D), dtype=F32, device=z.device)
+            dmu, dlv = dpk[:, :D], dpk[:, D:]
+        nws = lib.itcv_tc_full_bwd_workspace(Bl, Bt)
+        ws = _ws(nws, z.device)
+        call("itcv_tc_full_bwd", ptr(_f32c(g)), ptr(z), mu_all.data_ptr(), logvar_all.data_ptr(), ld, ptr(logqz), ptr(lse),
+             ptr(sjoint), ptr(ivar), ptr(dz), dmu.data_ptr(), dlv.data_ptr(), Bl, Bt, off, D, n, a, b, c, reduction,
+             ptr(ws), nws, stream())
+        return dz, dmu, dlv, None, None, None, None, None, None
+
+
 class ReconLossFn(Function):
     """scale * ops.reconstruction_loss(x, recon, loss_type, reduction) (ops.py:188-236 + the hook's beta): two launches
     forward, one backward; x is a constant."""

@@ -132,6 +132,27 @@ def tc_kl_loss(z, mu, logvar, dataset_size, beta, reduce="mean", mu_all=None, ro
                            1.0, 2 if reduce == "mean" else 0)
 
 
+def tc_full_loss(z, mu, logvar, dataset_size, alpha=1.0, beta=1.0, gamma=1.0, reduce="mean", mu_all=None,
+                 logvar_all=None, row_offset=0):
+    """alpha * mi + beta * tc + gamma * dwkl per sample: the full decomposition loss of solvers/tc.py:91-144 (the
+    reference's is alpha = gamma = 1) -- ops.py:24-29 density, variance of component i, stratified sampler -- fused into
+    the estimator's launches (3 forward, 2 backward), with gradients.  ``reduce`` as in the reference: 'mean', else per
+    sample.  ``mu_all`` / ``logvar_all`` / ``row_offset``: the data-parallel extension (the whole global batch's means
+    and log-variances, e.g. from ``hipvae.ddp.all_gather_mu_logvar``, and this rank's first global row); the local
+    ``mu`` / ``logvar`` are then not read."""
+    return _tc_full(z, mu, logvar, dataset_size, alpha, beta, gamma, reduce, mu_all, logvar_all, row_offset)[0]
+
+
+def _tc_full(z, mu, logvar, dataset_size, alpha, beta, gamma, reduce, mu_all=None, logvar_all=None, row_offset=0):
+    """tc_full_loss and the per-sample (mi, tc, dwkl) [3, B] of the same launches (no gradient)."""
+    if (mu_all is None) != (logvar_all is None):
+        raise ValueError("mu_all and logvar_all are given together")
+    if mu_all is None:
+        mu_all, logvar_all = mu, logvar
+    return HF.TcFullFn.apply(z, mu_all, logvar_all, int(dataset_size), int(row_offset), float(alpha), float(beta),
+                             float(gamma), 2 if reduce == "mean" else 0)
+
+
 def tc_components(z, mu, logvar, dataset_size, *, var_from_row=True, eps_density=True, weighted=False):
     """Fused ops.py:80-84 + :92-115: returns (logqz_prodmarginals [B], log_qz [B]) of the stratified
     (default) or weighted sampler, for either density flavour / variance orientation.  No grad."""
@@ -142,12 +163,18 @@ def tc_components(z, mu, logvar, dataset_size, *, var_from_row=True, eps_density
     return prodm, logqz
 
 
-def tc_decomposition(z, mu, logvar, dataset_size):
-    """solvers/tc.py:104-121 per-sample (mi, tc, dwkl): the dead-code decomposition of the reference
-    (un-eps'd density, variance indexed by component), offered as metrics."""
+def tc_decomposition(z, mu, logvar, dataset_size, mu_all=None, logvar_all=None, row_offset=0):
+    """solvers/tc.py:104-121 per-sample (mi, tc, dwkl): the decomposition of the reference's full hook
+    (un-eps'd density, variance indexed by component), offered as metrics.  ``mu_all`` / ``logvar_all`` /
+    ``row_offset``: the data-parallel extension, as in ``tc_full_loss``."""
+    if (mu_all is None) != (logvar_all is None):
+        raise ValueError("mu_all and logvar_all are given together")
     with torch.no_grad():
         logq_cx, logpz = HF.diag_logdensity_rows(z, mu, logvar)
-        prodm, logqz, _ = HF.tc_components(z, mu, logvar, dataset_size, 0, 0)
+        if mu_all is None:
+            prodm, logqz, _ = HF.tc_components(z, mu, logvar, dataset_size, 0, 0)
+        else:
+            prodm, logqz, _ = HF.tc_components(z, mu_all, logvar_all, dataset_size, row_offset, 0)
     return logq_cx - logqz, logqz - prodm, prodm - logpz
 
 

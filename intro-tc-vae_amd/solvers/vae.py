@@ -177,7 +177,8 @@ class VAESolver:
             return self._device_step(real)
         # the optimiser hyper-parameters are scalar kernel arguments frozen into a captured graph: the update specs are
         # part of its key, so a scheduler or manual decay of param_groups[0]["lr"] re-captures instead of being ignored
-        key = (tuple(real.shape), real.dtype, self.conv_math) + specs
+        # the TC solvers' KL hook ("simple" | "full") selects different kernels: a switch re-captures too
+        key = (tuple(real.shape), real.dtype, self.conv_math) + specs + (getattr(self, "kl_loss", None),)
         from hipvae.functional import bump_weight_epoch
         graphs = self.__dict__.setdefault("_graphs", {})
         ent = graphs.get(key)
