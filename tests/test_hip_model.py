@@ -766,8 +766,9 @@ def test_batched_passes_equal_unbatched_step():
         assert rel_err(out[True][2][k], v) < 1e-5, k
 
 
-def test_group_weight_packing_equals_per_layer_packing():
-    """After an optimiser step the split-bf16 conv operands of a whole network are re-packed by one launch per
+@pytest.mark.parametrize("math", ["bf16x3", "f16x3"])
+def test_group_weight_packing_equals_per_layer_packing(math):
+    """After an optimiser step the split-bf16 / fp16 conv operands of a whole network are re-packed by one launch per
     direction (device-resident descriptor table): three intro-TC steps at the benchmark shape are bit-identical to
     packing layer by layer, and the batched path was really taken."""
     import models
@@ -786,7 +787,7 @@ def test_group_weight_packing_equals_per_layer_packing():
             model = models.SoftIntroVAE(arch="res", **C2)
             model.load_state_dict(init)
             model = model.to(dev()).train()
-            solver = make_solver("intro_tc", model, hp, math="bf16x3")
+            solver = make_solver("intro_tc", model, hp, math=math)
             solver.batch_size = 8
             res = []
             for s in range(3):

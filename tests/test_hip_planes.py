@@ -227,9 +227,10 @@ def test_f16_planes_reconstruct(HF, magnitude):
 
 @pytest.mark.parametrize("case", PLANES_CASES[:7] + PLANES_CASES[7:9] + PERSIST_CASES[:2])
 def test_f16_planes_conv_vs_fp64(HF, case):
-    """Forward and data-gradient on fp16 planes (band, persistent band, 128-pixel kernels): within 1.5e-6 of the result
-    scale of an fp64 convolution -- the level of the exact-fp32 MFMA kernel (fp32 accumulation), 30x below bf16x3 -- with
-    the data-gradient's input at gradient-like magnitude (1e-7)."""
+    """Forward and data-gradient on fp16 planes (one-tile band, wide-image and 128-pixel kernels): within 1.5e-6 of the
+    result scale of an fp64 convolution -- the level of the exact-fp32 MFMA kernel (fp32 accumulation), 30x below bf16x3 --
+    with the data-gradient's input at gradient-like magnitude (1e-7).  B is capped at 6, so the PERSIST_CASES entries run
+    the one-tile band kernel with split-K, not the persistent kernel; test_hip_f16x3.py covers that one at full B."""
     B, Ci, H, W, Co, up2 = case
     B = min(B, 6)
     g = torch.Generator().manual_seed(sum(case[:5]))
