@@ -4,6 +4,8 @@
 // Replaces /root/reference/models.py:37-38,48-49,214-216,225,271,284-286,291.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace itcv {
@@ -36,6 +38,22 @@ struct BnFinal {   // arguments of the fused single-launch path (splits == 1)
   float* mean;
   float* rstd;
 };
+
+// The one finalisation of the batch statistics: channel sums -> (mean, biased variance) -> mean_c / rstd_c, and the update
+// of the running buffers at channel c (either may be null; the running variance takes the unbiased estimate).
+__device__ __forceinline__ void bn_finalize(double s1, double s2, double count, float eps, float momentum,
+                                            float* running_mean, float* running_var, int c, float& mean_c, float& rstd_c) {
+  const double m = s1 / count;
+  double var = s2 / count - m * m;
+  if (var < 0.0) var = 0.0;
+  mean_c = (float)m;
+  rstd_c = (float)(1.0 / sqrt(var + (double)eps));
+  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
+  if (running_var) {
+    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+  }
+}
 
 template <bool FUSED>
 __global__ __launch_bounds__(kRedThreads) void bn_moments_partial(const float* __restrict__ x,
@@ -72,16 +90,7 @@ __global__ __launch_bounds__(kRedThreads) void bn_moments_partial(const float* _
   s2 = block_sum(s2, scratch);
   if (threadIdx.x == 0) {
     if (FUSED) {   // one block owns the whole channel: finalise here, no second launch
-      const double m = s1 / f.count;
-      double var = s2 / f.count - m * m;
-      if (var < 0.0) var = 0.0;
-      f.mean[c] = (float)m;
-      f.rstd[c] = (float)(1.0 / sqrt(var + (double)f.eps));
-      if (f.running_mean) f.running_mean[c] = (1.f - f.momentum) * f.running_mean[c] + f.momentum * (float)m;
-      if (f.running_var) {
-        const double unbiased = f.count > 1.0 ? var * f.count / (f.count - 1.0) : var;
-        f.running_var[c] = (1.f - f.momentum) * f.running_var[c] + f.momentum * (float)unbiased;
-      }
+      bn_finalize(s1, s2, f.count, f.eps, f.momentum, f.running_mean, f.running_var, c, f.mean[c], f.rstd[c]);
       if (c == 0 && f.nbt) f.nbt[0] += 1;
     } else {
       part[((size_t)s * 2 + 0) * C + c] = s1;
@@ -104,16 +113,7 @@ __global__ void bn_finalize_kernel(const double* __restrict__ sums, double count
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c == 0 && nbt) nbt[0] += 1;
   if (c >= C) return;
-  const double m = sums[c] / count;
-  double var = sums[C + c] / count - m * m;
-  if (var < 0.0) var = 0.0;
-  mean[c] = (float)m;
-  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-  if (running_var) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
+  bn_finalize(sums[c], sums[C + c], count, eps, momentum, running_mean, running_var, c, mean[c], rstd[c]);
 }
 
 // statistics from the per-tile sums a conv epilogue wrote (fp32 per 256-value tile, folded here in fp64): block per channel
@@ -130,42 +130,12 @@ __global__ __launch_bounds__(256) void bn_tile_stats_finalize_kernel(const float
   s1 = block_sum(s1, scratch);
   s2 = block_sum(s2, scratch);
   if (threadIdx.x == 0) {
-    const double m = s1 / count;
-    double var = s2 / count - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[c] = (float)m;
-    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-    if (running_var) {
-      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
+    bn_finalize(s1, s2, count, eps, momentum, running_mean, running_var, c, mean[c], rstd[c]);
     if (c == 0 && nbt) nbt[0] += 1;
   }
 }
 
-// single-rank fast path: fold the partial sums and finalise in one launch
-__global__ void bn_combine_finalize_kernel(const double* __restrict__ part, int splits, double count, float eps,
-                                           float momentum, float* running_mean, float* running_var, int64_t* nbt,
-                                           float* mean, float* rstd, int C) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c == 0 && nbt) nbt[0] += 1;
-  if (c >= C) return;
-  const double s1 = fold_strided(0.0, part + c, (size_t)2 * C, splits);
-  const double s2 = fold_strided(0.0, part + C + c, (size_t)2 * C, splits);
-  const double m = s1 / count;
-  double var = s2 / count - m * m;
-  if (var < 0.0) var = 0.0;
-  mean[c] = (float)m;
-  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-  if (running_var) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-  }
-}
-
-// BatchNorm groups, sliced statistics: fold every group's partial sums and finalise the groups IN ORDER (running buffers)
+// sliced statistics: fold every group's partial sums and finalise the groups IN ORDER (running buffers); one group: G = 1
 __global__ void bn_combine_finalize_groups_kernel(const double* __restrict__ part, int splits, int G, double count, float eps,
                                                   float momentum, float* running_mean, float* running_var, int64_t* nbt,
                                                   float* mean, float* rstd, int C) {
@@ -176,18 +146,11 @@ __global__ void bn_combine_finalize_groups_kernel(const double* __restrict__ par
     const double* pg = part + (size_t)g * splits * 2 * C;
     const double s1 = fold_strided(0.0, pg + c, (size_t)2 * C, splits);
     const double s2 = fold_strided(0.0, pg + C + c, (size_t)2 * C, splits);
-    const double m = s1 / count;
-    double var = s2 / count - m * m;
-    if (var < 0.0) var = 0.0;
-    mean[(size_t)g * C + c] = (float)m;
-    rstd[(size_t)g * C + c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
-    if (running_var) {
-      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    }
+    bn_finalize(s1, s2, count, eps, momentum, running_mean, running_var, c, mean[(size_t)g * C + c], rstd[(size_t)g * C + c]);
   }
 }
+// backward: fold every group's partial sums into dsums [G][2C] and (optionally) the parameter gradients, which add up over
+// the groups in order
 __global__ void bn_combine_param_groups_kernel(const double* __restrict__ part, double* __restrict__ dsums, int C, int splits,
                                                int G, float* dgamma, float* dbeta, int accumulate) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -203,19 +166,6 @@ __global__ void bn_combine_param_groups_kernel(const double* __restrict__ part, 
   }
   if (dbeta) dbeta[c] = db;
   if (dgamma) dgamma[c] = dg;
-}
-
-// backward: fold the partial sums into dsums and (optionally) the parameter gradients
-__global__ void bn_combine_param_kernel(const double* __restrict__ part, double* __restrict__ dsums, int C,
-                                        int splits, float* dgamma, float* dbeta, int accumulate) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const double s1 = fold_strided(0.0, part + c, (size_t)2 * C, splits);
-  const double s2 = fold_strided(0.0, part + C + c, (size_t)2 * C, splits);
-  dsums[c] = s1;
-  dsums[C + c] = s2;
-  if (dbeta) dbeta[c] = (accumulate ? dbeta[c] : 0.f) + (float)s1;
-  if (dgamma) dgamma[c] = (accumulate ? dgamma[c] : 0.f) + (float)s2;
 }
 
 __global__ void bn_eval_stats_kernel(const float* rm, const float* rv, float eps, float* mean, float* rstd, int C) {
@@ -318,7 +268,7 @@ __device__ __forceinline__ void store_planes_wave(u32x4* __restrict__ planes, si
 }
 
 // F16: the planes are fp16 hi / lo of the output with scale 1 (activations are O(1); common.h), record behind plane 1.
-template <int POOL, int NS, bool STATS, bool STRIP = true, bool F16 = false>
+template <int POOL, int NS, bool STATS, bool F16 = false>
 __global__ __launch_bounds__(256) void bn_act_fwd_planes_kernel(
     const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ skip,
@@ -338,7 +288,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_planes_kernel(
   }
   __shared__ float s_mean[STATS ? kStatCh : 1], s_rstd[STATS ? kStatCh : 1];
   constexpr int PX = POOL ? 2 : 4;                      // output pixels per thread
-  __shared__ u32x4 strips[STRIP ? 4 : 1][STRIP ? 64 * PX : 1];
+  __shared__ u32x4 strips[4][64 * PX];
   const int HW = H * W, C8 = C >> 3;
   const int Ho = POOL ? H / 2 : H, Wo = POOL ? W / 2 : W, HWo = Ho * Wo;
   const uint32_t per_plane = (uint32_t)HWo / PX, total = (uint32_t)B * C8 * per_plane;
@@ -356,29 +306,21 @@ __global__ __launch_bounds__(256) void bn_act_fwd_planes_kernel(
         const double* part = st.part + (size_t)gz * st.splits * 2 * C;
         const double s1 = fold_strided(0.0, part + c, (size_t)2 * C, st.splits);
         const double s2 = fold_strided(0.0, part + C + c, (size_t)2 * C, st.splits);
-        const double m = s1 / st.count;
-        double var = s2 / st.count - m * m;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)m, rf = (float)(1.0 / sqrt(var + (double)st.eps));
+        float mf, rf;
+        bn_finalize(s1, s2, st.count, st.eps, 0.f, nullptr, nullptr, 0, mf, rf);
         s_mean[threadIdx.x] = mf, s_rstd[threadIdx.x] = rf;
         if (g < (uint32_t)C8 && g * per_plane >= base) {   // image 0, and the group starts inside this block
           st.mean_out[(size_t)gz * C + c] = mf, st.rstd_out[(size_t)gz * C + c] = rf;
           if (gz == 0) {
-            double mg = m, vg = var;
+            double t1 = s1, t2 = s2;
             for (uint32_t gg = 0; gg < G; ++gg) {
               if (gg) {
                 const double* pg = st.part + (size_t)gg * st.splits * 2 * C;
-                const double t1 = fold_strided(0.0, pg + c, (size_t)2 * C, st.splits);
-                const double t2 = fold_strided(0.0, pg + C + c, (size_t)2 * C, st.splits);
-                mg = t1 / st.count;
-                vg = t2 / st.count - mg * mg;
-                if (vg < 0.0) vg = 0.0;
+                t1 = fold_strided(0.0, pg + c, (size_t)2 * C, st.splits);
+                t2 = fold_strided(0.0, pg + C + c, (size_t)2 * C, st.splits);
               }
-              if (st.running_mean) st.running_mean[c] = (1.f - st.momentum) * st.running_mean[c] + st.momentum * (float)mg;
-              if (st.running_var) {
-                const double unbiased = st.count > 1.0 ? vg * st.count / (st.count - 1.0) : vg;
-                st.running_var[c] = (1.f - st.momentum) * st.running_var[c] + st.momentum * (float)unbiased;
-              }
+              float um, ur;   // (not stored: every group's own block records its mean / rstd)
+              bn_finalize(t1, t2, st.count, st.eps, st.momentum, st.running_mean, st.running_var, c, um, ur);
             }
             if (c == 0 && st.nbt) st.nbt[0] += G;
           }
@@ -447,8 +389,8 @@ __global__ __launch_bounds__(256) void bn_act_fwd_planes_kernel(
       split8<NS, F16>(v8, chk[px]);
     }
     const uint32_t cidx0 = base + (threadIdx.x & ~63u);
-    if (STRIP && cidx0 + 64 <= total) {   // whole wave in range (wave-uniform): coalesced plane stores
-      store_planes_wave<PX, NS>(planes, plane_stride, per_plane, (uint32_t)HWo, cidx0, chk, strips[STRIP ? threadIdx.x >> 6 : 0]);
+    if (cidx0 + 64 <= total) {   // whole wave in range (wave-uniform): coalesced plane stores
+      store_planes_wave<PX, NS>(planes, plane_stride, per_plane, (uint32_t)HWo, cidx0, chk, strips[threadIdx.x >> 6]);
     } else {
 #pragma unroll
       for (int px = 0; px < PX; ++px)
@@ -723,7 +665,7 @@ struct BnBwdSumsIn {
 // F16: dx goes out as fp16 hi / lo planes of S dx.  S is the same in every block of every group of the call: each block
 // takes the maxima U, V of the partial pass's mx arrays (see bn_bwd_partial_v4) and maps the bound U (2 + V) just under
 // 2^15; block 0 of group 0 records {S, 1/S} behind plane 1.
-template <int MODE, int NS, bool SUMS, bool STRIP = true, bool F16 = false>
+template <int MODE, int NS, bool SUMS, bool F16 = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_planes(
     const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -778,7 +720,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_planes(
     if (dskip) dskip += g * grp.xs;
   }
   __shared__ float s_m1[SUMS ? kStatCh : 1], s_m2[SUMS ? kStatCh : 1];
-  __shared__ u32x4 strips[STRIP ? 4 : 1][STRIP ? 64 * 4 : 1];
+  __shared__ u32x4 strips[4][64 * 4];
   const uint32_t HW = H * W, C8 = C >> 3, per_plane = HW / 4, total = (uint32_t)B * C8 * per_plane;
   const uint32_t sweep = gridDim.x * blockDim.x, rbase = (gridDim.x - 1 - blockIdx.x) * blockDim.x;
   for (int it = (int)((total + sweep - 1) / sweep) - 1; it >= 0; --it) {
@@ -878,8 +820,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_planes(
       split8<NS, F16>(v8, chk[px], pscale);
     }
     const uint32_t cidx0 = base + (threadIdx.x & ~63u);
-    if (STRIP && cidx0 + 64 <= total) {   // whole wave in range (wave-uniform): coalesced plane stores
-      store_planes_wave<4, NS>(planes, plane_stride, per_plane, HW, cidx0, chk, strips[STRIP ? threadIdx.x >> 6 : 0]);
+    if (cidx0 + 64 <= total) {   // whole wave in range (wave-uniform): coalesced plane stores
+      store_planes_wave<4, NS>(planes, plane_stride, per_plane, HW, cidx0, chk, strips[threadIdx.x >> 6]);
     } else {
 #pragma unroll
       for (int px = 0; px < 4; ++px)
@@ -974,10 +916,6 @@ static inline int grid_for(size_t n, int per_thread = 1) {
   return b < 1 ? 1 : (int)b;
 }
 
-// Plane stores of the apply kernels always go through the wave-private LDS strip (store_planes_wave): measured on one
-// box, whole c2 step, against direct stores: 19.75 -> 19.30 ms.  All BatchNorm groups of a layer are issued together and
-// the apply pass folds the per-slice partial sums itself where a thread block covers whole channel groups (the one-launch-
-// per-group and separate-finalize forms of round 2 were diagnostics and are gone).
 static inline bool bn_fmt_ok(int ns) { return ns == 2 || ns == 3 || ns == ITCV_PLANES_F16X2; }
 static inline int bn_splits(int B, int C, int HW) {
   const size_t total = (size_t)B * HW;
@@ -992,6 +930,210 @@ static inline int bn_splits(int B, int C, int HW) {
   return s;
 }
 
+// ------------------------------------------------------------------ host side: launch plan and dispatch
+// Every BatchNorm entry point builds one BnPlan and hands it to the four launch functions below; which launches a call gets
+// is decided in bn_plan() and nowhere else.  Plane stores of the apply kernels always go through the wave-private LDS strip
+// (store_planes_wave): measured on one box, whole c2 step, against direct stores: 19.75 -> 19.30 ms.
+enum class BnPath {
+  OneBlock,        // splits == 1: one block per channel reduces AND finalises (all groups, in order); planes apply
+  SlicedFold,      // sliced reduce; the planes apply launch folds the slices itself (its blocks cover whole channel groups)
+  SlicedCombine,   // sliced reduce, a combine launch, planes apply (per_plane < 64)
+  Fallback,        // no planes, or a shape the planes kernels do not take: reduce as above (by `splits`), plain apply kernels
+  PerGroup,        // groups > 1 that cannot go out as one launch: one call per group, each with a plan of its own
+  TileStats,       // forward: statistics from the tile sums of the producing conv's epilogue, then the apply pass alone
+};
+struct BnPlan {
+  BnPath path;
+  int G, splits, mode;      // groups (>= 1), slices per channel, 0 plain | 1 pool | 2 up2
+  bool vec, f16;            // float4 backward kernels usable; fp16 planes (the backward records maxima)
+  int per_plane, nmx;       // threads per (image, 8 channels) plane of the apply pass; maxima per array, all groups
+  BnGrp grp;
+  size_t pstride;           // chunks per plane
+  size_t part_doubles;      // workspace: [G][splits][2][C] fp64 partial sums, then (f16, backward) [2][nmx] fp32 maxima
+  size_t ws_need;
+  dim3 rgrid, agrid;        // reduce and apply launches
+};
+
+static inline size_t bn_ws_bytes(int G, int splits, int C, bool maxima) {
+  return (size_t)G * splits * 2 * C * (sizeof(double) + (maxima ? sizeof(float) : 0));
+}
+
+// B, C, H, W: one group.  `ws_bytes`: 0 without a workspace.
+static BnPlan bn_plan(bool bwd, int B, int C, int H, int W, int pool, int up2, int groups, bool planes, int ns,
+                      size_t plane_stride, size_t ws_bytes, bool tile_stats) {
+  BnPlan p{};
+  const bool opool = !bwd && pool;                   // the planes hold the pooled output
+  const int HW = H * W, HWo = opool ? HW / 4 : HW;
+  const size_t n = (size_t)B * C * HW;
+  p.G = groups > 1 ? groups : 1;
+  p.splits = bn_splits(B, C, HW);
+  p.mode = pool ? 1 : (up2 ? 2 : 0);
+  p.vec = W % 4 == 0 && n < (1ull << 31);
+  p.f16 = ns == ITCV_PLANES_F16X2 && (planes || (bwd && groups > 1));
+  p.per_plane = HWo / (opool ? 2 : 4);
+  p.nmx = p.G * p.splits * C;
+  p.grp = BnGrp{n, (size_t)B * C * HWo, pool ? n / 4 : (up2 ? n * 4 : n), (size_t)B * (C / 8) * HWo, C, p.G};
+  p.pstride = plane_stride ? plane_stride : p.grp.ps;
+  p.part_doubles = (size_t)p.G * p.splits * 2 * C;
+  p.ws_need = bn_ws_bytes(p.G, p.splits, C, bwd && p.f16);
+  const bool planes_ok = planes && bn_fmt_ok(ns) && itcv_bn_act_planes_supported(C, H, W, opool) && n < (1ull << 31);
+  if (tile_stats) p.path = groups > 1 ? BnPath::PerGroup : BnPath::TileStats;
+  else if (!planes_ok) p.path = groups > 1 ? BnPath::PerGroup : BnPath::Fallback;
+  else if (p.splits == 1) p.path = BnPath::OneBlock;
+  else if (groups > 1 && ws_bytes < p.ws_need) p.path = BnPath::PerGroup;
+  else p.path = p.per_plane >= 64 ? BnPath::SlicedFold : BnPath::SlicedCombine;
+  // a grouped one-block call touches the workspace only for the maxima (the single-group entry points always asked for it)
+  if (groups > 1 && p.path == BnPath::OneBlock && !(bwd && p.f16)) p.ws_need = 0;
+  p.rgrid = dim3(C, p.splits, p.splits == 1 ? 1 : p.G);
+  if (planes_ok) p.agrid = dim3(grid_for((size_t)B * (C / 8) * p.per_plane), 1, p.G);
+  else p.agrid = dim3(bwd ? grid_for(n, p.vec ? 4 : 1) : grid_for((size_t)B * C * HWo, pool ? 1 : 4));
+  return p;
+}
+
+// The one place where runtime switches become template arguments: f(std::integral_constant<int, v>) for v in [0, N)
+// (0 for anything else); nested for several switches.
+template <int N, typename F>
+static inline void bn_pick(int v, F&& f) {
+  if constexpr (N > 1) {
+    if (v == N - 1) return f(std::integral_constant<int, N - 1>{});
+    return bn_pick<N - 1>(v, f);
+  } else {
+    f(std::integral_constant<int, 0>{});
+  }
+}
+static inline int bn_fmt(int ns) { return ns == ITCV_PLANES_F16X2 ? 2 : (ns == 2 ? 0 : 1); }   // bf16x2 | bf16x3 | f16x2
+
+// statistics of all groups: into mean / rstd / the running buffers, or (SlicedFold) as far as the partial sums
+static int bn_stats_launch(const BnPlan& p, const float* x, int B, int C, int HW, const BnFinal& f, void* ws, size_t ws_bytes,
+                           hipStream_t st, const char* who) {
+  ITCV_REQUIRE(!p.ws_need || (ws && ws_bytes >= p.ws_need), who);
+  double* part = static_cast<double*>(ws);
+  if (p.splits == 1)
+    hipLaunchKernelGGL(bn_moments_partial<true>, p.rgrid, dim3(kRedThreads), 0, st, x, part, B, C, HW, 1, ilog2_exact(HW), f,
+                       p.grp);
+  else
+    hipLaunchKernelGGL(bn_moments_partial<false>, p.rgrid, dim3(kRedThreads), 0, st, x, part, B, C, HW, p.splits,
+                       ilog2_exact(HW), BnFinal{}, p.grp);
+  ITCV_CHECK_LAUNCH(who);
+  if (p.splits > 1 && p.path != BnPath::SlicedFold) {
+    hipLaunchKernelGGL(bn_combine_finalize_groups_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, p.splits, p.G, f.count,
+                       f.eps, f.momentum, f.running_mean, f.running_var, f.nbt, f.mean, f.rstd, C);
+    ITCV_CHECK_LAUNCH(who);
+  }
+  return 0;
+}
+
+// forward apply pass; `fold.part` set: the (planes) launch finalises the statistics from the partial sums itself
+static int bn_fwd_apply_launch(const BnPlan& p, const float* x, const float* mean, const float* rstd, const float* gamma,
+                               const float* beta, const float* skip, float* y, void* planes, int ns, int B, int C, int H, int W,
+                               float slope, int pool, const BnStatsIn& fold, hipStream_t st) {
+  ITCV_REQUIRE((size_t)B * C * H * W < (1ull << 31), "itcv_bn_act_fwd(tensor < 2^31 elements)");
+  if (planes) {
+    ITCV_REQUIRE(bn_fmt_ok(ns) && itcv_bn_act_planes_supported(C, H, W, pool), "itcv_bn_act_fwd(planes)");
+    bn_pick<2>(pool ? 1 : 0, [&](auto pool_c) {
+      bn_pick<3>(bn_fmt(ns), [&](auto fmt_c) {
+        bn_pick<2>(fold.part ? 1 : 0, [&](auto stats_c) {
+          constexpr int POOL = decltype(pool_c)::value, FMT = decltype(fmt_c)::value;
+          constexpr bool STATS = decltype(stats_c)::value != 0;
+          launch_timed((bn_act_fwd_planes_kernel<POOL, FMT == 1 ? 3 : 2, STATS, FMT == 2>), p.agrid, dim3(256), 0, st, x, mean,
+                       rstd, gamma, beta, skip, y, static_cast<u32x4*>(planes), B, C, H, W, slope, fold, p.pstride, p.grp);
+        });
+      });
+    });
+    ITCV_CHECK_LAUNCH("itcv_bn_act_fwd(planes)");
+    return 0;
+  }
+  if (pool) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_bn_act_fwd(pool)");
+  else ITCV_REQUIRE((H * W) % 4 == 0, "itcv_bn_act_fwd(H*W % 4)");
+  const size_t nout = pool ? (size_t)B * C * (H / 2) * (W / 2) : (size_t)B * C * H * W;
+  bn_pick<2>(pool ? 1 : 0, [&](auto pool_c) {
+    hipLaunchKernelGGL(bn_act_fwd_kernel<decltype(pool_c)::value>, p.agrid, dim3(256), 0, st, x, mean, rstd, gamma, beta, skip,
+                       y, C, H, W, nout, slope, ilog2_exact(H * W), ilog2_exact(C) >= 0 ? C - 1 : -1);
+  });
+  ITCV_CHECK_LAUNCH("itcv_bn_act_fwd");
+  return 0;
+}
+
+// backward sums of all groups: into dsums and the parameter gradients, or (SlicedFold) as far as the partial sums; fp16
+// planes: also the per-slice maxima behind the partial sums (see bn_bwd_partial_v4)
+static int bn_bwd_reduce_launch(const BnPlan& p, const float* x, const float* dy, const float* mean, const float* rstd,
+                                const float* gamma, const float* beta, const float* skip, double* dsums, float* dgamma,
+                                float* dbeta, int accumulate, int B, int C, int H, int W, float slope, void* ws, size_t ws_bytes,
+                                hipStream_t st, const char* who) {
+  if (p.mode == 1) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, who);
+  ITCV_REQUIRE(!p.ws_need || (ws && ws_bytes >= p.ws_need), who);
+  ITCV_REQUIRE(!p.f16 || p.vec, "itcv_bn_train_bwd(fp16 planes need W % 4 == 0)");
+  double* part = static_cast<double*>(ws);
+  float* mx = p.f16 ? reinterpret_cast<float*>(part + p.part_doubles) : nullptr;
+  const bool fused = p.vec && p.splits == 1;   // the reduce kernel writes dsums and the parameter gradients itself
+  const BnBwdFinal bf = fused ? BnBwdFinal{dsums, dgamma, dbeta, accumulate} : BnBwdFinal{};
+  bn_pick<3>(p.mode, [&](auto mode_c) {
+    constexpr int MODE = decltype(mode_c)::value;
+    if (!p.vec) {
+      hipLaunchKernelGGL(bn_bwd_partial<MODE>, p.rgrid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta, skip, part,
+                         B, C, H, W, slope, p.splits);
+      return;
+    }
+    bn_pick<2>(fused ? 1 : 0, [&](auto fused_c) {
+      bn_pick<2>(p.f16 ? 1 : 0, [&](auto mx_c) {
+        hipLaunchKernelGGL((bn_bwd_partial_v4<MODE, decltype(fused_c)::value != 0, decltype(mx_c)::value != 0>), p.rgrid,
+                           dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta, skip, part, B, C, H, W, slope, p.splits,
+                           ilog2_exact(W), ilog2_exact(H * W), bf, p.grp, mx, p.nmx);
+      });
+    });
+  });
+  ITCV_CHECK_LAUNCH(who);
+  if (!fused && p.path != BnPath::SlicedFold) {
+    hipLaunchKernelGGL(bn_combine_param_groups_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, dsums, C, p.splits, p.G,
+                       dgamma, dbeta, accumulate);
+    ITCV_CHECK_LAUNCH(who);
+  }
+  return 0;
+}
+
+// backward apply pass; `fold.part` set: the (planes) launch folds the partial sums itself and writes dsums and the
+// parameter gradients.  `mx`: the maxima of the reduce pass (fp16 planes).
+static int bn_bwd_apply_launch(const BnPlan& p, const float* x, const float* dy, const float* mean, const float* rstd,
+                               const float* gamma, const float* beta, const float* skip, const double* dsums, double count,
+                               float* dx, float* dskip, void* dx_planes, int ns, int B, int C, int H, int W, float slope,
+                               const BnBwdSumsIn& fold, const float* mx, hipStream_t st) {
+  ITCV_REQUIRE(x && dy && mean && rstd && gamma && beta && dsums && (dx || dx_planes) && B > 0 && C > 0 && count > 0,
+               "itcv_bn_act_bwd_apply");
+  const int wsh = ilog2_exact(W);
+  if (dx_planes) {
+    ITCV_REQUIRE(bn_fmt_ok(ns) && p.vec && itcv_bn_act_planes_supported(C, H, W, 0), "itcv_bn_act_bwd_apply(planes)");
+    if (ns == ITCV_PLANES_F16X2 && !mx)
+      return fail("%s: fp16 gradient planes take their scale from the maxima of the reduce pass: use itcv_bn_train_bwd",
+                  "itcv_bn_act_bwd_apply");
+    bn_pick<3>(p.mode, [&](auto mode_c) {
+      bn_pick<3>(bn_fmt(ns), [&](auto fmt_c) {
+        bn_pick<2>(fold.part ? 1 : 0, [&](auto sums_c) {
+          constexpr int MODE = decltype(mode_c)::value, FMT = decltype(fmt_c)::value;
+          constexpr bool SUMS = decltype(sums_c)::value != 0;
+          launch_timed((bn_bwd_apply_planes<MODE, FMT == 1 ? 3 : 2, SUMS, FMT == 2>), p.agrid, dim3(256), 0, st, x, dy, mean,
+                       rstd, gamma, beta, skip, SUMS ? static_cast<const double*>(nullptr) : dsums, count, dx, dskip,
+                       static_cast<u32x4*>(dx_planes), B, C, H, W, slope, wsh, fold, p.pstride, p.grp, mx, p.nmx);
+        });
+      });
+    });
+    ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_apply(planes)");
+    return 0;
+  }
+  const size_t n = (size_t)B * C * H * W;
+  bn_pick<3>(p.mode, [&](auto mode_c) {
+    constexpr int MODE = decltype(mode_c)::value;
+    if (p.vec)
+      hipLaunchKernelGGL(bn_bwd_apply_v4<MODE>, p.agrid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, skip, dsums, count,
+                         dx, dskip, C, H, W, (uint32_t)(n / 4), slope, wsh, ilog2_exact(H * W),
+                         ilog2_exact(C) >= 0 ? C - 1 : -1);
+    else
+      hipLaunchKernelGGL(bn_bwd_apply_kernel<MODE>, p.agrid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, skip, dsums,
+                         count, dx, dskip, C, H, W, n, slope);
+  });
+  ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_apply");
+  return 0;
+}
+
 }  // namespace itcv
 
 using namespace itcv;
@@ -1001,13 +1143,13 @@ extern "C" {
 size_t itcv_bn_workspace(int B, int C, int HW) {
   if (B <= 0 || C <= 0 || HW <= 0) return 0;
   // per-slice partial sums (fp64) + the per-slice maxima the backward of the fp16 planes format records (two floats)
-  return (size_t)bn_splits(B, C, HW) * 2 * C * (sizeof(double) + sizeof(float));
+  return bn_ws_bytes(1, bn_splits(B, C, HW), C, true);
 }
 
 int itcv_bn_moments(const float* x, double* sums, int B, int C, int HW, void* ws, size_t ws_bytes, void* stream) {
   ITCV_REQUIRE(x && sums && B > 0 && C > 0 && HW > 0, "itcv_bn_moments");
   const int splits = bn_splits(B, C, HW);
-  ITCV_REQUIRE(ws && ws_bytes >= (size_t)splits * 2 * C * sizeof(double), "itcv_bn_moments(workspace)");
+  ITCV_REQUIRE(ws && ws_bytes >= bn_ws_bytes(1, splits, C, false), "itcv_bn_moments(workspace)");
   double* part = static_cast<double*>(ws);
   hipLaunchKernelGGL(bn_moments_partial<false>, dim3(C, splits), dim3(kRedThreads), 0, S(stream), x, part, B, C, HW,
                      splits, ilog2_exact(HW), BnFinal{}, BnGrp{});
@@ -1021,23 +1163,9 @@ int itcv_bn_train_stats(const float* x, int B, int C, int HW, float eps, float m
                         float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd, void* ws,
                         size_t ws_bytes, void* stream) {
   ITCV_REQUIRE(x && mean && rstd && B > 0 && C > 0 && HW > 0, "itcv_bn_train_stats");
-  const int splits = bn_splits(B, C, HW);
-  ITCV_REQUIRE(ws && ws_bytes >= (size_t)splits * 2 * C * sizeof(double), "itcv_bn_train_stats(workspace)");
-  double* part = static_cast<double*>(ws);
-  if (splits == 1) {
-    const BnFinal f{(double)B * HW, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd};
-    hipLaunchKernelGGL(bn_moments_partial<true>, dim3(C, 1), dim3(kRedThreads), 0, S(stream), x, part, B, C, HW, 1,
-                       ilog2_exact(HW), f, BnGrp{});
-    ITCV_CHECK_LAUNCH("itcv_bn_train_stats(fused)");
-    return 0;
-  }
-  hipLaunchKernelGGL(bn_moments_partial<false>, dim3(C, splits), dim3(kRedThreads), 0, S(stream), x, part, B, C, HW,
-                     splits, ilog2_exact(HW), BnFinal{}, BnGrp{});
-  ITCV_CHECK_LAUNCH("itcv_bn_train_stats");
-  hipLaunchKernelGGL(bn_combine_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, S(stream), part, splits,
-                     (double)B * HW, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, C);
-  ITCV_CHECK_LAUNCH("itcv_bn_train_stats(finalize)");
-  return 0;
+  const BnPlan p = bn_plan(false, B, C, HW, 1, 0, 0, 1, false, 0, 0, ws ? ws_bytes : 0, false);
+  const BnFinal f{(double)B * HW, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd};
+  return bn_stats_launch(p, x, B, C, HW, f, ws, ws_bytes, S(stream), "itcv_bn_train_stats");
 }
 
 int itcv_bn_finalize(const double* sums, double count, float eps, float momentum, float* running_mean,
@@ -1067,188 +1195,46 @@ int itcv_bn_act_fwd(const float* x, const float* mean, const float* rstd, const 
                     const float* skip, float* y, int B, int C, int H, int W, float slope, int pool, void* planes,
                     int ns, size_t plane_stride, void* stream) {
   ITCV_REQUIRE(x && mean && rstd && gamma && beta && (y || planes) && B > 0 && C > 0 && H > 0 && W > 0, "itcv_bn_act_fwd");
-  ITCV_REQUIRE((size_t)B * C * H * W < (1ull << 31), "itcv_bn_act_fwd(tensor < 2^31 elements)");
-  if (planes) {
-    ITCV_REQUIRE(bn_fmt_ok(ns) && itcv_bn_act_planes_supported(C, H, W, pool), "itcv_bn_act_fwd(planes)");
-    const size_t threads = (size_t)B * (C / 8) * ((pool ? (H / 2) * (W / 2) : H * W) / (pool ? 2 : 4));
-    const dim3 grid(grid_for(threads)), blk(256);
-    u32x4* pl = static_cast<u32x4*>(planes);
-    const size_t pstride = plane_stride ? plane_stride : (size_t)B * (C / 8) * (pool ? (H / 2) * (W / 2) : H * W);
-#define ITCV_FWD_PLANES(POOL_, NS_, F_)                                                                               \
-  do {                                                                                                                \
-      launch_timed((bn_act_fwd_planes_kernel<POOL_, NS_, false, true, F_>), grid, blk, 0, S(stream), x, mean, rstd, gamma, \
-                         beta, skip, y, pl, B, C, H, W, slope, BnStatsIn{}, pstride, BnGrp{});                                   \
-  } while (0)
-#define ITCV_FWD_PLANES_NS(POOL_)                                   \
-  do {                                                              \
-    if (ns == ITCV_PLANES_F16X2) ITCV_FWD_PLANES(POOL_, 2, true);   \
-    else if (ns == 2) ITCV_FWD_PLANES(POOL_, 2, false);             \
-    else ITCV_FWD_PLANES(POOL_, 3, false);                          \
-  } while (0)
-    if (pool) ITCV_FWD_PLANES_NS(1);
-    else ITCV_FWD_PLANES_NS(0);
-#undef ITCV_FWD_PLANES_NS
-#undef ITCV_FWD_PLANES
-    ITCV_CHECK_LAUNCH("itcv_bn_act_fwd(planes)");
-    return 0;
-  }
-  if (pool) {
-    ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_bn_act_fwd(pool)");
-    const size_t nout = (size_t)B * C * (H / 2) * (W / 2);
-    hipLaunchKernelGGL(bn_act_fwd_kernel<1>, dim3(grid_for(nout)), dim3(256), 0, S(stream), x, mean, rstd, gamma,
-                       beta, skip, y, C, H, W, nout, slope, ilog2_exact(H * W), ilog2_exact(C) >= 0 ? C - 1 : -1);
-  } else {
-    ITCV_REQUIRE((H * W) % 4 == 0, "itcv_bn_act_fwd(H*W % 4)");
-    const size_t nout = (size_t)B * C * H * W;
-    hipLaunchKernelGGL(bn_act_fwd_kernel<0>, dim3(grid_for(nout, 4)), dim3(256), 0, S(stream), x, mean, rstd, gamma,
-                       beta, skip, y, C, H, W, nout, slope, ilog2_exact(H * W), ilog2_exact(C) >= 0 ? C - 1 : -1);
-  }
-  ITCV_CHECK_LAUNCH("itcv_bn_act_fwd");
-  return 0;
+  const BnPlan p = bn_plan(false, B, C, H, W, pool, 0, 1, planes != nullptr, ns, plane_stride, 0, false);
+  return bn_fwd_apply_launch(p, x, mean, rstd, gamma, beta, skip, y, planes, ns, B, C, H, W, slope, pool, BnStatsIn{},
+                             S(stream));
 }
 
-}  // extern "C"
-// mx != NULL (fp16 gradient planes): also record the per-slice maxima, mx[2][splits * C] (see bn_bwd_partial_v4)
-static int bwd_reduce_impl(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
-                           const float* beta, const float* skip, double* dsums, float* dgamma, float* dbeta,
-                           int accumulate, int B, int C, int H, int W, float slope, int pool, int up2, void* ws,
-                           size_t ws_bytes, float* mx, void* stream) {
-  ITCV_REQUIRE(x && dy && mean && rstd && gamma && beta && dsums && B > 0 && C > 0, "itcv_bn_act_bwd_reduce");
-  ITCV_REQUIRE(!(pool && up2), "itcv_bn_act_bwd_reduce(pool and up2 are exclusive)");
-  if (pool) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_bn_act_bwd_reduce(pool)");
-  const int splits = bn_splits(B, C, H * W);
-  ITCV_REQUIRE(ws && ws_bytes >= (size_t)splits * 2 * C * sizeof(double), "itcv_bn_act_bwd_reduce(workspace)");
-  double* part = static_cast<double*>(ws);
-  dim3 grid(C, splits);
-  const bool vec = (W % 4 == 0) && ((size_t)B * C * H * W < (1ull << 31));
-  const int wsh = ilog2_exact(W), hwsh = ilog2_exact(H * W);
-  hipStream_t st = S(stream);
-  ITCV_REQUIRE(!mx || vec, "itcv_bn_train_bwd(fp16 planes need W % 4 == 0)");
-  const int nmx = splits * C;
-#define ITCV_BWD_PARTIAL(MODE)                                                                                   \
-  do {                                                                                                           \
-    if (mx && splits == 1)                                                                                       \
-      hipLaunchKernelGGL((bn_bwd_partial_v4<MODE, true, true>), grid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, \
-                         gamma, beta, skip, part, B, C, H, W, slope, 1, wsh, hwsh,                               \
-                         BnBwdFinal{dsums, dgamma, dbeta, accumulate}, BnGrp{}, mx, nmx);                        \
-    else if (mx)                                                                                                 \
-      hipLaunchKernelGGL((bn_bwd_partial_v4<MODE, false, true>), grid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, \
-                         gamma, beta, skip, part, B, C, H, W, slope, splits, wsh, hwsh, BnBwdFinal{}, BnGrp{}, mx, nmx); \
-    else if (vec && splits == 1)                                                                                 \
-      hipLaunchKernelGGL((bn_bwd_partial_v4<MODE, true>), grid, dim3(kRedThreads), 0, st, x, dy, mean, rstd,      \
-                         gamma, beta, skip, part, B, C, H, W, slope, 1, wsh, hwsh,                               \
-                         BnBwdFinal{dsums, dgamma, dbeta, accumulate}, BnGrp{});                                          \
-    else if (vec)                                                                                                \
-      hipLaunchKernelGGL((bn_bwd_partial_v4<MODE, false>), grid, dim3(kRedThreads), 0, st, x, dy, mean, rstd,     \
-                         gamma, beta, skip, part, B, C, H, W, slope, splits, wsh, hwsh, BnBwdFinal{}, BnGrp{});           \
-    else                                                                                                         \
-      hipLaunchKernelGGL(bn_bwd_partial<MODE>, grid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta,    \
-                         skip, part, B, C, H, W, slope, splits);                                                 \
-  } while (0)
-  if (pool)
-    ITCV_BWD_PARTIAL(1);
-  else if (up2)
-    ITCV_BWD_PARTIAL(2);
-  else
-    ITCV_BWD_PARTIAL(0);
-#undef ITCV_BWD_PARTIAL
-  ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_reduce");
-  if (vec && splits == 1) return 0;   // the fused kernel already wrote dsums and the parameter gradients
-  hipLaunchKernelGGL(bn_combine_param_kernel, dim3(cdiv(C, 256)), dim3(256), 0, S(stream), part, dsums, C, splits,
-                     dgamma, dbeta, accumulate);
-  ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_reduce(combine)");
-  return 0;
-}
-
-static int bwd_apply_impl(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
-                          const float* beta, const float* skip, const double* dsums, const double* local_dsums,
-                          double count, float* dx, float* dskip, float* dgamma, float* dbeta, int accumulate, int B,
-                          int C, int H, int W, float slope, int pool, int up2, void* dx_planes, int ns,
-                          size_t plane_stride, const float* mx, int nmx, void* stream) {
-  ITCV_REQUIRE(x && dy && mean && rstd && gamma && beta && dsums && (dx || dx_planes) && B > 0 && C > 0 && count > 0,
-               "itcv_bn_act_bwd_apply");
-  const size_t pstride = plane_stride ? plane_stride : (size_t)B * (C / 8) * H * W;
-  ITCV_REQUIRE(!(pool && up2), "itcv_bn_act_bwd_apply(pool and up2 are exclusive)");
-  const size_t n = (size_t)B * C * H * W;
-  const bool vec = (W % 4 == 0) && (n < (1ull << 31));
-  const int wsh = ilog2_exact(W), hwsh = ilog2_exact(H * W), cmask = ilog2_exact(C) >= 0 ? C - 1 : -1;
-  hipStream_t st = S(stream);
-  if (dx_planes) {
-    ITCV_REQUIRE(bn_fmt_ok(ns) && vec && itcv_bn_act_planes_supported(C, H, W, 0), "itcv_bn_act_bwd_apply(planes)");
-    if (ns == ITCV_PLANES_F16X2 && !mx)
-      return fail("%s: fp16 gradient planes take their scale from the maxima of the reduce pass: use itcv_bn_train_bwd",
-                  "itcv_bn_act_bwd_apply");
-    const dim3 grid(grid_for(n / 32)), blk(256);
-    u32x4* pl = static_cast<u32x4*>(dx_planes);
-#define ITCV_BWD_PLANES(MODE_, NS_, F_)                                                                          \
-  do {                                                                                                           \
-      launch_timed((bn_bwd_apply_planes<MODE_, NS_, false, true, F_>), grid, blk, 0, st, x, dy, mean, rstd, gamma, beta, \
-                         skip, dsums, count, dx, dskip, pl, B, C, H, W, slope, wsh, BnBwdSumsIn{}, pstride, BnGrp{}, mx, nmx); \
-  } while (0)
-#define ITCV_BWD_PLANES_NS(MODE_)                                   \
-  do {                                                              \
-    if (ns == ITCV_PLANES_F16X2) ITCV_BWD_PLANES(MODE_, 2, true);   \
-    else if (ns == 2) ITCV_BWD_PLANES(MODE_, 2, false);             \
-    else ITCV_BWD_PLANES(MODE_, 3, false);                          \
-  } while (0)
-    if (pool) ITCV_BWD_PLANES_NS(1);
-    else if (up2) ITCV_BWD_PLANES_NS(2);
-    else ITCV_BWD_PLANES_NS(0);
-#undef ITCV_BWD_PLANES_NS
-#undef ITCV_BWD_PLANES
-    ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_apply(planes)");
-    if (dgamma || dbeta) {
-      hipLaunchKernelGGL(bn_param_grad_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, local_dsums ? local_dsums : dsums,
-                         dgamma, dbeta, C, accumulate);
-      ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_apply(param grads)");
-    }
-    return 0;
-  }
-#define ITCV_BWD_APPLY(MODE)                                                                                      \
-  do {                                                                                                            \
-    if (vec)                                                                                                      \
-      hipLaunchKernelGGL(bn_bwd_apply_v4<MODE>, dim3(grid_for(n, 4)), dim3(256), 0, st, x, dy, mean, rstd, gamma,  \
-                         beta, skip, dsums, count, dx, dskip, C, H, W, (uint32_t)(n / 4), slope, wsh, hwsh, cmask); \
-    else                                                                                                          \
-      hipLaunchKernelGGL(bn_bwd_apply_kernel<MODE>, dim3(grid_for(n)), dim3(256), 0, st, x, dy, mean, rstd, gamma, \
-                         beta, skip, dsums, count, dx, dskip, C, H, W, n, slope);                                 \
-  } while (0)
-  if (pool)
-    ITCV_BWD_APPLY(1);
-  else if (up2)
-    ITCV_BWD_APPLY(2);
-  else
-    ITCV_BWD_APPLY(0);
-#undef ITCV_BWD_APPLY
-  ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_apply");
-  if (dgamma || dbeta) {
-    hipLaunchKernelGGL(bn_param_grad_kernel, dim3(cdiv(C, 256)), dim3(256), 0, S(stream),
-                       local_dsums ? local_dsums : dsums, dgamma, dbeta, C, accumulate);
-    ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_apply(param grads)");
-  }
-  return 0;
-}
-
-extern "C" {
 int itcv_bn_act_bwd_reduce(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
                            const float* beta, const float* skip, double* dsums, float* dgamma, float* dbeta,
                            int accumulate, int B, int C, int H, int W, float slope, int pool, int up2, void* ws,
                            size_t ws_bytes, void* stream) {
-  return bwd_reduce_impl(x, dy, mean, rstd, gamma, beta, skip, dsums, dgamma, dbeta, accumulate, B, C, H, W, slope, pool, up2,
-                         ws, ws_bytes, nullptr, stream);
+  ITCV_REQUIRE(x && dy && mean && rstd && gamma && beta && dsums && B > 0 && C > 0, "itcv_bn_act_bwd_reduce");
+  ITCV_REQUIRE(!(pool && up2), "itcv_bn_act_bwd_reduce(pool and up2 are exclusive)");
+  const BnPlan p = bn_plan(true, B, C, H, W, pool, up2, 1, false, 0, 0, ws ? ws_bytes : 0, false);
+  return bn_bwd_reduce_launch(p, x, dy, mean, rstd, gamma, beta, skip, dsums, dgamma, dbeta, accumulate, B, C, H, W, slope, ws,
+                              ws_bytes, S(stream), "itcv_bn_act_bwd_reduce");
 }
+
 int itcv_bn_act_bwd_apply(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
                           const float* beta, const float* skip, const double* dsums, const double* local_dsums,
                           double count, float* dx, float* dskip, float* dgamma, float* dbeta, int accumulate, int B,
                           int C, int H, int W, float slope, int pool, int up2, void* dx_planes, int ns,
                           size_t plane_stride, void* stream) {
-  return bwd_apply_impl(x, dy, mean, rstd, gamma, beta, skip, dsums, local_dsums, count, dx, dskip, dgamma, dbeta, accumulate,
-                        B, C, H, W, slope, pool, up2, dx_planes, ns, plane_stride, nullptr, 0, stream);
+  ITCV_REQUIRE(!(pool && up2), "itcv_bn_act_bwd_apply(pool and up2 are exclusive)");
+  const BnPlan p = bn_plan(true, B, C, H, W, pool, up2, 1, dx_planes != nullptr, ns, plane_stride, 0, false);
+  if (int e = bn_bwd_apply_launch(p, x, dy, mean, rstd, gamma, beta, skip, dsums, count, dx, dskip, dx_planes, ns, B, C, H, W,
+                                  slope, BnBwdSumsIn{}, nullptr, S(stream)))
+    return e;
+  if (dgamma || dbeta) {   // Sync-BN: dsums are the all-reduced sums, the parameter gradients take the rank's own
+    hipLaunchKernelGGL(bn_param_grad_kernel, dim3(cdiv(C, 256)), dim3(256), 0, S(stream), local_dsums ? local_dsums : dsums,
+                       dgamma, dbeta, C, accumulate);
+    ITCV_CHECK_LAUNCH("itcv_bn_act_bwd_apply(param grads)");
+  }
+  return 0;
 }
 
 // ---- single-rank training forms: statistics + apply (forward), sums + apply (backward) ----------------------
 // Same results as itcv_bn_train_stats + itcv_bn_act_fwd (resp. itcv_bn_act_bwd_reduce + _apply); where the planes
 // kernels apply and the reduction is sliced, the apply launch folds the slices itself: two launches instead of three.
+// groups > 1: `groups` BatchNorm groups of B images each, stacked along the batch dimension of x / y / planes; mean / rstd
+// are [groups][C], dsums is [groups][2C].  One reduce launch (the running buffers and the parameter gradients advance group
+// by group, in order) and one apply launch with the group in blockIdx.z, or (BnPath::PerGroup) the groups one by one.
 int itcv_bn_train_fwd(const float* x, const float* gamma, const float* beta, const float* skip, float* y, void* planes,
                       int ns, int B, int C, int H, int W, float slope, int pool, float eps, float momentum,
                       float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd,
@@ -1260,141 +1246,34 @@ int itcv_bn_train_fwd(const float* x, const float* gamma, const float* beta, con
   const double px_out = (double)(groups > 1 ? groups : 1) * B * C * (pool ? H * W / 4 : H * W);
   ProfScope bn_prof(S(stream), 13, ilog2_exact(W) >= 0 ? ilog2_exact(W) : 0, C / 8, pool ? 1 : 0, planes ? ns : 0,
                     (double)(groups > 1 ? groups : 1) * B * C * H * W * 4.0 * (skip ? 2 : 1) + px_out * ((planes ? 4.0 : 0.0) + (y ? 4.0 : 0.0)));
-  if (groups > 1) {
-    // `groups` BatchNorm groups of B images each, stacked along the batch dimension of x / y / planes; mean / rstd are
-    // [groups][C].  Small layers (one block per channel computes the statistics): ONE statistics launch that walks the
-    // groups in order (the running buffers advance group by group) and ONE apply launch with the group in blockIdx.z.
-    // Other shapes: the groups are issued one after the other.
-    ITCV_REQUIRE(!planes || plane_stride, "itcv_bn_train_fwd(groups need the plane stride of the whole tensor)");
-    const int HWg = H * W, HWo = pool ? HWg / 4 : HWg;
-    const size_t xs = (size_t)B * C * HWg, os = (size_t)B * C * HWo, ps = (size_t)B * (C / 8) * HWo;
-    const int gsplits = bn_splits(B, C, HWg);
-    const bool mergeable = !tile_stats && planes && bn_fmt_ok(ns) && itcv_bn_act_planes_supported(C, H, W, pool) &&
-                           xs < (1ull << 31);
-    const bool merged = mergeable && gsplits == 1;
-    if (mergeable && gsplits > 1 && ws && ws_bytes >= (size_t)groups * gsplits * 2 * C * sizeof(double)) {
-      // large layers: sliced statistics of all groups in one launch (group = blockIdx.z), a fold that finalises the groups
-      // in order, one apply launch for all groups
-      const BnGrp grp{xs, os, 0, ps, C, groups};
-      double* part = static_cast<double*>(ws);
-      hipLaunchKernelGGL(bn_moments_partial<false>, dim3(C, gsplits, groups), dim3(kRedThreads), 0, S(stream), x, part, B, C,
-                         HWg, gsplits, ilog2_exact(HWg), BnFinal{}, grp);
-      ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(grouped partials)");
-      const int per_plane_g = pool ? (HWg / 4) / 2 : HWg / 4;
-      const bool fold_in_apply = per_plane_g >= 64;   // the apply pass folds the partial sums itself
-      if (!fold_in_apply) {
-        hipLaunchKernelGGL(bn_combine_finalize_groups_kernel, dim3(cdiv(C, 256)), dim3(256), 0, S(stream), part, gsplits,
-                           groups, (double)B * HWg, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd,
-                           C);
-        ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(grouped finalize)");
-      }
-      const BnStatsIn stg{part, gsplits, (double)B * HWg, eps, momentum, running_mean, running_var, num_batches_tracked, mean,
-                          rstd};
-      const size_t threads = (size_t)B * (C / 8) * (HWo / (pool ? 2 : 4));
-      const dim3 grid(grid_for(threads), 1, groups), blk(256);
-      u32x4* pl = static_cast<u32x4*>(planes);
-#define ITCV_FWD_GRP2_K(POOL_, NS_, ST_, F_)                                                                              \
-  launch_timed((bn_act_fwd_planes_kernel<POOL_, NS_, ST_, true, F_>), grid, blk, 0, S(stream), x, mean, rstd, gamma, beta, \
-                     skip, y, pl, B, C, H, W, slope, (ST_) ? stg : BnStatsIn{}, plane_stride, grp)
-#define ITCV_FWD_GRP2(POOL_, NS_, F_)                                  \
-  do {                                                                 \
-    if (fold_in_apply) ITCV_FWD_GRP2_K(POOL_, NS_, true, F_);          \
-    else ITCV_FWD_GRP2_K(POOL_, NS_, false, F_);                       \
-  } while (0)
-#define ITCV_FWD_GRP2_NS(POOL_)                                     \
-  do {                                                              \
-    if (ns == ITCV_PLANES_F16X2) ITCV_FWD_GRP2(POOL_, 2, true);     \
-    else if (ns == 2) ITCV_FWD_GRP2(POOL_, 2, false);               \
-    else ITCV_FWD_GRP2(POOL_, 3, false);                            \
-  } while (0)
-      if (pool) ITCV_FWD_GRP2_NS(1);
-      else ITCV_FWD_GRP2_NS(0);
-#undef ITCV_FWD_GRP2_NS
-#undef ITCV_FWD_GRP2_K
-#undef ITCV_FWD_GRP2
-      ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(grouped apply)");
-      return 0;
-    }
-    if (!merged) {
-      for (int g = 0; g < groups; ++g)
-        if (int e = itcv_bn_train_fwd(x + g * xs, gamma, beta, skip ? skip + g * xs : nullptr, y ? y + g * os : nullptr,
-                                      planes ? static_cast<u32x4*>(planes) + g * ps : nullptr, ns, B, C, H, W, slope, pool,
-                                      eps, momentum, running_mean, running_var, num_batches_tracked, mean + (size_t)g * C,
-                                      rstd + (size_t)g * C, ws, ws_bytes, plane_stride,
-                                      tile_stats ? tile_stats + (size_t)g * tiles : nullptr, tiles, tile_pitch, 1, stream))
-          return e;
-      return 0;
-    }
-    const BnGrp grp{xs, os, 0, ps, C, groups};
-    const BnFinal f{(double)B * HWg, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd};
-    hipLaunchKernelGGL(bn_moments_partial<true>, dim3(C, 1), dim3(kRedThreads), 0, S(stream), x, static_cast<double*>(nullptr),
-                       B, C, HWg, 1, ilog2_exact(HWg), f, grp);
-    ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(grouped statistics)");
-    const size_t threads = (size_t)B * (C / 8) * (HWo / (pool ? 2 : 4));
-    const dim3 grid(grid_for(threads), 1, groups), blk(256);
-    u32x4* pl = static_cast<u32x4*>(planes);
-#define ITCV_FWD_GRP(POOL_, NS_, F_)                                                                                      \
-  do {                                                                                                                    \
-      launch_timed((bn_act_fwd_planes_kernel<POOL_, NS_, false, true, F_>), grid, blk, 0, S(stream), x, mean, rstd, gamma, \
-                         beta, skip, y, pl, B, C, H, W, slope, BnStatsIn{}, plane_stride, grp);                             \
-  } while (0)
-#define ITCV_FWD_GRP_NS(POOL_)                                     \
-  do {                                                             \
-    if (ns == ITCV_PLANES_F16X2) ITCV_FWD_GRP(POOL_, 2, true);     \
-    else if (ns == 2) ITCV_FWD_GRP(POOL_, 2, false);               \
-    else ITCV_FWD_GRP(POOL_, 3, false);                            \
-  } while (0)
-    if (pool) ITCV_FWD_GRP_NS(1);
-    else ITCV_FWD_GRP_NS(0);
-#undef ITCV_FWD_GRP_NS
-#undef ITCV_FWD_GRP
-    ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(grouped apply)");
+  if (groups > 1) ITCV_REQUIRE(!planes || plane_stride, "itcv_bn_train_fwd(groups need the plane stride of the whole tensor)");
+  const BnPlan p = bn_plan(false, B, C, H, W, pool, 0, groups, planes != nullptr, ns, plane_stride, ws ? ws_bytes : 0,
+                           tile_stats != nullptr);
+  if (p.path == BnPath::PerGroup) {
+    const BnGrp& s = p.grp;
+    for (int g = 0; g < groups; ++g)
+      if (int e = itcv_bn_train_fwd(x + g * s.xs, gamma, beta, skip ? skip + g * s.xs : nullptr, y ? y + g * s.os : nullptr,
+                                    planes ? static_cast<u32x4*>(planes) + g * s.ps : nullptr, ns, B, C, H, W, slope, pool,
+                                    eps, momentum, running_mean, running_var, num_batches_tracked, mean + (size_t)g * C,
+                                    rstd + (size_t)g * C, ws, ws_bytes, plane_stride,
+                                    tile_stats ? tile_stats + (size_t)g * tiles : nullptr, tiles, tile_pitch, 1, stream))
+        return e;
     return 0;
   }
-  const size_t pstride = plane_stride ? plane_stride : (size_t)B * (C / 8) * (pool ? (H / 2) * (W / 2) : H * W);
-  if (tile_stats) {   // statistics come from the producing conv's epilogue: fold the tiles, then one apply pass
+  const BnFinal f{(double)B * H * W, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd};
+  if (p.path == BnPath::TileStats) {
     ITCV_REQUIRE(tiles > 0 && tile_pitch >= tiles, "itcv_bn_train_fwd(tile statistics)");
-    hipLaunchKernelGGL(bn_tile_stats_finalize_kernel, dim3(C), dim3(256), 0, S(stream), tile_stats, tiles, tile_pitch,
-                       (double)B * H * W, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, C);
+    hipLaunchKernelGGL(bn_tile_stats_finalize_kernel, dim3(C), dim3(256), 0, S(stream), tile_stats, tiles, tile_pitch, f.count,
+                       eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, C);
     ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(tile statistics)");
-    return itcv_bn_act_fwd(x, mean, rstd, gamma, beta, skip, y, B, C, H, W, slope, pool, planes, ns, plane_stride, stream);
+  } else if (int e = bn_stats_launch(p, x, B, C, H * W, f, ws, ws_bytes, S(stream), "itcv_bn_train_fwd(statistics)")) {
+    return e;
   }
-  const int HW = H * W, splits = bn_splits(B, C, HW);
-  const int per_plane = pool ? (HW / 4) / 2 : HW / 4;
-  const bool fusable = planes && bn_fmt_ok(ns) && itcv_bn_act_planes_supported(C, H, W, pool) && splits > 1 &&
-                       per_plane >= 64 && (size_t)B * C * HW < (1ull << 31);
-  if (!fusable) {
-    if (int e = itcv_bn_train_stats(x, B, C, HW, eps, momentum, running_mean, running_var, num_batches_tracked, mean,
-                                    rstd, ws, ws_bytes, stream))
-      return e;
-    return itcv_bn_act_fwd(x, mean, rstd, gamma, beta, skip, y, B, C, H, W, slope, pool, planes, ns, plane_stride, stream);
-  }
-  ITCV_REQUIRE(ws && ws_bytes >= (size_t)splits * 2 * C * sizeof(double), "itcv_bn_train_fwd(workspace)");
-  double* part = static_cast<double*>(ws);
-  hipLaunchKernelGGL(bn_moments_partial<false>, dim3(C, splits), dim3(kRedThreads), 0, S(stream), x, part, B, C, HW,
-                     splits, ilog2_exact(HW), BnFinal{}, BnGrp{});
-  ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(partials)");
-  const BnStatsIn st{part, splits, (double)B * HW, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd};
-  const size_t threads = (size_t)B * (C / 8) * per_plane;
-  const dim3 grid(grid_for(threads)), blk(256);
-  u32x4* pl = static_cast<u32x4*>(planes);
-#define ITCV_FWD_FUSED(POOL_, NS_, F_)                                                                               \
-  do {                                                                                                                \
-      launch_timed((bn_act_fwd_planes_kernel<POOL_, NS_, true, true, F_>), grid, blk, 0, S(stream), x, mean, rstd, gamma, \
-                         beta, skip, y, pl, B, C, H, W, slope, st, pstride, BnGrp{});                                            \
-  } while (0)
-#define ITCV_FWD_FUSED_NS(POOL_)                                     \
-  do {                                                               \
-    if (ns == ITCV_PLANES_F16X2) ITCV_FWD_FUSED(POOL_, 2, true);     \
-    else if (ns == 2) ITCV_FWD_FUSED(POOL_, 2, false);               \
-    else ITCV_FWD_FUSED(POOL_, 3, false);                            \
-  } while (0)
-  if (pool) ITCV_FWD_FUSED_NS(1);
-  else ITCV_FWD_FUSED_NS(0);
-#undef ITCV_FWD_FUSED_NS
-#undef ITCV_FWD_FUSED
-  ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(apply)");
-  return 0;
+  const BnStatsIn fold = p.path == BnPath::SlicedFold
+                             ? BnStatsIn{static_cast<const double*>(ws), p.splits, f.count, eps, momentum, running_mean,
+                                         running_var, num_batches_tracked, mean, rstd}
+                             : BnStatsIn{};
+  return bn_fwd_apply_launch(p, x, mean, rstd, gamma, beta, skip, y, planes, ns, B, C, H, W, slope, pool, fold, S(stream));
 }
 
 int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
@@ -1409,152 +1288,35 @@ int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const 
   ProfScope bn_prof(S(stream), 14, ilog2_exact(W) >= 0 ? ilog2_exact(W) : 0, C / 8, pool ? 1 : (up2 ? 2 : 0), dx_planes ? ns : 0,
                     bn_el * 4.0 * (1.0 + (pool ? 0.25 : (up2 ? 4.0 : 1.0)) + (skip ? 1.0 : 0.0)) +
                         bn_el * ((dx_planes ? 4.0 : 0.0) + (dx ? 4.0 : 0.0) + (dskip ? 4.0 : 0.0)));
-  if (groups > 1) {   // see itcv_bn_train_fwd; dsums is [groups][2C], the parameter gradients add up over the groups
-    ITCV_REQUIRE(!dx_planes || plane_stride, "itcv_bn_train_bwd(groups need the plane stride of the whole tensor)");
-    const int HWg = H * W;
-    const size_t xs = (size_t)B * C * HWg, dys = pool ? xs / 4 : (up2 ? xs * 4 : xs), ps = (size_t)B * (C / 8) * HWg;
-    const bool vecg = (W % 4 == 0) && xs < (1ull << 31);
-    const int gsplits = bn_splits(B, C, HWg);
-    const bool mergeable = vecg && dx_planes && bn_fmt_ok(ns) && itcv_bn_act_planes_supported(C, H, W, 0);
-    const bool merged = mergeable && gsplits == 1;
-    const bool f16 = ns == ITCV_PLANES_F16X2;
-    // fp16 planes: the maxima of all groups ([2][groups * gsplits * C] floats) follow the partial sums in the workspace
-    const int nmx = groups * gsplits * C;
-    const size_t ws_need = (size_t)groups * gsplits * 2 * C * sizeof(double) + (f16 ? (size_t)2 * nmx * sizeof(float) : 0);
-    float* mx = f16 && ws ? reinterpret_cast<float*>(static_cast<double*>(ws) + (size_t)groups * gsplits * 2 * C) : nullptr;
-    if (f16 && !(mergeable && ws && ws_bytes >= ws_need))
-      return fail("%s: fp16 gradient planes need the merged group path (W %% 4 == 0, planes, a workspace of itcv_bn_workspace * groups)",
-                  "itcv_bn_train_bwd");
-    if (mergeable && gsplits > 1 && ws && ws_bytes >= ws_need) {
-      if (pool) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_bn_train_bwd(pool)");
-      const BnGrp grp{xs, 0, dys, ps, C, groups};
-      hipStream_t st = S(stream);
-      const int wsh = ilog2_exact(W), hwsh = ilog2_exact(HWg);
-      double* part = static_cast<double*>(ws);
-      const dim3 rgrid(C, gsplits, groups), agrid(grid_for(xs / 32), 1, groups), blk(256);
-      u32x4* pl = static_cast<u32x4*>(dx_planes);
-      const double count = (double)B * HWg;
-      const bool fold_in_apply = HWg / 4 >= 64;   // the apply pass folds the partial sums itself
-      const BnBwdSumsIn smg{part, gsplits, dsums, dgamma, dbeta, accumulate};
-#define ITCV_BWD_GRP2_K(MODE_, NS_, SUMS_, F_)                                                                           \
-  launch_timed((bn_bwd_apply_planes<MODE_, NS_, SUMS_, true, F_>), agrid, blk, 0, st, x, dy, mean, rstd, gamma, beta, \
-                     skip, (SUMS_) ? static_cast<const double*>(nullptr) : dsums, count, dx, dskip, pl, B, C, H, W, slope, \
-                     wsh, (SUMS_) ? smg : BnBwdSumsIn{}, plane_stride, grp, mx, nmx)
-#define ITCV_BWD_GRP2(MODE_, NS_, F_)                                                                                    \
-  do {                                                                                                                   \
-    hipLaunchKernelGGL((bn_bwd_partial_v4<MODE_, false, F_>), rgrid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta, \
-                       skip, part, B, C, H, W, slope, gsplits, wsh, hwsh, BnBwdFinal{}, grp, mx, nmx);                   \
-    if (fold_in_apply) {                                                                                                 \
-      ITCV_BWD_GRP2_K(MODE_, NS_, true, F_);                                                                             \
-    } else {                                                                                                             \
-      hipLaunchKernelGGL(bn_combine_param_groups_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, dsums, C, gsplits,   \
-                         groups, dgamma, dbeta, accumulate);                                                             \
-      ITCV_BWD_GRP2_K(MODE_, NS_, false, F_);                                                                            \
-    }                                                                                                                    \
-  } while (0)
-#define ITCV_BWD_GRP2_NS(MODE_)                          \
-  do {                                                   \
-    if (f16) ITCV_BWD_GRP2(MODE_, 2, true);              \
-    else if (ns == 2) ITCV_BWD_GRP2(MODE_, 2, false);    \
-    else ITCV_BWD_GRP2(MODE_, 3, false);                 \
-  } while (0)
-      if (pool) ITCV_BWD_GRP2_NS(1);
-      else if (up2) ITCV_BWD_GRP2_NS(2);
-      else ITCV_BWD_GRP2_NS(0);
-#undef ITCV_BWD_GRP2_NS
-#undef ITCV_BWD_GRP2
-#undef ITCV_BWD_GRP2_K
-      ITCV_CHECK_LAUNCH("itcv_bn_train_bwd(grouped, sliced)");
-      return 0;
-    }
-    if (!merged) {
-      for (int g = 0; g < groups; ++g)
-        if (int e = itcv_bn_train_bwd(x + g * xs, dy + g * dys, mean + (size_t)g * C, rstd + (size_t)g * C, gamma, beta,
-                                      skip ? skip + g * xs : nullptr, dsums + (size_t)g * 2 * C, dx ? dx + g * xs : nullptr,
-                                      dskip ? dskip + g * xs : nullptr,
-                                      dx_planes ? static_cast<u32x4*>(dx_planes) + g * ps : nullptr, ns, dgamma, dbeta,
-                                      (accumulate || g > 0) ? 1 : 0, B, C, H, W, slope, pool, up2, ws, ws_bytes, plane_stride,
-                                      1, stream))
-          return e;
-      return 0;
-    }
-    if (pool) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_bn_train_bwd(pool)");
-    const BnGrp grp{xs, 0, dys, ps, C, groups};
-    hipStream_t st = S(stream);
-    const int wsh = ilog2_exact(W), hwsh = ilog2_exact(HWg);
-    const BnBwdFinal bf{dsums, dgamma, dbeta, accumulate};
-    const dim3 rgrid(C, 1), agrid(grid_for(xs / 32), 1, groups), blk(256);
-    u32x4* pl = static_cast<u32x4*>(dx_planes);
-    const double count = (double)B * HWg;
-#define ITCV_BWD_GRP(MODE_, NS_, F_)                                                                                     \
-  do {                                                                                                                   \
-    hipLaunchKernelGGL((bn_bwd_partial_v4<MODE_, true, F_>), rgrid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta, \
-                       skip, static_cast<double*>(nullptr), B, C, H, W, slope, 1, wsh, hwsh, bf, grp, mx, nmx);          \
-      launch_timed((bn_bwd_apply_planes<MODE_, NS_, false, true, F_>), agrid, blk, 0, st, x, dy, mean, rstd, gamma, beta, \
-                         skip, dsums, count, dx, dskip, pl, B, C, H, W, slope, wsh, BnBwdSumsIn{}, plane_stride, grp, mx, nmx); \
-  } while (0)
-#define ITCV_BWD_GRP_NS(MODE_)                          \
-  do {                                                  \
-    if (f16) ITCV_BWD_GRP(MODE_, 2, true);              \
-    else if (ns == 2) ITCV_BWD_GRP(MODE_, 2, false);    \
-    else ITCV_BWD_GRP(MODE_, 3, false);                 \
-  } while (0)
-    if (pool) ITCV_BWD_GRP_NS(1);
-    else if (up2) ITCV_BWD_GRP_NS(2);
-    else ITCV_BWD_GRP_NS(0);
-#undef ITCV_BWD_GRP_NS
-#undef ITCV_BWD_GRP
-    ITCV_CHECK_LAUNCH("itcv_bn_train_bwd(grouped)");
+  if (groups > 1) ITCV_REQUIRE(!dx_planes || plane_stride, "itcv_bn_train_bwd(groups need the plane stride of the whole tensor)");
+  const BnPlan p = bn_plan(true, B, C, H, W, pool, up2, groups, dx_planes != nullptr, ns, plane_stride, ws ? ws_bytes : 0,
+                           false);
+  const size_t ws_need = p.ws_need;
+  if (p.f16 && groups > 1 && (p.path == BnPath::PerGroup || !(ws && ws_bytes >= ws_need)))
+    return fail("%s: fp16 gradient planes need the merged group path (W %% 4 == 0, planes, a workspace of itcv_bn_workspace * groups)",
+                "itcv_bn_train_bwd");
+  if (p.path == BnPath::PerGroup) {   // the parameter gradients add up over the groups
+    const BnGrp& s = p.grp;
+    for (int g = 0; g < groups; ++g)
+      if (int e = itcv_bn_train_bwd(x + g * s.xs, dy + g * s.dys, mean + (size_t)g * C, rstd + (size_t)g * C, gamma, beta,
+                                    skip ? skip + g * s.xs : nullptr, dsums + (size_t)g * 2 * C, dx ? dx + g * s.xs : nullptr,
+                                    dskip ? dskip + g * s.xs : nullptr,
+                                    dx_planes ? static_cast<u32x4*>(dx_planes) + g * s.ps : nullptr, ns, dgamma, dbeta,
+                                    (accumulate || g > 0) ? 1 : 0, B, C, H, W, slope, pool, up2, ws, ws_bytes, plane_stride,
+                                    1, stream))
+        return e;
     return 0;
   }
-  const int HW = H * W, splits = bn_splits(B, C, HW);
-  const size_t n = (size_t)B * C * HW;
-  const bool vec = (W % 4 == 0) && n < (1ull << 31);
-  const bool fusable = dx_planes && bn_fmt_ok(ns) && vec && itcv_bn_act_planes_supported(C, H, W, 0) &&
-                       splits > 1 && HW / 4 >= 64;
-  const bool f16 = dx_planes && ns == ITCV_PLANES_F16X2;
-  const int nmx = splits * C;
-  const size_t ws_need = (size_t)splits * 2 * C * sizeof(double) + (f16 ? (size_t)2 * nmx * sizeof(float) : 0);
-  if (f16) ITCV_REQUIRE(ws && ws_bytes >= ws_need, "itcv_bn_train_bwd(workspace, fp16 planes)");
-  float* mx = f16 ? reinterpret_cast<float*>(static_cast<double*>(ws) + (size_t)splits * 2 * C) : nullptr;
-  if (!fusable) {
-    if (int e = bwd_reduce_impl(x, dy, mean, rstd, gamma, beta, skip, dsums, dgamma, dbeta, accumulate, B, C, H, W, slope,
-                                pool, up2, ws, ws_bytes, mx, stream))
-      return e;
-    return bwd_apply_impl(x, dy, mean, rstd, gamma, beta, skip, dsums, nullptr, (double)B * HW, dx, dskip, nullptr, nullptr,
-                          0, B, C, H, W, slope, pool, up2, dx_planes, ns, plane_stride, mx, nmx, stream);
-  }
-  if (pool) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_bn_train_bwd(pool)");
-  ITCV_REQUIRE(ws && ws_bytes >= ws_need, "itcv_bn_train_bwd(workspace)");
-  double* part = static_cast<double*>(ws);
-  hipStream_t st = S(stream);
-  const int wsh = ilog2_exact(W), hwsh = ilog2_exact(HW);
-  const BnBwdSumsIn sm{part, splits, dsums, dgamma, dbeta, accumulate};
-  const dim3 rgrid(C, splits), agrid(grid_for(n / 32)), blk(256);
-  u32x4* pl = static_cast<u32x4*>(dx_planes);
-  const double count = (double)B * HW;
-  const size_t pstride = plane_stride ? plane_stride : (size_t)B * (C / 8) * HW;
-#define ITCV_BWD_FUSED(MODE_, NS_, F_)                                                                                \
-  do {                                                                                                                \
-    hipLaunchKernelGGL((bn_bwd_partial_v4<MODE_, false, F_>), rgrid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, \
-                       beta, skip, part, B, C, H, W, slope, splits, wsh, hwsh, BnBwdFinal{}, BnGrp{}, mx, nmx);       \
-      launch_timed((bn_bwd_apply_planes<MODE_, NS_, true, true, F_>), agrid, blk, 0, st, x, dy, mean, rstd, gamma, beta, \
-                         skip, static_cast<const double*>(nullptr), count, dx, dskip, pl, B, C, H, W, slope, wsh, sm,   \
-                         pstride, BnGrp{}, mx, nmx);                                                                  \
-  } while (0)
-#define ITCV_BWD_FUSED_NS(MODE_)                          \
-  do {                                                    \
-    if (f16) ITCV_BWD_FUSED(MODE_, 2, true);              \
-    else if (ns == 2) ITCV_BWD_FUSED(MODE_, 2, false);    \
-    else ITCV_BWD_FUSED(MODE_, 3, false);                 \
-  } while (0)
-  if (pool) ITCV_BWD_FUSED_NS(1);
-  else if (up2) ITCV_BWD_FUSED_NS(2);
-  else ITCV_BWD_FUSED_NS(0);
-#undef ITCV_BWD_FUSED_NS
-#undef ITCV_BWD_FUSED
-  ITCV_CHECK_LAUNCH("itcv_bn_train_bwd");
-  return 0;
+  if (p.f16) ITCV_REQUIRE(ws && ws_bytes >= ws_need, "itcv_bn_train_bwd(workspace, fp16 planes)");
+  if (int e = bn_bwd_reduce_launch(p, x, dy, mean, rstd, gamma, beta, skip, dsums, dgamma, dbeta, accumulate, B, C, H, W, slope,
+                                   ws, ws_bytes, S(stream), "itcv_bn_train_bwd(sums)"))
+    return e;
+  const BnBwdSumsIn fold = p.path == BnPath::SlicedFold
+                               ? BnBwdSumsIn{static_cast<const double*>(ws), p.splits, dsums, dgamma, dbeta, accumulate}
+                               : BnBwdSumsIn{};
+  const float* mx = p.f16 ? reinterpret_cast<const float*>(static_cast<const double*>(ws) + p.part_doubles) : nullptr;
+  return bn_bwd_apply_launch(p, x, dy, mean, rstd, gamma, beta, skip, dsums, (double)B * H * W, dx, dskip, dx_planes, ns, B, C,
+                             H, W, slope, fold, mx, S(stream));
 }
 
 #define ITCV_POINTWISE(NAME, KERNEL, N, ...)                                                        \

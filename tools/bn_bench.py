@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time of one conv-BN unit's BatchNorm launches (forward statistics + apply, backward sums + apply, planes in and out)
-at the shapes of the 64x64 configuration, per plane-store form (ITCV_BN_STRIP mask; run once per value)."""
+at the shapes of the 64x64 configuration."""
 import os
 import sys
 
@@ -11,7 +11,6 @@ import torch  # noqa: E402
 from hipvae import functional as HF  # noqa: E402
 
 dev = torch.device("cuda:0")
-print("ITCV_BN_STRIP =", os.environ.get("ITCV_BN_STRIP", "(default)"))
 for B, C, H, W, pool in ((64, 64, 64, 64, False), (64, 128, 32, 32, False), (64, 256, 16, 16, False), (64, 64, 64, 64, True),
                          (64, 512, 8, 8, False)):
     g = torch.Generator().manual_seed(1)
