@@ -286,6 +286,20 @@ int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const 
                       int ns, float* dgamma, float* dbeta, int accumulate, int B, int C, int H, int W, float slope,
                       int pool, int up2, void* ws, size_t ws_bytes, size_t plane_stride, int groups, void* stream);
 
+/* Which launches a BatchNorm training call gets.  Pure host arithmetic (no launch, no device): the decision
+ * itcv_bn_train_fwd (bwd = 0) / itcv_bn_train_bwd (bwd = 1) make for one group of (B, C, H, W), `planes` != 0 when
+ * planes are requested in format `ns`, `ws_bytes` the workspace handed in, `tile_stats` != 0 when the conv epilogue's
+ * tile sums are given.  *path receives one of ITCV_BN_PATH_*, *splits the slices per channel of the reduction (either
+ * may be NULL).  Tests pin the path of every shape they run; returns non-zero for non-positive dimensions. */
+#define ITCV_BN_PATH_ONE_BLOCK 0      /* one block per channel reduces and finalises (all groups, in order); planes apply */
+#define ITCV_BN_PATH_SLICED_FOLD 1    /* sliced reduce; the planes apply launch folds the slices itself */
+#define ITCV_BN_PATH_SLICED_COMBINE 2 /* sliced reduce, a combine launch, planes apply (fewer than 64 threads a plane) */
+#define ITCV_BN_PATH_FALLBACK 3       /* no planes, or a shape the planes kernels do not take: plain apply kernels */
+#define ITCV_BN_PATH_PER_GROUP 4      /* groups > 1 that cannot go out as one launch: one call per group */
+#define ITCV_BN_PATH_TILE_STATS 5     /* forward: statistics from the producing conv's tile sums, then the apply pass */
+int itcv_bn_plan_query(int bwd, int B, int C, int H, int W, int pool, int up2, int groups, int planes, int ns,
+                       size_t ws_bytes, int tile_stats, int* path, int* splits);
+
 /* ---- pointwise / resampling ----------------------------------------------------------- */
 int itcv_lrelu_fwd(const float* x, float* y, size_t n, float slope, void* stream);     /* models.py:271 */
 int itcv_lrelu_bwd(const float* x, const float* dy, float* dx, size_t n, float slope, void* stream);

@@ -1249,6 +1249,10 @@ int itcv_bn_train_fwd(const float* x, const float* gamma, const float* beta, con
   if (groups > 1) ITCV_REQUIRE(!planes || plane_stride, "itcv_bn_train_fwd(groups need the plane stride of the whole tensor)");
   const BnPlan p = bn_plan(false, B, C, H, W, pool, 0, groups, planes != nullptr, ns, plane_stride, ws ? ws_bytes : 0,
                            tile_stats != nullptr);
+  // every per-group call would put the scale record behind ITS planes pointer + the whole tensor's stride: outside the buffer
+  if (p.path == BnPath::PerGroup && planes && ns == ITCV_PLANES_F16X2)
+    return fail("%s: fp16 planes need the merged group path (no tile statistics, a workspace of itcv_bn_workspace * groups)",
+                "itcv_bn_train_fwd");
   if (p.path == BnPath::PerGroup) {
     const BnGrp& s = p.grp;
     for (int g = 0; g < groups; ++g)
@@ -1317,6 +1321,21 @@ int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const 
   const float* mx = p.f16 ? reinterpret_cast<const float*>(static_cast<const double*>(ws) + p.part_doubles) : nullptr;
   return bn_bwd_apply_launch(p, x, dy, mean, rstd, gamma, beta, skip, dsums, (double)B * H * W, dx, dskip, dx_planes, ns, B, C,
                              H, W, slope, fold, mx, S(stream));
+}
+
+static_assert((int)BnPath::OneBlock == ITCV_BN_PATH_ONE_BLOCK && (int)BnPath::SlicedFold == ITCV_BN_PATH_SLICED_FOLD &&
+                  (int)BnPath::SlicedCombine == ITCV_BN_PATH_SLICED_COMBINE && (int)BnPath::Fallback == ITCV_BN_PATH_FALLBACK &&
+                  (int)BnPath::PerGroup == ITCV_BN_PATH_PER_GROUP && (int)BnPath::TileStats == ITCV_BN_PATH_TILE_STATS,
+              "ITCV_BN_PATH_* follow BnPath");
+
+// what bn_plan() decides for a call of itcv_bn_train_fwd / _bwd with these arguments (host only, nothing is launched)
+int itcv_bn_plan_query(int bwd, int B, int C, int H, int W, int pool, int up2, int groups, int planes, int ns,
+                       size_t ws_bytes, int tile_stats, int* path, int* splits) {
+  ITCV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0, "itcv_bn_plan_query");
+  const BnPlan p = bn_plan(bwd != 0, B, C, H, W, pool, up2, groups, planes != 0, ns, 0, ws_bytes, tile_stats != 0);
+  if (path) *path = (int)p.path;
+  if (splits) *splits = p.splits;
+  return 0;
 }
 
 #define ITCV_POINTWISE(NAME, KERNEL, N, ...)                                                        \

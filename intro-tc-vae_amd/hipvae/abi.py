@@ -100,6 +100,7 @@ SIGNATURES = {
                                 i32, p]),
     "itcv_bn_train_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, p, i32, p, p, i32, i32, i32, i32, i32, f32, i32, i32, p,
                                 sz, sz, i32, p]),
+    "itcv_bn_plan_query": (i32, [i32] * 10 + [sz, i32, p, p]),
     "itcv_lrelu_fwd": (i32, [p, p, sz, f32, p]),
     "itcv_lrelu_bwd": (i32, [p, p, p, sz, f32, p]),
     "itcv_sigmoid_fwd": (i32, [p, p, sz, p]),
@@ -156,6 +157,7 @@ SIGNATURES = {
 
 TC_VAR_FROM_ROW, TC_EPS_DENSITY, TC_WEIGHTED = 1, 2, 4
 TC_LIVE = TC_VAR_FROM_ROW | TC_EPS_DENSITY
+BN_PATHS = ("OneBlock", "SlicedFold", "SlicedCombine", "Fallback", "PerGroup", "TileStats")   # ITCV_BN_PATH_* in order
 LOSS_TYPES = {"mse": 0, "l1": 1, "bce": 2}
 OPT_MAXIMIZE, OPT_NESTEROV, OPT_AMSGRAD, OPT_DECOUPLED_WD, OPT_CENTERED = 0x1, 0x2, 0x4, 0x8, 0x10
 
@@ -247,3 +249,15 @@ def ptr(t):
 
 def call(name, *args):
     check(getattr(lib, name)(*args))
+
+
+def bn_plan_query(bwd, B, C, H, W, pool=0, up2=0, groups=1, planes=True, ns=2, ws_bytes=None, tile_stats=False):
+    """(path name, slices per channel) of the launch plan itcv_bn_train_fwd (``bwd`` false) / itcv_bn_train_bwd would
+    build for one BatchNorm group of (B, C, H, W).  Host arithmetic only; ``ws_bytes`` None: the workspace BnActFn
+    hands in (itcv_bn_workspace * groups)."""
+    if ws_bytes is None:
+        ws_bytes = lib.itcv_bn_workspace(B, C, H * W) * max(int(groups), 1)
+    path, splits = ctypes.c_int(-1), ctypes.c_int(-1)
+    call("itcv_bn_plan_query", int(bool(bwd)), B, C, H, W, int(pool), int(up2), int(groups), int(bool(planes)), int(ns),
+         ws_bytes, int(bool(tile_stats)), ctypes.byref(path), ctypes.byref(splits))
+    return BN_PATHS[path.value], splits.value

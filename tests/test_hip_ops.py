@@ -192,7 +192,8 @@ def test_batchnorm_act(HF, shape, pool, skip, slope):
 
 
 def test_bn_upsampled_gradient_mode(HF):
-    """itcv_bn_act_bwd_* with up2=1 (gradient arriving at x2 resolution) == upsample adjoint + plain."""
+    """itcv_bn_act_bwd_* with up2=1 (gradient arriving at x2 resolution) == upsample adjoint + plain.  (Against fp64, with
+    planes, groups and on every launch path: tests/test_hip_bn.py, cases j-*.)"""
     from hipvae.abi import call, lib, ptr, stream
     B, C, H, W = 3, 4, 6, 8
     g = torch.Generator().manual_seed(9)
