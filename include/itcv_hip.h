@@ -226,6 +226,11 @@ int itcv_bn_train_stats(const float* x, int B, int C, int HW, float eps, float m
 int itcv_bn_finalize(const double* sums, double count, float eps, float momentum, float* running_mean,
                      float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd, int C,
                      void* stream);
+/* The same, also writing the unbiased variance that running_var was blended with to unbiased_var [C] (may be NULL;
+ * written only when running_var is given): see itcv_bn_replay_many. */
+int itcv_bn_finalize_uv(const double* sums, double count, float eps, float momentum, float* running_mean,
+                        float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd, float* unbiased_var,
+                        int C, void* stream);
 /* eval mode: mean = running_mean, rstd = 1/sqrt(running_var + eps) */
 int itcv_bn_eval_stats(const float* running_mean, const float* running_var, float eps, float* mean,
                        float* rstd, int C, void* stream);
@@ -274,6 +279,27 @@ int itcv_bn_train_fwd(const float* x, const float* gamma, const float* beta, con
                       float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd,
                       void* ws, size_t ws_bytes, size_t plane_stride, const float* tile_stats, int tiles, int tile_pitch,
                       int groups, void* stream);
+/* itcv_bn_train_fwd_uv == itcv_bn_train_fwd, also leaving in unbiased_var [groups][C] (may be NULL; written only when
+ * running_var is given) the float every group blended into running_var.  With mean [groups][C] these are the values a
+ * later replay of the running-buffer update needs (itcv_bn_replay_many); rstd does not give the second back bit for bit. */
+int itcv_bn_train_fwd_uv(const float* x, const float* gamma, const float* beta, const float* skip, float* y, void* planes,
+                         int ns, int B, int C, int H, int W, float slope, int pool, float eps, float momentum,
+                         float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd,
+                         float* unbiased_var, void* ws, size_t ws_bytes, size_t plane_stride, const float* tile_stats,
+                         int tiles, int tile_pitch, int groups, void* stream);
+/* Replay of running-buffer updates: when a network pass is reused instead of recomputed (same weights, same input, batch
+ * statistics: solvers/intro.py:119-120 repeats :70,75), every BatchNorm layer still owes the update the repeated pass
+ * would have made, at that point of the stream.  ONE launch for all layers: the caller fills a host array of n
+ * descriptors of itcv_bn_replay_desc_bytes() each (returns the blocks the layer adds, 0 when all three buffers are NULL
+ * -- leave such a layer out -- and < 0 on error; block0 = their running sum), copies it to the device and launches with
+ * the total.  Per channel, group by group in order: running = (1 - momentum) * running + momentum * saved, the
+ * expression of the forward; num_batches_tracked += groups.  Bitwise the buffers the repeated forward would leave.  The
+ * device table must stay alive as long as a captured graph may replay the launch. */
+size_t itcv_bn_replay_desc_bytes(void);
+int itcv_bn_replay_desc(void* host_desc, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                        const float* mean, const float* unbiased_var, int C, int groups, float momentum, int block0);
+int itcv_bn_replay_many(const void* dev_table, int n, int total_blocks, void* stream);
+int itcv_bn_replay_max_descs(void);   /* descriptors one table (one launch) may hold */
 /* groups > 1 (itcv_bn_train_fwd / _bwd): x / y / planes (dy / dx / dx_planes) hold `groups` BatchNorm groups of B images
  * each, stacked along the batch dimension; mean / rstd are [groups][C], dsums [groups][2C]; plane_stride is that of the
  * whole tensor.  Every group is normalised with its own statistics and advances the running buffers on its own, in

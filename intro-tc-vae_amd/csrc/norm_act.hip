@@ -37,21 +37,37 @@ struct BnFinal {   // arguments of the fused single-launch path (splits == 1)
   int64_t* nbt;
   float* mean;
   float* rstd;
+  float* uvar;   // [G][C] or null: the unbiased variance blended into running_var (see bn_finalize)
 };
+
+// One step of a running buffer.  bn_finalize and the replay kernel (bn_replay_many) share this expression, and it is never
+// contracted: two products, one sum, each rounded.  Left to the compiler, whether one product is fused into the sum depends
+// on the code around the call (exporting the variance turned the update of two finalising kernels into mul + fmac), and
+// the kernels that advance the same buffer would stop agreeing in the last bit.
+// The empty asm makes both products opaque to the combiner, whatever the contraction flags of the build.
+__device__ __forceinline__ float bn_blend(float r, float s, float momentum) {
+  float a = (1.f - momentum) * r, b = momentum * s;
+  asm volatile("" : "+v"(a), "+v"(b));
+  return a + b;
+}
 
 // The one finalisation of the batch statistics: channel sums -> (mean, biased variance) -> mean_c / rstd_c, and the update
 // of the running buffers at channel c (either may be null; the running variance takes the unbiased estimate).
+// `uvar_c` (may be null): receives the float that running_var was blended with -- together with mean_c the two values a
+// later replay of this update needs (1 / rstd^2 - eps does not give it back bit for bit).  Written only with running_var.
 __device__ __forceinline__ void bn_finalize(double s1, double s2, double count, float eps, float momentum,
-                                            float* running_mean, float* running_var, int c, float& mean_c, float& rstd_c) {
+                                            float* running_mean, float* running_var, int c, float& mean_c, float& rstd_c,
+                                            float* uvar_c = nullptr) {
   const double m = s1 / count;
   double var = s2 / count - m * m;
   if (var < 0.0) var = 0.0;
   mean_c = (float)m;
   rstd_c = (float)(1.0 / sqrt(var + (double)eps));
-  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)m;
+  if (running_mean) running_mean[c] = bn_blend(running_mean[c], (float)m, momentum);
   if (running_var) {
     const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+    running_var[c] = bn_blend(running_var[c], (float)unbiased, momentum);
+    if (uvar_c) *uvar_c = (float)unbiased;
   }
 }
 
@@ -90,7 +106,8 @@ __global__ __launch_bounds__(kRedThreads) void bn_moments_partial(const float* _
   s2 = block_sum(s2, scratch);
   if (threadIdx.x == 0) {
     if (FUSED) {   // one block owns the whole channel: finalise here, no second launch
-      bn_finalize(s1, s2, f.count, f.eps, f.momentum, f.running_mean, f.running_var, c, f.mean[c], f.rstd[c]);
+      bn_finalize(s1, s2, f.count, f.eps, f.momentum, f.running_mean, f.running_var, c, f.mean[c], f.rstd[c],
+                  f.uvar ? f.uvar + (size_t)gi * grp.cs + c : nullptr);
       if (c == 0 && f.nbt) f.nbt[0] += 1;
     } else {
       part[((size_t)s * 2 + 0) * C + c] = s1;
@@ -109,18 +126,19 @@ __global__ void combine_partials(const double* __restrict__ part, double* __rest
 
 __global__ void bn_finalize_kernel(const double* __restrict__ sums, double count, float eps, float momentum,
                                    float* running_mean, float* running_var, int64_t* nbt, float* mean, float* rstd,
-                                   int C) {
+                                   float* uvar, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c == 0 && nbt) nbt[0] += 1;
   if (c >= C) return;
-  bn_finalize(sums[c], sums[C + c], count, eps, momentum, running_mean, running_var, c, mean[c], rstd[c]);
+  bn_finalize(sums[c], sums[C + c], count, eps, momentum, running_mean, running_var, c, mean[c], rstd[c],
+              uvar ? uvar + c : nullptr);
 }
 
 // statistics from the per-tile sums a conv epilogue wrote (fp32 per 256-value tile, folded here in fp64): block per channel
 __global__ __launch_bounds__(256) void bn_tile_stats_finalize_kernel(const float* __restrict__ ts, int tiles, int pitch,
                                                                     double count, float eps, float momentum,
                                                                     float* running_mean, float* running_var, int64_t* nbt,
-                                                                    float* mean, float* rstd, int C) {
+                                                                    float* mean, float* rstd, float* uvar, int C) {
   __shared__ double scratch[4];
   const int c = blockIdx.x;
   const float* p1 = ts + (size_t)c * pitch;
@@ -130,7 +148,7 @@ __global__ __launch_bounds__(256) void bn_tile_stats_finalize_kernel(const float
   s1 = block_sum(s1, scratch);
   s2 = block_sum(s2, scratch);
   if (threadIdx.x == 0) {
-    bn_finalize(s1, s2, count, eps, momentum, running_mean, running_var, c, mean[c], rstd[c]);
+    bn_finalize(s1, s2, count, eps, momentum, running_mean, running_var, c, mean[c], rstd[c], uvar ? uvar + c : nullptr);
     if (c == 0 && nbt) nbt[0] += 1;
   }
 }
@@ -138,7 +156,7 @@ __global__ __launch_bounds__(256) void bn_tile_stats_finalize_kernel(const float
 // sliced statistics: fold every group's partial sums and finalise the groups IN ORDER (running buffers); one group: G = 1
 __global__ void bn_combine_finalize_groups_kernel(const double* __restrict__ part, int splits, int G, double count, float eps,
                                                   float momentum, float* running_mean, float* running_var, int64_t* nbt,
-                                                  float* mean, float* rstd, int C) {
+                                                  float* mean, float* rstd, float* uvar, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c == 0 && nbt) nbt[0] += G;
   if (c >= C) return;
@@ -146,7 +164,8 @@ __global__ void bn_combine_finalize_groups_kernel(const double* __restrict__ par
     const double* pg = part + (size_t)g * splits * 2 * C;
     const double s1 = fold_strided(0.0, pg + c, (size_t)2 * C, splits);
     const double s2 = fold_strided(0.0, pg + C + c, (size_t)2 * C, splits);
-    bn_finalize(s1, s2, count, eps, momentum, running_mean, running_var, c, mean[(size_t)g * C + c], rstd[(size_t)g * C + c]);
+    bn_finalize(s1, s2, count, eps, momentum, running_mean, running_var, c, mean[(size_t)g * C + c], rstd[(size_t)g * C + c],
+                uvar ? uvar + (size_t)g * C + c : nullptr);
   }
 }
 // backward: fold every group's partial sums into dsums [G][2C] and (optionally) the parameter gradients, which add up over
@@ -173,6 +192,44 @@ __global__ void bn_eval_stats_kernel(const float* rm, const float* rv, float eps
   if (c >= C) return;
   mean[c] = rm[c];
   rstd[c] = 1.f / sqrtf(rv[c] + eps);
+}
+
+// Replay of running-buffer updates.  A network pass whose results are reused instead of recomputed (same weights, same
+// input: solvers/intro.py:119-120 after :70,75) still owes every BatchNorm layer the update the second pass would have
+// made: the same batch statistics, blended once more into buffers that other passes have advanced in between.  One
+// launch for all layers of the network: record i covers blocks [block0, block0 + cdiv(C, 256)), a thread owns a channel
+// and walks the groups in order with the expression of bn_finalize (bn_blend); `mean` / `uvar` are the [G][C] floats the
+// forward saved (BnFinal::mean / ::uvar).
+struct BnReplayDesc {
+  float* running_mean;   // may be null
+  float* running_var;    // may be null
+  int64_t* nbt;          // may be null
+  const float* mean;
+  const float* uvar;
+  int C, G;
+  float momentum;
+  int block0;
+};
+static_assert(sizeof(BnReplayDesc) == 56, "BnReplayDesc layout is part of the ABI (itcv_bn_replay_desc_bytes)");
+constexpr int kBnReplayMaxDesc = 64;
+
+__global__ __launch_bounds__(256) void bn_replay_many(const BnReplayDesc* __restrict__ tab, int n) {
+  int di = 0;
+  while (di + 1 < n && (int)blockIdx.x >= tab[di + 1].block0) ++di;
+  const BnReplayDesc d = tab[di];
+  const int c = ((int)blockIdx.x - d.block0) * 256 + (int)threadIdx.x;
+  if (c >= d.C) return;
+  if (c == 0 && d.nbt) d.nbt[0] += d.G;
+  if (d.running_mean) {
+    float r = d.running_mean[c];
+    for (int g = 0; g < d.G; ++g) r = bn_blend(r, d.mean[(size_t)g * d.C + c], d.momentum);
+    d.running_mean[c] = r;
+  }
+  if (d.running_var) {
+    float r = d.running_var[c];
+    for (int g = 0; g < d.G; ++g) r = bn_blend(r, d.uvar[(size_t)g * d.C + c], d.momentum);
+    d.running_var[c] = r;
+  }
 }
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
@@ -242,6 +299,7 @@ struct BnStatsIn {
   int64_t* nbt;
   float* mean_out;
   float* rstd_out;
+  float* uvar_out;   // [G][C] or null, as BnFinal::uvar
 };
 
 // Plane stores of a wave: every thread holds PX consecutive 16-byte chunks (its PX pixels) per plane.  Stored straight
@@ -320,7 +378,8 @@ __global__ __launch_bounds__(256) void bn_act_fwd_planes_kernel(
                 t2 = fold_strided(0.0, pg + C + c, (size_t)2 * C, st.splits);
               }
               float um, ur;   // (not stored: every group's own block records its mean / rstd)
-              bn_finalize(t1, t2, st.count, st.eps, st.momentum, st.running_mean, st.running_var, c, um, ur);
+              bn_finalize(t1, t2, st.count, st.eps, st.momentum, st.running_mean, st.running_var, c, um, ur,
+                          st.uvar_out ? st.uvar_out + (size_t)gg * C + c : nullptr);
             }
             if (c == 0 && st.nbt) st.nbt[0] += G;
           }
@@ -1017,7 +1076,7 @@ static int bn_stats_launch(const BnPlan& p, const float* x, int B, int C, int HW
   ITCV_CHECK_LAUNCH(who);
   if (p.splits > 1 && p.path != BnPath::SlicedFold) {
     hipLaunchKernelGGL(bn_combine_finalize_groups_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, p.splits, p.G, f.count,
-                       f.eps, f.momentum, f.running_mean, f.running_var, f.nbt, f.mean, f.rstd, C);
+                       f.eps, f.momentum, f.running_mean, f.running_var, f.nbt, f.mean, f.rstd, f.uvar, C);
     ITCV_CHECK_LAUNCH(who);
   }
   return 0;
@@ -1164,18 +1223,25 @@ int itcv_bn_train_stats(const float* x, int B, int C, int HW, float eps, float m
                         size_t ws_bytes, void* stream) {
   ITCV_REQUIRE(x && mean && rstd && B > 0 && C > 0 && HW > 0, "itcv_bn_train_stats");
   const BnPlan p = bn_plan(false, B, C, HW, 1, 0, 0, 1, false, 0, 0, ws ? ws_bytes : 0, false);
-  const BnFinal f{(double)B * HW, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd};
+  const BnFinal f{(double)B * HW, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, nullptr};
   return bn_stats_launch(p, x, B, C, HW, f, ws, ws_bytes, S(stream), "itcv_bn_train_stats");
+}
+
+int itcv_bn_finalize_uv(const double* sums, double count, float eps, float momentum, float* running_mean,
+                        float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd, float* unbiased_var,
+                        int C, void* stream) {
+  ITCV_REQUIRE(sums && mean && rstd && C > 0 && count > 0, "itcv_bn_finalize");
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, S(stream), sums, count, eps, momentum,
+                     running_mean, running_var, num_batches_tracked, mean, rstd, unbiased_var, C);
+  ITCV_CHECK_LAUNCH("itcv_bn_finalize");
+  return 0;
 }
 
 int itcv_bn_finalize(const double* sums, double count, float eps, float momentum, float* running_mean,
                      float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd, int C,
                      void* stream) {
-  ITCV_REQUIRE(sums && mean && rstd && C > 0 && count > 0, "itcv_bn_finalize");
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, S(stream), sums, count, eps, momentum,
-                     running_mean, running_var, num_batches_tracked, mean, rstd, C);
-  ITCV_CHECK_LAUNCH("itcv_bn_finalize");
-  return 0;
+  return itcv_bn_finalize_uv(sums, count, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, nullptr,
+                             C, stream);
 }
 
 int itcv_bn_eval_stats(const float* running_mean, const float* running_var, float eps, float* mean, float* rstd,
@@ -1235,11 +1301,13 @@ int itcv_bn_act_bwd_apply(const float* x, const float* dy, const float* mean, co
 // groups > 1: `groups` BatchNorm groups of B images each, stacked along the batch dimension of x / y / planes; mean / rstd
 // are [groups][C], dsums is [groups][2C].  One reduce launch (the running buffers and the parameter gradients advance group
 // by group, in order) and one apply launch with the group in blockIdx.z, or (BnPath::PerGroup) the groups one by one.
-int itcv_bn_train_fwd(const float* x, const float* gamma, const float* beta, const float* skip, float* y, void* planes,
-                      int ns, int B, int C, int H, int W, float slope, int pool, float eps, float momentum,
-                      float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd,
-                      void* ws, size_t ws_bytes, size_t plane_stride, const float* tile_stats, int tiles, int tile_pitch,
-                      int groups, void* stream) {
+// itcv_bn_train_fwd_uv: the same call, also leaving the unbiased variance every group blended into running_var in
+// unbiased_var [groups][C] (null: not wanted) -- what itcv_bn_replay_many needs to repeat the update later.
+int itcv_bn_train_fwd_uv(const float* x, const float* gamma, const float* beta, const float* skip, float* y, void* planes,
+                         int ns, int B, int C, int H, int W, float slope, int pool, float eps, float momentum,
+                         float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd,
+                         float* unbiased_var, void* ws, size_t ws_bytes, size_t plane_stride, const float* tile_stats,
+                         int tiles, int tile_pitch, int groups, void* stream) {
   ITCV_REQUIRE(x && gamma && beta && mean && rstd && (y || planes) && B > 0 && C > 0 && H > 0 && W > 0, "itcv_bn_train_fwd");
   // roofline leg of bench.py: one event pair around the apply kernel (HBM-bound: its "work" is algorithmic bytes -- read
   // x once more [+ skip], write the planes [+ the fp32 output])
@@ -1256,28 +1324,69 @@ int itcv_bn_train_fwd(const float* x, const float* gamma, const float* beta, con
   if (p.path == BnPath::PerGroup) {
     const BnGrp& s = p.grp;
     for (int g = 0; g < groups; ++g)
-      if (int e = itcv_bn_train_fwd(x + g * s.xs, gamma, beta, skip ? skip + g * s.xs : nullptr, y ? y + g * s.os : nullptr,
-                                    planes ? static_cast<u32x4*>(planes) + g * s.ps : nullptr, ns, B, C, H, W, slope, pool,
-                                    eps, momentum, running_mean, running_var, num_batches_tracked, mean + (size_t)g * C,
-                                    rstd + (size_t)g * C, ws, ws_bytes, plane_stride,
-                                    tile_stats ? tile_stats + (size_t)g * tiles : nullptr, tiles, tile_pitch, 1, stream))
+      if (int e = itcv_bn_train_fwd_uv(x + g * s.xs, gamma, beta, skip ? skip + g * s.xs : nullptr, y ? y + g * s.os : nullptr,
+                                       planes ? static_cast<u32x4*>(planes) + g * s.ps : nullptr, ns, B, C, H, W, slope, pool,
+                                       eps, momentum, running_mean, running_var, num_batches_tracked, mean + (size_t)g * C,
+                                       rstd + (size_t)g * C, unbiased_var ? unbiased_var + (size_t)g * C : nullptr, ws,
+                                       ws_bytes, plane_stride, tile_stats ? tile_stats + (size_t)g * tiles : nullptr, tiles,
+                                       tile_pitch, 1, stream))
         return e;
     return 0;
   }
-  const BnFinal f{(double)B * H * W, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd};
+  const BnFinal f{(double)B * H * W, eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, unbiased_var};
   if (p.path == BnPath::TileStats) {
     ITCV_REQUIRE(tiles > 0 && tile_pitch >= tiles, "itcv_bn_train_fwd(tile statistics)");
     hipLaunchKernelGGL(bn_tile_stats_finalize_kernel, dim3(C), dim3(256), 0, S(stream), tile_stats, tiles, tile_pitch, f.count,
-                       eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, C);
+                       eps, momentum, running_mean, running_var, num_batches_tracked, mean, rstd, unbiased_var, C);
     ITCV_CHECK_LAUNCH("itcv_bn_train_fwd(tile statistics)");
   } else if (int e = bn_stats_launch(p, x, B, C, H * W, f, ws, ws_bytes, S(stream), "itcv_bn_train_fwd(statistics)")) {
     return e;
   }
   const BnStatsIn fold = p.path == BnPath::SlicedFold
                              ? BnStatsIn{static_cast<const double*>(ws), p.splits, f.count, eps, momentum, running_mean,
-                                         running_var, num_batches_tracked, mean, rstd}
+                                         running_var, num_batches_tracked, mean, rstd, unbiased_var}
                              : BnStatsIn{};
   return bn_fwd_apply_launch(p, x, mean, rstd, gamma, beta, skip, y, planes, ns, B, C, H, W, slope, pool, fold, S(stream));
+}
+
+int itcv_bn_train_fwd(const float* x, const float* gamma, const float* beta, const float* skip, float* y, void* planes,
+                      int ns, int B, int C, int H, int W, float slope, int pool, float eps, float momentum,
+                      float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd,
+                      void* ws, size_t ws_bytes, size_t plane_stride, const float* tile_stats, int tiles, int tile_pitch,
+                      int groups, void* stream) {
+  return itcv_bn_train_fwd_uv(x, gamma, beta, skip, y, planes, ns, B, C, H, W, slope, pool, eps, momentum, running_mean,
+                              running_var, num_batches_tracked, mean, rstd, nullptr, ws, ws_bytes, plane_stride, tile_stats,
+                              tiles, tile_pitch, groups, stream);
+}
+
+// ---- replay of running-buffer updates (see BnReplayDesc) ------------------------------------------------------------
+size_t itcv_bn_replay_desc_bytes(void) { return sizeof(BnReplayDesc); }
+int itcv_bn_replay_max_descs(void) { return kBnReplayMaxDesc; }
+int itcv_bn_replay_desc(void* host_desc, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                        const float* mean, const float* unbiased_var, int C, int groups, float momentum, int block0) {
+  if (!(host_desc && C > 0 && groups >= 1 && block0 >= 0 && momentum >= 0.f && momentum <= 1.f) ||
+      (running_mean && !mean) || (running_var && !unbiased_var)) {
+    fail("%s: bad argument (descriptor, C > 0, groups >= 1, block0 >= 0, momentum in [0, 1], the saved statistics of every "
+         "running buffer given)", "itcv_bn_replay_desc");
+    return -1;
+  }
+  if (!running_mean && !running_var && !num_batches_tracked) return 0;   // track_running_stats=False: nothing to replay
+  BnReplayDesc d;
+  memset(&d, 0, sizeof(d));
+  d.running_mean = running_mean, d.running_var = running_var, d.nbt = num_batches_tracked;
+  d.mean = mean, d.uvar = unbiased_var;
+  d.C = C, d.G = groups, d.momentum = momentum, d.block0 = block0;
+  memcpy(host_desc, &d, sizeof(d));
+  return cdiv(C, 256);
+}
+int itcv_bn_replay_many(const void* dev_table, int n, int total_blocks, void* stream) {
+  ITCV_REQUIRE(dev_table && n > 0 && total_blocks > 0, "itcv_bn_replay_many");
+  if (n > kBnReplayMaxDesc)
+    return fail("%s: at most %d descriptors per table (itcv_bn_replay_max_descs)", "itcv_bn_replay_many", kBnReplayMaxDesc);
+  hipLaunchKernelGGL(bn_replay_many, dim3(total_blocks), dim3(256), 0, S(stream),
+                     static_cast<const BnReplayDesc*>(dev_table), n);
+  ITCV_CHECK_LAUNCH("itcv_bn_replay_many");
+  return 0;
 }
 
 int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,

@@ -89,6 +89,7 @@ SIGNATURES = {
     "itcv_bn_moments": (i32, [p, p, i32, i32, i32, p, sz, p]),
     "itcv_bn_train_stats": (i32, [p, i32, i32, i32, f32, f32, p, p, p, p, p, p, sz, p]),
     "itcv_bn_finalize": (i32, [p, f64, f32, f32, p, p, p, p, p, i32, p]),
+    "itcv_bn_finalize_uv": (i32, [p, f64, f32, f32, p, p, p, p, p, p, i32, p]),
     "itcv_bn_eval_stats": (i32, [p, p, f32, p, p, i32, p]),
     "itcv_bn_act_planes_supported": (i32, [i32] * 4),
     "itcv_bn_act_fwd": (i32, [p, p, p, p, p, p, p, i32, i32, i32, i32, f32, i32, p, i32, sz, p]),
@@ -98,6 +99,12 @@ SIGNATURES = {
                                     i32, i32, p, i32, sz, p]),
     "itcv_bn_train_fwd": (i32, [p, p, p, p, p, p, i32, i32, i32, i32, i32, f32, i32, f32, f32, p, p, p, p, p, p, sz, sz, p, i32, i32,
                                 i32, p]),
+    "itcv_bn_train_fwd_uv": (i32, [p, p, p, p, p, p, i32, i32, i32, i32, i32, f32, i32, f32, f32, p, p, p, p, p, p, p, sz, sz, p, i32,
+                                   i32, i32, p]),
+    "itcv_bn_replay_desc_bytes": (sz, []),
+    "itcv_bn_replay_desc": (i32, [p, p, p, p, p, p, i32, i32, f32, i32]),
+    "itcv_bn_replay_many": (i32, [p, i32, i32, p]),
+    "itcv_bn_replay_max_descs": (i32, []),
     "itcv_bn_train_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, p, i32, p, p, i32, i32, i32, i32, i32, f32, i32, i32, p,
                                 sz, sz, i32, p]),
     "itcv_bn_plan_query": (i32, [i32] * 10 + [sz, i32, p, p]),

@@ -74,6 +74,101 @@ def _grad_target(param):
     return g if (g is not None and g.is_contiguous() and g.dtype == F32) else None
 
 
+# ------------------------------------------------------------------ one recorded pass, two backward passes
+# A network pass that two losses need with the same weights and the same input is recorded once (the intro step's
+# dec(noise | z), solvers/intro.py).  What the skipped second pass would have done beyond recomputing the same tensors
+# is made up for here:
+#   * its BatchNorm running-buffer updates: BnActFn leaves the two floats every group blended into the buffers in a
+#     persistent [2][G][C] tensor per layer and ``replay()`` repeats the updates, for all layers in one launch, at the
+#     point of the stream where the second pass used to run;
+#   * its parameter gradients: the pass is recorded with its parameters requiring a gradient, and ``param_grads`` tells
+#     Conv2dFn / LinearFn / BnActFn.backward whether a backward pass through it may compute and accumulate them (they add
+#     straight into the flat .grad buffers from inside those functions, out of autograd's sight);
+#   * ``input_grad`` False: the first function of the pass does not compute the gradient of the pass's input.
+_SHARED_PASS = [None]
+
+
+class SharedPass:
+    """Owned by a solver (the statistics buffers and the device table are persistent: a captured hipGraph bakes their
+    addresses in, so they are never freed or rebuilt while this object lives)."""
+
+    def __init__(self):
+        self.param_grads = True
+        self.input_grad = True
+        self.records = []
+        self._first = False
+        self._pool = {}
+        self._tables = {}
+
+    @contextlib.contextmanager
+    def record(self):
+        """Forward calls inside this block belong to the pass: their BatchNorm layers are collected for ``replay``."""
+        prev, _SHARED_PASS[0] = _SHARED_PASS[0], self
+        self.records, self._first = [], True
+        self.param_grads = self.input_grad = True
+        try:
+            yield self
+        finally:
+            _SHARED_PASS[0] = prev
+
+    def _claim_first(self):
+        first, self._first = self._first, False
+        return first
+
+    def _stats(self, G, C, device):
+        """[2][G][C] (mean, unbiased variance) of the next BatchNorm layer of the pass: one buffer per position."""
+        k = (len(self.records), G, C, str(device))
+        buf = self._pool.get(k)
+        if buf is None:
+            buf = self._pool[k] = torch.empty((2, G, C), dtype=F32, device=device)
+        return buf
+
+    def replay(self):
+        """Repeats the running-buffer updates of every BatchNorm layer recorded by the last ``record()`` block."""
+        replay_bn_running(self.records, self._tables)
+
+
+def _shared_ok(ctx, what):
+    sp = ctx.shared
+    return sp is None or getattr(sp, what)
+
+
+def replay_bn_running(records, tables=None):
+    """records: (running_mean, running_var, num_batches_tracked, mean [G][C], unbiased variance [G][C], momentum) per
+    BatchNorm call, as BnActFn leaves them inside ``SharedPass.record()``.  Advances every layer's buffers as a second
+    forward over the same batch would: ONE launch (itcv_bn_replay_many).  ``tables``: dict that keeps the device tables
+    alive, one per sequence of pointers; the caller owns it for as long as a captured graph may replay the launch.
+    Without it the table lives for this (eager, stream-ordered) launch only."""
+    import ctypes
+    if tables is None:
+        tables = {}
+    recs = [r for r in records if r[0] is not None or r[1] is not None or r[2] is not None]
+    if not recs:
+        return
+    key = tuple((0 if r[0] is None else r[0].data_ptr(), 0 if r[1] is None else r[1].data_ptr(),
+                 0 if r[2] is None else r[2].data_ptr(), r[3].data_ptr(), r[4].data_ptr(), tuple(r[3].shape), r[5])
+                for r in recs)
+    tab = tables.get(key)
+    if tab is None:
+        if len(recs) > lib.itcv_bn_replay_max_descs():
+            raise abi.HipExtensionError("replay_bn_running: more BatchNorm layers than one table holds")
+        nb = lib.itcv_bn_replay_desc_bytes()
+        host = (ctypes.c_uint8 * (nb * len(recs)))()
+        blocks = 0
+        for i, (rm, rv, nbt, mean, uvar, momentum) in enumerate(recs):
+            G, C = mean.shape
+            got = lib.itcv_bn_replay_desc(ctypes.byref(host, i * nb), ptr(rm), ptr(rv), ptr(nbt), ptr(mean), ptr(uvar), C, G,
+                                          float(momentum), blocks)
+            if got <= 0:
+                raise abi.HipExtensionError("itcv_bn_replay_desc: " + abi.last_error())
+            blocks += got
+        # the records keep the tensors the table points at alive with the table
+        tab = tables[key] = (torch.frombuffer(bytearray(host), dtype=torch.uint8).to(recs[0][3].device), len(recs), blocks,
+                             recs)
+    call("itcv_bn_replay_many", ptr(tab[0]), tab[1], tab[2], stream())
+
+
+
 # (Round 1 issued the weight-gradient GEMMs on a second HIP stream; with the batched passes of round 2 they fill the chip
 # on their own and running them beside the data-gradient chain cost more than the gaps it filled -- same-box A/B of the c2
 # step 18.45 vs 18.0 ms -- so the side stream is gone.)
@@ -681,6 +776,8 @@ class Conv2dFn(Function):
         ctx.save_for_backward(None if keep_xp is not None else _require_fp32(x, "Conv2dFn.forward (saved input)"),
                               weight, bias, keep_xp)
         ctx.cfg = (B, Ci, H, W, Co, KS, up2, bias is not None, (Hs, Ws))
+        ctx.shared = _SHARED_PASS[0]
+        ctx.shared_first = ctx.shared is not None and ctx.shared._claim_first()
         return y
 
     @staticmethod
@@ -690,13 +787,17 @@ class Conv2dFn(Function):
         B, Ci, H, W, Co, KS, up2, has_bias, (Hs, Ws) = ctx.cfg
         dy = _f32c(dy)
         dx = dw = db = None
-        ns_d = _planes_ns(Co, Ci, KS, False) if ctx.needs_input_grad[0] else 0
-        wg_planes = ctx.needs_input_grad[1] and _wgrad_planes_ok(B, Ci, H, W, Co, KS)
+        # a pass shared by two backward passes (SharedPass): parameter / input gradients only where this one wants them
+        need_x = ctx.needs_input_grad[0] and not (ctx.shared_first and not ctx.shared.input_grad)
+        need_w = ctx.needs_input_grad[1] and _shared_ok(ctx, "param_grads")
+        need_b = ctx.needs_input_grad[2] and _shared_ok(ctx, "param_grads")
+        ns_d = _planes_ns(Co, Ci, KS, False) if need_x else 0
+        wg_planes = need_w and _wgrad_planes_ok(B, Ci, H, W, Co, KS)
         dyp = None
         fmt2 = F16X2 if _NS[_CONV_MATH[0]] == F16X2 else 2       # the two-plane format of the current mode
         if ns_d or wg_planes:
             dyp = planes_of(dy, ns_d if ns_d else fmt2, gradient=True)
-        if ctx.needs_input_grad[0]:
+        if need_x:
             if ns_d:
                 dx = conv_apply_planes(dyp, weight, weight, 1, None, B, Co, H, W, Ci, KS, False, ns_d)
             else:
@@ -705,7 +806,7 @@ class Conv2dFn(Function):
                 lo = torch.empty((B, Ci, H // 2, W // 2), dtype=F32, device=dy.device)
                 call("itcv_upsample2_bwd", ptr(dx), ptr(lo), B * Ci, H // 2, W // 2, stream())
                 dx = lo
-        wg5 = _wgrad5_mode(Ci, H, W, Co, KS, up2) if ctx.needs_input_grad[1] else None
+        wg5 = _wgrad5_mode(Ci, H, W, Co, KS, up2) if need_w else None
         if wg5 == "predict" and xp is None and x is None:
             wg5 = None
         if wg5 is not None:
@@ -719,7 +820,7 @@ class Conv2dFn(Function):
                 conv_wgrad5_planes(small, big, B, cs, H, W, wg5 == "stem", out=tgt, accumulate=True, ns=fmt2)
             else:
                 dw = conv_wgrad5_planes(small, big, B, cs, H, W, wg5 == "stem", ns=fmt2)
-        elif ctx.needs_input_grad[1]:
+        elif need_w:
             tgt = _grad_target(weight)
             if wg_planes and (ns_d in (0, fmt2)):
                 if xp is None:
@@ -736,7 +837,7 @@ class Conv2dFn(Function):
                     conv_wgrad_raw(x, dy, B, Ci, H, W, Co, KS, up2, out=tgt, accumulate=True)
                 else:
                     dw = conv_wgrad_raw(x, dy, B, Ci, H, W, Co, KS, up2)
-        if has_bias and ctx.needs_input_grad[2]:
+        if has_bias and need_b:
             db = bias_grad_raw(_require_fp32(dy, "Conv2dFn.backward (bias gradient)"), B, Co, H * W, _grad_target(bias))
         return dx, dw, db, None
 
@@ -756,6 +857,8 @@ class LinearFn(Function):
              nws, stream())
         ctx.save_for_backward(x, weight, bias)
         ctx.cfg = (B, K, N, bias is not None)
+        ctx.shared = _SHARED_PASS[0]
+        ctx.shared_first = ctx.shared is not None and ctx.shared._claim_first()
         return y
 
     @staticmethod
@@ -766,17 +869,18 @@ class LinearFn(Function):
         dy = _f32c(dy)
         dx = dw = db = None
         nws = lib.itcv_linear_workspace(B, K, N)
-        if ctx.needs_input_grad[0]:
+        need_p = _shared_ok(ctx, "param_grads")       # see SharedPass
+        if ctx.needs_input_grad[0] and not (ctx.shared_first and not ctx.shared.input_grad):
             dx = torch.empty((B, K), dtype=F32, device=dy.device)
             ws = _ws(nws, dy.device) if nws else None
             call("itcv_linear_dgrad", ptr(dy), ptr(weight), ptr(dx), B, K, N, ptr(ws), nws, stream())
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and need_p:
             tgt = _grad_target(weight)
             dw = None if tgt is not None else torch.empty((N, K), dtype=F32, device=dy.device)
             ws = _ws(nws, dy.device) if nws else None
             call("itcv_linear_wgrad", ptr(dy), ptr(x), ptr(tgt if tgt is not None else dw), B, K, N,
                  int(tgt is not None), ptr(ws), nws, stream())
-        if has_bias and ctx.needs_input_grad[2]:
+        if has_bias and ctx.needs_input_grad[2] and need_p:
             db = bias_grad_raw(dy, B, N, 1, _grad_target(bias))
         return dx, dw, db
 
@@ -805,7 +909,13 @@ class BnActFn(Function):
             raise abi.HipExtensionError(f"BatchNorm groups: batch {B} is not {G} equal passes")
         Bg = B // G
         dev = x.device
-        mean = torch.empty((G, C), dtype=F32, device=dev)
+        shared = _SHARED_PASS[0]
+        uvar = None
+        if shared is not None and training:
+            # mean and the unbiased variance blended into running_var go to the pass's persistent buffer (SharedPass.replay)
+            mean, uvar = shared._stats(G, C, dev)
+        else:
+            mean = torch.empty((G, C), dtype=F32, device=dev)
         rstd = torch.empty((G, C), dtype=F32, device=dev)
         world = _world(group) if training else 1
         oshape = (B, C, H // 2, W // 2) if pool else (B, C, H, W)
@@ -828,10 +938,15 @@ class BnActFn(Function):
             # statistics + apply for all G groups in one call (small layers: one statistics launch walking the groups in
             # order + one apply launch; large layers: the groups one after the other inside the library)
             ws = _ws(nws, dev)
-            call("itcv_bn_train_fwd", ptr(x), ptr(gamma), ptr(beta), ptr(skip), ptr(y) if write_y else None, ptr(yp),
-                 int(out_planes), Bg, C, H, W, float(slope), int(pool), float(eps), float(momentum), ptr(running_mean),
-                 ptr(running_var), ptr(nbt), ptr(mean), ptr(rstd), ptr(ws), nws, pstride,
-                 None if ts is None else ts[0].data_ptr(), ts[1] if ts else 0, ts[2] if ts else 0, G, stream())
+            head = (ptr(x), ptr(gamma), ptr(beta), ptr(skip), ptr(y) if write_y else None, ptr(yp), int(out_planes), Bg, C, H,
+                    W, float(slope), int(pool), float(eps), float(momentum), ptr(running_mean), ptr(running_var), ptr(nbt),
+                    ptr(mean), ptr(rstd))
+            tail = (ptr(ws), nws, pstride, None if ts is None else ts[0].data_ptr(), ts[1] if ts else 0, ts[2] if ts else 0,
+                    G, stream())
+            if uvar is None:
+                call("itcv_bn_train_fwd", *head, *tail)
+            else:
+                call("itcv_bn_train_fwd_uv", *head, ptr(uvar), *tail)
         for g in (range(G) if not (training and world == 1) else ()):
             r = slice(g * Bg, (g + 1) * Bg)
             xg, yg = x[r], (y[r] if write_y else None)
@@ -842,8 +957,9 @@ class BnActFn(Function):
                 sums = torch.empty((2 * C,), dtype=torch.float64, device=dev)
                 call("itcv_bn_moments", ptr(xg), ptr(sums), Bg, C, H * W, ptr(ws), nws, stream())
                 dist.all_reduce(sums, group=group)
-                call("itcv_bn_finalize", ptr(sums), float(Bg * H * W * world), float(eps), float(momentum),
-                     ptr(running_mean), ptr(running_var), ptr(nbt), ptr(mean[g]), ptr(rstd[g]), C, stream())
+                call("itcv_bn_finalize_uv", ptr(sums), float(Bg * H * W * world), float(eps), float(momentum),
+                     ptr(running_mean), ptr(running_var), ptr(nbt), ptr(mean[g]), ptr(rstd[g]),
+                     None if uvar is None else ptr(uvar[g]), C, stream())
             else:
                 call("itcv_bn_eval_stats", ptr(running_mean), ptr(running_var), float(eps), ptr(mean[g]), ptr(rstd[g]), C,
                      stream())
@@ -853,6 +969,9 @@ class BnActFn(Function):
             if _POISON[0] and not out_fp32:
                 y.fill_(float("nan"))
             _tag_planes(y, yp, out_planes, bool(out_fp32))
+        if uvar is not None:
+            shared.records.append((running_mean, running_var, nbt, mean, uvar, float(momentum)))
+        ctx.shared = shared
         ctx.save_for_backward(x, gamma, beta, mean, rstd, skip)
         ctx.params = (gamma, beta)
         if not lib.itcv_bn_act_planes_supported(C, H, W, 0):
@@ -875,15 +994,17 @@ class BnActFn(Function):
         nws = lib.itcv_bn_workspace(Bg, C, H * W) * G
         # parameter gradients come out of the reduce launch: either added straight into .grad
         # (solver mode) or into fresh tensors handed to autograd
-        tg = _grad_target(gamma) if ctx.needs_input_grad[1] else None
-        tb = _grad_target(beta) if ctx.needs_input_grad[2] else None
+        need_g = ctx.needs_input_grad[1] and _shared_ok(ctx, "param_grads")       # see SharedPass
+        need_b = ctx.needs_input_grad[2] and _shared_ok(ctx, "param_grads")
+        tg = _grad_target(gamma) if need_g else None
+        tb = _grad_target(beta) if need_b else None
         direct = tg is not None and tb is not None
         dgamma = dbeta = None
         if direct:
             pg, pb = tg, tb
         else:
-            dgamma = torch.empty_like(gamma) if ctx.needs_input_grad[1] else None
-            dbeta = torch.empty_like(beta) if ctx.needs_input_grad[2] else None
+            dgamma = torch.empty_like(gamma) if need_g else None
+            dbeta = torch.empty_like(beta) if need_b else None
             pg, pb = dgamma, dbeta
         dx = torch.empty_like(x)
         dskip = torch.empty_like(x) if (skip is not None and ctx.needs_input_grad[3]) else None

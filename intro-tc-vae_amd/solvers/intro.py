@@ -11,8 +11,8 @@ import torch
 from torch import Tensor
 
 from hipvae import ddp
-from hipvae.functional import ExpElboFn
-from models import bn_groups
+from hipvae.functional import ExpElboFn, SharedPass
+from models import _has_hooks, bn_groups
 from ops import noise, reparameterize
 from solvers.vae import VAESolver
 
@@ -31,6 +31,22 @@ class IntroSolver(VAESolver):
         # the pixels, and the results are those of separate passes (per-pass batch statistics, same draw order, same
         # running-buffer order).  ``batch_passes = False`` issues the 13 passes one by one (the tests compare the two).
         self.batch_passes = True
+        # Both phases open with dec(noise | z) (intro.py:70,75 and :119-120).  Between the two only the ENCODER is updated:
+        # same decoder weights, same noise, same z, batch statistics, deterministic kernels -- the second pass recomputes
+        # the first bit for bit.  With ``share_decoder_pass`` the batched schedule records it once, with the decoder's
+        # parameters requiring a gradient: phase E's backward runs through it for the data gradient alone, phase D's a
+        # second time for the decoder's gradients, and where phase D used to issue the pass one launch repeats its
+        # BatchNorm running-buffer updates (hipvae.functional.SharedPass).  Losses, norms, parameters, optimiser state and
+        # buffers are bitwise those of ``False``, the schedule with the pass issued twice (the tests compare the two).
+        # A decoder with forward hooks always takes that schedule: a hook must fire once per pass of the reference.
+        self.share_decoder_pass = True
+        self._shared_pass = SharedPass()
+
+    def _shares_pass(self) -> bool:
+        return bool(self.batch_passes and self.share_decoder_pass) and not _has_hooks(self.model.decoder)
+
+    def _schedule_key(self) -> tuple:
+        return (bool(self.batch_passes), self._shares_pass())
 
     def _exp_elbo(self, rec_rows: Tensor, kl_rows: Tensor) -> Tensor:
         """intro.py:102-103  mean_j exp(-2 * scale * (rec_j + kl_j))."""
@@ -51,13 +67,20 @@ class IntroSolver(VAESolver):
         def two():
             return bn_groups(2)
 
+        share, shared = self._shares_pass(), self._shared_pass
         noise_batch = noise((real.size(0), model.zdim), self.device)               # intro.py:61
         # ================= update E (decoder frozen) ======================== intro.py:65-116
         self._set_trainable(encoder=True, decoder=False)
         real_mu, real_logvar = model.encode(real)
         z = reparameterize(real_mu, real_logvar)
-        with two():                                    # fake = sample(noise) | rec = decoder(z)      intro.py:70,75
-            fake, rec = model.decoder(cat([noise_batch, z])).chunk(2)
+        if share:                                      # the one dec(noise | z) of the step: recorded for both phases
+            self._set_trainable(encoder=True, decoder=True)
+            with two(), shared.record():
+                fake, rec = model.decoder(cat([noise_batch, z])).chunk(2)
+            self._set_trainable(encoder=True, decoder=False)
+        else:
+            with two():                                # fake = sample(noise) | rec = decoder(z)      intro.py:70,75
+                fake, rec = model.decoder(cat([noise_batch, z])).chunk(2)
         loss_rec = self.compute_rec_loss(real, rec, reduction="mean")
         loss_e_real_kl = self.compute_kl_loss(z, real_mu, real_logvar, write=True)
         with two():                                    # model(rec.detach()) | model(fake.detach())   intro.py:81-82
@@ -73,15 +96,30 @@ class IntroSolver(VAESolver):
         expelbo_fake = self._exp_elbo(self.compute_rec_loss(fake, rec_fake, reduction="none"), kl_fake)
         # scale * (loss_rec + loss_e_real_kl) + 0.25 * (expelbo_rec + expelbo_fake), intro.py:105-108
         loss_e = self._lincomb((scale, scale, 0.25, 0.25), loss_rec, loss_e_real_kl, expelbo_rec, expelbo_fake)
-        finish_average = self._backward(loss_e, ("encoder",), defer_average=True)
+        # the shared pass: data gradient down to z only -- _clip() below takes its norm over the decoder's STALE gradients
+        # (intro.py:113-115), one stray add into them changes norm_E and the encoder update -- and its tape survives
+        shared.param_grads = False
+        finish_average = self._backward(loss_e, ("encoder",), defer_average=True, retain_graph=share)
+        shared.param_grads = True
 
         # ================= update D (encoder frozen) ======================== intro.py:118-160
-        # The decoder-only pass that opens this phase depends neither on the encoder's gradients nor on its update: it
-        # is issued while the encoder-gradient all-reduce is in flight (data-parallel runs), then the encoder update
-        # completes.  Single-process: same kernels, same results, commuting order.
         self._set_trainable(encoder=False, decoder=True)
-        with two():                                    # fake = sample(noise) | rec = decoder(z.detach())   intro.py:119-120
-            fake, rec = model.decoder(cat([noise_batch, z.detach()])).chunk(2)
+        if share:
+            # phase E's tape was retained for the shared pass alone: every other reference into it goes now
+            loss_e, loss_e_real_kl, expelbo_fake = loss_e.detach(), loss_e_real_kl.detach(), expelbo_fake.detach()
+            del (loss_rec, mu2, logvar2, rec_mu, fake_mu, rec_logvar, fake_logvar, z_rec, z_fake, rec_rec, rec_fake, kl_rec,
+                 kl_fake, expelbo_rec, real_mu, real_logvar, z)
+            # fake | rec of intro.py:119-120 are the tensors phase E holds.  What the repeated pass would still have done
+            # happens here, where it used to run: every decoder BatchNorm layer's running buffers advance once more, after
+            # the updates dec(z_rec | z_fake) made above.  One short launch: in data-parallel runs nothing of substance
+            # overlaps the encoder-gradient all-reduce any more.
+            shared.replay()
+        else:
+            # The decoder-only pass that opens this phase depends neither on the encoder's gradients nor on its update: it
+            # is issued while the encoder-gradient all-reduce is in flight (data-parallel runs), then the encoder update
+            # completes.  Single-process: same kernels, same results, commuting order.
+            with two():                                # fake = sample(noise) | rec = decoder(z.detach())   intro.py:119-120
+                fake, rec = model.decoder(cat([noise_batch, z.detach()])).chunk(2)
         finish_average()
         norm_e = self._clip()
         self._step("encoder")
@@ -101,7 +139,13 @@ class IntroSolver(VAESolver):
         # scale * (loss_rec + (kl_rec + kl_fake) * 0.5 + (rec_rec + fake_rec) * 0.5), intro.py:149-151
         loss_d = self._lincomb((scale, 0.5 * scale, 0.5 * scale, 0.5 * scale, 0.5 * scale), loss_rec, loss_d_rec_kl,
                                loss_d_fake_kl, loss_rec_rec, loss_fake_rec)
-        self._backward(loss_d, ("decoder",))
+        if share:
+            # second walk through the shared pass, now for the decoder's gradients; it stops at the pass's input (no
+            # gradient for z, no second walk into the encoder's real-image pass, whose tape hangs behind it)
+            shared.input_grad = False
+            self._backward(loss_d, ("decoder",), inputs=self._params("decoder"))
+        else:
+            self._backward(loss_d, ("decoder",))
         norm_d = self._clip()
         self._step("decoder")
 

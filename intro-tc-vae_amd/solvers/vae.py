@@ -107,17 +107,18 @@ class VAESolver:
         for p in self._params("decoder"):
             p.requires_grad = decoder
 
-    def _backward(self, loss, parts, defer_average=False):
+    def _backward(self, loss, parts, defer_average=False, retain_graph=False, inputs=None):
         """optimizer.zero_grad() of ``parts`` + loss.backward() + gradient averaging over ranks.  With
         ``defer_average`` the all-reduces are only started; the returned callable finishes them (data-parallel runs
-        overlap them with work that does not depend on the averaged gradients)."""
+        overlap them with work that does not depend on the averaged gradients).  ``retain_graph`` / ``inputs``: those of
+        ``Tensor.backward`` (``inputs``: the walk runs only the nodes that lead to these tensors)."""
         groups = [self._group(p) for p in parts]
         for g in groups:
             g.zero_grad()
         # wgrad / BN / bias kernels add straight into the flat buffers; the planes weight gradients' slab reduces of the whole
         # backward pass are folded by one launch when it is over
         with direct_grad_accumulation(), deferred_wgrad_reduces():
-            loss.backward()
+            loss.backward(retain_graph=retain_graph, inputs=inputs)
         if defer_average:
             pending = [ddp.average_async(g.flat_g) for g in groups]
             return lambda: [f() for f in pending]
@@ -178,7 +179,8 @@ class VAESolver:
         # the optimiser hyper-parameters are scalar kernel arguments frozen into a captured graph: the update specs are
         # part of its key, so a scheduler or manual decay of param_groups[0]["lr"] re-captures instead of being ignored
         # the TC solvers' KL hook ("simple" | "full") selects different kernels: a switch re-captures too
-        key = (tuple(real.shape), real.dtype, self.conv_math) + specs + (getattr(self, "kl_loss", None),)
+        key = (tuple(real.shape), real.dtype, self.conv_math) + specs + self._schedule_key() \
+            + (getattr(self, "kl_loss", None),)
         from hipvae.functional import bump_weight_epoch
         graphs = self.__dict__.setdefault("_graphs", {})
         ent = graphs.get(key)
@@ -216,6 +218,10 @@ class VAESolver:
         ent["graph"].replay()
         bump_weight_epoch()                              # eager users after a replay must re-pack
         return ent["out"]
+
+    def _schedule_key(self) -> tuple:
+        """What else selects the kernels of a step (part of the captured graph's key)."""
+        return ()
 
     # ---- solvers/vae.py:89-136 ---------------------------------------------------------------
     def _device_step(self, real: Tensor) -> Tensor:
