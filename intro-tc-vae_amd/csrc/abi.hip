@@ -15,7 +15,7 @@ static bool g_prof_on = false;
 static std::vector<ProfRec> g_prof;
 
 static thread_local int g_prof_depth = 0;   // nested scopes (an entry point calling another one) belong to the outermost
-ProfScope::ProfScope(hipStream_t stream, int kind, int ks, int bm, int up2, int ns, double flop) : st(stream), slot(-1) {
+ProfScope::ProfScope(hipStream_t stream, ProfKind kind, int ks, int bm, int up2, int ns, double flop) : st(stream), slot(-1) {
   if (++g_prof_depth > 1 || !g_prof_on) return;
   ProfRec r;
   r.code = kind | (ks << 4) | (bm << 8) | (up2 << 16) | (ns << 20);

@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/itcv_hip.h"
 
 namespace itcv {
@@ -194,10 +196,29 @@ constexpr int kAbsmaxParts = 256;   // block maxima written by itcv_absmax (one 
 // When enabled, a HIP event pair is recorded on the launch stream immediately around the MAIN kernel
 // of a conv call (not its split-K reduce), tagged with the kernel family / template parameters and the
 // algorithmic FLOP of the launch.  Off by default; never used under graph capture.
+// Which kernel family a record belongs to.  The values are part of the record's code, which hipvae/functional.py decodes
+// by number (LaunchProfile.KINDS): keep the two in step.
+enum ProfKind : int {
+  kProfFwd = 0,             // conv_fwd_kernel
+  kProfFwdB = 1,            // conv_fwd_bf16s_ws_kernel
+  kProfWgrad = 2,           // conv_wgrad_kernel
+  kProfWgradB = 3,          // conv_wgrad_bf16s_kernel
+  kProfSmallCout = 4,       // conv_small_cout_kernel
+  kProfSmallCin = 5,        // conv_small_cin_kernel
+  kProfFwdP = 6,            // conv_fwd_bf16p_kernel
+  kProfWgradP = 7,          // conv_wgrad_bf16p_kernel
+  kProfFwdBand = 8,         // conv_fwd_bf16p2_kernel
+  kProfFwdBandPersist = 9,  // conv_fwd_bf16p3_kernel
+  kProfSmallCoutP = 10,     // conv_small_cout_planes_kernel
+  kProfSmallCinMfma = 11,   // conv_small_cin_mfma_kernel
+  kProfWgrad5 = 12,         // conv_wgrad5_planes_kernel
+  kProfBnFwd = 13,          // bn_act_fwd_planes_kernel
+  kProfBnBwd = 14,          // bn_bwd_apply_planes
+};
 struct ProfScope {
   hipStream_t st;
   int slot;
-  ProfScope(hipStream_t stream, int kind, int ks, int bm, int up2, int ns, double flop);
+  ProfScope(hipStream_t stream, ProfKind kind, int ks, int bm, int up2, int ns, double flop);
   ~ProfScope();
 };
 // Event pair of the innermost live ProfScope (null when not profiling).  launch_timed() hands it to
@@ -214,6 +235,40 @@ inline void launch_timed(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_
   } else {
     hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
   }
+}
+
+// Dynamic LDS above the default limit needs the kernel's attribute raised first: done once per kernel, again only when a
+// later call asks for more (the band kernels' LDS size varies per call).  The state is keyed on the kernel VALUE: a static
+// inside `template <typename K>` would be shared by every instantiation with the same parameter list (one pointer type).
+template <auto Kernel, typename... Args>
+inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+  static size_t have = 0;
+  if (have < lds) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    have = lds;
+  }
+  launch_timed(Kernel, grid, block, lds, st, args...);
+}
+
+// ---- run-time switches -> template arguments ----------------------------------------------------
+// The one place where they turn: pick<N>(v, f) calls f(std::integral_constant<int, v>) for v in [0, N) (0 for anything
+// else); pick_of<A, B, ..., Z>(v, f) calls it with the listed value equal to v (Z for anything else).  Nested for several
+// switches; an `if constexpr` inside the innermost callable keeps combinations that have no kernel from being instantiated.
+template <int N, typename F>
+inline void pick(int v, F&& f) {
+  if constexpr (N > 1) {
+    if (v == N - 1) return f(std::integral_constant<int, N - 1>{});
+    return pick<N - 1>(v, f);
+  } else {
+    f(std::integral_constant<int, 0>{});
+  }
+}
+template <int V0, int... Vs, typename F>
+inline void pick_of(int v, F&& f) {
+  if constexpr (sizeof...(Vs) > 0) {
+    if (v != V0) return pick_of<Vs...>(v, f);
+  }
+  f(std::integral_constant<int, V0>{});
 }
 
 }  // namespace itcv

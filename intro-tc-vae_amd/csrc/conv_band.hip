@@ -676,14 +676,14 @@ __global__ __launch_bounds__(768) void conv_fwd_bf16p3_kernel(ConvArgsP2 a) {
   }
 }
 
-FwdPlanP2 plan_fwd_p2(int B, int Ci, int H, int W, int Co, int KS, int ns) {
-  FwdPlanP2 p;
+// Tiling, band geometry and split-K of the band kernels (the path among them is plan_fwd_planes's part)
+bool plan_fwd_band(FwdPlanP& p, int B, int Ci, int H, int W, int Co, int KS, int ns) {
   memset(&p, 0, sizeof(p));
   const int lw = log2_exact(W), lh = log2_exact(H);
   // (The band form for 4-pixel-wide images -- the 4x4 layers -- was built, verified and measured no faster than the
   // 128-pixel planes kernel, 512 -> 512 @ 4x4 x 128 images: 302 vs 312 TFLOP/s: those launches are bound by streaming
   // 9.4 MB of weights per 128-pixel tile, not by the 9x activation re-reads the band form removes.  Removed.)
-  if (KS != 3 || ns != 2 || lw < 3 || lw > 8 || lh < 0 || Ci % 32 || Co < 33) return p;
+  if (KS != 3 || ns != 2 || lw < 3 || lw > 8 || lh < 0 || Ci % 32 || Co < 33) return false;
   // 128- and 256-wide images: 128-pixel tiles (two rows x 64 columns), persistent kernel only
   p.bn = lw > 6 ? 128 : 256;
   p.rows2 = (lw > 6 && H >= 2) ? 1 : 0;
@@ -693,7 +693,7 @@ FwdPlanP2 plan_fwd_p2(int B, int Ci, int H, int W, int Co, int KS, int ns) {
   p.NP = p.NSEG * (p.SR + 2) * (WBh + 2);
   p.NPC = cdiv(p.NP, 64);
   p.PXB = p.NPC * 64;
-  if (p.NPC > 7) return p;
+  if (p.NPC > 7) return false;
   p.nt = (int)(((long long)B * H * W + p.bn - 1) / p.bn);
   p.bm = Co <= 64 ? 64 : 128;
   // mid-sized layers: 64-row tiles when that fills the chip without split-K and 128-row tiles would not
@@ -701,16 +701,13 @@ FwdPlanP2 plan_fwd_p2(int B, int Ci, int H, int W, int Co, int KS, int ns) {
   p.lds = ((size_t)3 * band_taps_per_stage(p.bm, p.bn, lw) * 2 * 4 * p.bm + (size_t)2 * 2 * 4 * p.PXB) * 16;   // [3][G] weight ring + 2 bands
   const size_t stage_bytes = p.bn == 256 ? (size_t)p.bm * (256 + 4) * sizeof(float) : 0;   // the staged epilogue's tile reuses the allocation
   if (p.lds < stage_bytes) p.lds = stage_bytes;
-  if (p.lds > 160 * 1024) return p;
+  if (p.lds > 160 * 1024) return false;
   p.mt = cdiv(Co, p.bm);
   p.cpt = Ci / 32;
   const int tiles = p.mt * p.nt;
   // mid-sized layers: 128-pixel tiles (conv_fwd_bf16p_kernel) already fill the chip without split-K, 256-pixel
   // bands would not -- measured faster there
-  if (tiles < 192 && cdiv(Co, 128) * (int)(((long long)B * H * W + 127) / 128) >= 192 && Co > 64) {
-    p.ok = 0;
-    return p;
-  }
+  if (tiles < 192 && cdiv(Co, 128) * (int)(((long long)B * H * W + 127) / 128) >= 192 && Co > 64) return false;
   int splits = 1;
   constexpr int target = 256;   // blocks aimed at when K is split: one per CU
   if (tiles < 192 && p.cpt >= 2) {
@@ -720,118 +717,46 @@ FwdPlanP2 plan_fwd_p2(int B, int Ci, int H, int W, int Co, int KS, int ns) {
   }
   p.cps = cdiv(p.cpt, splits);
   p.splits = cdiv(p.cpt, p.cps);
-  p.ok = 1;
-  return p;
+  return true;
 }
 
-static int band_persistent_blocks() { return g_opt.band_persist_blocks; }   // itcv_set_option("band_persist_blocks")
-
-template <typename K>
-static void set_lds(K kern, size_t& have, size_t lds) {
-  if (have < lds) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    have = lds;
-  }
-}
-
-// W <= 64: 256-pixel tiles.  More tiles than CUs (and no tile statistics wanted): persistent blocks (one per CU) that
-// prefetch the next tile's band under the current MFMAs; else one tile per block.
-template <int LOG2W, int BM, bool UP2, bool F16>
-static void launch_fwd_p2_cfg(const ConvArgsP2& a, int splits, size_t lds, hipStream_t st) {
-  const int ids = cdiv(a.nt, 8) * 8 * a.mt, pb = band_persistent_blocks();
-  const bool persistent = !a.stats && pb > 0 && ids > pb;
-  const bool m16 = F16 || (band_m16() && !a.stats);    // launches that produce tile statistics keep the 32x32x16 form
-  if (persistent) {
-    if (m16) {
-      auto pk = conv_fwd_bf16p3_kernel<LOG2W, BM, UP2, 256, true, false, F16>;
-      static size_t have = 0;
-      set_lds(pk, have, lds);
-      launch_timed(pk, dim3(pb, splits), dim3(768), lds, st, a);
-    } else if constexpr (!F16) {
-      auto pk = conv_fwd_bf16p3_kernel<LOG2W, BM, UP2, 256, false, false, false>;
-      static size_t have = 0;
-      set_lds(pk, have, lds);
-      launch_timed(pk, dim3(pb, splits), dim3(768), lds, st, a);
-    }
-    return;
-  }
-  const dim3 grid(ids, splits);
-  if (m16) {
-    auto k16 = conv_fwd_bf16p2_kernel<LOG2W, BM, UP2, true, F16>;
-    static size_t have = 0;
-    set_lds(k16, have, lds);
-    launch_timed(k16, grid, dim3(768), lds, st, a);
-  } else if constexpr (!F16) {
-    auto kern = conv_fwd_bf16p2_kernel<LOG2W, BM, UP2, false, false>;
-    static size_t have = 0;
-    set_lds(kern, have, lds);
-    launch_timed(kern, grid, dim3(768), lds, st, a);
-  }
-}
-template <int LOG2W, bool F16>
-static void launch_fwd_p2_w(const ConvArgsP2& a, int bm, int up2, int splits, size_t lds, hipStream_t st) {
-  if (bm == 64) {
-    if (up2) launch_fwd_p2_cfg<LOG2W, 64, true, F16>(a, splits, lds, st);
-    else launch_fwd_p2_cfg<LOG2W, 64, false, F16>(a, splits, lds, st);
-  } else {
-    if (up2) launch_fwd_p2_cfg<LOG2W, 128, true, F16>(a, splits, lds, st);
-    else launch_fwd_p2_cfg<LOG2W, 128, false, F16>(a, splits, lds, st);
-  }
-}
-
-// 128- / 256-wide images: the persistent kernel with 128-pixel tiles (2 rows x 64 columns)
-template <int LOG2W, int BM, bool UP2, bool M16, bool ROWS2, bool F16>
-static void launch_fwd_p3_wide_k(const ConvArgsP2& a, int splits, size_t lds, hipStream_t st) {
-  auto pk = conv_fwd_bf16p3_kernel<LOG2W, BM, UP2, 128, M16, ROWS2, F16>;
-  static size_t have = 0;
-  set_lds(pk, have, lds);
-  const int ids = cdiv(a.nt, 8) * 8 * a.mt, nb = band_persistent_blocks() > 0 ? band_persistent_blocks() : 256;
-  launch_timed(pk, dim3(ids < nb ? ids : nb, splits), dim3(768), lds, st, a);
-}
-template <int LOG2W, int BM, bool UP2, bool F16>
-static void launch_fwd_p3_wide_cfg(const ConvArgsP2& a, int splits, size_t lds, int rows2, hipStream_t st) {
-  const bool m16 = F16 || band_m16();
-  if (rows2) {
-    if (m16) launch_fwd_p3_wide_k<LOG2W, BM, UP2, true, true, F16>(a, splits, lds, st);
-    else if constexpr (!F16) launch_fwd_p3_wide_k<LOG2W, BM, UP2, false, true, false>(a, splits, lds, st);
-    return;
-  }
-  if (m16) launch_fwd_p3_wide_k<LOG2W, BM, UP2, true, false, F16>(a, splits, lds, st);
-  else if constexpr (!F16) launch_fwd_p3_wide_k<LOG2W, BM, UP2, false, false, false>(a, splits, lds, st);
-}
-template <int LOG2W, bool F16>
-static void launch_fwd_p3_wide(const ConvArgsP2& a, int bm, int up2, int splits, size_t lds, int rows2, hipStream_t st) {
-  if (bm == 64) {
-    if (up2) launch_fwd_p3_wide_cfg<LOG2W, 64, true, F16>(a, splits, lds, rows2, st);
-    else launch_fwd_p3_wide_cfg<LOG2W, 64, false, F16>(a, splits, lds, rows2, st);
-  } else {
-    if (up2) launch_fwd_p3_wide_cfg<LOG2W, 128, true, F16>(a, splits, lds, rows2, st);
-    else launch_fwd_p3_wide_cfg<LOG2W, 128, false, F16>(a, splits, lds, rows2, st);
-  }
-}
-
-bool band_is_persistent(const ConvArgsP2& a, const FwdPlanP2& p) {
-  const int ids = cdiv(a.nt, 8) * 8 * a.mt;
-  return p.bn == 128 || (!a.stats && band_persistent_blocks() > 0 && ids > band_persistent_blocks());
-}
-
-template <bool F16>
-static void launch_fwd_p2_t(const ConvArgsP2& a, const FwdPlanP2& p, int W, int up2, hipStream_t st) {
-  if (p.bn == 128) {
-    if (log2_exact(W) == 7) launch_fwd_p3_wide<7, F16>(a, p.bm, up2, p.splits, p.lds, p.rows2, st);
-    else launch_fwd_p3_wide<8, F16>(a, p.bm, up2, p.splits, p.lds, p.rows2, st);
-    return;
-  }
-  switch (log2_exact(W)) {
-    case 3: launch_fwd_p2_w<3, F16>(a, p.bm, up2, p.splits, p.lds, st); break;
-    case 4: launch_fwd_p2_w<4, F16>(a, p.bm, up2, p.splits, p.lds, st); break;
-    case 5: launch_fwd_p2_w<5, F16>(a, p.bm, up2, p.splits, p.lds, st); break;
-    default: launch_fwd_p2_w<6, F16>(a, p.bm, up2, p.splits, p.lds, st); break;
-  }
-}
-void launch_fwd_p2(const ConvArgsP2& a, const FwdPlanP2& p, int W, int up2, int f16, hipStream_t st) {
-  if (f16) launch_fwd_p2_t<true>(a, p, W, up2, st);
-  else launch_fwd_p2_t<false>(a, p, W, up2, st);
+// One launch expression per band kernel.  MFMA form: fp16 planes exist as 16x16x32 only; launches that produce tile
+// statistics keep the 32x32x16 form (the staged epilogue is written for that accumulator layout).
+void launch_fwd_band(const ConvArgsP2& a, const FwdPlanP& p, int W, int up2, int f16, hipStream_t st) {
+  const bool m16 = f16 || (band_m16() && !a.stats);
+  const int ids = cdiv(a.nt, 8) * 8 * a.mt, pb = g_opt.band_persist_blocks, lw = log2_exact(W);
+  pick<2>(f16 ? 1 : 0, [&](auto f16_c) {
+    pick<2>(m16 ? 1 : 0, [&](auto m16_c) {
+      pick_of<64, 128>(p.bm, [&](auto bm_c) {
+        pick<2>(up2 ? 1 : 0, [&](auto up2_c) {
+          constexpr bool F16 = f16_c.value != 0, M16 = m16_c.value != 0, UP2 = up2_c.value != 0;
+          constexpr int BM = bm_c.value;
+          if constexpr (M16 || !F16) {
+            if (p.path == FwdPath::Band) {
+              // W <= 64, 256-pixel tiles, one per block
+              pick_of<3, 4, 5, 6>(lw, [&](auto lw_c) {
+                launch_lds<conv_fwd_bf16p2_kernel<lw_c.value, BM, UP2, M16, F16>>(dim3(ids, p.splits), dim3(768), p.lds, st, a);
+              });
+              return;
+            }
+            // persistent blocks that prefetch the next tile's band under the current MFMAs: the 256-pixel tiles on
+            // band_persist_blocks blocks (one per CU); 128- / 256-wide images always, with 128-pixel tiles
+            const int nb = pb > 0 ? pb : 256;
+            const int blocks = p.path == FwdPath::BandPersistent ? pb : (ids < nb ? ids : nb);
+            pick_of<3, 4, 5, 6, 7, 8>(lw, [&](auto lw_c) {
+              pick<2>(p.rows2, [&](auto rows2_c) {
+                constexpr int LW = lw_c.value;
+                constexpr bool ROWS2 = rows2_c.value != 0;
+                if constexpr (LW > 6 || !ROWS2)
+                  launch_lds<conv_fwd_bf16p3_kernel<LW, BM, UP2, (LW > 6 ? 128 : 256), M16, ROWS2, F16>>(
+                      dim3(blocks, p.splits), dim3(768), p.lds, st, a);
+              });
+            });
+          }
+        });
+      });
+    });
+  });
 }
 
 }  // namespace itcv

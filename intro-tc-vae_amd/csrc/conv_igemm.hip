@@ -2120,206 +2120,158 @@ __global__ void bias_grad_combine(const double* __restrict__ part, float* __rest
 }
 
 // ------------------------------------------------------------------------------ host side
-static inline int pad16(int c) { return (c + 15) & ~15; }
+// Every entry point builds ONE plan for its shape and reads everything from it: the kernel and its template arguments,
+// the grid, the workspace it needs (also what the *_workspace / *_slabs / *_stat_tiles queries return) and the profiling
+// label.  Each templated kernel has one launch expression, reached through pick / pick_of (common.h) with the plan's
+// fields.
+static inline int pad_to(int c, int m) { return (c + m - 1) / m * m; }
+static inline int pad16(int c) { return pad_to(c, 16); }
+static inline int pad32(int c) { return pad_to(c, 32); }
+
+static int check_ws(const char* name, const void* ws, size_t ws_bytes, size_t need) {
+  if (need && (!ws || ws_bytes < need)) return fail("%s: workspace too small (need %lld bytes)", name, (long long)need);
+  return 0;
+}
+
+// the epilogue of a forward that wrote split-K slabs into `ws`: y = sum of the slabs + bias
+static int reduce_fwd_splits(const char* name, const void* ws, const float* bias, float* y, size_t out_elems, int splits,
+                             int HW, int Co, hipStream_t st) {
+  if (splits <= 1) return 0;
+  const int blocks = (int)(cdivz(out_elems, 256) < 2048 ? cdivz(out_elems, 256) : 2048);
+  hipLaunchKernelGGL(splitk_reduce_fwd, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(ws), bias, y, out_elems,
+                     out_elems, splits, HW, Co);
+  ITCV_CHECK_LAUNCH(name);
+  return 0;
+}
+
+// ---- forward in M x N tiles with K split over grid.y: the fp32 kernel, the in-kernel-split kernel and the 128-pixel
+// planes kernel plan alike, up to three constants
+struct FwdRule {
+  int kchunk;         // channels per K tile
+  bool rows32;        // 32-row tiles for Co <= 32 (else 64 is the smallest)
+  int split_target;   // blocks aimed at when K is split
+};
+constexpr FwdRule kFwdF32 = {16, true, 512};
+// in-kernel-split / planes: one block per CU -- half the slabs and prologues of a 512-block split (measured +2 % step)
+constexpr FwdRule kFwdSplit = {32, false, 256};
 
 struct FwdPlan {
   int bm, bn, mt, nt, cip, ktiles, splits, kps;
+  size_t ws_need;
 };
-
-static FwdPlan plan_fwd(int B, int Ci, int H, int W, int Co, int KS) {
+static FwdPlan plan_fwd(const FwdRule& r, int B, int Ci, int H, int W, int Co, int KS) {
   FwdPlan p;
   const long long N = (long long)B * H * W;
-  p.bm = tile_rows_for(Co);
+  p.bm = r.rows32 ? tile_rows_for(Co) : (Co <= 64 ? 64 : 128);
   p.bn = p.bm == 128 ? 128 : 256;
   p.mt = cdiv(Co, p.bm);
   p.nt = (int)((N + p.bn - 1) / p.bn);
-  p.cip = pad16(Ci);
-  p.ktiles = KS * KS * (p.cip / 16);
+  p.cip = pad_to(Ci, r.kchunk);
+  p.ktiles = KS * KS * (p.cip / r.kchunk);
   const int tiles = p.mt * p.nt;
   int splits = 1;
   if (tiles < 192 && p.ktiles >= 8) {
-    splits = cdiv(512, tiles);
+    splits = cdiv(r.split_target, tiles);
     if (splits > p.ktiles / 4) splits = p.ktiles / 4;
     if (splits > 64) splits = 64;
     if (splits < 1) splits = 1;
   }
   p.kps = cdiv(p.ktiles, splits);
   p.splits = cdiv(p.ktiles, p.kps);
+  p.ws_need = p.splits > 1 ? (size_t)p.splits * B * Co * H * W * sizeof(float) : 0;
   return p;
 }
 
+// forward on pre-split planes: the band kernels where they take the shape (tap reuse through LDS), else 128-pixel tiles.
+// `ns`: planes per tensor; `stats`: the call wants tile statistics (such a launch does not run persistent).
+static FwdPlanP plan_fwd_planes(int B, int Ci, int H, int W, int Co, int KS, int ns, bool stats) {
+  FwdPlanP p;
+  if (plan_fwd_band(p, B, Ci, H, W, Co, KS, ns)) {
+    // W <= 64 and more tiles than CUs (and no tile statistics wanted): persistent blocks, one per CU
+    const int ids = cdiv(p.nt, 8) * 8 * p.mt, pb = g_opt.band_persist_blocks;
+    p.path = p.bn == 128 ? FwdPath::WidePersistent : ((!stats && pb > 0 && ids > pb) ? FwdPath::BandPersistent : FwdPath::Band);
+    p.stat_tiles = (p.splits == 1 && p.bn == 256) ? p.nt : 0;   // split-K slabs, or a tile form without the staged epilogue: none
+  } else {
+    const FwdPlan t = plan_fwd(kFwdSplit, B, Ci, H, W, Co, KS);
+    memset(&p, 0, sizeof(p));
+    p.path = FwdPath::Planes128;
+    p.bm = t.bm, p.bn = t.bn, p.mt = t.mt, p.nt = t.nt, p.splits = t.splits, p.ktiles = t.ktiles, p.kps = t.kps;
+  }
+  p.ws_need = p.splits > 1 ? (size_t)p.splits * B * Co * H * W * sizeof(float) : 0;
+  return p;
+}
+
+// ---- weight gradient, fp32 and in-kernel-split: split-K slabs of [Co][nt * 128] in the workspace
 static inline bool wgrad_swapped(int Ci, int Co) { return Co <= 4 && Ci > 4; }
 
 struct WgPlan {
   int bm, cb, cip, mt, nt, tiles, ktiles, splits, kps;
+  int grid;         // blocks
+  size_t slab;      // elements of one slab
+  size_t ws_need;   // bytes: `splits` slabs
 };
 
-static WgPlan plan_wgrad(int B, int Ci, int H, int W, int Co, int KS) {
+static WgPlan plan_wgrad(int B, int Ci, int H, int W, int Co, int KS, int min_bm = 32) {
   WgPlan p;
   const long long Ktot = (long long)B * H * W;
   p.bm = tile_rows_for(Co);
+  if (p.bm < min_bm) p.bm = min_bm;   // (the in-kernel-split kernel has no 32-row form; same slab layout)
   p.cb = Ci <= 4 ? 4 : (Ci <= 16 ? 16 : (Ci <= 32 ? 32 : (Ci <= 64 ? 64 : 128)));
   p.cip = p.cb < 128 ? p.cb : (Ci + 127) / 128 * 128;
-  p.mt = cdiv(Co, p.bm);
   p.nt = p.cb == 128 ? KS * KS * (p.cip / 128) : cdiv(KS * KS, 128 / p.cb);
-  p.tiles = p.mt * p.nt;
+  // the split count follows the tiles of the fp32 tiling, whichever kernel runs
+  const int tiles = cdiv(Co, tile_rows_for(Co)) * p.nt;
   p.ktiles = (int)((Ktot + 31) / 32);
-  int splits = cdiv(768, p.tiles);
-  if (p.cb == 4) splits = cdiv(256, p.tiles);   // one 128-column tile: a block per CU with long K slices; the slab reduce shrinks with the splits
+  int splits = cdiv(768, tiles);
+  if (p.cb == 4) splits = cdiv(256, tiles);   // one 128-column tile: a block per CU with long K slices; the slab reduce shrinks with the splits
   if (splits > p.ktiles / 8) splits = p.ktiles / 8;
   if (splits > 256) splits = 256;
   if (splits < 1) splits = 1;
   p.kps = cdiv(p.ktiles, splits);
   p.splits = cdiv(p.ktiles, p.kps);
-  return p;
-}
-
-template <int KS, int BM, int BN, int WM, int WN>
-static void launch_fwd_cfg(const ConvArgs& a, int splits, int up2, hipStream_t st) {
-  dim3 grid(cdiv(a.nt, 8) * 8 * a.mt, splits), block(WM * WN * 64);
-  const bool tail = (a.Ci & 15) != 0;
-  if (up2 && tail)
-    launch_timed((conv_fwd_kernel<KS, BM, BN, WM, WN, true, true>), grid, block, 0, st, a);
-  else if (up2)
-    launch_timed((conv_fwd_kernel<KS, BM, BN, WM, WN, true, false>), grid, block, 0, st, a);
-  else if (tail)
-    launch_timed((conv_fwd_kernel<KS, BM, BN, WM, WN, false, true>), grid, block, 0, st, a);
-  else
-    launch_timed((conv_fwd_kernel<KS, BM, BN, WM, WN, false, false>), grid, block, 0, st, a);
-}
-
-template <int KS>
-static void launch_fwd(const ConvArgs& a, int bm, int splits, int up2, hipStream_t st) {
-  if (bm == 32)
-    launch_fwd_cfg<KS, 32, 256, 1, 4>(a, splits, up2, st);
-  else if (bm == 64)
-    launch_fwd_cfg<KS, 64, 256, 1, 4>(a, splits, up2, st);
-  else
-    launch_fwd_cfg<KS, 128, 128, 2, 2>(a, splits, up2, st);
-}
-
-template <int KS, int CB, bool UP2>
-static void launch_wgrad_bm(const WgradArgs& a, int bm, hipStream_t st) {
-  dim3 grid(cdiv(a.splits, 8) * 8 * a.tiles);
-  if (bm == 32)
-    launch_timed((conv_wgrad_kernel<KS, 32, CB, 1, 4, UP2, 1>), grid, dim3(256), 0, st, a);
-  else if (bm == 64)
-    launch_timed((conv_wgrad_kernel<KS, 64, CB, 1, 4, UP2, 1>), grid, dim3(256), 0, st, a);
-  else
-    launch_timed((conv_wgrad_kernel<KS, 128, CB, 2, 2, UP2, 1>), grid, dim3(256), 0, st, a);
-}
-template <int KS, bool UP2>
-static void launch_wgrad_cb(const WgradArgs& a, int bm, int cb, hipStream_t st) {
-  if (cb == 4)
-    launch_wgrad_bm<KS, 4, UP2>(a, bm, st);
-  else if (cb == 16)
-    launch_wgrad_bm<KS, 16, UP2>(a, bm, st);
-  else if (cb == 32)
-    launch_wgrad_bm<KS, 32, UP2>(a, bm, st);
-  else if (cb == 64)
-    launch_wgrad_bm<KS, 64, UP2>(a, bm, st);
-  else
-    launch_wgrad_bm<KS, 128, UP2>(a, bm, st);
-}
-template <int KS>
-static void launch_wgrad(const WgradArgs& a, int bm, int cb, int up2, hipStream_t st) {
-  if (up2)
-    launch_wgrad_cb<KS, true>(a, bm, cb, st);
-  else
-    launch_wgrad_cb<KS, false>(a, bm, cb, st);
-}
-
-static inline int pad32(int c) { return (c + 31) & ~31; }
-
-struct FwdPlanB {
-  int bm, bn, mt, nt, cip, ktiles, splits, kps;
-};
-// blocks aimed at when K is split: one block per CU -- half the slabs and prologues of a 512-block split (measured +2 % step)
-constexpr int kFwdBSplitTarget = 256;
-static FwdPlanB plan_fwd_b(int B, int Ci, int H, int W, int Co, int KS) {
-  FwdPlanB p;
-  const long long N = (long long)B * H * W;
-  p.bm = Co <= 64 ? 64 : 128;
-  p.bn = p.bm == 128 ? 128 : 256;
   p.mt = cdiv(Co, p.bm);
-  p.nt = (int)((N + p.bn - 1) / p.bn);
-  p.cip = pad32(Ci);
-  p.ktiles = KS * KS * (p.cip / 32);
-  const int tiles = p.mt * p.nt;
-  int splits = 1;
-  if (tiles < 192 && p.ktiles >= 8) {
-    splits = cdiv(kFwdBSplitTarget, tiles);
-    if (splits > p.ktiles / 4) splits = p.ktiles / 4;
-    if (splits > 64) splits = 64;
-    if (splits < 1) splits = 1;
-  }
-  p.kps = cdiv(p.ktiles, splits);
-  p.splits = cdiv(p.ktiles, p.kps);
+  p.tiles = p.mt * p.nt;
+  p.grid = cdiv(p.splits, 8) * 8 * p.tiles;
+  p.slab = (size_t)Co * p.nt * 128;
+  p.ws_need = (size_t)p.splits * p.slab * sizeof(float);
   return p;
 }
 
-template <int KS, int NS>
-static void launch_fwd_b(const ConvArgsB& a, int bm, int splits, int up2, hipStream_t st) {
-  dim3 grid(cdiv(a.nt, 8) * 8 * a.mt, splits), blk(512);
-  if (bm == 64) {
-    if (up2) launch_timed((conv_fwd_bf16s_ws_kernel<KS, 64, 256, 1, 4, true, NS>), grid, blk, 0, st, a);
-    else launch_timed((conv_fwd_bf16s_ws_kernel<KS, 64, 256, 1, 4, false, NS>), grid, blk, 0, st, a);
-  } else {
-    if (up2) launch_timed((conv_fwd_bf16s_ws_kernel<KS, 128, 128, 2, 2, true, NS>), grid, blk, 0, st, a);
-    else launch_timed((conv_fwd_bf16s_ws_kernel<KS, 128, 128, 2, 2, false, NS>), grid, blk, 0, st, a);
+// Plan and kernel arguments of one weight-gradient call.  `swap` (few output channels, the predict conv 64 -> 3):
+// the operands are exchanged so that the wide tensor is the GEMM's row side and the 3-channel one the gathered side
+// (4-channel column groups):
+//   dW[co][ci][tap] = sum_q x[ci][q] * dy[co][q - tap]  =  wgrad(x' = dy, dy' = x)[ci][co][KK-1-tap]
+static WgPlan plan_wgrad_call(WgradArgs& a, const float* x, const float* dy, void* ws, int B, int Ci, int H, int W, int Co,
+                              int KS, int up2, bool swap, int min_bm) {
+  if (swap) {
+    const float* tp = x;
+    x = dy, dy = tp;
+    const int tc = Ci;
+    Ci = Co, Co = tc;
   }
+  const WgPlan p = plan_wgrad(B, Ci, H, W, Co, KS, min_bm);
+  a.x = x, a.dy = dy;
+  a.out = static_cast<float*>(ws);
+  a.B = B, a.Ci = Ci, a.H = H, a.W = W, a.Co = Co;
+  a.Cip = p.cip;
+  a.Np = p.nt * 128;
+  a.Ktot = B * H * W;
+  a.mt = p.mt, a.nt = p.nt, a.tiles = p.tiles;
+  a.ktiles = p.ktiles, a.ktiles_per_split = p.kps, a.splits = p.splits;
+  a.w_shift = log2_exact(W), a.hw_shift = log2_exact(H * W);
+  a.x_bytes = (uint32_t)((size_t)B * Ci * (up2 ? (H / 2) * (W / 2) : H * W) * sizeof(float));
+  a.dy_bytes = (uint32_t)((size_t)B * Co * H * W * sizeof(float));
+  a.slab_stride = p.slab;
+  return p;
 }
 
-template <int KS, int BM, int BN, int WM, int WN, bool UP2, int NS, int NSTAGE, bool F16>
-static void launch_fwd_p_cfg(const ConvArgsP& a, int splits, hipStream_t st) {
-  constexpr size_t lds = (size_t)NSTAGE * NS * 4 * (BM + BN) * 16;
-  static_assert(lds <= 160 * 1024, "LDS ring too large");
-  dim3 grid(cdiv(a.nt, 8) * 8 * a.mt, splits), blk(64 * (WM * WN + 4));
-  if constexpr (NS == 2) {
-    if (F16 || band_m16()) {
-      auto k16 = conv_fwd_bf16p_kernel<KS, BM, BN, WM, WN, UP2, NS, NSTAGE, true, F16>;
-      static bool attr16 = false;
-      if (!attr16) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k16), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr16 = true;
-      }
-      launch_timed(k16, grid, blk, lds, st, a);
-      return;
-    }
-  }
-  if constexpr (!F16) {
-    auto kern = conv_fwd_bf16p_kernel<KS, BM, BN, WM, WN, UP2, NS, NSTAGE>;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    launch_timed(kern, grid, blk, lds, st, a);
-  }
-}
-template <int KS, int NS, int NSTAGE, bool F16>
-static void launch_fwd_p_st(const ConvArgsP& a, int bm, int splits, int up2, hipStream_t st) {
-  if (bm == 64) {
-    if (up2) launch_fwd_p_cfg<KS, 64, 256, 1, 4, true, NS, NSTAGE, F16>(a, splits, st);
-    else launch_fwd_p_cfg<KS, 64, 256, 1, 4, false, NS, NSTAGE, F16>(a, splits, st);
-  } else if (NS == 2 && g_opt.planes_mfma_waves == 8 && (F16 || band_m16())) {
-    if constexpr (NS == 2) {   // eight MFMA waves of 64 x 32 (16x16x32 form)
-      if (up2) launch_fwd_p_cfg<KS, 128, 128, 2, 4, true, NS, NSTAGE, F16>(a, splits, st);
-      else launch_fwd_p_cfg<KS, 128, 128, 2, 4, false, NS, NSTAGE, F16>(a, splits, st);
-    }
-  } else {
-    if (up2) launch_fwd_p_cfg<KS, 128, 128, 2, 2, true, NS, NSTAGE, F16>(a, splits, st);
-    else launch_fwd_p_cfg<KS, 128, 128, 2, 2, false, NS, NSTAGE, F16>(a, splits, st);
-  }
-}
-template <int KS, int NS, bool F16 = false>
-static void launch_fwd_p(const ConvArgsP& a, int bm, int splits, int up2, hipStream_t st) {
-  launch_fwd_p_st<KS, NS, NS == 2 ? 3 : 2, F16>(a, bm, splits, up2, st);   // ring depth: three stages where LDS allows (two planes)
-}
-
+// ---- weight gradient on pre-split planes
 struct WgPlanP {
   int bm, bn, tiles_m, tiles_n, steps, splits, sps;
-  int kh;   // slabs per K slice (2 for the 64 x 64 tile: its wave groups keep separate slabs)
+  int kh;           // slabs per K slice (2 for the 64 x 64 tile: its wave groups keep separate slabs)
+  int slabs;        // splits * kh
+  int groups, blocks;
+  size_t ws_need;   // bytes: `slabs` slabs of [3][3][Co][Ci]
 };
 static WgPlanP plan_wgrad_p(int B, int Ci, int H, int W, int Co) {
   WgPlanP p;
@@ -2342,77 +2294,140 @@ static WgPlanP plan_wgrad_p(int B, int Ci, int H, int W, int Co) {
   if (splits < 1) splits = 1;
   p.sps = cdiv(p.steps, splits);
   p.splits = cdiv(p.steps, p.sps);
+  p.slabs = p.splits * p.kh;
+  p.groups = p.tiles_m * p.tiles_n * p.splits;
+  p.blocks = cdiv(p.groups, 8) * 24;
+  p.ws_need = (size_t)p.slabs * 9 * Co * Ci * sizeof(float);
   return p;
 }
 
-template <int LOG2W, bool UP2, int BM, int BN, int KH, bool F16>
-static void launch_wgrad_p_cfg(const WgradArgsP& a, int blocks, hipStream_t st) {
-  constexpr int W = 1 << LOG2W, NP = (64 >> LOG2W) * (W + 2), PXB = ((NP + 11) / 16) * 16 + 4;
-  constexpr size_t stage_bytes = (size_t)(2 * (BM / 8) * 68 + 2 * (BN / 8) * PXB) * 16;
-  constexpr int NST = 3 * stage_bytes <= 160 * 1024 ? 3 : 2;     // three stages where LDS allows (W = 32 / 64 bands)
-  constexpr size_t lds = NST * stage_bytes;
-  if constexpr (lds <= 160 * 1024) {
-    constexpr int NLW = 4;   // loader waves (eight were measured no faster, and spill in the 128 x 128 form)
-    // 16x16x32 by default (tools/wgrad_m16_bench.py, c2 shapes, f16x3: -7.8 % summed over the layers; +14 % on the
-    // 128-column tiles, +9 % on the 4x4 layers, within -3.5 % on two shapes)
-    const bool m16 = g_opt.wgrad_m16 != 0;
-    if (m16) {
-      auto kern = conv_wgrad_bf16p_kernel<LOG2W, UP2, BM, BN, NST, NLW, KH, F16, true>;
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-      }
-      launch_timed(kern, dim3(blocks), dim3(512 + 64 * NLW), lds, st, a);
-      return;
-    }
-    auto kern = conv_wgrad_bf16p_kernel<LOG2W, UP2, BM, BN, NST, NLW, KH, F16>;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
-    launch_timed(kern, dim3(blocks), dim3(512 + 64 * NLW), lds, st, a);
-  }
-}
-template <int LOG2W, bool F16>
-static void launch_wgrad_p_t(const WgradArgsP& a, int bm, int bn, int up2, int blocks, hipStream_t st) {
-  if (bm == 64 && bn == 64) {
-    if (up2) launch_wgrad_p_cfg<LOG2W, true, 64, 64, 2, F16>(a, blocks, st);
-    else launch_wgrad_p_cfg<LOG2W, false, 64, 64, 2, F16>(a, blocks, st);
-  } else if (bm == 64) {
-    if (up2) launch_wgrad_p_cfg<LOG2W, true, 64, 128, 1, F16>(a, blocks, st);
-    else launch_wgrad_p_cfg<LOG2W, false, 64, 128, 1, F16>(a, blocks, st);
-  } else if (bn == 128) {
-    if (up2) launch_wgrad_p_cfg<LOG2W, true, 128, 128, 1, F16>(a, blocks, st);
-    else launch_wgrad_p_cfg<LOG2W, false, 128, 128, 1, F16>(a, blocks, st);
-  } else {
-    if (up2) launch_wgrad_p_cfg<LOG2W, true, 128, 64, 1, F16>(a, blocks, st);
-    else launch_wgrad_p_cfg<LOG2W, false, 128, 64, 1, F16>(a, blocks, st);
-  }
-}
-template <int LOG2W>
-static void launch_wgrad_p(const WgradArgsP& a, int bm, int bn, int up2, int blocks, int f16, hipStream_t st) {
-  if (f16) launch_wgrad_p_t<LOG2W, true>(a, bm, bn, up2, blocks, st);
-  else launch_wgrad_p_t<LOG2W, false>(a, bm, bn, up2, blocks, st);
+// ---- launches: one expression per kernel
+// plane format code -> template arguments <planes, fp16>: <2, false> | <3, false> | <2, true>
+template <typename F>
+static inline void pick_fmt(int fmt, F&& f) {
+  pick<3>(fmt == ITCV_PLANES_F16X2 ? 2 : (fmt == 2 ? 0 : 1), [&](auto i) {
+    f(std::integral_constant<int, i.value == 1 ? 3 : 2>{}, std::integral_constant<bool, i.value == 2>{});
+  });
 }
 
-template <int KS, int CB, int NS>
-static void launch_wgrad_b_bm(const WgradArgs& a, int bm, hipStream_t st) {
-  dim3 grid(cdiv(a.splits, 8) * 8 * a.tiles);
-  if (bm == 64)
-    launch_timed((conv_wgrad_bf16s_kernel<KS, 64, CB, 1, 4, NS>), grid, dim3(256), 0, st, a);
-  else
-    launch_timed((conv_wgrad_bf16s_kernel<KS, 128, CB, 2, 2, NS>), grid, dim3(256), 0, st, a);
+// M x N tiles of the igemm kernels: 32 x 256 and 64 x 256 on 1 x 4 waves, 128 x 128 on 2 x 2
+template <int BM>
+struct IgemmTile {
+  static constexpr int BN = BM == 128 ? 128 : 256, WM = BM == 128 ? 2 : 1, WN = BM == 128 ? 2 : 4;
+};
+
+static void launch_fwd(const ConvArgs& a, const FwdPlan& p, int KS, int up2, hipStream_t st) {
+  const dim3 grid(cdiv(a.nt, 8) * 8 * a.mt, p.splits);
+  pick_of<1, 3, 5>(KS, [&](auto ks) {
+    pick_of<32, 64, 128>(p.bm, [&](auto bm) {
+      pick<2>(up2 ? 1 : 0, [&](auto u) {
+        pick<2>((a.Ci & 15) ? 1 : 0, [&](auto tail) {
+          using T = IgemmTile<bm.value>;
+          launch_timed((conv_fwd_kernel<ks.value, bm.value, T::BN, T::WM, T::WN, u.value != 0, tail.value != 0>), grid,
+                       dim3(T::WM * T::WN * 64), 0, st, a);
+        });
+      });
+    });
+  });
 }
-template <int KS, int NS>
-static void launch_wgrad_b(const WgradArgs& a, int bm, int cb, hipStream_t st) {
-  if (cb == 32)
-    launch_wgrad_b_bm<KS, 32, NS>(a, bm, st);
-  else if (cb == 64)
-    launch_wgrad_b_bm<KS, 64, NS>(a, bm, st);
-  else
-    launch_wgrad_b_bm<KS, 128, NS>(a, bm, st);
+
+static void launch_fwd_b(const ConvArgsB& a, const FwdPlan& p, int KS, int up2, int ns, hipStream_t st) {
+  const dim3 grid(cdiv(a.nt, 8) * 8 * a.mt, p.splits);
+  pick_of<1, 3>(KS, [&](auto ks) {
+    pick_of<2, 3>(ns, [&](auto nsc) {
+      pick_of<64, 128>(p.bm, [&](auto bm) {
+        pick<2>(up2 ? 1 : 0, [&](auto u) {
+          using T = IgemmTile<bm.value>;
+          launch_timed((conv_fwd_bf16s_ws_kernel<ks.value, bm.value, T::BN, T::WM, T::WN, u.value != 0, nsc.value>), grid,
+                       dim3(512), 0, st, a);
+        });
+      });
+    });
+  });
+}
+
+// 128-pixel planes kernel.  Two planes run the 16x16x32 MFMA form (fp16 planes: always; bf16: band_m16), and their
+// 128 x 128 tile then eight MFMA waves of 64 x 32 (planes_mfma_waves); ring depth: three stages where LDS allows (two planes).
+static void launch_fwd_p(const ConvArgsP& a, const FwdPlanP& p, int KS, int up2, int fmt, hipStream_t st) {
+  const dim3 grid(cdiv(a.nt, 8) * 8 * a.mt, p.splits);
+  const bool m16 = fmt == ITCV_PLANES_F16X2 || (fmt == 2 && band_m16());
+  const bool waves8 = m16 && p.bm == 128 && g_opt.planes_mfma_waves == 8;
+  pick_of<1, 3>(KS, [&](auto ks) {
+    pick_fmt(fmt, [&](auto nsc, auto f16) {
+      pick_of<64, 128>(p.bm, [&](auto bm) {
+        pick<2>(up2 ? 1 : 0, [&](auto u) {
+          pick<2>(waves8 ? 1 : 0, [&](auto w8) {
+            pick<2>(m16 ? 1 : 0, [&](auto m) {
+              constexpr int NS = nsc.value, BM = bm.value, NSTAGE = NS == 2 ? 3 : 2;
+              constexpr bool F16 = f16.value, M16 = m.value != 0, W8 = w8.value != 0;
+              using T = IgemmTile<BM>;
+              constexpr int WN = W8 ? 4 : T::WN;
+              constexpr size_t lds = (size_t)NSTAGE * NS * 4 * (BM + T::BN) * 16;
+              static_assert(lds <= 160 * 1024, "LDS ring too large");
+              if constexpr ((M16 || !F16) && !(M16 && NS == 3) && !(W8 && !(NS == 2 && BM == 128)))
+                launch_lds<conv_fwd_bf16p_kernel<ks.value, BM, T::BN, T::WM, WN, u.value != 0, NS, NSTAGE, M16, F16>>(
+                    grid, dim3(64 * (T::WM * WN + 4)), lds, st, a);
+            });
+          });
+        });
+      });
+    });
+  });
+}
+
+static void launch_wgrad(const WgradArgs& a, const WgPlan& p, int KS, int up2, hipStream_t st) {
+  pick_of<1, 3, 5>(KS, [&](auto ks) {
+    pick<2>(up2 ? 1 : 0, [&](auto u) {
+      pick_of<4, 16, 32, 64, 128>(p.cb, [&](auto cb) {
+        pick_of<32, 64, 128>(p.bm, [&](auto bm) {
+          using T = IgemmTile<bm.value>;
+          launch_timed((conv_wgrad_kernel<ks.value, bm.value, cb.value, T::WM, T::WN, u.value != 0, 1>), dim3(p.grid),
+                       dim3(256), 0, st, a);
+        });
+      });
+    });
+  });
+}
+
+static void launch_wgrad_b(const WgradArgs& a, const WgPlan& p, int KS, int ns, hipStream_t st) {
+  pick_of<1, 3>(KS, [&](auto ks) {
+    pick_of<2, 3>(ns, [&](auto nsc) {
+      pick_of<32, 64, 128>(p.cb, [&](auto cb) {
+        pick_of<64, 128>(p.bm, [&](auto bm) {
+          using T = IgemmTile<bm.value>;
+          launch_timed((conv_wgrad_bf16s_kernel<ks.value, bm.value, cb.value, T::WM, T::WN, nsc.value>), dim3(p.grid),
+                       dim3(256), 0, st, a);
+        });
+      });
+    });
+  });
+}
+
+static void launch_wgrad_p(const WgradArgsP& a, const WgPlanP& p, int lw, int up2, int f16, hipStream_t st) {
+  // 16x16x32 by default (tools/wgrad_m16_bench.py, c2 shapes, f16x3: -7.8 % summed over the layers; +14 % on the
+  // 128-column tiles, +9 % on the 4x4 layers, within -3.5 % on two shapes)
+  const bool m16 = g_opt.wgrad_m16 != 0;
+  pick_of<2, 3, 4, 5, 6>(lw, [&](auto lwc) {
+    pick<2>(f16 ? 1 : 0, [&](auto f) {
+      pick_of<64, 128>(p.bm, [&](auto bm) {
+        pick_of<64, 128>(p.bn, [&](auto bn) {
+          pick<2>(up2 ? 1 : 0, [&](auto u) {
+            pick<2>(m16 ? 1 : 0, [&](auto m) {
+              constexpr int LOG2W = lwc.value, BM = bm.value, BN = bn.value, KH = (BM == 64 && BN == 64) ? 2 : 1;
+              constexpr int W = 1 << LOG2W, NP = (64 >> LOG2W) * (W + 2), PXB = ((NP + 11) / 16) * 16 + 4;
+              constexpr size_t stage_bytes = (size_t)(2 * (BM / 8) * 68 + 2 * (BN / 8) * PXB) * 16;
+              constexpr int NST = 3 * stage_bytes <= 160 * 1024 ? 3 : 2;     // three stages where LDS allows (W = 32 / 64 bands)
+              constexpr size_t lds = NST * stage_bytes;
+              constexpr int NLW = 4;   // loader waves (eight were measured no faster, and spill in the 128 x 128 form)
+              if constexpr (lds <= 160 * 1024)
+                launch_lds<conv_wgrad_bf16p_kernel<LOG2W, u.value != 0, BM, BN, NST, NLW, KH, f.value != 0, m.value != 0>>(
+                    dim3(p.blocks), dim3(512 + 64 * NLW), lds, st, a);
+            });
+          });
+        });
+      });
+    });
+  });
 }
 
 static int check_dims(const char* name, int B, int Ci, int H, int W, int Co, int KS) {
@@ -2432,7 +2447,6 @@ static inline int bias_splits(int B, int C, int HW) {
   if (s > kBiasSplitsMax) s = kBiasSplitsMax;
   return s < 1 ? 1 : s;
 }
-
 }  // namespace itcv
 
 using namespace itcv;
@@ -2459,8 +2473,7 @@ int itcv_conv2d_pack_weight(const float* w, float* wp, int Co, int Ci, int KS, i
 
 size_t itcv_conv2d_fwd_workspace(int B, int Ci, int H, int W, int Co, int KS) {
   if (B <= 0 || Ci <= 0 || H <= 0 || W <= 0 || Co <= 0) return 0;
-  const FwdPlan p = plan_fwd(B, Ci, H, W, Co, KS);
-  return p.splits > 1 ? (size_t)p.splits * B * Co * H * W * sizeof(float) : 0;
+  return plan_fwd(kFwdF32, B, Ci, H, W, Co, KS).ws_need;
 }
 
 int itcv_conv2d_fwd(const float* x, const float* wp, const float* bias, float* y, int B, int Ci, int H, int W,
@@ -2468,11 +2481,9 @@ int itcv_conv2d_fwd(const float* x, const float* wp, const float* bias, float* y
   if (int e = check_dims("itcv_conv2d_fwd", B, Ci, H, W, Co, KS)) return e;
   ITCV_REQUIRE(x && wp && y, "itcv_conv2d_fwd");
   if (up2) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_conv2d_fwd(up2)");
-  const FwdPlan p = plan_fwd(B, Ci, H, W, Co, KS);
+  const FwdPlan p = plan_fwd(kFwdF32, B, Ci, H, W, Co, KS);
   const size_t out_elems = (size_t)B * Co * H * W;
-  if (p.splits > 1 && (!ws || ws_bytes < (size_t)p.splits * out_elems * sizeof(float)))
-    return fail("%s: workspace too small (need %lld bytes)", "itcv_conv2d_fwd",
-                (long long)((size_t)p.splits * out_elems * sizeof(float)));
+  if (int e = check_ws("itcv_conv2d_fwd", ws, ws_bytes, p.ws_need)) return e;
   ConvArgs a;
   a.x = x;
   a.wp = wp;
@@ -2487,22 +2498,11 @@ int itcv_conv2d_fwd(const float* x, const float* wp, const float* bias, float* y
   a.slab_stride = p.splits > 1 ? out_elems : 0;
   hipStream_t st = S(stream);
   {
-    ProfScope prof(st, 0, KS, p.bm, up2 ? 1 : 0, 0, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
-    if (KS == 1)
-      launch_fwd<1>(a, p.bm, p.splits, up2, st);
-    else if (KS == 3)
-      launch_fwd<3>(a, p.bm, p.splits, up2, st);
-    else
-      launch_fwd<5>(a, p.bm, p.splits, up2, st);
+    ProfScope prof(st, kProfFwd, KS, p.bm, up2 ? 1 : 0, 0, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
+    launch_fwd(a, p, KS, up2, st);
   }
   ITCV_CHECK_LAUNCH("itcv_conv2d_fwd");
-  if (p.splits > 1) {
-    const int blocks = (int)(cdivz(out_elems, 256) < 2048 ? cdivz(out_elems, 256) : 2048);
-    hipLaunchKernelGGL(splitk_reduce_fwd, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(ws), bias, y,
-                       out_elems, out_elems, p.splits, H * W, Co);
-    ITCV_CHECK_LAUNCH("itcv_conv2d_fwd(reduce)");
-  }
-  return 0;
+  return reduce_fwd_splits("itcv_conv2d_fwd(reduce)", ws, bias, y, out_elems, p.splits, H * W, Co, st);
 }
 
 // ---- split-bf16 forward / data-gradient (throughput mode) -----------------------------------
@@ -2525,15 +2525,10 @@ int itcv_conv2d_pack_weight_bf16s(const float* w, void* wp, int Co, int Ci, int 
   const int M = for_dgrad ? Ci : Co, C = for_dgrad ? Co : Ci;
   const int bm = M <= 64 ? 64 : 128, Mp = cdiv(M, bm) * bm, cpt = pad32(C) / 32;
   const int blocks = (Mp / 32) * cpt;   // one block per 32 x 32-channel tile
-  if (ns == ITCV_PLANES_F16X2)
-    hipLaunchKernelGGL((pack_weight_bf16s_kernel<2, true>), dim3(blocks), dim3(256), 0, S(stream), w, static_cast<u32x4*>(wp),
-                       Co, Ci, KS * KS, for_dgrad, C, M, cpt, Mp);
-  else if (ns == 2)
-    hipLaunchKernelGGL(pack_weight_bf16s_kernel<2>, dim3(blocks), dim3(256), 0, S(stream), w, static_cast<u32x4*>(wp),
-                       Co, Ci, KS * KS, for_dgrad, C, M, cpt, Mp);
-  else
-    hipLaunchKernelGGL(pack_weight_bf16s_kernel<3>, dim3(blocks), dim3(256), 0, S(stream), w, static_cast<u32x4*>(wp),
-                       Co, Ci, KS * KS, for_dgrad, C, M, cpt, Mp);
+  pick_fmt(ns, [&](auto nsc, auto f16) {
+    hipLaunchKernelGGL((pack_weight_bf16s_kernel<nsc.value, f16.value>), dim3(blocks), dim3(256), 0, S(stream), w,
+                       static_cast<u32x4*>(wp), Co, Ci, KS * KS, for_dgrad, C, M, cpt, Mp);
+  });
   ITCV_CHECK_LAUNCH("itcv_conv2d_pack_weight_bf16s");
   return 0;
 }
@@ -2561,27 +2556,22 @@ int itcv_conv2d_pack_desc_bf16s(void* host_desc, const float* w, void* wp, int C
 int itcv_conv2d_pack_weights_bf16s(const void* dev_table, int n, int total_blocks, int ns, void* stream) {
   ITCV_REQUIRE(dev_table && n > 0 && total_blocks > 0 && fmt_ok(ns), "itcv_conv2d_pack_weights_bf16s");
   const PackDesc* tab = static_cast<const PackDesc*>(dev_table);
-  if (ns == ITCV_PLANES_F16X2)
-    hipLaunchKernelGGL((pack_weights_bf16s_table_kernel<2, true>), dim3(total_blocks), dim3(256), 0, S(stream), tab, n);
-  else if (ns == 2)
-    hipLaunchKernelGGL(pack_weights_bf16s_table_kernel<2>, dim3(total_blocks), dim3(256), 0, S(stream), tab, n);
-  else
-    hipLaunchKernelGGL(pack_weights_bf16s_table_kernel<3>, dim3(total_blocks), dim3(256), 0, S(stream), tab, n);
+  pick_fmt(ns, [&](auto nsc, auto f16) {
+    hipLaunchKernelGGL((pack_weights_bf16s_table_kernel<nsc.value, f16.value>), dim3(total_blocks), dim3(256), 0, S(stream),
+                       tab, n);
+  });
   ITCV_CHECK_LAUNCH("itcv_conv2d_pack_weights_bf16s");
   return 0;
 }
 
 size_t itcv_conv2d_fwd_bf16s_workspace(int B, int Ci, int H, int W, int Co, int KS) {
   if (B <= 0 || Ci <= 0 || H <= 0 || W <= 0 || Co <= 0) return 0;
-  const FwdPlanB p = plan_fwd_b(B, Ci, H, W, Co, KS);
-  return p.splits > 1 ? (size_t)p.splits * B * Co * H * W * sizeof(float) : 0;
+  return plan_fwd(kFwdSplit, B, Ci, H, W, Co, KS).ws_need;
 }
 
 size_t itcv_conv2d_fwd_bf16p_workspace(int B, int Ci, int H, int W, int Co, int KS, int ns) {
   if (B <= 0 || Ci <= 0 || H <= 0 || W <= 0 || Co <= 0) return 0;
-  const FwdPlanP2 p2 = plan_fwd_p2(B, Ci, H, W, Co, KS, planes_of_fmt(ns));
-  if (p2.ok) return p2.splits > 1 ? (size_t)p2.splits * B * Co * H * W * sizeof(float) : 0;
-  return itcv_conv2d_fwd_bf16s_workspace(B, Ci, H, W, Co, KS);
+  return plan_fwd_planes(B, Ci, H, W, Co, KS, planes_of_fmt(ns), false).ws_need;
 }
 
 int itcv_conv2d_fwd_bf16s(const float* x, const void* wp, const float* bias, float* y, int B, int Ci, int H, int W,
@@ -2591,11 +2581,9 @@ int itcv_conv2d_fwd_bf16s(const float* x, const void* wp, const float* bias, flo
   if (!itcv_conv2d_bf16s_supported(Ci, Co, KS))
     return fail("%s: shape not supported by the split-bf16 kernel (Ci %% 32, Co > 32, KS 1/3)", "itcv_conv2d_fwd_bf16s");
   if (up2) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_conv2d_fwd_bf16s(up2)");
-  const FwdPlanB p = plan_fwd_b(B, Ci, H, W, Co, KS);
+  const FwdPlan p = plan_fwd(kFwdSplit, B, Ci, H, W, Co, KS);
   const size_t out_elems = (size_t)B * Co * H * W;
-  if (p.splits > 1 && (!ws || ws_bytes < (size_t)p.splits * out_elems * sizeof(float)))
-    return fail("%s: workspace too small (need %lld bytes)", "itcv_conv2d_fwd_bf16s",
-                (long long)((size_t)p.splits * out_elems * sizeof(float)));
+  if (int e = check_ws("itcv_conv2d_fwd_bf16s", ws, ws_bytes, p.ws_need)) return e;
   ConvArgsB a;
   a.x = x;
   a.wp = static_cast<const u32x4*>(wp);
@@ -2612,23 +2600,11 @@ int itcv_conv2d_fwd_bf16s(const float* x, const void* wp, const float* bias, flo
 #endif
   hipStream_t st = S(stream);
   {
-    ProfScope prof(st, 1, KS, p.bm, up2 ? 1 : 0, ns, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
-    if (KS == 1) {
-      if (ns == 2) launch_fwd_b<1, 2>(a, p.bm, p.splits, up2, st);
-      else launch_fwd_b<1, 3>(a, p.bm, p.splits, up2, st);
-    } else {
-      if (ns == 2) launch_fwd_b<3, 2>(a, p.bm, p.splits, up2, st);
-      else launch_fwd_b<3, 3>(a, p.bm, p.splits, up2, st);
-    }
+    ProfScope prof(st, kProfFwdB, KS, p.bm, up2 ? 1 : 0, ns, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
+    launch_fwd_b(a, p, KS, up2, ns, st);
   }
   ITCV_CHECK_LAUNCH("itcv_conv2d_fwd_bf16s");
-  if (p.splits > 1) {
-    const int blocks = (int)(cdivz(out_elems, 256) < 2048 ? cdivz(out_elems, 256) : 2048);
-    hipLaunchKernelGGL(splitk_reduce_fwd, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(ws), bias, y,
-                       out_elems, out_elems, p.splits, H * W, Co);
-    ITCV_CHECK_LAUNCH("itcv_conv2d_fwd_bf16s(reduce)");
-  }
-  return 0;
+  return reduce_fwd_splits("itcv_conv2d_fwd_bf16s(reduce)", ws, bias, y, out_elems, p.splits, H * W, Co, st);
 }
 
 size_t itcv_planes_bytes(int B, int C, int HW, int ns) {
@@ -2649,13 +2625,10 @@ int itcv_split_planes_scaled(const float* x, void* planes, int B, int C, int HW,
   ITCV_REQUIRE(!amax || ns == ITCV_PLANES_F16X2, "itcv_split_planes(a scale only applies to fp16 planes)");
   const size_t total = (size_t)B * (C / 8) * HW;
   const int blocks = (int)(cdivz(total, 256) < 8192 ? cdivz(total, 256) : 8192);
-  u32x4* pl = static_cast<u32x4*>(planes);
-  if (ns == ITCV_PLANES_F16X2)
-    hipLaunchKernelGGL((split_planes_kernel<2, true>), dim3(blocks), dim3(256), 0, S(stream), x, pl, B, C / 8, HW, amax);
-  else if (ns == 2)
-    hipLaunchKernelGGL(split_planes_kernel<2>, dim3(blocks), dim3(256), 0, S(stream), x, pl, B, C / 8, HW, amax);
-  else
-    hipLaunchKernelGGL(split_planes_kernel<3>, dim3(blocks), dim3(256), 0, S(stream), x, pl, B, C / 8, HW, amax);
+  pick_fmt(ns, [&](auto nsc, auto f16) {
+    hipLaunchKernelGGL((split_planes_kernel<nsc.value, f16.value>), dim3(blocks), dim3(256), 0, S(stream), x,
+                       static_cast<u32x4*>(planes), B, C / 8, HW, amax);
+  });
   ITCV_CHECK_LAUNCH("itcv_split_planes");
   return 0;
 }
@@ -2675,113 +2648,84 @@ int itcv_conv2d_fwd_bf16p(const void* xplanes, const void* wp, const float* bias
 int itcv_conv2d_fwd_bf16p_stat_tiles(int B, int Ci, int H, int W, int Co, int KS, int ns) {
   if (B <= 0 || Ci <= 0 || H <= 0 || W <= 0 || Co <= 0 || !itcv_conv2d_bf16s_supported(Ci, Co, KS)) return 0;
   if (ns == ITCV_PLANES_F16X2) return 0;     // the staged epilogue exists for the bf16 32x32x16 form only
-  const FwdPlanP2 p2 = plan_fwd_p2(B, Ci, H, W, Co, KS, ns);
-  return (p2.ok && p2.splits == 1 && p2.bn == 256) ? p2.nt : 0;
+  return plan_fwd_planes(B, Ci, H, W, Co, KS, ns, true).stat_tiles;
 }
 
 int itcv_conv2d_fwd_bf16p_st(const void* xplanes, const void* wp, const float* bias, float* y, int B, int Ci, int H,
-                             int W, int Co, int KS, int up2, int ns, float* tile_stats, void* ws, size_t ws_bytes,
+                             int W, int Co, int KS, int up2, int fmt, float* tile_stats, void* ws, size_t ws_bytes,
                              void* stream) {
   if (int e = check_dims("itcv_conv2d_fwd_bf16p", B, Ci, H, W, Co, KS)) return e;
-  ITCV_REQUIRE(xplanes && wp && y && fmt_ok(ns), "itcv_conv2d_fwd_bf16p");
-  const int f16 = ns == ITCV_PLANES_F16X2;
-  ns = planes_of_fmt(ns);
+  ITCV_REQUIRE(xplanes && wp && y && fmt_ok(fmt), "itcv_conv2d_fwd_bf16p");
+  const int f16 = fmt == ITCV_PLANES_F16X2, ns = planes_of_fmt(fmt);
   if (tile_stats && (f16 || !itcv_conv2d_fwd_bf16p_stat_tiles(B, Ci, H, W, Co, KS, ns)))
     return fail("%s: tile statistics are not available for this shape / format (see itcv_conv2d_fwd_bf16p_stat_tiles)",
                 "itcv_conv2d_fwd_bf16p_st");
   const size_t in_plane = (size_t)B * (Ci / 8) * (up2 ? (H / 2) * (W / 2) : H * W);
-  const ScaleRec* xrec = f16 ? reinterpret_cast<const ScaleRec*>(static_cast<const u32x4*>(xplanes) + 2 * in_plane) : nullptr;
+  const u32x4* xp = static_cast<const u32x4*>(xplanes);
+  const ScaleRec* xrec = f16 ? reinterpret_cast<const ScaleRec*>(xp + 2 * in_plane) : nullptr;
   if (!itcv_conv2d_bf16s_supported(Ci, Co, KS))
     return fail("%s: shape not supported by the split-bf16 kernel (Ci %% 32, Co > 32, KS 1/3)", "itcv_conv2d_fwd_bf16p");
   if (up2) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_conv2d_fwd_bf16p(up2)");
   const size_t out_elems = (size_t)B * Co * H * W;
-  const FwdPlanP2 p2 = plan_fwd_p2(B, Ci, H, W, Co, KS, ns);
-  if (p2.ok) {   // band kernel: tap reuse through LDS
-    if (p2.splits > 1 && (!ws || ws_bytes < (size_t)p2.splits * out_elems * sizeof(float)))
-      return fail("%s: workspace too small (need %lld bytes)", "itcv_conv2d_fwd_bf16p",
-                  (long long)((size_t)p2.splits * out_elems * sizeof(float)));
+  const FwdPlanP p = plan_fwd_planes(B, Ci, H, W, Co, KS, ns, tile_stats != nullptr);
+  if (int e = check_ws("itcv_conv2d_fwd_bf16p", ws, ws_bytes, p.ws_need)) return e;
+  const bool split = p.splits > 1;
+  const double flop = 2.0 * B * H * W * (double)Co * Ci * KS * KS;
+  hipStream_t st = S(stream);
+  if (p.path != FwdPath::Planes128) {   // band kernels: tap reuse through LDS
     ConvArgsP2 a;
-    a.xp = static_cast<const u32x4*>(xplanes);
+    a.xp = xp;
     a.wp = static_cast<const u32x4*>(wp);
-    a.bias = p2.splits > 1 ? nullptr : bias;
-    a.y = p2.splits > 1 ? static_cast<float*>(ws) : y;
+    a.bias = split ? nullptr : bias;
+    a.y = split ? static_cast<float*>(ws) : y;
     a.B = B, a.Ci = Ci, a.H = H, a.Co = Co;
-    a.Mp = p2.mt * p2.bm;
+    a.Mp = p.mt * p.bm;
     a.N = B * H * W;
-    a.mt = p2.mt, a.nt = p2.nt, a.cpt = p2.cpt, a.cpt_per_split = p2.cps;
-    a.SR = p2.SR, a.NSEG = p2.NSEG, a.NP = p2.NP, a.NPC = p2.NPC, a.PXB = p2.PXB;
+    a.mt = p.mt, a.nt = p.nt, a.cpt = p.cpt, a.cpt_per_split = p.cps;
+    a.SR = p.SR, a.NSEG = p.NSEG, a.NP = p.NP, a.NPC = p.NPC, a.PXB = p.PXB;
     a.h_shift = log2_exact(H);
-    a.stats = tile_stats, a.stat_T = p2.nt;
+    a.stats = tile_stats, a.stat_T = p.nt;
     a.xscale = xrec;
-    a.slab_stride = p2.splits > 1 ? out_elems : 0;
-    a.plane_stride = (size_t)B * (Ci / 8) * (up2 ? (H / 2) * (W / 2) : H * W);
+    a.slab_stride = split ? out_elems : 0;
+    a.plane_stride = in_plane;
 #ifdef ITCV_DIAG
     a.debug = (diag_ablate() & 64) ? 1 : 0;
 #endif
-    hipStream_t st = S(stream);
     {
-      ProfScope prof(st, band_is_persistent(a, p2) ? 9 : 8, log2_exact(W), p2.bm, up2 ? 1 : 0, f16 ? ITCV_PLANES_F16X2 : ns,
-                     2.0 * B * H * W * (double)Co * Ci * KS * KS);
-      launch_fwd_p2(a, p2, W, up2, f16, st);
+      ProfScope prof(st, p.path == FwdPath::Band ? kProfFwdBand : kProfFwdBandPersist, log2_exact(W), p.bm, up2 ? 1 : 0, fmt, flop);
+      launch_fwd_band(a, p, W, up2, f16, st);
     }
     ITCV_CHECK_LAUNCH("itcv_conv2d_fwd_bf16p(band)");
-    if (p2.splits > 1) {
-      const int blocks = (int)(cdivz(out_elems, 256) < 2048 ? cdivz(out_elems, 256) : 2048);
-      hipLaunchKernelGGL(splitk_reduce_fwd, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(ws), bias, y,
-                         out_elems, out_elems, p2.splits, H * W, Co);
-      ITCV_CHECK_LAUNCH("itcv_conv2d_fwd_bf16p(reduce)");
-    }
-    return 0;
-  }
-  const FwdPlanB p = plan_fwd_b(B, Ci, H, W, Co, KS);
-  if (p.splits > 1 && (!ws || ws_bytes < (size_t)p.splits * out_elems * sizeof(float)))
-    return fail("%s: workspace too small (need %lld bytes)", "itcv_conv2d_fwd_bf16p",
-                (long long)((size_t)p.splits * out_elems * sizeof(float)));
-  ConvArgsP a;
-  a.xp = static_cast<const u32x4*>(xplanes);
-  a.wp = static_cast<const u32x4*>(wp);
-  a.bias = p.splits > 1 ? nullptr : bias;
-  a.y = p.splits > 1 ? static_cast<float*>(ws) : y;
-  a.B = B, a.Ci = Ci, a.H = H, a.W = W, a.Co = Co;
-  a.Mp = p.mt * p.bm;
-  a.N = B * H * W;
-  a.mt = p.mt, a.nt = p.nt, a.ktiles = p.ktiles, a.ktiles_per_split = p.kps;
-  a.slab_stride = p.splits > 1 ? out_elems : 0;
-  a.plane_stride = in_plane;
-  a.xscale = xrec;
+  } else {
+    ConvArgsP a;
+    a.xp = xp;
+    a.wp = static_cast<const u32x4*>(wp);
+    a.bias = split ? nullptr : bias;
+    a.y = split ? static_cast<float*>(ws) : y;
+    a.B = B, a.Ci = Ci, a.H = H, a.W = W, a.Co = Co;
+    a.Mp = p.mt * p.bm;
+    a.N = B * H * W;
+    a.mt = p.mt, a.nt = p.nt, a.ktiles = p.ktiles, a.ktiles_per_split = p.kps;
+    a.slab_stride = split ? out_elems : 0;
+    a.plane_stride = in_plane;
+    a.xscale = xrec;
 #ifdef ITCV_DIAG
-  a.ablate = diag_ablate();
+    a.ablate = diag_ablate();
 #endif
-  hipStream_t st = S(stream);
-  {
-    ProfScope prof(st, 6, KS, p.bm, up2 ? 1 : 0, f16 ? ITCV_PLANES_F16X2 : ns, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
-    if (KS == 1) {
-      if (f16) launch_fwd_p<1, 2, true>(a, p.bm, p.splits, up2, st);
-      else if (ns == 2) launch_fwd_p<1, 2>(a, p.bm, p.splits, up2, st);
-      else launch_fwd_p<1, 3>(a, p.bm, p.splits, up2, st);
-    } else {
-      if (f16) launch_fwd_p<3, 2, true>(a, p.bm, p.splits, up2, st);
-      else if (ns == 2) launch_fwd_p<3, 2>(a, p.bm, p.splits, up2, st);
-      else launch_fwd_p<3, 3>(a, p.bm, p.splits, up2, st);
+    {
+      ProfScope prof(st, kProfFwdP, KS, p.bm, up2 ? 1 : 0, fmt, flop);
+      launch_fwd_p(a, p, KS, up2, fmt, st);
     }
+    ITCV_CHECK_LAUNCH("itcv_conv2d_fwd_bf16p");
   }
-  ITCV_CHECK_LAUNCH("itcv_conv2d_fwd_bf16p");
-  if (p.splits > 1) {
-    const int blocks = (int)(cdivz(out_elems, 256) < 2048 ? cdivz(out_elems, 256) : 2048);
-    hipLaunchKernelGGL(splitk_reduce_fwd, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(ws), bias, y,
-                       out_elems, out_elems, p.splits, H * W, Co);
-    ITCV_CHECK_LAUNCH("itcv_conv2d_fwd_bf16p(reduce)");
-  }
-  return 0;
+  return reduce_fwd_splits("itcv_conv2d_fwd_bf16p(reduce)", ws, bias, y, out_elems, p.splits, H * W, Co, st);
 }
 
 size_t itcv_conv2d_wgrad_workspace(int B, int Ci, int H, int W, int Co, int KS) {
   if (B <= 0 || Ci <= 0 || H <= 0 || W <= 0 || Co <= 0) return 0;
-  const WgPlan p = plan_wgrad(B, Ci, H, W, Co, KS);
-  size_t n = (size_t)p.splits * Co * p.nt * 128 * sizeof(float);
-  if (wgrad_swapped(Ci, Co)) {   // the call may run with its operands exchanged (see itcv_conv2d_wgrad)
-    const WgPlan q = plan_wgrad(B, Co, H, W, Ci, KS);
-    const size_t m = (size_t)q.splits * Ci * q.nt * 128 * sizeof(float);
+  size_t n = plan_wgrad(B, Ci, H, W, Co, KS).ws_need;
+  if (wgrad_swapped(Ci, Co)) {   // the call may run with its operands exchanged (see plan_wgrad_call)
+    const size_t m = plan_wgrad(B, Co, H, W, Ci, KS).ws_need;
     if (m > n) n = m;
   }
   return n;
@@ -2792,55 +2736,25 @@ int itcv_conv2d_wgrad(const float* x, const float* dy, float* dw, int B, int Ci,
   if (int e = check_dims("itcv_conv2d_wgrad", B, Ci, H, W, Co, KS)) return e;
   ITCV_REQUIRE(x && dy && dw, "itcv_conv2d_wgrad");
   if (up2) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_conv2d_wgrad(up2)");
-  // Few output channels (the predict conv, 64 -> 3): exchange the operands so that the wide tensor is the
-  // GEMM's row side and the 3-channel one the gathered side (4-channel column groups):
-  //   dW[co][ci][tap] = sum_q x[ci][q] * dy[co][q - tap]  =  wgrad(x' = dy, dy' = x)[ci][co][KK-1-tap]
   const bool swapped = !up2 && wgrad_swapped(Ci, Co);
-  const int Co_dw = Co, Ci_dw = Ci;
-  if (swapped) {
-    const float* tp = x;
-    x = dy, dy = tp;
-    const int tc = Ci;
-    Ci = Co, Co = tc;
-  }
-  const WgPlan p = plan_wgrad(B, Ci, H, W, Co, KS);
-  const size_t slab = (size_t)Co * p.nt * 128;
-  if (!ws || ws_bytes < (size_t)p.splits * slab * sizeof(float))
-    return fail("%s: workspace too small (need %lld bytes)", "itcv_conv2d_wgrad",
-                (long long)((size_t)p.splits * slab * sizeof(float)));
   WgradArgs a;
-  a.x = x, a.dy = dy;
-  a.out = static_cast<float*>(ws);
-  a.B = B, a.Ci = Ci, a.H = H, a.W = W, a.Co = Co;
-  a.Cip = p.cip;
-  a.Np = p.nt * 128;
-  a.Ktot = B * H * W;
-  a.mt = p.mt, a.nt = p.nt, a.tiles = p.tiles;
-  a.ktiles = p.ktiles, a.ktiles_per_split = p.kps, a.splits = p.splits;
-  a.w_shift = log2_exact(W), a.hw_shift = log2_exact(H * W);
-  a.x_bytes = (uint32_t)((size_t)B * Ci * (up2 ? (H / 2) * (W / 2) : H * W) * sizeof(float));
-  a.dy_bytes = (uint32_t)((size_t)B * Co * H * W * sizeof(float));
-  a.slab_stride = slab;
+  const WgPlan p = plan_wgrad_call(a, x, dy, ws, B, Ci, H, W, Co, KS, up2, swapped, 32);
+  if (int e = check_ws("itcv_conv2d_wgrad", ws, ws_bytes, p.ws_need)) return e;
   hipStream_t st = S(stream);
   {
-    ProfScope prof(st, 2, KS, p.bm, up2 ? 1 : 0, 0, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
-    if (KS == 1)
-      launch_wgrad<1>(a, p.bm, p.cb, up2, st);
-    else if (KS == 3)
-      launch_wgrad<3>(a, p.bm, p.cb, up2, st);
-    else
-      launch_wgrad<5>(a, p.bm, p.cb, up2, st);
+    ProfScope prof(st, kProfWgrad, KS, p.bm, up2 ? 1 : 0, 0, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
+    launch_wgrad(a, p, KS, up2, st);
   }
   ITCV_CHECK_LAUNCH("itcv_conv2d_wgrad");
   const size_t dw_elems = (size_t)Co * Ci * KS * KS;
   const int blocks = (int)(cdivz(dw_elems, 256) < 2048 ? cdivz(dw_elems, 256) : 2048);
   if (dw_elems <= 65536 && p.splits >= 32)
     hipLaunchKernelGGL(splitk_reduce_wgrad_small, dim3((int)cdivz(dw_elems, 16)), dim3(256), 0, st,
-                       static_cast<const float*>(ws), dw, Co_dw, Ci_dw, KS * KS, p.cip, p.cb, a.Np, slab, p.splits,
+                       static_cast<const float*>(ws), dw, Co, Ci, KS * KS, p.cip, p.cb, a.Np, p.slab, p.splits,
                        accumulate, swapped ? 1 : 0);
   else
-    hipLaunchKernelGGL(splitk_reduce_wgrad, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(ws), dw, Co_dw,
-                       Ci_dw, KS * KS, p.cip, p.cb, a.Np, slab, p.splits, accumulate, swapped ? 1 : 0);
+    hipLaunchKernelGGL(splitk_reduce_wgrad, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(ws), dw, Co, Ci,
+                       KS * KS, p.cip, p.cb, a.Np, p.slab, p.splits, accumulate, swapped ? 1 : 0);
   ITCV_CHECK_LAUNCH("itcv_conv2d_wgrad(reduce)");
   return 0;
 }
@@ -2857,41 +2771,19 @@ int itcv_conv2d_wgrad_bf16s(const float* x, const float* dy, float* dw, int B, i
   if (!itcv_conv2d_wgrad_bf16s_supported(Ci, H, W, Co, KS))
     return fail("%s: shape not supported by the split-bf16 kernel (Ci %% 32, W %% 8, Co > 32, KS 1/3)",
                 "itcv_conv2d_wgrad_bf16s");
-  WgPlan p = plan_wgrad(B, Ci, H, W, Co, KS);     // same tiling / slab layout as the fp32 kernel
-  if (p.bm < 64) p.bm = 64, p.mt = cdiv(Co, 64), p.tiles = p.mt * p.nt;
-  const size_t slab = (size_t)Co * p.nt * 128;
-  if (!ws || ws_bytes < (size_t)p.splits * slab * sizeof(float))
-    return fail("%s: workspace too small (need %lld bytes)", "itcv_conv2d_wgrad_bf16s",
-                (long long)((size_t)p.splits * slab * sizeof(float)));
   WgradArgs a;
-  a.x = x, a.dy = dy;
-  a.out = static_cast<float*>(ws);
-  a.B = B, a.Ci = Ci, a.H = H, a.W = W, a.Co = Co;
-  a.Cip = p.cip;
-  a.Np = p.nt * 128;
-  a.Ktot = B * H * W;
-  a.mt = p.mt, a.nt = p.nt, a.tiles = p.tiles;
-  a.ktiles = p.ktiles, a.ktiles_per_split = p.kps, a.splits = p.splits;
-  a.w_shift = log2_exact(W), a.hw_shift = log2_exact(H * W);
-  a.x_bytes = (uint32_t)((size_t)B * Ci * H * W * sizeof(float));
-  a.dy_bytes = (uint32_t)((size_t)B * Co * H * W * sizeof(float));
-  a.slab_stride = slab;
+  const WgPlan p = plan_wgrad_call(a, x, dy, ws, B, Ci, H, W, Co, KS, 0, false, 64);   // tiling / slab layout of the fp32 kernel
+  if (int e = check_ws("itcv_conv2d_wgrad_bf16s", ws, ws_bytes, p.ws_need)) return e;
   hipStream_t st = S(stream);
   {
-    ProfScope prof(st, 3, KS, p.bm, 0, ns, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
-    if (KS == 1) {
-      if (ns == 2) launch_wgrad_b<1, 2>(a, p.bm, p.cb, st);
-      else launch_wgrad_b<1, 3>(a, p.bm, p.cb, st);
-    } else {
-      if (ns == 2) launch_wgrad_b<3, 2>(a, p.bm, p.cb, st);
-      else launch_wgrad_b<3, 3>(a, p.bm, p.cb, st);
-    }
+    ProfScope prof(st, kProfWgradB, KS, p.bm, 0, ns, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
+    launch_wgrad_b(a, p, KS, ns, st);
   }
   ITCV_CHECK_LAUNCH("itcv_conv2d_wgrad_bf16s");
   const size_t dw_elems = (size_t)Co * Ci * KS * KS;
   const int blocks = (int)(cdivz(dw_elems, 256) < 2048 ? cdivz(dw_elems, 256) : 2048);
   hipLaunchKernelGGL(splitk_reduce_wgrad, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(ws), dw, Co, Ci,
-                     KS * KS, p.cip, p.cb, a.Np, slab, p.splits, accumulate, 0);
+                     KS * KS, p.cip, p.cb, a.Np, p.slab, p.splits, accumulate, 0);
   ITCV_CHECK_LAUNCH("itcv_conv2d_wgrad_bf16s(reduce)");
   return 0;
 }
@@ -2908,8 +2800,7 @@ int itcv_conv2d_wgrad_bf16p_supported(int B, int Ci, int H, int W, int Co, int K
 
 size_t itcv_conv2d_wgrad_bf16p_workspace(int B, int Ci, int H, int W, int Co, int KS) {
   if (!itcv_conv2d_wgrad_bf16p_supported(B, Ci, H, W, Co, KS)) return 0;
-  const WgPlanP p = plan_wgrad_p(B, Ci, H, W, Co);
-  return (size_t)p.splits * p.kh * 9 * Co * Ci * sizeof(float);
+  return plan_wgrad_p(B, Ci, H, W, Co).ws_need;
 }
 
 // dw[Co][Ci][3][3] (+)= conv weight gradient from the pre-split planes of x ([2][B][Ci/8][Hs][Ws]; Hs,Ws =
@@ -2923,8 +2814,7 @@ int itcv_conv2d_wgrad_bf16p(const void* xplanes, const void* dyplanes, float* dw
     return fail("%s: shape not supported (KS 3, W a power of two in 4..256, H a power of two, C %% 8)", "itcv_conv2d_wgrad_bf16p");
   if (up2) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_conv2d_wgrad_bf16p(up2)");
   const WgPlanP p = plan_wgrad_p(B, Ci, H, W, Co);
-  const size_t need = (size_t)p.splits * p.kh * 9 * Co * Ci * sizeof(float);
-  if (!ws || ws_bytes < need) return fail("%s: workspace too small (need %lld bytes)", "itcv_conv2d_wgrad_bf16p", (long long)need);
+  if (int e = check_ws("itcv_conv2d_wgrad_bf16p", ws, ws_bytes, p.ws_need)) return e;
   WgradArgsP a;
   a.xp = static_cast<const u32x4*>(xplanes), a.dyp = static_cast<const u32x4*>(dyplanes);
   a.slab = static_cast<float*>(ws);
@@ -2941,25 +2831,17 @@ int itcv_conv2d_wgrad_bf16p(const void* xplanes, const void* dyplanes, float* dw
   a.debug = (diag_ablate() & 64) ? 1 : 0;
 #endif
   hipStream_t st = S(stream);
-  a.groups = p.tiles_m * p.tiles_n * p.splits;
-  const int blocks = cdiv(a.groups, 8) * 24;
+  a.groups = p.groups;
   {
-    ProfScope prof(st, 7, log2_exact(W), p.bm, up2 ? 1 : 0, ns, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
-    switch (log2_exact(W)) {
-      case 2: launch_wgrad_p<2>(a, p.bm, p.bn, up2, blocks, f16, st); break;
-      case 3: launch_wgrad_p<3>(a, p.bm, p.bn, up2, blocks, f16, st); break;
-      case 4: launch_wgrad_p<4>(a, p.bm, p.bn, up2, blocks, f16, st); break;
-      case 5: launch_wgrad_p<5>(a, p.bm, p.bn, up2, blocks, f16, st); break;
-      default: launch_wgrad_p<6>(a, p.bm, p.bn, up2, blocks, f16, st); break;
-    }
+    ProfScope prof(st, kProfWgradP, log2_exact(W), p.bm, up2 ? 1 : 0, ns, 2.0 * B * H * W * (double)Co * Ci * KS * KS);
+    launch_wgrad_p(a, p, log2_exact(W), up2, f16, st);
   }
   ITCV_CHECK_LAUNCH("itcv_conv2d_wgrad_bf16p");
   if (accumulate == 2) return 0;     // deferred: the slabs stay in `ws` for itcv_wgrad_reduce_many
   const int coci = Co * Ci;
-  const int rsplits = p.splits * p.kh;
-  const bool fine = wgrad_reduce_fine(&rsplits, 1);
+  const bool fine = wgrad_reduce_fine(&p.slabs, 1);
   hipLaunchKernelGGL(wgrad_p_reduce, dim3(wgrad_reduce_blocks(coci, fine)), dim3(256), 0, st, static_cast<const float*>(ws),
-                     dw, coci, rsplits, accumulate, fine ? 1 : 0);
+                     dw, coci, p.slabs, accumulate, fine ? 1 : 0);
   ITCV_CHECK_LAUNCH("itcv_conv2d_wgrad_bf16p(reduce)");
   return 0;
 }
@@ -2967,8 +2849,7 @@ int itcv_conv2d_wgrad_bf16p(const void* xplanes, const void* dyplanes, float* dw
 // Deferred reduce of itcv_conv2d_wgrad_bf16p(accumulate = 2) calls: slabs per call = itcv_conv2d_wgrad_bf16p_slabs.
 int itcv_conv2d_wgrad_bf16p_slabs(int B, int Ci, int H, int W, int Co, int KS) {
   if (!itcv_conv2d_wgrad_bf16p_supported(B, Ci, H, W, Co, KS)) return 0;
-  const WgPlanP p = plan_wgrad_p(B, Ci, H, W, Co);
-  return p.splits * p.kh;
+  return plan_wgrad_p(B, Ci, H, W, Co).slabs;
 }
 size_t itcv_wgrad_reduce_desc_bytes(void) { return sizeof(WgReduceDesc); }
 int itcv_wgrad_reduce_desc(void* host_desc, const float* const* slabs, const int* splits, int nsrc, float* dw, int Co, int Ci,
@@ -3112,23 +2993,18 @@ int itcv_conv2d_wgrad5_bf16p(const float* small, const void* big_planes, float* 
   if (!itcv_conv2d_wgrad5_bf16p_supported(Cs, 64, H, W))
     return fail("%s: needs Cs <= 3, 64 channels on the other side, W in {32, 64}", "itcv_conv2d_wgrad5_bf16p");
   const int rpj = wgrad5_rows_per_job(B, H), njobs = B * cdiv(H, rpj);
-  const size_t need = (size_t)njobs * 16 * 5 * 64 * sizeof(float);
-  if (!ws || ws_bytes < need) return fail("%s: workspace too small (need %lld bytes)", "itcv_conv2d_wgrad5_bf16p", (long long)need);
+  if (int e = check_ws("itcv_conv2d_wgrad5_bf16p", ws, ws_bytes, itcv_conv2d_wgrad5_bf16p_workspace(B, H))) return e;
   hipStream_t st = S(stream);
   const size_t plane_stride = (size_t)B * 8 * H * W;
   {
-    ProfScope prof(st, 12, 5, Cs, stem ? 1 : 0, ns, 2.0 * B * H * W * 64.0 * Cs * 25);
-    const dim3 grid(cdiv(njobs, 4)), blk(256);
-    const u32x4* bp = static_cast<const u32x4*>(big_planes);
-    float* slab = static_cast<float*>(ws);
-    if (stem && f16)
-      launch_timed((conv_wgrad5_planes_kernel<1, true>), grid, blk, 0, st, small, bp, slab, B, Cs, H, W, rpj, njobs, plane_stride, small_amax);
-    else if (stem)
-      launch_timed((conv_wgrad5_planes_kernel<1, false>), grid, blk, 0, st, small, bp, slab, B, Cs, H, W, rpj, njobs, plane_stride, small_amax);
-    else if (f16)
-      launch_timed((conv_wgrad5_planes_kernel<-1, true>), grid, blk, 0, st, small, bp, slab, B, Cs, H, W, rpj, njobs, plane_stride, small_amax);
-    else
-      launch_timed((conv_wgrad5_planes_kernel<-1, false>), grid, blk, 0, st, small, bp, slab, B, Cs, H, W, rpj, njobs, plane_stride, small_amax);
+    ProfScope prof(st, kProfWgrad5, 5, Cs, stem ? 1 : 0, ns, 2.0 * B * H * W * 64.0 * Cs * 25);
+    pick<2>(stem ? 1 : 0, [&](auto stem_c) {
+      pick<2>(f16 ? 1 : 0, [&](auto f16_c) {
+        launch_timed((conv_wgrad5_planes_kernel<(stem_c.value ? 1 : -1), f16_c.value != 0>), dim3(cdiv(njobs, 4)), dim3(256), 0,
+                     st, small, static_cast<const u32x4*>(big_planes), static_cast<float*>(ws), B, Cs, H, W, rpj, njobs,
+                     plane_stride, small_amax);
+      });
+    });
   }
   ITCV_CHECK_LAUNCH("itcv_conv2d_wgrad5_bf16p");
   const int total = Cs * 25 * 64;
@@ -3142,7 +3018,7 @@ int itcv_conv2d_wgrad5_bf16p(const float* small, const void* big_planes, float* 
 //   bits 0-7 block rows BM, 8-15 KS, 16 up2, 20-31 split-K factor
 int itcv_conv2d_fwd_variant(int B, int Ci, int H, int W, int Co, int KS, int up2) {
   if (B <= 0 || Ci <= 0 || H <= 0 || W <= 0 || Co <= 0) return -1;
-  const FwdPlan p = plan_fwd(B, Ci, H, W, Co, KS);
+  const FwdPlan p = plan_fwd(kFwdF32, B, Ci, H, W, Co, KS);
   return p.bm | (KS << 8) | ((up2 ? 1 : 0) << 16) | (p.splits << 20);
 }
 int itcv_conv2d_wgrad_variant(int B, int Ci, int H, int W, int Co, int KS, int up2) {

@@ -123,15 +123,27 @@ struct Options {
 extern Options g_opt;
 inline int band_m16() { return g_opt.band_m16; }
 
-struct FwdPlanP2 {
-  int ok, bm, bn, mt, nt, cpt, splits, cps, SR, NSEG, NP, NPC, PXB;
-  int rows2;   // wide images: the 128-pixel tile is 2 rows x 64 columns
+// Which kernel a forward on pre-split planes runs on.  plan_fwd_planes() (conv_igemm.hip) decides it once per call; the
+// workspace and statistics queries, the entry point, the launch and the profiling label all read the plan.
+enum class FwdPath {
+  Band,             // conv_fwd_bf16p2_kernel: 256-pixel bands, one tile per block
+  BandPersistent,   // conv_fwd_bf16p3_kernel: the same tiles on a fixed number of blocks
+  WidePersistent,   // conv_fwd_bf16p3_kernel: 128- / 256-wide images, 128-pixel tiles
+  Planes128,        // conv_fwd_bf16p_kernel: 128-pixel tiles without tap reuse
+};
+struct FwdPlanP {
+  FwdPath path;
+  int bm, bn, mt, nt, splits;
+  int stat_tiles;   // pixel tiles for which the kernel can report per-channel output sums (0: it cannot)
+  size_t ws_need;   // split-K slabs
+  int cpt, cps, SR, NSEG, NP, NPC, PXB;   // band paths: 32-channel groups (per split) and the band geometry (ConvArgsP2)
+  int rows2;        // wide images: the 128-pixel tile is 2 rows x 64 columns
   size_t lds;
+  int ktiles, kps;  // Planes128: K tiles of 32 channels (per split)
 };
 
 // conv_band.hip
-FwdPlanP2 plan_fwd_p2(int B, int Ci, int H, int W, int Co, int KS, int ns);
-void launch_fwd_p2(const ConvArgsP2& a, const FwdPlanP2& p, int W, int up2, int f16, hipStream_t st);
-bool band_is_persistent(const ConvArgsP2& a, const FwdPlanP2& p);   // will launch_fwd_p2 use the persistent kernel?
+bool plan_fwd_band(FwdPlanP& p, int B, int Ci, int H, int W, int Co, int KS, int ns);   // false: the band kernels do not take the shape
+void launch_fwd_band(const ConvArgsP2& a, const FwdPlanP& p, int W, int up2, int f16, hipStream_t st);
 
 }  // namespace itcv

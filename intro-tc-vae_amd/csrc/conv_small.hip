@@ -395,31 +395,17 @@ int itcv_conv2d_small_cout_fwd(const float* x, const float* w, const float* bias
   dim3 grid(B * tx * ty), block(256);
   hipStream_t st = S(stream);
   const int Cw = for_dgrad ? Co : C;   // inner dimension of the weight tensor as indexed by the kernel
-#define ITCV_SMALL(KS_, CO_)                                                                                       \
-  do {                                                                                                             \
-    if (for_dgrad)                                                                                                 \
-      launch_timed((conv_small_cout_kernel<KS_, CO_, true>), grid, block, 0, st, x, w, bias, y, C, H, W, Cw, \
-                         tx, ty);                                                                                  \
-    else                                                                                                           \
-      launch_timed((conv_small_cout_kernel<KS_, CO_, false>), grid, block, 0, st, x, w, bias, y, C, H, W,    \
-                         Cw, tx, ty);                                                                              \
-  } while (0)
-#define ITCV_SMALL_KS(KS_)                    \
-  do {                                        \
-    if (Co == 1) ITCV_SMALL(KS_, 1);          \
-    else if (Co == 2) ITCV_SMALL(KS_, 2);     \
-    else if (Co == 3) ITCV_SMALL(KS_, 3);     \
-    else ITCV_SMALL(KS_, 4);                  \
-  } while (0)
   {
-    ProfScope prof(st, 4, KS, Co, 0, 0, 2.0 * B * H * W * (double)Co * C * KS * KS);
-    if (KS == 3)
-      ITCV_SMALL_KS(3);
-    else
-      ITCV_SMALL_KS(5);
+    ProfScope prof(st, kProfSmallCout, KS, Co, 0, 0, 2.0 * B * H * W * (double)Co * C * KS * KS);
+    pick_of<3, 5>(KS, [&](auto ks) {
+      pick_of<1, 2, 3, 4>(Co, [&](auto co) {
+        pick<2>(for_dgrad ? 1 : 0, [&](auto dg) {
+          launch_timed((conv_small_cout_kernel<ks.value, co.value, dg.value != 0>), grid, block, 0, st, x, w, bias, y, C, H, W,
+                       Cw, tx, ty);
+        });
+      });
+    });
   }
-#undef ITCV_SMALL_KS
-#undef ITCV_SMALL
   ITCV_CHECK_LAUNCH("itcv_conv2d_small_cout_fwd");
   return 0;
 }
@@ -440,19 +426,14 @@ int itcv_conv2d_small_cout_fwd_bf16p(const void* xplanes, const float* w, const 
   hipStream_t st = S(stream);
   const size_t plane_stride = (size_t)B * 8 * H * W;
   const u32x4* xp = static_cast<const u32x4*>(xplanes);
-  ProfScope prof(st, 10, KS, Co, 0, ns, 2.0 * B * H * W * (double)Co * C * KS * KS);
+  ProfScope prof(st, kProfSmallCoutP, KS, Co, 0, ns, 2.0 * B * H * W * (double)Co * C * KS * KS);
   const dim3 grid(cdiv(njobs, 4)), blk(256);
-#define ITCV_SCOUT_P(DG_, F_)                                                                                      \
-  launch_timed((conv_small_cout_planes_kernel<DG_, F_>), grid, blk, 0, st, xp, w, bias, y, B, H, W, Co, strips, \
-               row_blocks, RB, plane_stride, njobs)
-  if (for_dgrad) {
-    if (f16) ITCV_SCOUT_P(true, true);
-    else ITCV_SCOUT_P(true, false);
-  } else {
-    if (f16) ITCV_SCOUT_P(false, true);
-    else ITCV_SCOUT_P(false, false);
-  }
-#undef ITCV_SCOUT_P
+  pick<2>(for_dgrad ? 1 : 0, [&](auto dg) {
+    pick<2>(f16 ? 1 : 0, [&](auto f) {
+      launch_timed((conv_small_cout_planes_kernel<dg.value != 0, f.value != 0>), grid, blk, 0, st, xp, w, bias, y, B, H, W, Co,
+                   strips, row_blocks, RB, plane_stride, njobs);
+    });
+  });
   ITCV_CHECK_LAUNCH("itcv_conv2d_small_cout_fwd_bf16p");
   return 0;
 }
@@ -469,31 +450,17 @@ int itcv_conv2d_small_cin_fwd(const float* x, const float* w, const float* bias,
   const int tx = cdiv(W, kTile), ty = cdiv(H, kTile);
   dim3 grid(B * tx * ty), block(256);
   hipStream_t st = S(stream);
-#define ITCV_SCIN(KS_, CI_)                                                                                      \
-  do {                                                                                                           \
-    if (for_dgrad)                                                                                               \
-      launch_timed((conv_small_cin_kernel<KS_, CI_, true>), grid, block, 0, st, x, w, bias, y, Co, H, W, tx, \
-                         ty);                                                                                    \
-    else                                                                                                         \
-      launch_timed((conv_small_cin_kernel<KS_, CI_, false>), grid, block, 0, st, x, w, bias, y, Co, H, W,  \
-                         tx, ty);                                                                                \
-  } while (0)
-#define ITCV_SCIN_KS(KS_)                 \
-  do {                                    \
-    if (C == 1) ITCV_SCIN(KS_, 1);        \
-    else if (C == 2) ITCV_SCIN(KS_, 2);   \
-    else if (C == 3) ITCV_SCIN(KS_, 3);   \
-    else ITCV_SCIN(KS_, 4);               \
-  } while (0)
   {
-    ProfScope prof(st, 5, KS, C, 0, 0, 2.0 * B * H * W * (double)Co * C * KS * KS);
-    if (KS == 3)
-      ITCV_SCIN_KS(3);
-    else
-      ITCV_SCIN_KS(5);
+    ProfScope prof(st, kProfSmallCin, KS, C, 0, 0, 2.0 * B * H * W * (double)Co * C * KS * KS);
+    pick_of<3, 5>(KS, [&](auto ks) {
+      pick_of<1, 2, 3, 4>(C, [&](auto ci) {
+        pick<2>(for_dgrad ? 1 : 0, [&](auto dg) {
+          launch_timed((conv_small_cin_kernel<ks.value, ci.value, dg.value != 0>), grid, block, 0, st, x, w, bias, y, Co, H, W,
+                       tx, ty);
+        });
+      });
+    });
   }
-#undef ITCV_SCIN_KS
-#undef ITCV_SCIN
   ITCV_CHECK_LAUNCH("itcv_conv2d_small_cin_fwd");
   return 0;
 }
@@ -521,27 +488,17 @@ int itcv_conv2d_small_cin_fwd_bf16x3(const float* x, const float* w, const float
   row_blocks = cdiv(H, RB);
   const int njobs = B * row_blocks * strips;
   hipStream_t st = S(stream);
-  ProfScope prof(st, 11, KS, C, 0, ns, 2.0 * B * H * W * (double)Co * C * KS * KS);
+  ProfScope prof(st, kProfSmallCinMfma, KS, C, 0, ns, 2.0 * B * H * W * (double)Co * C * KS * KS);
   // (Requesting each input row one output row ahead of its use -- AHEAD = 1 -- was measured slower, 37 -> 43 us at
   // 128 x 3 x 64 x 64: the kernel is bound by its 134 MB of stores, and the longer ring costs registers.)
-#define ITCV_SCIN_K(CI_, DG_, F_)                                                                                       \
-  launch_timed((conv_small_cin_mfma_kernel<CI_, DG_, 0, F_>), dim3(cdiv(njobs, 4)), dim3(256), 0, st, x, w, bias, y, H, W, \
-               strips, row_blocks, RB, njobs, x_amax)
-#define ITCV_SCIN_M(CI_)                             \
-  do {                                               \
-    if (for_dgrad) {                                 \
-      if (f16) ITCV_SCIN_K(CI_, true, true);         \
-      else ITCV_SCIN_K(CI_, true, false);            \
-    } else {                                         \
-      if (f16) ITCV_SCIN_K(CI_, false, true);        \
-      else ITCV_SCIN_K(CI_, false, false);           \
-    }                                                \
-  } while (0)
-  if (C == 1) ITCV_SCIN_M(1);
-  else if (C == 2) ITCV_SCIN_M(2);
-  else ITCV_SCIN_M(3);
-#undef ITCV_SCIN_K
-#undef ITCV_SCIN_M
+  pick_of<1, 2, 3>(C, [&](auto ci) {
+    pick<2>(for_dgrad ? 1 : 0, [&](auto dg) {
+      pick<2>(f16 ? 1 : 0, [&](auto f) {
+        launch_timed((conv_small_cin_mfma_kernel<ci.value, dg.value != 0, 0, f.value != 0>), dim3(cdiv(njobs, 4)), dim3(256), 0,
+                     st, x, w, bias, y, H, W, strips, row_blocks, RB, njobs, x_amax);
+      });
+    });
+  });
   ITCV_CHECK_LAUNCH("itcv_conv2d_small_cin_fwd_bf16x3");
   return 0;
 }

@@ -1049,17 +1049,7 @@ static BnPlan bn_plan(bool bwd, int B, int C, int H, int W, int pool, int up2, i
   return p;
 }
 
-// The one place where runtime switches become template arguments: f(std::integral_constant<int, v>) for v in [0, N)
-// (0 for anything else); nested for several switches.
-template <int N, typename F>
-static inline void bn_pick(int v, F&& f) {
-  if constexpr (N > 1) {
-    if (v == N - 1) return f(std::integral_constant<int, N - 1>{});
-    return bn_pick<N - 1>(v, f);
-  } else {
-    f(std::integral_constant<int, 0>{});
-  }
-}
+// (runtime switches become template arguments through pick<N>, common.h)
 static inline int bn_fmt(int ns) { return ns == ITCV_PLANES_F16X2 ? 2 : (ns == 2 ? 0 : 1); }   // bf16x2 | bf16x3 | f16x2
 
 // statistics of all groups: into mean / rstd / the running buffers, or (SlicedFold) as far as the partial sums
@@ -1089,9 +1079,9 @@ static int bn_fwd_apply_launch(const BnPlan& p, const float* x, const float* mea
   ITCV_REQUIRE((size_t)B * C * H * W < (1ull << 31), "itcv_bn_act_fwd(tensor < 2^31 elements)");
   if (planes) {
     ITCV_REQUIRE(bn_fmt_ok(ns) && itcv_bn_act_planes_supported(C, H, W, pool), "itcv_bn_act_fwd(planes)");
-    bn_pick<2>(pool ? 1 : 0, [&](auto pool_c) {
-      bn_pick<3>(bn_fmt(ns), [&](auto fmt_c) {
-        bn_pick<2>(fold.part ? 1 : 0, [&](auto stats_c) {
+    pick<2>(pool ? 1 : 0, [&](auto pool_c) {
+      pick<3>(bn_fmt(ns), [&](auto fmt_c) {
+        pick<2>(fold.part ? 1 : 0, [&](auto stats_c) {
           constexpr int POOL = decltype(pool_c)::value, FMT = decltype(fmt_c)::value;
           constexpr bool STATS = decltype(stats_c)::value != 0;
           launch_timed((bn_act_fwd_planes_kernel<POOL, FMT == 1 ? 3 : 2, STATS, FMT == 2>), p.agrid, dim3(256), 0, st, x, mean,
@@ -1105,7 +1095,7 @@ static int bn_fwd_apply_launch(const BnPlan& p, const float* x, const float* mea
   if (pool) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_bn_act_fwd(pool)");
   else ITCV_REQUIRE((H * W) % 4 == 0, "itcv_bn_act_fwd(H*W % 4)");
   const size_t nout = pool ? (size_t)B * C * (H / 2) * (W / 2) : (size_t)B * C * H * W;
-  bn_pick<2>(pool ? 1 : 0, [&](auto pool_c) {
+  pick<2>(pool ? 1 : 0, [&](auto pool_c) {
     hipLaunchKernelGGL(bn_act_fwd_kernel<decltype(pool_c)::value>, p.agrid, dim3(256), 0, st, x, mean, rstd, gamma, beta, skip,
                        y, C, H, W, nout, slope, ilog2_exact(H * W), ilog2_exact(C) >= 0 ? C - 1 : -1);
   });
@@ -1126,15 +1116,15 @@ static int bn_bwd_reduce_launch(const BnPlan& p, const float* x, const float* dy
   float* mx = p.f16 ? reinterpret_cast<float*>(part + p.part_doubles) : nullptr;
   const bool fused = p.vec && p.splits == 1;   // the reduce kernel writes dsums and the parameter gradients itself
   const BnBwdFinal bf = fused ? BnBwdFinal{dsums, dgamma, dbeta, accumulate} : BnBwdFinal{};
-  bn_pick<3>(p.mode, [&](auto mode_c) {
+  pick<3>(p.mode, [&](auto mode_c) {
     constexpr int MODE = decltype(mode_c)::value;
     if (!p.vec) {
       hipLaunchKernelGGL(bn_bwd_partial<MODE>, p.rgrid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta, skip, part,
                          B, C, H, W, slope, p.splits);
       return;
     }
-    bn_pick<2>(fused ? 1 : 0, [&](auto fused_c) {
-      bn_pick<2>(p.f16 ? 1 : 0, [&](auto mx_c) {
+    pick<2>(fused ? 1 : 0, [&](auto fused_c) {
+      pick<2>(p.f16 ? 1 : 0, [&](auto mx_c) {
         hipLaunchKernelGGL((bn_bwd_partial_v4<MODE, decltype(fused_c)::value != 0, decltype(mx_c)::value != 0>), p.rgrid,
                            dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta, skip, part, B, C, H, W, slope, p.splits,
                            ilog2_exact(W), ilog2_exact(H * W), bf, p.grp, mx, p.nmx);
@@ -1164,9 +1154,9 @@ static int bn_bwd_apply_launch(const BnPlan& p, const float* x, const float* dy,
     if (ns == ITCV_PLANES_F16X2 && !mx)
       return fail("%s: fp16 gradient planes take their scale from the maxima of the reduce pass: use itcv_bn_train_bwd",
                   "itcv_bn_act_bwd_apply");
-    bn_pick<3>(p.mode, [&](auto mode_c) {
-      bn_pick<3>(bn_fmt(ns), [&](auto fmt_c) {
-        bn_pick<2>(fold.part ? 1 : 0, [&](auto sums_c) {
+    pick<3>(p.mode, [&](auto mode_c) {
+      pick<3>(bn_fmt(ns), [&](auto fmt_c) {
+        pick<2>(fold.part ? 1 : 0, [&](auto sums_c) {
           constexpr int MODE = decltype(mode_c)::value, FMT = decltype(fmt_c)::value;
           constexpr bool SUMS = decltype(sums_c)::value != 0;
           launch_timed((bn_bwd_apply_planes<MODE, FMT == 1 ? 3 : 2, SUMS, FMT == 2>), p.agrid, dim3(256), 0, st, x, dy, mean,
@@ -1179,7 +1169,7 @@ static int bn_bwd_apply_launch(const BnPlan& p, const float* x, const float* dy,
     return 0;
   }
   const size_t n = (size_t)B * C * H * W;
-  bn_pick<3>(p.mode, [&](auto mode_c) {
+  pick<3>(p.mode, [&](auto mode_c) {
     constexpr int MODE = decltype(mode_c)::value;
     if (p.vec)
       hipLaunchKernelGGL(bn_bwd_apply_v4<MODE>, p.agrid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, skip, dsums, count,
@@ -1312,7 +1302,7 @@ int itcv_bn_train_fwd_uv(const float* x, const float* gamma, const float* beta, 
   // roofline leg of bench.py: one event pair around the apply kernel (HBM-bound: its "work" is algorithmic bytes -- read
   // x once more [+ skip], write the planes [+ the fp32 output])
   const double px_out = (double)(groups > 1 ? groups : 1) * B * C * (pool ? H * W / 4 : H * W);
-  ProfScope bn_prof(S(stream), 13, ilog2_exact(W) >= 0 ? ilog2_exact(W) : 0, C / 8, pool ? 1 : 0, planes ? ns : 0,
+  ProfScope bn_prof(S(stream), kProfBnFwd, ilog2_exact(W) >= 0 ? ilog2_exact(W) : 0, C / 8, pool ? 1 : 0, planes ? ns : 0,
                     (double)(groups > 1 ? groups : 1) * B * C * H * W * 4.0 * (skip ? 2 : 1) + px_out * ((planes ? 4.0 : 0.0) + (y ? 4.0 : 0.0)));
   if (groups > 1) ITCV_REQUIRE(!planes || plane_stride, "itcv_bn_train_fwd(groups need the plane stride of the whole tensor)");
   const BnPlan p = bn_plan(false, B, C, H, W, pool, 0, groups, planes != nullptr, ns, plane_stride, ws ? ws_bytes : 0,
@@ -1398,7 +1388,7 @@ int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const 
   ITCV_REQUIRE(!(pool && up2), "itcv_bn_train_bwd(pool and up2 are exclusive)");
   // roofline leg of bench.py: the apply kernel reads x and dy once more and writes the planes [+ fp32 dx, + dskip]
   const double bn_el = (double)(groups > 1 ? groups : 1) * B * C * H * W;
-  ProfScope bn_prof(S(stream), 14, ilog2_exact(W) >= 0 ? ilog2_exact(W) : 0, C / 8, pool ? 1 : (up2 ? 2 : 0), dx_planes ? ns : 0,
+  ProfScope bn_prof(S(stream), kProfBnBwd, ilog2_exact(W) >= 0 ? ilog2_exact(W) : 0, C / 8, pool ? 1 : (up2 ? 2 : 0), dx_planes ? ns : 0,
                     bn_el * 4.0 * (1.0 + (pool ? 0.25 : (up2 ? 4.0 : 1.0)) + (skip ? 1.0 : 0.0)) +
                         bn_el * ((dx_planes ? 4.0 : 0.0) + (dx ? 4.0 : 0.0) + (dskip ? 4.0 : 0.0)));
   if (groups > 1) ITCV_REQUIRE(!dx_planes || plane_stride, "itcv_bn_train_bwd(groups need the plane stride of the whole tensor)");

@@ -101,7 +101,7 @@ def ref_dgrad(dy, w, KS=3):
 
 
 # ---- 1. persistent band kernel ----------------------------------------------------------------------------------------
-# (LOG2W, BM) of the forward launch of each PERSIST_CASES entry (plan_fwd_p2; the comments there)
+# (LOG2W, BM) of the forward launch of each PERSIST_CASES entry (plan_fwd_band; the comments there)
 PERSIST_FORMS = [(6, 64), (6, 64), (5, 128), (5, 64), (5, 64), (4, 128), (4, 64), (3, 64), (3, 128)]
 
 
@@ -133,7 +133,7 @@ def test_f16_persistent_band_kernel_vs_one_tile_kernel_and_fp64(HF, case, form):
 
 
 # ---- 2. wide images (W = 128 / 256) -----------------------------------------------------------------------------------
-# plan_fwd_p2 gives 128- and 256-wide images 128-pixel tiles of the persistent kernel: the two-row form (2 rows x 64
+# plan_fwd_band gives 128- and 256-wide images 128-pixel tiles of the persistent kernel: the two-row form (2 rows x 64
 # columns, rows2 = 1) at any H >= 2 and the one-row form (128 columns of one row) only at H = 1 (so never with up2).  BM 128
 # does not fit those tiles into 160 KB of LDS (176 KB two-row, 208 KB one-row): a layer with more than 64 output channels
 # runs the band kernel with BM 64 only where the mid-sized-layer rule picks 64-row tiles, else the 128-pixel planes
@@ -159,7 +159,7 @@ WIDE_CASES = [
 def test_f16_wide_image_kernels_vs_fp64(HF, case, form):
     """128- and 256-wide images in f16x3 (the c3 / c5 configurations): forward and data-gradient bit-identical with 256
     and with 5 persistent blocks, within 1.5e-6 of fp64 (kernel-level bar of test_f16_planes_conv_vs_fp64) on the first
-    and last image; every launch NS=4 and the forward on the kernel form plan_fwd_p2 selects (see WIDE_CASES)."""
+    and last image; every launch NS=4 and the forward on the kernel form plan_fwd_planes selects (see WIDE_CASES)."""
     B, Ci, H, W, Co, up2 = case
     x, w, dy = make_conv(case)
     xd, wd, dyd = x.to(dev()), w.to(dev()), dy.to(dev())
@@ -180,7 +180,7 @@ def test_f16_wide_image_kernels_vs_fp64(HF, case, form):
 
 
 # ---- 3. 128-pixel-tile planes kernel ----------------------------------------------------------------------------------
-PLANES128_CASES = [  # B, Ci, H, W, Co, KS, up2 -- plan_fwd_p2 refuses W < 8 and KS != 3: conv_fwd_bf16p_kernel
+PLANES128_CASES = [  # B, Ci, H, W, Co, KS, up2 -- plan_fwd_band refuses W < 8 and KS != 3: conv_fwd_bf16p_kernel
     (4, 128, 4, 4, 256, 3, False), (32, 512, 4, 4, 256, 3, False),        # 4x4 layers, the second split-K (K = 4608)
     (64, 256, 4, 4, 520, 3, False), (16, 256, 4, 4, 544, 3, True),        # ragged M tile (520), up2
     (2, 64, 8, 8, 64, 1, False), (5, 64, 1, 1, 70, 1, False), (3, 128, 16, 16, 96, 1, False),   # KS = 1 (res / 1x1 convs)

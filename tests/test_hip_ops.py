@@ -43,6 +43,8 @@ CONV_CASES = [
     (2, 8, 16, 16, 8, 3, True),       # fused nearest upsample
     (1, 12, 8, 8, 20, 1, True),
     (2, 512, 4, 4, 64, 3, False),     # deep K = 4608 -> split-K path
+    (2, 8, 8, 8, 8, 5, False),        # 5x5 on the igemm kernels (more than 4 channels on both sides): bm 32, K tail, cb 16
+    (2, 16, 8, 8, 72, 5, True),       # 5x5, bm 128, no K tail, fused upsample
 ]
 
 
