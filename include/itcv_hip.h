@@ -439,6 +439,34 @@ int itcv_sampling_bwd(const float* g_prodm, const float* g_logqz, const float* l
 /* ops.py:118-122 for x[m][n] with m == n or m == 1: diag[min(m,n)], off[m][n][n] = x - diag_embed(x) */
 int itcv_on_off_diag(const float* x, float* diag, float* off, int m, int n, void* stream);
 
+/* ---- disentanglement scores (evaluation/utils.py:245-273,323-335, metrics.py:169-219) -- */
+/* Mutual information between every discretised latent column of mu[N][D] (fp32, row stride ld elements) and every
+ * ground-truth factor column of v[N][K] (int32, values 0..fsize[k]-1), from integer joint histograms.
+ * Supported: 1 <= bins <= 32, 1 <= K <= 16, 1 <= fsize[k] <= 256, 1 <= N <= 2^30, any D >= 1; anything else returns non-zero
+ * before a launch.  fsize is a HOST array of K ints.
+ * Binning rule (np.histogram's edges + np.digitize(x, edges[:-1])), in fp64, each operation rounded on its own:
+ *   lo = (double)min_d, hi = (double)max_d; if (lo == hi) lo -= 0.5, hi += 0.5;
+ *   bin(x) = #{ j in 0..bins-1 : (double)x >= lo + j * ((hi - lo) / bins) }        (1..bins; stored 0-based in counts)
+ * flags[2] (int, zeroed by the caller, only ever set): [0] a non-finite element of mu (minmax), [1] a factor value
+ * outside [0, fsize[k]) (hist; that sample is not added for that factor).
+ *   _minmax: mn[D], mx[D]; workspace itcv_disent_minmax_workspace.
+ *   _bins:   out[N][D] = bin(mu[n][d]), dense int32.
+ *   _hist:   counts[d][bins * off[k] + b * fsize[k] + f] (off = prefix sums of fsize; itcv_disent_counts_elems uint32,
+ *            fsum = off[K]) and the factor marginals vcount[off[k] + f]; both are cleared by the call.  Integer sums:
+ *            bitwise reproducible.
+ *   _mi:     mi[D][K] = max(0, sum_{c>0} (c/N)(log c - log r_b - log s_f + log N)) in nats (r, s: row / column sums of the
+ *            pair's table) and h[K] = sum_{s>0} -(s/N) log(s/N), in fp64. */
+size_t itcv_disent_minmax_workspace(int N, int D);
+int itcv_disent_minmax(const float* mu, size_t ld, int N, int D, float* mn, float* mx, int* flags, void* ws,
+                       size_t ws_bytes, void* stream);
+int itcv_disent_bins(const float* mu, size_t ld, int N, int D, const float* mn, const float* mx, int bins, int* out,
+                     void* stream);
+size_t itcv_disent_counts_elems(int D, int fsum, int bins);
+int itcv_disent_hist(const float* mu, size_t ld, const int* v, int N, int D, int K, const int* fsize, int bins,
+                     const float* mn, const float* mx, unsigned* counts, unsigned* vcount, int* flags, void* stream);
+int itcv_disent_mi(const unsigned* counts, const unsigned* vcount, int N, int D, int K, const int* fsize, int bins,
+                   double* mi, double* h, void* stream);
+
 /* ---- reconstruction loss (ops.py:188-236) --------------------------------------------- */
 #define ITCV_LOSS_MSE 0
 #define ITCV_LOSS_L1 1

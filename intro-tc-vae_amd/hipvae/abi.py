@@ -139,6 +139,12 @@ SIGNATURES = {
     "itcv_sampling_fwd": (i32, [p, p, p, p, p, i32, i32, i64, i32, p]),
     "itcv_sampling_bwd": (i32, [p, p, p, p, p, p, p, i32, i32, i64, i32, p]),
     "itcv_on_off_diag": (i32, [p, p, p, i32, i32, p]),
+    "itcv_disent_minmax_workspace": (sz, [i32, i32]),
+    "itcv_disent_minmax": (i32, [p, sz, i32, i32, p, p, p, p, sz, p]),
+    "itcv_disent_bins": (i32, [p, sz, i32, i32, p, p, i32, p, p]),
+    "itcv_disent_counts_elems": (sz, [i32, i32, i32]),
+    "itcv_disent_hist": (i32, [p, sz, p, i32, i32, i32, p, i32, p, p, p, p, p, p]),
+    "itcv_disent_mi": (i32, [p, p, i32, i32, i32, p, i32, p, p, p]),
     "itcv_recon_workspace": (sz, [i32, sz]),
     "itcv_recon_rows_fwd": (i32, [p, p, p, i32, sz, i32, p, sz, p]),
     "itcv_recon_rows_bwd": (i32, [p, p, p, p, i32, sz, i32, p]),

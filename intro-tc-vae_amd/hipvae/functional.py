@@ -1565,3 +1565,81 @@ class ReconRowsFn(Function):
         d = torch.empty_like(recon)
         call("itcv_recon_rows_bwd", ptr(x), ptr(recon), ptr(g), ptr(d), B, P, lt, stream())
         return None, d, None
+
+
+# ------------------------------------------------------------------ disentanglement scores (csrc/disent.hip)
+def _disent_mu(mu):
+    """mu as an fp32 [N, D] device tensor with unit column stride (a row stride is passed to the kernels as is)."""
+    if mu.dim() != 2 or mu.shape[0] < 1 or mu.shape[1] < 1:
+        raise abi.HipExtensionError(f"disent: representations must be a non-empty [N, D] tensor (got {tuple(mu.shape)})")
+    if mu.dtype != F32:
+        raise abi.HipExtensionError(f"HIP path is fp32 only (got {mu.dtype})")
+    if not mu.is_cuda:
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    mu = mu.detach()
+    if mu.stride(1) != 1 or mu.stride(0) < mu.shape[1]:
+        mu = mu.contiguous()
+    return mu
+
+
+def disent_flags(device):
+    """The two sticky flags of the disent kernels ([0] non-finite representation, [1] factor value out of range)."""
+    return torch.zeros(2, dtype=torch.int32, device=device)
+
+
+def disent_minmax(mu, flags):
+    """Per-column (min[D], max[D]) of mu[N, D]; sets flags[0] on a non-finite element."""
+    mu = _disent_mu(mu)
+    N, D = mu.shape
+    mn, mx = torch.empty((D,), dtype=F32, device=mu.device), torch.empty((D,), dtype=F32, device=mu.device)
+    nws = lib.itcv_disent_minmax_workspace(N, D)
+    ws = _ws(nws, mu.device)
+    call("itcv_disent_minmax", mu.data_ptr(), mu.stride(0), N, D, ptr(mn), ptr(mx), ptr(flags), ptr(ws), nws, stream())
+    return mn, mx
+
+
+def disent_bins(mu, mn, mx, bins):
+    """int32 [N, D] bin numbers 1..bins of the fixed fp64 binning rule (include/itcv_hip.h)."""
+    mu = _disent_mu(mu)
+    N, D = mu.shape
+    out = torch.empty((N, D), dtype=torch.int32, device=mu.device)
+    call("itcv_disent_bins", mu.data_ptr(), mu.stride(0), N, D, ptr(mn), ptr(mx), int(bins), ptr(out), stream())
+    return out
+
+
+def _disent_factors(factors, factor_sizes, N, device):
+    import ctypes
+    sizes = [int(s) for s in factor_sizes]
+    v = factors if isinstance(factors, torch.Tensor) else torch.as_tensor(factors)
+    if v.dim() != 2 or v.shape[0] != N or v.shape[1] != len(sizes):
+        raise abi.HipExtensionError(
+            f"disent: factors must be [N = {N}, K = {len(sizes)}] (got {tuple(v.shape)})")
+    v = v.to(device=device, dtype=torch.int32).contiguous()
+    return v, sizes, (ctypes.c_int * len(sizes))(*sizes)
+
+
+def disent_hist(mu, factors, factor_sizes, mn, mx, bins, flags):
+    """(counts, vcount) as flat uint32 tables viewed as int32 tensors: counts[d][bins * off[k] + b * size[k] + f] and
+    vcount[off[k] + f]; sets flags[1] on a factor value outside its range.  The range checks of the library (bins, K, sizes)
+    raise before any launch."""
+    mu = _disent_mu(mu)
+    N, D = mu.shape
+    v, sizes, csizes = _disent_factors(factors, factor_sizes, N, mu.device)
+    fsum = sum(sizes)
+    n = lib.itcv_disent_counts_elems(D, fsum, int(bins))              # 0 for sizes the call below refuses
+    counts = torch.empty((max(n, 1),), dtype=torch.int32, device=mu.device)
+    vcount = torch.empty((max(fsum, 1),), dtype=torch.int32, device=mu.device)
+    call("itcv_disent_hist", mu.data_ptr(), mu.stride(0), ptr(v), N, D, len(sizes), csizes, int(bins), ptr(mn), ptr(mx),
+         ptr(counts), ptr(vcount), ptr(flags), stream())
+    return counts, vcount
+
+
+def disent_mi(counts, vcount, N, D, factor_sizes, bins):
+    """(MI[D, K], H[K]) in fp64 from the integer tables of ``disent_hist``."""
+    import ctypes
+    sizes = [int(s) for s in factor_sizes]
+    mi = torch.empty((D, len(sizes)), dtype=torch.float64, device=counts.device)
+    h = torch.empty((len(sizes),), dtype=torch.float64, device=counts.device)
+    call("itcv_disent_mi", ptr(counts), ptr(vcount), int(N), int(D), len(sizes), (ctypes.c_int * len(sizes))(*sizes),
+         int(bins), ptr(mi), ptr(h), stream())
+    return mi, h

@@ -49,6 +49,9 @@ class VAESolver:
         import os as _os
         self.conv_math = _os.environ.get("ITCV_CONV_MATH") or ("f16x3" if use_amp else "fp32")
         self.writer, self.test_iter, self.clip = writer, test_iter, clip
+        # MIG and modularity on the device (hipvae.disentangle): None -> when the reference's ``evaluation`` package cannot
+        # be imported; True -> always (its classifier-based writers are still called when it imports); False -> never
+        self.device_scores = None
         self.recon_loss_type = recon_loss_type
         self.scale = 1 / (self.model.cdim * self.model.encoder.image_size ** 2)   # solvers/vae.py:61
         self._flat = {}
@@ -293,19 +296,35 @@ class VAESolver:
             self.writer.add_scalars("losses", losses, global_step=cur_iter)
 
     def write_disentanglemnt_scores(self, cur_iter: int, num_samples: int = 10000):
-        """Delegates to the reference's CPU evaluation package when it is importable; out of scope here."""
+        """solvers/vae.py:188-213.  The reference's ``evaluation`` package writes all four scores when it imports (it needs
+        sklearn and xgboost).  MIG and modularity do not need it: they are computed on the device (``device_scores``,
+        hipvae.disentangle) from one encode of the sampled images, in eval mode, with a private numpy generator (torch's
+        RNG streams and the BatchNorm running buffers are untouched).  The classifier-based scores stay delegated."""
         if self.writer is None or not isinstance(self.dataset, DisentanglementDataset) or cur_iter % self.test_iter:
             return
         try:
             from evaluation import metrics as M
         except Exception:  # noqa: BLE001
+            M = None
+        native = (M is None) if self.device_scores is None else bool(self.device_scores)
+        if M is None and not native:
             return
+        if native:
+            from hipvae import disentangle
+            if getattr(self, "latent_generator", None) is None:
+                self.latent_generator = disentangle.FactorSampler(self.dataset, self.device)
         was_training = self.model.training
         self.model.eval()
         n = num_samples if len(self.dataset) >= num_samples else len(self.dataset) // 2
-        kw = dict(latent_generator=self.latent_generator, model=self.model, num_samples=n, batch_size=self.batch_size)
-        for fn in (M.write_bvae_score, M.write_dci_score, M.write_mig_score, M.write_mod_expl_score):
-            fn(self.writer, cur_iter, **kw)
+        if M is not None:
+            kw = dict(latent_generator=self.latent_generator, model=self.model, num_samples=n, batch_size=self.batch_size)
+            writers = (M.write_bvae_score, M.write_dci_score) + (() if native else (M.write_mig_score, M.write_mod_expl_score))
+            for fn in writers:
+                fn(self.writer, cur_iter, **kw)
+        if native:
+            got = disentangle.compute_scores(self.latent_generator, self.model, num_samples=n, batch_size=self.batch_size)
+            self.writer.add_scalar("mig_score", got["mig"], global_step=cur_iter)
+            self.writer.add_scalars("mod_expl", dict(modularity_score=got["modularity"]), global_step=cur_iter)
         if was_training:
             self.model.train()
 
