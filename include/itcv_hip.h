@@ -467,6 +467,42 @@ int itcv_disent_hist(const float* mu, size_t ld, const int* v, int N, int D, int
 int itcv_disent_mi(const unsigned* counts, const unsigned* vcount, int N, int D, int K, const int* fsize, int bins,
                    double* mi, double* h, void* stream);
 
+/* ---- classifier-based disentanglement scores (evaluation/metrics.py:20-79,237-304; utils.py:60-174,277-320) -- */
+/* The beta-VAE score and explicitness are the optimum of an L2-regularised softmax regression plus accuracy / one-vs-rest
+ * ROC AUC of its probabilities.  All arithmetic is fp64; x[N][D] is fp32 with row stride ld (elements).
+ * K problems share x: y[N][K] int32 labels, csize[K] class counts (a HOST array; coff = prefix sums, csum = coff[K]),
+ * cvalid[csum] int32 (non-zero: the class takes part), theta[(D + 1)][csum] fp64 (row D: the intercepts).
+ * mean / scale: both NULL (raw x) or both given (x is standardised on the fly as (x - mean[d]) / scale[d]).
+ * Rule for problem p, with V its valid classes, its valid rows those with y in V, n their number:
+ *   F_p = (1/n) sum_valid [ logsumexp_{c in V}(x.W_c + b_c) - (x.W_y + b_y) ] + (lambda/2) sum_{c in V} |W_c|^2,
+ *   lambda = m / (C n), m = 2 when |V| == 2 (sklearn's binary model), else 1; intercepts are not penalised; the gradient
+ *   of an invalid class is exactly 0.
+ * Supported: 1 <= K <= 16, 1 <= csize[k] <= 256, 1 <= D <= 512, 1 <= N <= 2^30; anything else returns non-zero before a
+ * launch.  flags[2] as for itcv_disent_*: [0] a non-finite element of x, [1] a label outside [0, csize[k]).
+ * Every floating-point reduction has a fixed order: two calls with the same inputs return the same bits.
+ *   _colstats: mean[D], scale[D] = sqrt(population variance), 1 where the variance is 0 (StandardScaler).
+ *   _valgrad:  f[K], grad[(D + 1)][csum]; workspace itcv_logreg_workspace(N, D, K, csum).
+ *   _proba:    P[N][csum] (0 for invalid classes and for rows whose label is invalid), pred[N][K] = first argmax of the
+ *              logits over the valid classes (every row).
+ *   _auc:      per valid class c over the problem's valid rows, s = P[:, c]:
+ *              count2[c] = sum_{i: y_i = c} sum_{j: y_j != c} (2 [s_i > s_j] + [s_i == s_j]), pos[c], neg[c] (uint64, cleared by
+ *              the call); AUC_c = count2 / (2 pos neg).
+ *   itcv_zdiff_row: out[d] = fp32( mean_b |a[b][d] - b[b][d]| ), accumulated in fp64 (utils.py:106-109). */
+size_t itcv_logreg_colstats_workspace(int N, int D);
+int itcv_logreg_colstats(const float* x, size_t ld, int N, int D, double* mean, double* scale, int* flags, void* ws,
+                         size_t ws_bytes, void* stream);
+size_t itcv_logreg_workspace(int N, int D, int K, int csum);
+int itcv_logreg_valgrad(const float* x, size_t ld, const double* mean, const double* scale, const int* y, int N, int D,
+                        int K, const int* csize, const int* cvalid, const double* theta, double C, double* f,
+                        double* grad, int* flags, void* ws, size_t ws_bytes, void* stream);
+int itcv_logreg_proba(const float* x, size_t ld, const double* mean, const double* scale, const int* y, int N, int D,
+                      int K, const int* csize, const int* cvalid, const double* theta, double* P, int* pred, int* flags,
+                      void* stream);
+int itcv_logreg_auc(const double* P, const int* y, int N, int K, const int* csize, const int* cvalid,
+                    unsigned long long* count2, unsigned long long* pos, unsigned long long* neg, int* flags,
+                    void* stream);
+int itcv_zdiff_row(const float* a, const float* b, size_t ld, int B, int D, float* out, void* stream);
+
 /* ---- reconstruction loss (ops.py:188-236) --------------------------------------------- */
 #define ITCV_LOSS_MSE 0
 #define ITCV_LOSS_L1 1

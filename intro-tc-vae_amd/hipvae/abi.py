@@ -145,6 +145,13 @@ SIGNATURES = {
     "itcv_disent_counts_elems": (sz, [i32, i32, i32]),
     "itcv_disent_hist": (i32, [p, sz, p, i32, i32, i32, p, i32, p, p, p, p, p, p]),
     "itcv_disent_mi": (i32, [p, p, i32, i32, i32, p, i32, p, p, p]),
+    "itcv_logreg_colstats_workspace": (sz, [i32, i32]),
+    "itcv_logreg_colstats": (i32, [p, sz, i32, i32, p, p, p, p, sz, p]),
+    "itcv_logreg_workspace": (sz, [i32] * 4),
+    "itcv_logreg_valgrad": (i32, [p, sz, p, p, p, i32, i32, i32, p, p, p, f64, p, p, p, p, sz, p]),
+    "itcv_logreg_proba": (i32, [p, sz, p, p, p, i32, i32, i32, p, p, p, p, p, p, p]),
+    "itcv_logreg_auc": (i32, [p, p, i32, i32, p, p, p, p, p, p, p]),
+    "itcv_zdiff_row": (i32, [p, p, sz, i32, i32, p, p]),
     "itcv_recon_workspace": (sz, [i32, sz]),
     "itcv_recon_rows_fwd": (i32, [p, p, p, i32, sz, i32, p, sz, p]),
     "itcv_recon_rows_bwd": (i32, [p, p, p, p, i32, sz, i32, p]),

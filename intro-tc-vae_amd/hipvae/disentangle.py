@@ -8,8 +8,14 @@ table -- the joint histogram of (latent bin, factor value) per pair -- so here t
     minmax -> joint histograms (integer, LDS + global atomics) -> MI[D, K], H[K] in fp64        (csrc/disent.hip)
 
 and the two scores are a few fp64 tensor operations on MI and H.  One host read-back returns the scores together with
-the two error flags.  Nothing here needs sklearn or xgboost; the classifier-based scores (beta-VAE, DCI, explicitness)
-stay with the reference's package.
+the two error flags.  Nothing here needs sklearn or xgboost.
+
+The beta-VAE score (evaluation/metrics.py:20-79, utils.py:60-174) and explicitness (metrics.py:237-304,
+utils.py:277-320) are classifier-based, but they are mathematics too: each is read off the optimum of an L2-regularised
+softmax regression (C = 1), which is strictly convex in the weights and so does not depend on the solver.  The rule is
+in include/itcv_hip.h; csrc/logreg.hip evaluates all K problems in one launch in fp64, hipvae/logreg.py minimises them
+to ``max|grad F_p| <= gtol`` for every problem (or raises), accuracy comes from the predictions and one-vs-rest ROC AUC
+from integer pair counts.  Only DCI (gradient-boosted trees) stays with the reference's package.
 
 The binning rule is fixed (include/itcv_hip.h): with lo / hi the column's minimum / maximum as fp64 (lo -= 0.5, hi += 0.5
 when they are equal), ``bin(x) = #{j in 0..bins-1 : x >= lo + j * ((hi - lo) / bins)}`` -- ``np.histogram``'s edges
@@ -25,9 +31,12 @@ import numpy as np
 import torch
 
 from . import functional as HF
+from . import logreg
 
 __all__ = ["discretize", "factor_counts", "mutual_info", "mig_score", "modularity_score", "scores", "FactorSampler",
-           "factor_representations", "compute_mig_score", "compute_modularity_score", "compute_scores"]
+           "factor_representations", "compute_mig_score", "compute_modularity_score", "compute_scores",
+           "fit_softmax", "factor_change_accuracy", "explicitness", "factor_change_rows", "compute_bvae_score",
+           "compute_explicitness_score", "compute_mod_expl_score"]
 
 
 def _raise_on(flags):
@@ -230,3 +239,145 @@ def compute_scores(latent_generator, model, num_samples=10000, batch_size=64, pa
     params = params or {}
     mu, v = factor_representations(latent_generator, model, num_samples, batch_size)
     return scores(mu, v, _latent_sizes(latent_generator), params.get("mig_bins", 10), params.get("modularity_bins", 20))
+
+
+# ---- classifier-based scores: beta-VAE and explicitness --------------------------------------------------------------
+def _offsets(sizes):
+    off = [0]
+    for s in sizes:
+        off.append(off[-1] + int(s))
+    return off
+
+
+def _present(y, sizes):
+    """int32 [csum] device mask: class c of problem k occurs in column k of y (labels outside the range are left to the
+    kernels' flag)."""
+    off = _offsets(sizes)
+    out = torch.zeros((off[-1],), dtype=torch.int32, device=y.device)
+    for k, s in enumerate(sizes):
+        col = y[:, k].long()
+        ok = (col >= 0) & (col < s)
+        out[off[k]:off[k + 1]] = (torch.bincount(col[ok], minlength=s) > 0).to(torch.int32)
+    return out
+
+
+def fit_softmax(x, y, class_sizes, cvalid, stats=None, C=1.0, gtol=1e-9, max_iter=2000, flags=None):
+    """Fit the K softmax regressions of (x[N, D], y[N, K]) jointly.  Returns ``(problem, theta, info)``: the
+    ``HF.LogregProblem``, the optimum ``theta[(D + 1), csum]`` and the solver's report.  A problem with fewer than two
+    valid classes raises ``ValueError`` (as sklearn's ``fit``); non-convergence raises ``RuntimeError``."""
+    sizes = [int(s) for s in class_sizes]
+    off = _offsets(sizes)
+    flags = HF.disent_flags(x.device) if flags is None else flags
+    prob = HF.LogregProblem(x, y, sizes, cvalid, flags, stats=stats, C=C)
+    nvalid = [int(v) for v in torch.stack([prob.cvalid[a:b].ne(0).sum() for a, b in zip(off[:-1], off[1:])]).tolist()]
+    for k, nv in enumerate(nvalid):
+        if nv < 2:
+            raise ValueError(f"logreg: problem {k} needs samples of at least 2 classes, but the data contains {nv}")
+    theta, info = logreg.minimize(prob.valgrad, (prob.D + 1, prob.csum), off, prob.x.device, gtol=gtol, max_iter=max_iter,
+                                  check=(lambda: flags, _raise_on))
+    return prob, theta, info
+
+
+def _macro_auc(count2, pos, neg, cvalid, sizes):
+    """Mean over the problems of the mean AUC over each problem's valid classes: an fp64 device scalar."""
+    off = _offsets(sizes)
+    auc = count2.to(torch.float64) / (2.0 * pos.to(torch.float64) * neg.to(torch.float64))
+    per = [auc[a:b][cvalid[a:b].ne(0)].mean() for a, b in zip(off[:-1], off[1:])]
+    return torch.stack(per).mean()
+
+
+def factor_change_accuracy(x_train, y_train, x_test, y_test, num_classes, scale=False, gtol=1e-9, max_iter=2000):
+    """evaluation/utils.py:156-174 at the optimum: accuracy on the test rows of the softmax regression fitted on the
+    training rows (optionally standardised with the training statistics).  A test label unseen in training counts as wrong."""
+    flags = HF.disent_flags(x_train.device)
+    y_train, y_test = y_train.reshape(-1, 1), y_test.reshape(-1, 1)
+    stats = HF.logreg_colstats(x_train, flags) if scale else None
+    yt = torch.as_tensor(y_train).to(device=x_train.device, dtype=torch.int32)
+    prob, theta, _ = fit_softmax(x_train, yt, [num_classes], _present(yt, [num_classes]), stats=stats, gtol=gtol,
+                                 max_iter=max_iter, flags=flags)
+    ye = torch.as_tensor(y_test).to(device=x_train.device, dtype=torch.int32)
+    _, pred = prob.proba(theta, x_test, ye)
+    return _read([(pred == ye).sum().to(torch.float64)], flags)[0] / ye.shape[0]      # an integer count: exact
+
+
+def explicitness(x_train, y_train, x_test, y_test, factor_sizes, gtol=1e-9, max_iter=2000):
+    """``(train, test)`` explicitness (evaluation/metrics.py:296-302, utils.py:285-320) at the optimum: both sets are
+    standardised with the training statistics, per factor the classes present in BOTH sets take part, and the score is the
+    mean over factors of the macro one-vs-rest AUC of the fitted probabilities."""
+    sizes = [int(s) for s in factor_sizes]
+    flags = HF.disent_flags(x_train.device)
+    y_train = torch.as_tensor(y_train).to(device=x_train.device, dtype=torch.int32)
+    y_test = torch.as_tensor(y_test).to(device=x_train.device, dtype=torch.int32)
+    cvalid = _present(y_train, sizes) * _present(y_test, sizes)
+    stats = HF.logreg_colstats(x_train, flags)
+    prob, theta, _ = fit_softmax(x_train, y_train, sizes, cvalid, stats=stats, gtol=gtol, max_iter=max_iter, flags=flags)
+    out = []
+    for x, y in ((None, None), (x_test, y_test)):
+        P, _ = prob.proba(theta, x, y)
+        yy = prob.y if y is None else y
+        out.append(_macro_auc(*HF.logreg_auc(P, yy, sizes, cvalid, flags), cvalid, sizes))
+    return tuple(_read(out, flags))
+
+
+def factor_change_rows(latent_generator, model, num_samples, batch_size, index_state=None):
+    """``(z_diff [num_batches, D] fp32 on the device, y [num_batches] numpy int64)``: evaluation/utils.py:60-153.  Each row
+    comes from two factor draws that share one column, two observation draws and ONE eval-mode encode of the 2 B stacked
+    images (eval BatchNorm makes stacking exact).  The fixed factor's index is drawn, as the reference writes it, from a
+    fresh ``RandomState(latent_generator.seed)`` per batch, or from ``index_state`` if given."""
+    nb = int(np.ceil(num_samples / batch_size))
+    was_training = model.training
+    model.eval()
+    rows, y = None, np.empty((nb,), dtype=np.int64)
+    try:
+        with torch.no_grad():
+            for r in range(nb):
+                rs = index_state if index_state is not None else np.random.RandomState(latent_generator.seed)
+                y[r] = k = rs.randint(latent_generator.num_latents)
+                v_li = latent_generator.sample_factors_of_variation(batch_size)
+                v_lj = latent_generator.sample_factors_of_variation(batch_size)
+                v_li[:, k] = v_lj[:, k]
+                x_li = latent_generator.sample_observations_from_factors(v_li)
+                x_lj = latent_generator.sample_observations_from_factors(v_lj)
+                mu, _ = model.encode(torch.cat([x_li, x_lj], 0))
+                mu = mu.reshape(2 * batch_size, -1)
+                if rows is None:
+                    rows = torch.empty((nb, mu.shape[1]), dtype=torch.float32, device=mu.device)
+                HF.zdiff_row(mu[:batch_size], mu[batch_size:], rows[r])
+    finally:
+        model.train(was_training)
+    return rows, y
+
+
+def compute_bvae_score(latent_generator, model, num_samples=10000, batch_size=64, index_state=None, gtol=1e-9,
+                       max_iter=2000):
+    """evaluation/metrics.py:20-79 with the reference's argument names: ``(score, score_scaled)``."""
+    nl = int(latent_generator.num_latents)
+    xtr, ytr = factor_change_rows(latent_generator, model, num_samples, batch_size, index_state)
+    xte, yte = factor_change_rows(latent_generator, model, num_samples, batch_size, index_state)
+    return tuple(factor_change_accuracy(xtr, ytr, xte, yte, nl, scale=s, gtol=gtol, max_iter=max_iter)
+                 for s in (False, True))
+
+
+def _train_test(latent_generator, model, num_samples, batch_size):
+    return (factor_representations(latent_generator, model, num_samples, batch_size),
+            factor_representations(latent_generator, model, num_samples, batch_size))
+
+
+def compute_explicitness_score(latent_generator, model, num_samples=10000, batch_size=64, params=None,
+                               return_train=False):
+    """The explicitness half of evaluation/metrics.py:237-304: the test score (``return_train``: ``(train, test)``).
+    ``params``: ``gtol`` / ``max_iter`` of the solver."""
+    params = params or {}
+    (xtr, ytr), (xte, yte) = _train_test(latent_generator, model, num_samples, batch_size)
+    got = explicitness(xtr, ytr, xte, yte, _latent_sizes(latent_generator), params.get("gtol", 1e-9),
+                       params.get("max_iter", 2000))
+    return got if return_train else got[1]
+
+
+def compute_mod_expl_score(latent_generator, model, num_samples=10000, batch_size=64, params=None):
+    """evaluation/metrics.py:237-304: ``(modularity, explicitness)``; modularity from the TRAIN representations."""
+    params = params or {}
+    sizes = _latent_sizes(latent_generator)
+    (xtr, ytr), (xte, yte) = _train_test(latent_generator, model, num_samples, batch_size)
+    mod = modularity_score(xtr, ytr, sizes, params.get("bins", 20))
+    return mod, explicitness(xtr, ytr, xte, yte, sizes, params.get("gtol", 1e-9), params.get("max_iter", 2000))[1]

@@ -1643,3 +1643,92 @@ def disent_mi(counts, vcount, N, D, factor_sizes, bins):
     call("itcv_disent_mi", ptr(counts), ptr(vcount), int(N), int(D), len(sizes), (ctypes.c_int * len(sizes))(*sizes),
          int(bins), ptr(mi), ptr(h), stream())
     return mi, h
+
+
+# ------------------------------------------------------------------ classifier-based scores (csrc/logreg.hip)
+F64 = torch.float64
+
+
+def _lr_sizes(class_sizes):
+    import ctypes
+    sizes = [int(s) for s in class_sizes]
+    return sizes, (ctypes.c_int * max(len(sizes), 1))(*sizes)
+
+
+def logreg_colstats(x, flags):
+    """StandardScaler's (mean[D], scale[D]) of x[N, D] in fp64: population variance, scale 1 where it is 0."""
+    x = _disent_mu(x)
+    N, D = x.shape
+    mean, scale = torch.empty((D,), dtype=F64, device=x.device), torch.empty((D,), dtype=F64, device=x.device)
+    nws = lib.itcv_logreg_colstats_workspace(N, D)
+    ws = _ws(nws, x.device)
+    call("itcv_logreg_colstats", x.data_ptr(), x.stride(0), N, D, ptr(mean), ptr(scale), ptr(flags), ptr(ws), nws, stream())
+    return mean, scale
+
+
+class LogregProblem:
+    """The fixed inputs of K softmax regressions that share x[N, D]: labels y[N, K], class counts, the class mask and the
+    optional standardisation (mean, scale).  ``valgrad`` / ``proba`` evaluate at a theta[(D + 1), csum] fp64."""
+
+    def __init__(self, x, y, class_sizes, cvalid, flags, stats=None, C=1.0):
+        self.x = _disent_mu(x)
+        self.N, self.D = self.x.shape
+        self.y, self.sizes, self.csizes = _disent_factors(y, class_sizes, self.N, self.x.device)
+        self.K, self.csum = len(self.sizes), sum(self.sizes)
+        self.cvalid = cvalid.to(device=self.x.device, dtype=torch.int32).contiguous()
+        if self.cvalid.numel() != self.csum:
+            raise abi.HipExtensionError(f"logreg: the class mask needs {self.csum} entries (got {self.cvalid.numel()})")
+        self.mean, self.scale = stats if stats is not None else (None, None)
+        self.flags, self.C = flags, float(C)
+        self.nws = lib.itcv_logreg_workspace(self.N, self.D, self.K, self.csum)      # 0 for what the calls refuse
+        self.ws = torch.empty((max(self.nws, 8),), dtype=torch.uint8, device=self.x.device)
+
+    def _theta(self, theta):
+        if theta.dtype != F64 or tuple(theta.shape) != (self.D + 1, self.csum) or not theta.is_contiguous():
+            raise abi.HipExtensionError(f"logreg: theta must be a dense fp64 [{self.D + 1}, {self.csum}] tensor")
+        return theta
+
+    def valgrad(self, theta):
+        """(f[K], grad[(D + 1), csum]) at theta, as fp64 device tensors."""
+        f = torch.empty((self.K,), dtype=F64, device=self.x.device)
+        g = torch.empty((self.D + 1, self.csum), dtype=F64, device=self.x.device)
+        call("itcv_logreg_valgrad", self.x.data_ptr(), self.x.stride(0), ptr(self.mean), ptr(self.scale), ptr(self.y), self.N,
+             self.D, self.K, self.csizes, ptr(self.cvalid), ptr(self._theta(theta)), self.C, ptr(f), ptr(g), ptr(self.flags),
+             ptr(self.ws), self.nws, stream())
+        return f, g
+
+    def proba(self, theta, x=None, y=None):
+        """(P[N, csum] fp64, pred[N, K] int32) at theta, of this problem's rows or of another (x, y) of the same width."""
+        x = self.x if x is None else _disent_mu(x)
+        N = x.shape[0]
+        if x.shape[1] != self.D:
+            raise abi.HipExtensionError(f"logreg: x must have {self.D} columns (got {x.shape[1]})")
+        y = self.y if y is None else _disent_factors(y, self.sizes, N, x.device)[0]
+        P = torch.empty((N, self.csum), dtype=F64, device=x.device)
+        pred = torch.empty((N, self.K), dtype=torch.int32, device=x.device)
+        call("itcv_logreg_proba", x.data_ptr(), x.stride(0), ptr(self.mean), ptr(self.scale), ptr(y), N, self.D, self.K,
+             self.csizes, ptr(self.cvalid), ptr(self._theta(theta)), ptr(P), ptr(pred), ptr(self.flags), stream())
+        return P, pred
+
+
+def logreg_auc(P, y, class_sizes, cvalid, flags):
+    """(count2, pos, neg) as int64 [csum] tensors: the pair counts of every valid class over its problem's valid rows."""
+    sizes, csizes = _lr_sizes(class_sizes)
+    N = P.shape[0]
+    y = _disent_factors(y, sizes, N, P.device)[0]
+    if P.dtype != F64 or P.dim() != 2 or P.shape[1] != sum(sizes) or not P.is_contiguous():
+        raise abi.HipExtensionError("logreg: P must be a dense fp64 [N, csum] tensor")
+    cvalid = cvalid.to(device=P.device, dtype=torch.int32).contiguous()
+    out = torch.empty((3, max(sum(sizes), 1)), dtype=torch.int64, device=P.device)
+    call("itcv_logreg_auc", ptr(P), ptr(y), N, len(sizes), csizes, ptr(cvalid), ptr(out[0]), ptr(out[1]), ptr(out[2]),
+         ptr(flags), stream())
+    return out[0], out[1], out[2]
+
+
+def zdiff_row(a, b, out):
+    """out[d] = mean_b |a[b, d] - b[b, d]| (fp64 accumulation) into the fp32 row ``out`` of a preallocated buffer."""
+    if a.shape != b.shape or a.dim() != 2 or a.dtype != F32 or b.dtype != F32 or a.stride(1) != 1 or b.stride(1) != 1 \
+            or a.stride(0) != b.stride(0) or out.dtype != F32 or out.numel() != a.shape[1] or not out.is_contiguous():
+        raise abi.HipExtensionError("zdiff_row: a, b must be fp32 [B, D] with one row stride, out a dense fp32 [D] row")
+    call("itcv_zdiff_row", a.data_ptr(), b.data_ptr(), a.stride(0), a.shape[0], a.shape[1], out.data_ptr(), stream())
+    return out

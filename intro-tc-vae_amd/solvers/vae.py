@@ -299,7 +299,9 @@ class VAESolver:
         """solvers/vae.py:188-213.  The reference's ``evaluation`` package writes all four scores when it imports (it needs
         sklearn and xgboost).  MIG and modularity do not need it: they are computed on the device (``device_scores``,
         hipvae.disentangle) from one encode of the sampled images, in eval mode, with a private numpy generator (torch's
-        RNG streams and the BatchNorm running buffers are untouched).  The classifier-based scores stay delegated."""
+        RNG streams and the BatchNorm running buffers are untouched).  The classifier-based scores stay delegated unless
+        ``device_scores == "all"``: then ``bvae_score`` {score, scaled} and ``mod_expl`` {modularity_score,
+        explicitness_score} are written from the device too (metrics.py:11-17, 222-234) and only DCI is delegated."""
         if self.writer is None or not isinstance(self.dataset, DisentanglementDataset) or cur_iter % self.test_iter:
             return
         try:
@@ -316,12 +318,22 @@ class VAESolver:
         was_training = self.model.training
         self.model.eval()
         n = num_samples if len(self.dataset) >= num_samples else len(self.dataset) // 2
+        everything = isinstance(self.device_scores, str) and self.device_scores == "all"
         if M is not None:
             kw = dict(latent_generator=self.latent_generator, model=self.model, num_samples=n, batch_size=self.batch_size)
-            writers = (M.write_bvae_score, M.write_dci_score) + (() if native else (M.write_mig_score, M.write_mod_expl_score))
+            writers = (() if everything else (M.write_bvae_score,)) + (M.write_dci_score,) + \
+                (() if native else (M.write_mig_score, M.write_mod_expl_score))
             for fn in writers:
                 fn(self.writer, cur_iter, **kw)
-        if native:
+        if everything:
+            kw = dict(num_samples=n, batch_size=self.batch_size)
+            score, scaled = disentangle.compute_bvae_score(self.latent_generator, self.model, **kw)
+            self.writer.add_scalars("bvae_score", dict(score=score, scaled=scaled), global_step=cur_iter)
+            self.writer.add_scalar("mig_score", disentangle.compute_mig_score(self.latent_generator, self.model, **kw),
+                                   global_step=cur_iter)
+            mod, expl = disentangle.compute_mod_expl_score(self.latent_generator, self.model, **kw)
+            self.writer.add_scalars("mod_expl", dict(modularity_score=mod, explicitness_score=expl), global_step=cur_iter)
+        elif native:
             got = disentangle.compute_scores(self.latent_generator, self.model, num_samples=n, batch_size=self.batch_size)
             self.writer.add_scalar("mig_score", got["mig"], global_step=cur_iter)
             self.writer.add_scalars("mod_expl", dict(modularity_score=got["modularity"]), global_step=cur_iter)
