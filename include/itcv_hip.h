@@ -503,6 +503,77 @@ int itcv_logreg_auc(const double* P, const int* y, int N, int K, const int* csiz
                     void* stream);
 int itcv_zdiff_row(const float* a, const float* b, size_t ld, int B, int D, float* out, void* stream);
 
+/* ---- DCI: histogram gradient-boosted trees (evaluation/metrics.py:82-161; utils.py:178-241) -- */
+/* A multi-class gradient-boosted tree classifier after xgboost's documented `hist` algorithm and defaults, as a fixed
+ * rule.  K problems share x[N][D] (fp32, row stride ld): y[N][K] int32 labels, csize[K] class counts (a HOST array;
+ * coff = prefix sums, csum = coff[K]), cvalid[csum] int32 (non-zero: the class takes part; hipvae sets it iff the class
+ * occurs in the training labels).  A "class slot" c in 0..csum-1 is class c - coff[k] of its problem k.
+ * Supported: 1 <= K <= 16, 1 <= csize[k] <= 256, 1 <= D <= 512, 2 <= N <= 2^30 training rows (1 <= N for the entry points
+ * that only read rows), 1 <= max_depth <= 6, 2 <= max_bin <= 256, rounds >= 1; anything else returns non-zero before a
+ * launch.  flags[2] as for itcv_disent_*: [0] a non-finite element of x (bin), [1] a label outside [0, csize[k]) (grad,
+ * predict).
+ * Cuts (per feature d; s = the training column sorted ascending, B = max_bin): the candidates s[(j * N) / B] (integer
+ *   division), j = 1..B-1; kept are the distinct values greater than s[0], ascending.  bin(x) = #{cuts <= x}, uint8,
+ *   stored feature-major bins[D][N]; nbins[d] = #cuts + 1.  Test rows are binned with the training cuts.
+ * Round: every valid class of a problem starts from margin 0 (margins F[csum][N] fp64, class-major).  p = softmax over
+ *   the problem's valid classes in fp64, max-subtracted; for class c: g = p_c - [y == c], h = max((2 p_c)(1 - p_c), 1e-16),
+ *   quantised gq = llrint(g * 2^24), hq = llrint(h * 2^24) (int64).  Every sum of gradients below is an INTEGER sum of gq /
+ *   hq (|sum| <= 2^54): exact, and free of any summation order.  A row whose label is not a valid class of problem k has
+ *   gq = hq = 0 for the classes of problem k (it takes no part), but is still routed and its margins still advance.
+ * Tree: one per valid class per round, grown level by level to max_depth; lambda (default 1), eta (default 0.3),
+ *   gamma = 0, min_child_weight = 1.  Nodes are heap-indexed (root 0, children of i: 2 i + 1, 2 i + 2; ITCV_GBT_TREE_NODES
+ *   slots per tree); node[csum][N] uint8 holds the node every row sits in.
+ * Candidate (d, b), b = 0..nbins[d]-2: left is bin <= b; admissible iff HLq >= 2^24 and HRq >= 2^24 (integer compares).
+ * Gain: G = (double)Gq * 2^-24, H likewise; score(G, H) = (G * G) / (H + lambda); gain = 0.5 * ((score_L + score_R) -
+ *   score_P); each operation rounded on its own (no fused multiply-add).  A node splits on the admissible candidate of
+ *   largest gain if that gain is > 1e-6; bit-equal gains go to the smallest d, then the smallest b; otherwise it is a leaf.
+ *   Leaf value ((-G) / (H + lambda)) * eta; train and test margins advance by the leaf values at the end of the round.
+ * Tree arrays, [rounds][csum][ITCV_GBT_TREE_NODES]: tfeat (int32, -1: leaf or absent; the caller fills -1 before the
+ *   fit), tbin (int32), tvalue (fp64 leaf value of every node that exists), tgain (fp64, of the split nodes; 0 else).
+ * Prediction: first argmax of the margins over the valid classes (-1 without one); a label that is not a valid class
+ *   counts as wrong.  Importance of problem k: imp[d] = (total gain of the splits on d) / (number of splits on d), 0 without
+ *   a split, then imp / sum_d imp (all 0 if no tree ever split): xgboost's `gain` importance.  The totals are fp64 sums in
+ *   the order round, class, node index; the normaliser in the order d = 0..D-1.  Same inputs, same bits.
+ *   _cuts:       sorted[D][N] (feature-major, each row ascending) -> cuts[D][max_bin - 1], nbins[D].
+ *   _bin:        x -> bins[D][N] with given cuts.
+ *   _grad:       F -> gq, hq [csum][N] (and g, h as fp64 when both are non-NULL).
+ *   _hist:       tab[nc][2^level][D][max_bin][2] int64 (G, H) of class slots c0..c0+nc-1 and the nodes of `level`, from
+ *                the rows whose node id lies in that level; cleared by the call; tab_bytes >= what that takes.
+ *   _split:      reads tab, writes the level's nodes of the tree arrays (pointers to ONE round's [csum][NODES] slices) and
+ *                nsum[csum][NODES][2] (int64 G, H of every node that exists).
+ *   _advance:    node ids of `level` one level down.        _margins: F[c][n] += leaf value (node == NULL: rows walk the
+ *                tree from the root, as the test rows do).
+ *   _round:      the whole launch sequence of one boosting round; classes are taken in chunks of tab_bytes /
+ *                (2^(max_depth-1) * D * max_bin * 16) slots.  itcv_gbt_workspace: the table bytes that keep a chunk inside
+ *                the budget of ITCV_GBT_TABLE_BUDGET bytes (at least one class slot). */
+#define ITCV_GBT_TREE_NODES 127
+#define ITCV_GBT_TABLE_BUDGET ((size_t)512 << 20)
+size_t itcv_gbt_workspace(int N, int D, int K, int csum, int max_depth, int max_bin);
+int itcv_gbt_cuts(const float* sorted, int N, int D, int max_bin, float* cuts, int* nbins, void* stream);
+int itcv_gbt_bin(const float* x, size_t ld, int N, int D, int max_bin, const float* cuts, const int* nbins,
+                 unsigned char* bins, int* flags, void* stream);
+int itcv_gbt_grad(const double* F, const int* y, int N, int K, const int* csize, const int* cvalid, long long* gq,
+                  long long* hq, double* g, double* h, int* flags, void* stream);
+int itcv_gbt_hist(const unsigned char* bins, int N, int D, int max_bin, const long long* gq, const long long* hq,
+                  const unsigned char* node, const int* cvalid, int c0, int nc, int level, long long* tab,
+                  size_t tab_bytes, void* stream);
+int itcv_gbt_split(const long long* tab, const int* nbins, int D, int max_bin, const int* cvalid, int c0, int nc,
+                   int level, double lam, double eta, long long* nsum, int* tfeat, int* tbin, double* tvalue,
+                   double* tgain, void* stream);
+int itcv_gbt_advance(const unsigned char* bins, int N, int csum, const int* cvalid, const int* tfeat, const int* tbin,
+                     int level, unsigned char* node, void* stream);
+int itcv_gbt_margins(const unsigned char* bins, int N, int csum, const int* cvalid, const unsigned char* node,
+                     const int* tfeat, const int* tbin, const double* tvalue, int max_depth, double* F, void* stream);
+int itcv_gbt_predict(const double* F, const int* y, int N, int K, const int* csize, const int* cvalid, int* pred,
+                     unsigned long long* correct, int* flags, void* stream);
+int itcv_gbt_importance(const int* tfeat, const double* tgain, int rounds, int K, const int* csize, int D, double* imp,
+                        void* stream);
+int itcv_gbt_round(const unsigned char* bins, int N, int D, int max_bin, const int* nbins, const int* y, int K,
+                   const int* csize, const int* cvalid, double* F, const unsigned char* bins_test, int Nt, double* Ft,
+                   int max_depth, double lam, double eta, long long* gq, long long* hq, unsigned char* node,
+                   long long* nsum, long long* tab, size_t tab_bytes, int* tfeat, int* tbin, double* tvalue,
+                   double* tgain, int* flags, void* stream);
+
 /* ---- reconstruction loss (ops.py:188-236) --------------------------------------------- */
 #define ITCV_LOSS_MSE 0
 #define ITCV_LOSS_L1 1

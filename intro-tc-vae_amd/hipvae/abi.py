@@ -152,6 +152,17 @@ SIGNATURES = {
     "itcv_logreg_proba": (i32, [p, sz, p, p, p, i32, i32, i32, p, p, p, p, p, p, p]),
     "itcv_logreg_auc": (i32, [p, p, i32, i32, p, p, p, p, p, p, p]),
     "itcv_zdiff_row": (i32, [p, p, sz, i32, i32, p, p]),
+    "itcv_gbt_workspace": (sz, [i32] * 6),
+    "itcv_gbt_cuts": (i32, [p, i32, i32, i32, p, p, p]),
+    "itcv_gbt_bin": (i32, [p, sz, i32, i32, i32, p, p, p, p, p]),
+    "itcv_gbt_grad": (i32, [p, p, i32, i32, p, p, p, p, p, p, p, p]),
+    "itcv_gbt_hist": (i32, [p, i32, i32, i32, p, p, p, p, i32, i32, i32, p, sz, p]),
+    "itcv_gbt_split": (i32, [p, p, i32, i32, p, i32, i32, i32, f64, f64, p, p, p, p, p, p]),
+    "itcv_gbt_advance": (i32, [p, i32, i32, p, p, p, i32, p, p]),
+    "itcv_gbt_margins": (i32, [p, i32, i32, p, p, p, p, p, i32, p, p]),
+    "itcv_gbt_predict": (i32, [p, p, i32, i32, p, p, p, p, p, p]),
+    "itcv_gbt_importance": (i32, [p, p, i32, i32, p, i32, p, p]),
+    "itcv_gbt_round": (i32, [p, i32, i32, i32, p, p, i32, p, p, p, p, i32, p, i32, f64, f64] + [p] * 5 + [sz] + [p] * 6),
     "itcv_recon_workspace": (sz, [i32, sz]),
     "itcv_recon_rows_fwd": (i32, [p, p, p, i32, sz, i32, p, sz, p]),
     "itcv_recon_rows_bwd": (i32, [p, p, p, p, i32, sz, i32, p]),

@@ -1,4 +1,4 @@
-"""Disentanglement scores computed on the device: MIG and modularity.
+"""Disentanglement scores computed on the device: MIG, modularity, beta-VAE, explicitness and DCI.
 
 The reference's ``evaluation`` package (evaluation/metrics.py:169-219, 293-304; evaluation/utils.py:245-273, 323-335)
 pulls every encoded batch to the host, bins each latent column with ``np.histogram`` / ``np.digitize`` and calls
@@ -15,7 +15,15 @@ utils.py:277-320) are classifier-based, but they are mathematics too: each is re
 softmax regression (C = 1), which is strictly convex in the weights and so does not depend on the solver.  The rule is
 in include/itcv_hip.h; csrc/logreg.hip evaluates all K problems in one launch in fp64, hipvae/logreg.py minimises them
 to ``max|grad F_p| <= gtol`` for every problem (or raises), accuracy comes from the predictions and one-vs-rest ROC AUC
-from integer pair counts.  Only DCI (gradient-boosted trees) stays with the reference's package.
+from integer pair counts.
+
+DCI (evaluation/metrics.py:82-161, utils.py:178-241) needs a gradient-boosted tree classifier per factor; the reference
+asks xgboost for ``tree_method="gpu_hist"``.  Here the booster is a fixed rule after xgboost's documented ``hist``
+algorithm and defaults (include/itcv_hip.h; csrc/gbt.hip, hipvae/gbt.py): quantile cuts, uint8 bins, gradients
+quantised to integers so that every histogram is an exact, order-free integer sum and a fit is bitwise reproducible.
+Informativeness is the mean test accuracy; completeness and disentanglement are the reference's closed forms
+(utils.py:220-241 with ops.entropy, eps = 1e-9) on the ``[K, D]`` matrix of xgboost's ``gain`` importances, a few fp64
+tensor operations.  With that, no score of the reference's writer needs its ``evaluation`` package.
 
 The binning rule is fixed (include/itcv_hip.h): with lo / hi the column's minimum / maximum as fp64 (lo -= 0.5, hi += 0.5
 when they are equal), ``bin(x) = #{j in 0..bins-1 : x >= lo + j * ((hi - lo) / bins)}`` -- ``np.histogram``'s edges
@@ -31,12 +39,14 @@ import numpy as np
 import torch
 
 from . import functional as HF
+from . import gbt
 from . import logreg
 
 __all__ = ["discretize", "factor_counts", "mutual_info", "mig_score", "modularity_score", "scores", "FactorSampler",
            "factor_representations", "compute_mig_score", "compute_modularity_score", "compute_scores",
            "fit_softmax", "factor_change_accuracy", "explicitness", "factor_change_rows", "compute_bvae_score",
-           "compute_explicitness_score", "compute_mod_expl_score"]
+           "compute_explicitness_score", "compute_mod_expl_score", "fit_boosted_trees", "dci_completeness",
+           "dci_disentanglement", "dci", "compute_dci_score"]
 
 
 def _raise_on(flags):
@@ -381,3 +391,59 @@ def compute_mod_expl_score(latent_generator, model, num_samples=10000, batch_siz
     (xtr, ytr), (xte, yte) = _train_test(latent_generator, model, num_samples, batch_size)
     mod = modularity_score(xtr, ytr, sizes, params.get("bins", 20))
     return mod, explicitness(xtr, ytr, xte, yte, sizes, params.get("gtol", 1e-9), params.get("max_iter", 2000))[1]
+
+
+# ---- DCI: boosted trees, then closed forms on the importance matrix ---------------------------------------------------
+fit_boosted_trees = gbt.fit_boosted_trees
+
+
+def _entropy(x, base, dim, eps=1e-9):
+    """ops.entropy (ops.py:125-133) along ``dim`` of an fp64 tensor."""
+    p = (x + eps) / (x + eps).sum(dim=dim, keepdim=True)
+    return -(p * torch.log(p + eps)).sum(dim=dim) / float(np.log(base + eps))
+
+
+def _weights(P, dim):
+    """utils.py:226-228 / 238-240: the share of every column (dim = 0) or row (dim = 1); uniform when P is all zero."""
+    Q = torch.where(P.sum() == 0, torch.ones_like(P), P)
+    return Q.sum(dim=dim) / Q.sum()
+
+
+def dci_disentanglement(P):
+    """evaluation/utils.py:220-229 on the fp64 ``[K, D]`` importance matrix: an fp64 device scalar."""
+    return (_weights(P, 0) * (1.0 - _entropy(P, P.shape[0], 0))).sum()
+
+
+def dci_completeness(P):
+    """evaluation/utils.py:232-241: an fp64 device scalar."""
+    return (_weights(P, 1) * (1.0 - _entropy(P, P.shape[1], 1))).sum()
+
+
+def dci(x_train, y_train, x_test, y_test, factor_sizes, **booster):
+    """``(informativeness, completeness, disentanglement)`` (evaluation/metrics.py:157-161): the mean test accuracy of the
+    K boosted-tree classifiers and the closed forms on their importances.  ``booster``: ``rounds``, ``max_depth``,
+    ``max_bin``, ``eta``, ``lam`` of ``fit_boosted_trees``.  One host read-back."""
+    fit = gbt.fit_device(x_train, y_train, x_test, y_test, factor_sizes, **booster)
+    P = fit["importance"]
+    _, test, (comp, dis) = gbt.read_back(fit, (dci_completeness(P), dci_disentanglement(P)))
+    return float(np.mean([c / fit["Nt"] for c in test])), comp, dis
+
+
+_BOOSTER_KEYS = {"n_estimators": "rounds", "max_depth": "max_depth", "learning_rate": "eta", "reg_lambda": "lam",
+                 "max_bin": "max_bin"}
+
+
+def compute_dci_score(latent_generator, model, num_samples=10000, batch_size=64, params=None):
+    """evaluation/metrics.py:106-161 with the reference's arguments and return order: ``(informativeness, completeness,
+    disentanglement)``.  ``params["informativeness_params"]`` may carry ``n_estimators``, ``max_depth``,
+    ``learning_rate``, ``reg_lambda`` and ``max_bin``; other keys (the reference passes xgboost's ``tree_method``,
+    ``gpu_id``, ``eval_metric``, ``use_label_encoder``) select nothing here and are ignored."""
+    params = params or {}
+    method = params.get("informativeness_method")
+    if method not in (None, "xgb"):
+        raise NotImplementedError(f"compute_dci_score: informativeness_method = {method!r} (only None / 'xgb': the "
+                                  "device-side histogram booster)")
+    given = params.get("informativeness_params") or {}
+    booster = {ours: given[theirs] for theirs, ours in _BOOSTER_KEYS.items() if theirs in given}
+    (xtr, ytr), (xte, yte) = _train_test(latent_generator, model, num_samples, batch_size)
+    return dci(xtr, ytr, xte, yte, _latent_sizes(latent_generator), **booster)

@@ -1732,3 +1732,110 @@ def zdiff_row(a, b, out):
         raise abi.HipExtensionError("zdiff_row: a, b must be fp32 [B, D] with one row stride, out a dense fp32 [D] row")
     call("itcv_zdiff_row", a.data_ptr(), b.data_ptr(), a.stride(0), a.shape[0], a.shape[1], out.data_ptr(), stream())
     return out
+
+
+# ------------------------------------------------------------------ boosted trees for DCI (csrc/gbt.hip)
+GBT_NODES = 127          # ITCV_GBT_TREE_NODES: heap slots of one tree
+U8, I64 = torch.uint8, torch.int64
+
+
+def _gbt_dense(t, dtype, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise abi.HipExtensionError(f"gbt: {what} must be a dense {dtype} device tensor; there is no CPU path")
+    return t
+
+
+def gbt_cuts(x_train, max_bin):
+    """(cuts[D, max_bin - 1] fp32, nbins[D] int32) of the training rows: the columns are sorted on the device by
+    ``torch.sort``, the cut selection is a kernel."""
+    x = _disent_mu(x_train)
+    N, D = x.shape
+    srt = torch.sort(x.t().contiguous(), dim=1).values
+    cuts = torch.zeros((D, max(int(max_bin) - 1, 1)), dtype=F32, device=x.device)
+    nbins = torch.empty((D,), dtype=torch.int32, device=x.device)
+    call("itcv_gbt_cuts", ptr(srt), N, D, int(max_bin), ptr(cuts), ptr(nbins), stream())
+    return cuts, nbins
+
+
+def gbt_bin(x, cuts, nbins, max_bin, flags):
+    """uint8 bins[D, N] (feature-major) of x[N, D] under the given cuts; sets flags[0] on a non-finite element."""
+    x = _disent_mu(x)
+    N, D = x.shape
+    if cuts.shape[0] != D:
+        raise abi.HipExtensionError(f"gbt: x must have {cuts.shape[0]} columns (got {D})")
+    out = torch.empty((D, N), dtype=U8, device=x.device)
+    call("itcv_gbt_bin", x.data_ptr(), x.stride(0), N, D, int(max_bin), ptr(_gbt_dense(cuts, F32, "cuts")),
+         ptr(_gbt_dense(nbins, torch.int32, "nbins")), ptr(out), ptr(flags), stream())
+    return out
+
+
+def gbt_grad(F, y, class_sizes, cvalid, flags, with_fp64=False):
+    """(gq, hq) int64 [csum, N] from the margins F[csum, N] (``with_fp64``: also g, h before quantisation)."""
+    sizes, csizes = _lr_sizes(class_sizes)
+    F = _gbt_dense(F, F64, "the margins")
+    csum, N = F.shape
+    y = _disent_factors(y, sizes, N, F.device)[0]
+    gq, hq = torch.empty((csum, N), dtype=I64, device=F.device), torch.empty((csum, N), dtype=I64, device=F.device)
+    g = torch.empty((csum, N), dtype=F64, device=F.device) if with_fp64 else None
+    h = torch.empty((csum, N), dtype=F64, device=F.device) if with_fp64 else None
+    call("itcv_gbt_grad", ptr(F), ptr(y), N, len(sizes), csizes, ptr(_gbt_dense(cvalid, torch.int32, "cvalid")), ptr(gq),
+         ptr(hq), ptr(g), ptr(h), ptr(flags), stream())
+    return (gq, hq, g, h) if with_fp64 else (gq, hq)
+
+
+def gbt_hist(bins, gq, hq, node, cvalid, level, max_bin, c0=0, nc=None):
+    """int64 tab[nc, 2^level, D, max_bin, 2]: (G, H) sums of class slots c0..c0+nc-1 over the rows whose node id (heap
+    index, uint8 [csum, N]) lies in ``level``."""
+    bins, node = _gbt_dense(bins, U8, "bins"), _gbt_dense(node, U8, "node")
+    D, N = bins.shape
+    nc = gq.shape[0] - c0 if nc is None else nc
+    tab = torch.empty((nc, 1 << int(level), D, int(max_bin), 2), dtype=I64, device=bins.device)
+    call("itcv_gbt_hist", ptr(bins), N, D, int(max_bin), ptr(_gbt_dense(gq, I64, "gq")), ptr(_gbt_dense(hq, I64, "hq")),
+         ptr(node), ptr(_gbt_dense(cvalid, torch.int32, "cvalid")), int(c0), int(nc), int(level), ptr(tab),
+         tab.numel() * 8, stream())
+    return tab
+
+
+def gbt_tree_arrays(rounds, csum, device):
+    """(tfeat, tbin, tvalue, tgain), each [rounds, csum, GBT_NODES]; tfeat filled with -1 (leaf or absent)."""
+    shape = (int(rounds), int(csum), GBT_NODES)
+    return (torch.full(shape, -1, dtype=torch.int32, device=device), torch.zeros(shape, dtype=torch.int32, device=device),
+            torch.zeros(shape, dtype=F64, device=device), torch.zeros(shape, dtype=F64, device=device))
+
+
+def gbt_split(tab, nbins, cvalid, level, trees, nsum, lam=1.0, eta=0.3, c0=0):
+    """Choose the splits of the nodes of ``level`` from tab[nc, 2^level, D, max_bin, 2] and write them into ONE round's tree
+    arrays ``trees`` = (tfeat, tbin, tvalue, tgain), each [csum, GBT_NODES], and the node sums nsum[csum, GBT_NODES, 2]."""
+    tab = _gbt_dense(tab, I64, "the table")
+    nc, nn, D, B, _ = tab.shape
+    if nn != 1 << int(level):
+        raise abi.HipExtensionError(f"gbt: a table of level {level} has {1 << int(level)} nodes (got {nn})")
+    tfeat, tbin, tvalue, tgain = trees
+    call("itcv_gbt_split", ptr(tab), ptr(_gbt_dense(nbins, torch.int32, "nbins")), D, B,
+         ptr(_gbt_dense(cvalid, torch.int32, "cvalid")), int(c0), nc, int(level), float(lam), float(eta),
+         ptr(_gbt_dense(nsum, I64, "nsum")), ptr(_gbt_dense(tfeat, torch.int32, "tfeat")),
+         ptr(_gbt_dense(tbin, torch.int32, "tbin")), ptr(_gbt_dense(tvalue, F64, "tvalue")),
+         ptr(_gbt_dense(tgain, F64, "tgain")), stream())
+
+
+def gbt_predict(F, y, class_sizes, cvalid, flags):
+    """(pred[N, K] int32, correct[K] int64): first argmax of F[csum, N] over the valid classes and the number of rows whose
+    label equals it; sets flags[1] on a label outside its range."""
+    sizes, csizes = _lr_sizes(class_sizes)
+    F = _gbt_dense(F, F64, "the margins")
+    N = F.shape[1]
+    y = _disent_factors(y, sizes, N, F.device)[0]
+    pred = torch.empty((N, len(sizes)), dtype=torch.int32, device=F.device)
+    correct = torch.empty((max(len(sizes), 1),), dtype=I64, device=F.device)
+    call("itcv_gbt_predict", ptr(F), ptr(y), N, len(sizes), csizes, ptr(_gbt_dense(cvalid, torch.int32, "cvalid")),
+         ptr(pred), ptr(correct), ptr(flags), stream())
+    return pred, correct
+
+
+def gbt_importance(tfeat, tgain, class_sizes, D):
+    """fp64 imp[K, D]: xgboost's `gain` importance of every problem from the tree arrays [rounds, csum, GBT_NODES]."""
+    sizes, csizes = _lr_sizes(class_sizes)
+    imp = torch.empty((len(sizes), int(D)), dtype=F64, device=tfeat.device)
+    call("itcv_gbt_importance", ptr(_gbt_dense(tfeat, torch.int32, "tfeat")), ptr(_gbt_dense(tgain, F64, "tgain")),
+         tfeat.shape[0], len(sizes), csizes, int(D), ptr(imp), stream())
+    return imp

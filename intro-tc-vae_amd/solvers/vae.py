@@ -50,8 +50,10 @@ class VAESolver:
         self.conv_math = _os.environ.get("ITCV_CONV_MATH") or ("f16x3" if use_amp else "fp32")
         self.writer, self.test_iter, self.clip = writer, test_iter, clip
         # MIG and modularity on the device (hipvae.disentangle): None -> when the reference's ``evaluation`` package cannot
-        # be imported; True -> always (its classifier-based writers are still called when it imports); False -> never
+        # be imported; True -> always (its classifier-based writers are still called when it imports); False -> never;
+        # "all" -> the beta-VAE score and explicitness too; "all+dci" -> DCI as well, nothing delegated
         self.device_scores = None
+        self.dci_params = None       # ``params`` of hipvae.disentangle.compute_dci_score (None: 100 rounds, depth 6)
         self.recon_loss_type = recon_loss_type
         self.scale = 1 / (self.model.cdim * self.model.encoder.image_size ** 2)   # solvers/vae.py:61
         self._flat = {}
@@ -301,13 +303,19 @@ class VAESolver:
         hipvae.disentangle) from one encode of the sampled images, in eval mode, with a private numpy generator (torch's
         RNG streams and the BatchNorm running buffers are untouched).  The classifier-based scores stay delegated unless
         ``device_scores == "all"``: then ``bvae_score`` {score, scaled} and ``mod_expl`` {modularity_score,
-        explicitness_score} are written from the device too (metrics.py:11-17, 222-234) and only DCI is delegated."""
+        explicitness_score} are written from the device too (metrics.py:11-17, 222-234) and only DCI is delegated.
+        ``device_scores == "all+dci"`` writes those three records and then ``dci`` {dci_informativeness_score,
+        dci_completeness_score, dci_disentanglement_score} from the device (metrics.py:82-103) and delegates nothing:
+        ``evaluation`` is not imported."""
         if self.writer is None or not isinstance(self.dataset, DisentanglementDataset) or cur_iter % self.test_iter:
             return
-        try:
-            from evaluation import metrics as M
-        except Exception:  # noqa: BLE001
-            M = None
+        with_dci = isinstance(self.device_scores, str) and self.device_scores == "all+dci"
+        M = None
+        if not with_dci:
+            try:
+                from evaluation import metrics as M
+            except Exception:  # noqa: BLE001
+                M = None
         native = (M is None) if self.device_scores is None else bool(self.device_scores)
         if M is None and not native:
             return
@@ -318,7 +326,7 @@ class VAESolver:
         was_training = self.model.training
         self.model.eval()
         n = num_samples if len(self.dataset) >= num_samples else len(self.dataset) // 2
-        everything = isinstance(self.device_scores, str) and self.device_scores == "all"
+        everything = with_dci or (isinstance(self.device_scores, str) and self.device_scores == "all")
         if M is not None:
             kw = dict(latent_generator=self.latent_generator, model=self.model, num_samples=n, batch_size=self.batch_size)
             writers = (() if everything else (M.write_bvae_score,)) + (M.write_dci_score,) + \
@@ -333,6 +341,11 @@ class VAESolver:
                                    global_step=cur_iter)
             mod, expl = disentangle.compute_mod_expl_score(self.latent_generator, self.model, **kw)
             self.writer.add_scalars("mod_expl", dict(modularity_score=mod, explicitness_score=expl), global_step=cur_iter)
+            if with_dci:
+                info, comp, dis = disentangle.compute_dci_score(self.latent_generator, self.model, params=self.dci_params,
+                                                                **kw)
+                self.writer.add_scalars("dci", dict(dci_informativeness_score=info, dci_completeness_score=comp,
+                                                    dci_disentanglement_score=dis), global_step=cur_iter)
         elif native:
             got = disentangle.compute_scores(self.latent_generator, self.model, num_samples=n, batch_size=self.batch_size)
             self.writer.add_scalar("mig_score", got["mig"], global_step=cur_iter)
