@@ -574,6 +574,62 @@ int itcv_gbt_round(const unsigned char* bins, int N, int D, int max_bin, const i
                    long long* nsum, long long* tab, size_t tab_bytes, int* tfeat, int* tbin, double* tvalue,
                    double* tgain, int* flags, void* stream);
 
+/* ---- FactorVAE and SAP scores (not in the reference; Kim & Mnih 2018, Kumar et al. 2018) ------------------------ */
+/* Both scores are fixed rules; all arithmetic is fp64 on fp32 representations (row stride ld elements), every operation
+ * rounded on its own (no fused multiply-add), every floating-point sum in a fixed order: same inputs, same bits.
+ * flags[3] (int, zeroed by the caller, only ever set): [0] a non-finite representation, [1] a factor index / label outside
+ * its range, [2] a SAP classifier that did not converge.
+ *
+ * FactorVAE score.  Inputs mu_var[Nv][D]; mu_train[Mt * L][D] with fidx_train[Mt]; mu_eval[Me * L][D] with fidx_eval[Me].  A
+ * group is L consecutive rows, encoded from L factor vectors whose column fidx was overwritten with row 0's value.
+ *   1. gvar[d] = the ddof = 1 variance of mu_var[:, d] (the mean first, then the squared deviations).
+ *   2. d is ACTIVE iff sqrt(gvar[d]) >= threshold (default 0.05).  No active dimension: both accuracies are 0.
+ *   3. Per group, lvar[d] = (sum_r (x_r - m)^2) / (L - 1), m = (sum_r x_r) / L, both sums over the rows in ascending order.
+ *   4. The group votes for d* = argmin over the active d of lvar[d] / gvar[d], ties to the smallest d: votes[d*][fidx] += 1
+ *      (int64; integer atomics, so the table does not depend on the order of arrival).  d* indexes ALL dimensions.
+ *   5. classifier[d] = argmax_k votes_train[d][k], ties to the smallest k;
+ *      train_accuracy = sum_d votes_train[d][classifier[d]] / Mt, eval_accuracy = sum_d votes_eval[d][classifier[d]] / Me.
+ * Supported: 2 <= L <= 2^16, 2 <= Nv <= 2^24, M * L <= 2^24, 1 <= D <= 512, 1 <= K <= 256; anything else returns non-zero
+ * before a launch.
+ *   _gvar:     gvar[D].
+ *   _votes:    votes[D][K], cleared by the call; fidx[M] int32 on the device.
+ *   _classify: classifier[D] int32 and res[3] = {train_accuracy, eval_accuracy, number of active dimensions}. */
+int itcv_fvae_gvar(const float* mu, size_t ld, int N, int D, double* gvar, int* flags, void* stream);
+int itcv_fvae_votes(const float* mu, size_t ld, int M, int L, int D, const double* gvar, double threshold, const int* fidx,
+                    int K, long long* votes, int* flags, void* stream);
+int itcv_fvae_classify(const long long* votes_train, const long long* votes_eval, int D, int K, int Mt, int Me,
+                       const double* gvar, double threshold, int* classifier, double* res, void* stream);
+/* SAP score, discrete factors.  K factors share x[N][D]: y[N][K] int32 labels, csize[K] class counts (a HOST array; coff =
+ * prefix sums, csum = coff[K]).  For latent i and factor j: V = the classes present in the train labels, n = N the train
+ * rows, bw_c = n / (|V| count_c), x = column i as fp64, C = 0.01 by default.
+ *   |V| >= 3: for each c in V minimise F(w, b) = (w^2 + b^2) / 2 + sum_n C_n max(0, 1 - t_n (w x_n + b))^2 with t_n = +1 where
+ *             y_n == c, else -1; C_n = C bw_c on the positive rows, C on the others (liblinear's one-vs-rest with
+ *             class_weight = "balanced").  Prediction: argmax_{c in V} (w_c x + b_c), ties to the smallest c.
+ *   |V| == 2: ONE problem, stored at the slot of the larger class value V[1], whose rows are the positives; every row carries
+ *             its own class's weight C_n = C bw_{y_n}.  Prediction: V[1] iff w x + b > 0, else V[0].
+ *   |V| == 1: that class is predicted; nothing is solved.
+ *   S[i][j] = (test rows whose prediction equals the label) / N_test; a test label outside V counts as wrong.  The score is
+ *   the mean over j of (largest - second largest of S[:, j]), summed in factor order.
+ * Solve: F is 1-strongly convex, so the optimum is unique and |theta - theta*|_2 <= |grad F(theta)|_2.  From (0, 0): Newton
+ *   steps d = -H^-1 g with the generalised Hessian H = I + 2 sum_{1 - t z > 0} C_n [x^2, x; x, 1]; the step length starts at
+ *   1 and is halved (50 times at the most) until F(theta + a d) <= F(theta) + 1e-4 a g.d, or until the trial point itself
+ *   meets the stopping rule max(|dF/dw|, |dF/db|) <= gtol (default 1e-10).  A problem that has not met it after max_iter
+ *   (default 100) Newton steps, or whose step lengths are exhausted, sets flags[2].
+ * Supported: 1 <= K <= 16, 1 <= csize[k] <= 256, 1 <= D <= 512, 1 <= N <= 2^24; anything else returns non-zero before a launch.
+ *   _fit:   theta[D][csum][2] = (w, b), gnorm[D][csum] = the final max-norm of the gradient, iters[D][csum] = Newton steps
+ *           taken (all 0 at a slot without a problem), cvalid[csum] = the class occurs in the train labels.  Two launches:
+ *           feature-major copies xt[D][N] / yt[K][N] with the class counts (integer atomics), then ONE launch that solves
+ *           every problem, a wave each; up to itcv_sap_svc_lds_rows() rows the column and the labels sit in LDS, above
+ *           that they are streamed from the copies.  Workspace: itcv_sap_svc_workspace.
+ *   _score: correct[D][K] int64 (cleared by the call) and, when non-NULL, pred[D][K][Nt] int32. */
+int itcv_sap_svc_lds_rows(void);
+size_t itcv_sap_svc_workspace(int N, int D, int K, int csum);
+int itcv_sap_svc_fit(const float* x, size_t ld, const int* y, int N, int D, int K, const int* csize, double C, double gtol,
+                     int max_iter, double* theta, double* gnorm, int* iters, int* cvalid, int* flags, void* ws,
+                     size_t ws_bytes, void* stream);
+int itcv_sap_svc_score(const float* x, size_t ld, const int* y, int Nt, int D, int K, const int* csize, const int* cvalid,
+                       const double* theta, long long* correct, int* pred, int* flags, void* stream);
+
 /* ---- reconstruction loss (ops.py:188-236) --------------------------------------------- */
 #define ITCV_LOSS_MSE 0
 #define ITCV_LOSS_L1 1

@@ -163,6 +163,13 @@ SIGNATURES = {
     "itcv_gbt_predict": (i32, [p, p, i32, i32, p, p, p, p, p, p]),
     "itcv_gbt_importance": (i32, [p, p, i32, i32, p, i32, p, p]),
     "itcv_gbt_round": (i32, [p, i32, i32, i32, p, p, i32, p, p, p, p, i32, p, i32, f64, f64] + [p] * 5 + [sz] + [p] * 6),
+    "itcv_fvae_gvar": (i32, [p, sz, i32, i32, p, p, p]),
+    "itcv_fvae_votes": (i32, [p, sz, i32, i32, i32, p, f64, p, i32, p, p, p]),
+    "itcv_fvae_classify": (i32, [p, p, i32, i32, i32, i32, p, f64, p, p, p]),
+    "itcv_sap_svc_lds_rows": (i32, []),
+    "itcv_sap_svc_workspace": (sz, [i32] * 4),
+    "itcv_sap_svc_fit": (i32, [p, sz, p, i32, i32, i32, p, f64, f64, i32, p, p, p, p, p, p, sz, p]),
+    "itcv_sap_svc_score": (i32, [p, sz, p, i32, i32, i32, p, p, p, p, p, p, p]),
     "itcv_recon_workspace": (sz, [i32, sz]),
     "itcv_recon_rows_fwd": (i32, [p, p, p, i32, sz, i32, p, sz, p]),
     "itcv_recon_rows_bwd": (i32, [p, p, p, p, i32, sz, i32, p]),

@@ -1,4 +1,4 @@
-"""Disentanglement scores computed on the device: MIG, modularity, beta-VAE, explicitness and DCI.
+"""Disentanglement scores computed on the device: MIG, modularity, beta-VAE, explicitness, DCI, FactorVAE and SAP.
 
 The reference's ``evaluation`` package (evaluation/metrics.py:169-219, 293-304; evaluation/utils.py:245-273, 323-335)
 pulls every encoded batch to the host, bins each latent column with ``np.histogram`` / ``np.digitize`` and calls
@@ -34,6 +34,12 @@ that takes one value has H = 0 and makes MIG ``nan`` (0 / 0) or ``inf``; a laten
 (theta = 0) or a single factor (K = 1) makes modularity ``nan``.  MIG of a single latent has no second-largest value and
 raises, as the reference's indexing does.  Non-finite representations and factor values outside ``[0, size)`` raise
 ``ValueError`` (``np.histogram`` raises on the former too).
+
+The FactorVAE score (Kim & Mnih 2018) and the SAP score (Kumar et al. 2018) are not in the reference; they complete the
+usual seven-metric table.  Both are fixed rules (include/itcv_hip.h, csrc/extra_scores.hip): FactorVAE is a majority-vote
+classifier on integer vote tables, one wave per group of images with one factor held fixed; SAP's default form fits
+``D x sum(sizes)`` two-parameter squared-hinge classifiers (liblinear's ``LinearSVC(C=0.01, class_weight="balanced")``
+objective, whose optimum is unique) to convergence in one launch and counts correct test predictions as integers.
 """
 import numpy as np
 import torch
@@ -46,7 +52,8 @@ __all__ = ["discretize", "factor_counts", "mutual_info", "mig_score", "modularit
            "factor_representations", "compute_mig_score", "compute_modularity_score", "compute_scores",
            "fit_softmax", "factor_change_accuracy", "explicitness", "factor_change_rows", "compute_bvae_score",
            "compute_explicitness_score", "compute_mod_expl_score", "fit_boosted_trees", "dci_completeness",
-           "dci_disentanglement", "dci", "compute_dci_score"]
+           "dci_disentanglement", "dci", "compute_dci_score", "factor_vae_votes", "factor_vae_score",
+           "compute_factor_vae_score", "fit_sap_classifiers", "sap_score_matrix", "sap_score", "compute_sap_score"]
 
 
 def _raise_on(flags):
@@ -191,6 +198,13 @@ class FactorSampler:
 
     def sample(self, n):
         factors = self.sample_factors_of_variation(n)
+        return factors, self.sample_observations_from_factors(factors)
+
+    def sample_fixed_factor(self, n, k):
+        """``(factors, observations)`` of one FactorVAE group: n factor vectors whose column ``k`` is overwritten with row
+        0's value.  Draws, in this order: the factors, then (inside the observation lookup) the factors that do not vary."""
+        factors = self.sample_factors_of_variation(n)
+        factors[:, k] = factors[0, k]
         return factors, self.sample_observations_from_factors(factors)
 
     def generate(self, n_samples=1000, batch_size=64, drop_last=False):
@@ -447,3 +461,178 @@ def compute_dci_score(latent_generator, model, num_samples=10000, batch_size=64,
     booster = {ours: given[theirs] for theirs, ours in _BOOSTER_KEYS.items() if theirs in given}
     (xtr, ytr), (xte, yte) = _train_test(latent_generator, model, num_samples, batch_size)
     return dci(xtr, ytr, xte, yte, _latent_sizes(latent_generator), **booster)
+
+
+# ---- FactorVAE score: majority vote on the arg-min normalised variance ------------------------------------------------
+def _raise_on_extra(flags):
+    _raise_on(flags[:2])
+    if len(flags) > 2 and flags[2]:
+        raise RuntimeError("sap: a squared-hinge classifier did not converge (raise max_iter, or check the representations)")
+
+
+def factor_vae_votes(mu_var, mu_train, fidx_train, mu_eval, fidx_eval, L, num_factors, threshold=0.05):
+    """Everything the score is made of, for inspection: a dict of ``gvar [D]`` fp64, ``votes_train`` / ``votes_eval
+    [D, K]`` int64, ``classifier [D]`` int32 (device tensors) and the floats ``train_accuracy``, ``eval_accuracy``,
+    ``num_active``.  One host read-back."""
+    L = int(L)
+    if L < 2:
+        raise ValueError(f"factor_vae: a group needs L >= 2 rows for a ddof = 1 variance (got L = {L})")
+    if mu_var.dim() != 2 or mu_var.shape[0] < 2:
+        raise ValueError("factor_vae: the variance estimate needs at least 2 rows of [N, D] representations")
+    flags = HF.extra_flags(mu_var.device)
+    gvar = HF.fvae_gvar(mu_var, flags)
+    vt = HF.fvae_votes(mu_train, L, gvar, threshold, fidx_train, num_factors, flags)
+    ve = HF.fvae_votes(mu_eval, L, gvar, threshold, fidx_eval, num_factors, flags)
+    classifier, res = HF.fvae_classify(vt, ve, mu_train.shape[0] // L, mu_eval.shape[0] // L, gvar, threshold)
+    out = torch.cat([res, flags.to(torch.float64)]).tolist()
+    _raise_on_extra(out[3:])
+    return dict(gvar=gvar, votes_train=vt, votes_eval=ve, classifier=classifier, train_accuracy=out[0],
+                eval_accuracy=out[1], num_active=int(out[2]))
+
+
+def factor_vae_score(mu_var, mu_train, fidx_train, mu_eval, fidx_eval, L, num_factors, threshold=0.05):
+    """``(train_accuracy, eval_accuracy)`` of the FactorVAE majority-vote classifier (rule: include/itcv_hip.h).
+    ``mu_train [Mt * L, D]`` / ``mu_eval [Me * L, D]``: groups of L consecutive rows with one factor held fixed,
+    ``fidx_*``: that factor's index per group; ``mu_var [Nv, D]``: the rows of the global variance estimate."""
+    got = factor_vae_votes(mu_var, mu_train, fidx_train, mu_eval, fidx_eval, L, num_factors, threshold)
+    return got["train_accuracy"], got["eval_accuracy"]
+
+
+def _index_state(generator):
+    rs = getattr(generator, "random_state", None)
+    return rs if rs is not None else np.random.RandomState(getattr(generator, "seed", None))
+
+
+def _fixed_factor_group(generator, n, k):
+    if hasattr(generator, "sample_fixed_factor"):
+        return generator.sample_fixed_factor(n, k)
+    factors = np.asarray(generator.sample_factors_of_variation(n)).copy()
+    factors[:, k] = factors[0, k]
+    return factors, generator.sample_observations_from_factors(factors)
+
+
+def _fixed_factor_representations(generator, model, num_groups, L, stack):
+    """``(mu [num_groups * L, D] fp32 on the device, fidx [num_groups] numpy int64)``: per group the factor index is drawn
+    first, then the group.  ``stack`` groups go through one eval-mode forward call (eval BatchNorm normalises every image
+    with the running statistics, so stacking is exact per image); the means land in one preallocated buffer."""
+    rs = _index_state(generator)
+    fidx = np.empty((num_groups,), dtype=np.int64)
+    mu, row = None, 0
+    for g0 in range(0, num_groups, stack):
+        obs = []
+        for g in range(g0, min(num_groups, g0 + stack)):
+            fidx[g] = k = rs.randint(generator.num_latents)
+            obs.append(_fixed_factor_group(generator, L, k)[1])
+        m, _ = model.encode(torch.cat(obs, 0) if len(obs) > 1 else obs[0])
+        m = m.reshape(m.shape[0], -1)
+        if mu is None:
+            mu = torch.empty((num_groups * L, m.shape[1]), dtype=m.dtype, device=m.device)
+        mu[row:row + m.shape[0]].copy_(m)
+        row += m.shape[0]
+    return mu, fidx
+
+
+def compute_factor_vae_score(latent_generator, model, batch_size=64, num_train=10000, num_eval=5000,
+                             num_variance_estimate=10000, params=None):
+    """``(train_accuracy, eval_accuracy)``: ``num_variance_estimate`` images for the global variances, then ``num_train`` /
+    ``num_eval`` groups of ``batch_size`` images with one factor fixed, all encoded in eval mode without gradients (as many
+    groups per forward call as fit in 1024 images).  ``params`` may override any of the counts and carry ``threshold``."""
+    params = params or {}
+    L = int(params.get("batch_size", batch_size))
+    if L < 2:
+        raise ValueError(f"factor_vae: a group needs L >= 2 rows for a ddof = 1 variance (got L = {L})")
+    nt, ne = int(params.get("num_train", num_train)), int(params.get("num_eval", num_eval))
+    nv = int(params.get("num_variance_estimate", num_variance_estimate))
+    mu_var, _ = factor_representations(latent_generator, model, nv, L)
+    stack = max(1, 1024 // L)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            mu_t, f_t = _fixed_factor_representations(latent_generator, model, nt, L, stack)
+            mu_e, f_e = _fixed_factor_representations(latent_generator, model, ne, L, stack)
+    finally:
+        model.train(was_training)
+    return factor_vae_score(mu_var, mu_t, f_t, mu_e, f_e, L, int(latent_generator.num_latents),
+                            params.get("threshold", 0.05))
+
+
+# ---- SAP score: separated attribute predictability --------------------------------------------------------------------
+def _sap_inputs(x_train, x_test):
+    for x in (x_train, x_test):
+        if x.dim() != 2 or x.shape[1] < 2:
+            raise ValueError(f"sap: the score needs at least two latents, representations [N, D >= 2] (got "
+                             f"{tuple(x.shape)}): there is no second-largest predictability")
+    if x_train.shape[1] != x_test.shape[1]:
+        raise ValueError("sap: train and test representations differ in width")
+
+
+def fit_sap_classifiers(x_train, y_train, factor_sizes, C=0.01, gtol=1e-10, max_iter=100, flags=None):
+    """The classifiers alone: ``(theta [D, csum, 2], gnorm [D, csum], iters [D, csum], cvalid [csum])`` as device tensors.
+    With ``flags`` None the flags are read back and raise; else the caller owns them."""
+    own = flags is None
+    flags = HF.extra_flags(x_train.device) if own else flags
+    out = HF.sap_svc_fit(x_train, y_train, factor_sizes, flags, C, gtol, max_iter)
+    if own:
+        _raise_on_extra(flags.tolist())
+    return out
+
+
+def _sap_matrix(x_train, y_train, x_test, y_test, factor_sizes, continuous_factors, C, gtol, max_iter, flags):
+    _sap_inputs(x_train, x_test)
+    if continuous_factors:
+        x = HF._disent_mu(x_train).to(torch.float64)
+        y = torch.as_tensor(y_train).to(device=x.device, dtype=torch.float64)
+        if y.dim() != 2 or y.shape[0] != x.shape[0] or x.shape[0] < 2:
+            raise ValueError("sap: continuous factors must be [N >= 2, K], one row per representation")
+        flags[0:1].bitwise_or_((~torch.isfinite(x).all()).to(torch.int32))
+        xc, yc = x - x.mean(0, keepdim=True), y - y.mean(0, keepdim=True)
+        cov = xc.t() @ yc / (x.shape[0] - 1)
+        vx, vy = (xc * xc).sum(0) / (x.shape[0] - 1), (yc * yc).sum(0) / (x.shape[0] - 1)
+        S = cov * cov / (vx[:, None] * vy[None, :])
+        return torch.where(vx[:, None] > 1e-12, S, torch.zeros_like(S))
+    theta, _, _, cvalid = HF.sap_svc_fit(x_train, y_train, factor_sizes, flags, C, gtol, max_iter)
+    correct = HF.sap_svc_score(x_test, y_test, factor_sizes, cvalid, theta, flags)
+    # integer counts over a TENSOR divisor: a true fp64 division (a Python divisor becomes a product with 1 / N_test)
+    return correct.to(torch.float64) / torch.full((), float(x_test.shape[0]), dtype=torch.float64, device=correct.device)
+
+
+def _sap(S):
+    """mean_j (largest - second largest of S[:, j]); the sum runs in factor order, so the bits are defined."""
+    top = S.topk(2, dim=0).values
+    diff = top[0] - top[1]
+    tot = diff[0]
+    for j in range(1, diff.shape[0]):
+        tot = tot + diff[j]
+    return tot / torch.full((), float(diff.shape[0]), dtype=torch.float64, device=S.device)
+
+
+def sap_score_matrix(x_train, y_train, x_test, y_test, factor_sizes, continuous_factors=False, C=0.01, gtol=1e-10,
+                     max_iter=100):
+    """fp64 device tensor ``S [D, K]``: test accuracy of the classifier that predicts factor j from latent i alone, or,
+    with ``continuous_factors``, the squared correlation of the pair on the train rows (0 where var(x_i) <= 1e-12)."""
+    flags = HF.extra_flags(x_train.device)
+    S = _sap_matrix(x_train, y_train, x_test, y_test, factor_sizes, continuous_factors, C, gtol, max_iter, flags)
+    _raise_on_extra(flags.tolist())
+    return S
+
+
+def sap_score(x_train, y_train, x_test, y_test, factor_sizes, continuous_factors=False, C=0.01, gtol=1e-10,
+              max_iter=100):
+    """The SAP score: the mean over the factors of (largest - second largest entry of the column of S).  One read-back."""
+    flags = HF.extra_flags(x_train.device)
+    S = _sap_matrix(x_train, y_train, x_test, y_test, factor_sizes, continuous_factors, C, gtol, max_iter, flags)
+    out = torch.cat([_sap(S).reshape(1), flags.to(torch.float64)]).tolist()
+    _raise_on_extra(out[1:])
+    return out[0]
+
+
+def compute_sap_score(latent_generator, model, num_train=10000, num_test=5000, batch_size=64, params=None):
+    """SAP of ``num_train`` / ``num_test`` sampled images encoded in eval mode.  ``params`` may override the counts and
+    carry ``continuous_factors``, ``C``, ``gtol``, ``max_iter``."""
+    params = params or {}
+    bs = int(params.get("batch_size", batch_size))
+    xtr, ytr = factor_representations(latent_generator, model, int(params.get("num_train", num_train)), bs)
+    xte, yte = factor_representations(latent_generator, model, int(params.get("num_test", num_test)), bs)
+    return sap_score(xtr, ytr, xte, yte, _latent_sizes(latent_generator), params.get("continuous_factors", False),
+                     params.get("C", 0.01), params.get("gtol", 1e-10), params.get("max_iter", 100))

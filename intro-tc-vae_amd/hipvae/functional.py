@@ -1839,3 +1839,103 @@ def gbt_importance(tfeat, tgain, class_sizes, D):
     call("itcv_gbt_importance", ptr(_gbt_dense(tfeat, torch.int32, "tfeat")), ptr(_gbt_dense(tgain, F64, "tgain")),
          tfeat.shape[0], len(sizes), csizes, int(D), ptr(imp), stream())
     return imp
+
+
+# ------------------------------------------------------------------ FactorVAE and SAP scores (csrc/extra_scores.hip)
+def extra_flags(device):
+    """The three sticky flags of the FactorVAE / SAP kernels ([0] non-finite representation, [1] factor index or label out
+    of range, [2] a SAP classifier that did not converge)."""
+    return torch.zeros(3, dtype=torch.int32, device=device)
+
+
+def _fvae_groups(mu, L):
+    """mu[M * L, D] checked BEFORE anything touches the device: (mu, M, L)."""
+    L = int(L)
+    if L < 2:
+        raise ValueError(f"factor_vae: a group needs L >= 2 rows for a ddof = 1 variance (got L = {L})")
+    if mu.dim() != 2 or mu.shape[0] < L or mu.shape[0] % L:
+        raise ValueError(f"factor_vae: the representations must be [M * L, D] with L = {L} (got {tuple(mu.shape)})")
+    return _disent_mu(mu), mu.shape[0] // L, L
+
+
+def fvae_gvar(mu, flags):
+    """fp64 gvar[D]: the ddof = 1 variance of every column of mu[N, D], N >= 2; sets flags[0] on a non-finite element."""
+    if mu.dim() == 2 and mu.shape[0] < 2:
+        raise ValueError(f"factor_vae: the variance estimate needs at least 2 rows (got {mu.shape[0]})")
+    mu = _disent_mu(mu)
+    N, D = mu.shape
+    gvar = torch.empty((D,), dtype=F64, device=mu.device)
+    call("itcv_fvae_gvar", mu.data_ptr(), mu.stride(0), N, D, ptr(gvar), ptr(flags), stream())
+    return gvar
+
+
+def fvae_votes(mu, L, gvar, threshold, fidx, num_factors, flags):
+    """int64 votes[D, K]: every group of L consecutive rows of mu[M * L, D] votes for (argmin over the active dimensions of
+    its variance / gvar, fidx[group]).  Sets flags[0] / flags[1] on a non-finite element / an index outside [0, K)."""
+    mu, M, L = _fvae_groups(mu, L)
+    D, K = mu.shape[1], int(num_factors)
+    fidx = torch.as_tensor(fidx).reshape(-1)
+    if fidx.numel() != M:
+        raise ValueError(f"factor_vae: {M} groups need {M} factor indices (got {fidx.numel()})")
+    fidx = fidx.to(device=mu.device, dtype=torch.int32).contiguous()
+    gvar = _gbt_dense(gvar, F64, "gvar")
+    if gvar.numel() != D:
+        raise abi.HipExtensionError(f"factor_vae: gvar needs {D} entries (got {gvar.numel()})")
+    votes = torch.empty((D, max(K, 1)), dtype=I64, device=mu.device)
+    call("itcv_fvae_votes", mu.data_ptr(), mu.stride(0), M, L, D, ptr(gvar), float(threshold), ptr(fidx), K, ptr(votes),
+         ptr(flags), stream())
+    return votes
+
+
+def fvae_classify(votes_train, votes_eval, num_train, num_eval, gvar, threshold):
+    """(classifier[D] int32, res[3] fp64 = train accuracy, eval accuracy, active dimensions) from the two vote tables."""
+    vt, ve = _gbt_dense(votes_train, I64, "votes"), _gbt_dense(votes_eval, I64, "votes")
+    D, K = vt.shape
+    if ve.shape != vt.shape:
+        raise abi.HipExtensionError("factor_vae: the two vote tables differ in shape")
+    classifier = torch.empty((D,), dtype=torch.int32, device=vt.device)
+    res = torch.empty((3,), dtype=F64, device=vt.device)
+    call("itcv_fvae_classify", ptr(vt), ptr(ve), D, K, int(num_train), int(num_eval), ptr(_gbt_dense(gvar, F64, "gvar")),
+         float(threshold), ptr(classifier), ptr(res), stream())
+    return classifier, res
+
+
+def sap_svc_lds_rows():
+    """Train rows up to which itcv_sap_svc_fit keeps a block's column and labels in LDS (above: streamed)."""
+    return lib.itcv_sap_svc_lds_rows()
+
+
+def sap_svc_fit(x, y, class_sizes, flags, C=0.01, gtol=1e-10, max_iter=100):
+    """Every (latent, factor, class) squared-hinge classifier of x[N, D] / y[N, K] in one solve launch.  Returns
+    ``(theta [D, csum, 2], gnorm [D, csum], iters [D, csum] int32, cvalid [csum] int32)``; flags[2] is set when a problem
+    did not converge."""
+    x = _disent_mu(x)
+    N, D = x.shape
+    y, sizes, csizes = _disent_factors(y, class_sizes, N, x.device)
+    K, csum = len(sizes), sum(sizes)
+    nws = lib.itcv_sap_svc_workspace(N, D, K, csum)                     # 0 for what the call below refuses
+    ws = torch.empty((max(nws, 8),), dtype=torch.uint8, device=x.device)
+    theta = torch.empty((D, max(csum, 1), 2), dtype=F64, device=x.device)
+    gnorm = torch.empty((D, max(csum, 1)), dtype=F64, device=x.device)
+    iters = torch.empty((D, max(csum, 1)), dtype=torch.int32, device=x.device)
+    cvalid = torch.empty((max(csum, 1),), dtype=torch.int32, device=x.device)
+    call("itcv_sap_svc_fit", x.data_ptr(), x.stride(0), ptr(y), N, D, K, csizes, float(C), float(gtol), int(max_iter),
+         ptr(theta), ptr(gnorm), ptr(iters), ptr(cvalid), ptr(flags), ptr(ws), nws, stream())
+    return theta, gnorm, iters, cvalid
+
+
+def sap_svc_score(x, y, class_sizes, cvalid, theta, flags, with_pred=False):
+    """int64 correct[D, K]: the test rows of x[Nt, D] / y[Nt, K] whose prediction under ``theta`` equals the label
+    (``with_pred``: also pred[D, K, Nt] int32)."""
+    x = _disent_mu(x)
+    Nt, D = x.shape
+    y, sizes, csizes = _disent_factors(y, class_sizes, Nt, x.device)
+    K, csum = len(sizes), sum(sizes)
+    theta, cvalid = _gbt_dense(theta, F64, "theta"), _gbt_dense(cvalid, torch.int32, "cvalid")
+    if tuple(theta.shape) != (D, csum, 2) or cvalid.numel() != csum:
+        raise abi.HipExtensionError(f"sap: theta must be [{D}, {csum}, 2] and cvalid [{csum}]")
+    correct = torch.empty((D, K), dtype=I64, device=x.device)
+    pred = torch.empty((D, K, Nt), dtype=torch.int32, device=x.device) if with_pred else None
+    call("itcv_sap_svc_score", x.data_ptr(), x.stride(0), ptr(y), Nt, D, K, csizes, ptr(cvalid), ptr(theta), ptr(correct),
+         ptr(pred), ptr(flags), stream())
+    return (correct, pred) if with_pred else correct

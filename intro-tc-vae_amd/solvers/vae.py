@@ -54,6 +54,11 @@ class VAESolver:
         # "all" -> the beta-VAE score and explicitness too; "all+dci" -> DCI as well, nothing delegated
         self.device_scores = None
         self.dci_params = None       # ``params`` of hipvae.disentangle.compute_dci_score (None: 100 rounds, depth 6)
+        # scores the reference does not have, written from the device on top of the above: a tuple drawn from
+        # {"factor_vae", "sap"}; ``params`` of hipvae.disentangle.compute_factor_vae_score / compute_sap_score
+        self.extra_scores = ()
+        self.factor_vae_params = None
+        self.sap_params = None
         self.recon_loss_type = recon_loss_type
         self.scale = 1 / (self.model.cdim * self.model.encoder.image_size ** 2)   # solvers/vae.py:61
         self._flat = {}
@@ -306,9 +311,15 @@ class VAESolver:
         explicitness_score} are written from the device too (metrics.py:11-17, 222-234) and only DCI is delegated.
         ``device_scores == "all+dci"`` writes those three records and then ``dci`` {dci_informativeness_score,
         dci_completeness_score, dci_disentanglement_score} from the device (metrics.py:82-103) and delegates nothing:
-        ``evaluation`` is not imported."""
+        ``evaluation`` is not imported.
+        ``extra_scores`` adds, after all of the above and whatever ``device_scores`` says, ``factor_vae`` {train_accuracy,
+        eval_accuracy} and / or ``sap_score`` from the device (hipvae.disentangle; neither is in the reference)."""
         if self.writer is None or not isinstance(self.dataset, DisentanglementDataset) or cur_iter % self.test_iter:
             return
+        extras = tuple(self.extra_scores or ())
+        unknown = [e for e in extras if e not in ("factor_vae", "sap")]
+        if unknown:
+            raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: 'factor_vae', 'sap')")
         with_dci = isinstance(self.device_scores, str) and self.device_scores == "all+dci"
         M = None
         if not with_dci:
@@ -317,9 +328,9 @@ class VAESolver:
             except Exception:  # noqa: BLE001
                 M = None
         native = (M is None) if self.device_scores is None else bool(self.device_scores)
-        if M is None and not native:
+        if M is None and not native and not extras:
             return
-        if native:
+        if native or extras:
             from hipvae import disentangle
             if getattr(self, "latent_generator", None) is None:
                 self.latent_generator = disentangle.FactorSampler(self.dataset, self.device)
@@ -350,6 +361,13 @@ class VAESolver:
             got = disentangle.compute_scores(self.latent_generator, self.model, num_samples=n, batch_size=self.batch_size)
             self.writer.add_scalar("mig_score", got["mig"], global_step=cur_iter)
             self.writer.add_scalars("mod_expl", dict(modularity_score=got["modularity"]), global_step=cur_iter)
+        if "factor_vae" in extras:
+            train, ev = disentangle.compute_factor_vae_score(self.latent_generator, self.model, batch_size=self.batch_size,
+                                                             params=self.factor_vae_params)
+            self.writer.add_scalars("factor_vae", dict(train_accuracy=train, eval_accuracy=ev), global_step=cur_iter)
+        if "sap" in extras:
+            self.writer.add_scalar("sap_score", disentangle.compute_sap_score(
+                self.latent_generator, self.model, batch_size=self.batch_size, params=self.sap_params), global_step=cur_iter)
         if was_training:
             self.model.train()
 
