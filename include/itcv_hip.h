@@ -126,6 +126,13 @@ int itcv_conv2d_fwd_bf16p_stat_tiles(int B, int Ci, int H, int W, int Co, int KS
 int itcv_conv2d_fwd_bf16p_st(const void* xplanes, const void* wp, const float* bias, float* y, int B, int Ci, int H,
                              int W, int Co, int KS, int up2, int ns, float* tile_stats, void* ws, size_t ws_bytes,
                              void* stream);
+/* itcv_conv2d_fwd_bf16p on the images [b0, b0 + nb) of the B-image tensors xplanes / y (both given WHOLE): the planes are
+ * read at the whole tensor's plane stride and scale record, y is written in that image range only, and every written
+ * value is bit for bit the one the full call writes -- tile shape, MFMA form and K split are planned for B, not nb.
+ * Workspace: that of the full call.  Used for the data gradient of a batch of which only some images carry a gradient. */
+int itcv_conv2d_fwd_bf16p_sub(const void* xplanes, const void* wp, const float* bias, float* y, int B, int Ci, int H,
+                              int W, int Co, int KS, int up2, int ns, int b0, int nb, void* ws, size_t ws_bytes,
+                              void* stream);
 /* Weight gradient from the same planes (x: [2][B][Ci/8][Hs][Ws], dy: [2][B][Co/8][H][W]); the pixel
  * reduction runs through the gfx950 transposing LDS read, so no pixel-major copy is needed.  bf16x3
  * only; KS = 3, W a power of two in 4..64, H a power of two, B*H*W % 64 == 0 (see _supported).  Replaces
@@ -311,6 +318,17 @@ int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const 
                       const float* beta, const float* skip, double* dsums, float* dx, float* dskip, void* dx_planes,
                       int ns, float* dgamma, float* dbeta, int accumulate, int B, int C, int H, int W, float slope,
                       int pool, int up2, void* ws, size_t ws_bytes, size_t plane_stride, int groups, void* stream);
+/* itcv_bn_train_bwd for a dy that is exactly zero outside the groups [live0, live0 + nlive) (the caller's guarantee; a
+ * batched pass of which one half only feeds constants).  Live groups: launches, arithmetic and results of the full call on
+ * every path of itcv_bn_plan_query.  Dead groups: dy and skip are not read, dx / dskip / dx_planes are not written, their
+ * dsums are 0 and the parameter gradients receive nothing from them.  fp16 planes: the reduce pass still reads a dead
+ * group's x for max|xhat|, so the scale record -- one per tensor, where the whole tensor's planes put it -- and the live
+ * groups' chunks are bit for bit those of the full call.  live0 = 0, nlive = groups is itcv_bn_train_bwd. */
+int itcv_bn_train_bwd_live(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
+                           const float* beta, const float* skip, double* dsums, float* dx, float* dskip, void* dx_planes,
+                           int ns, float* dgamma, float* dbeta, int accumulate, int B, int C, int H, int W, float slope,
+                           int pool, int up2, void* ws, size_t ws_bytes, size_t plane_stride, int groups, int live0,
+                           int nlive, void* stream);
 
 /* Which launches a BatchNorm training call gets.  Pure host arithmetic (no launch, no device): the decision
  * itcv_bn_train_fwd (bwd = 0) / itcv_bn_train_bwd (bwd = 1) make for one group of (B, C, H, W), `planes` != 0 when

@@ -2651,26 +2651,41 @@ int itcv_conv2d_fwd_bf16p_stat_tiles(int B, int Ci, int H, int W, int Co, int KS
   return plan_fwd_planes(B, Ci, H, W, Co, KS, ns, true).stat_tiles;
 }
 
-int itcv_conv2d_fwd_bf16p_st(const void* xplanes, const void* wp, const float* bias, float* y, int B, int Ci, int H,
-                             int W, int Co, int KS, int up2, int fmt, float* tile_stats, void* ws, size_t ws_bytes,
-                             void* stream) {
+// Images [b0, b0 + nb) of a B-image tensor (the whole tensor: b0 = 0, nb = B).  Host side only: the plan -- tile shape,
+// MFMA form, band geometry and above all the K split, which fixes the fp32 summation order -- is the one of the WHOLE batch;
+// the kernels are handed the sub-range as a batch of nb images whose planes start b0 images into every plane, at the whole
+// tensor's plane stride and scale record, and write (slabs of) nb images that land in y's sub-range.  Among the band
+// kernels the one-tile-per-block and the persistent form (bit-identical) are chosen by the launched tile count.
+static int fwd_planes_run(const void* xplanes, const void* wp, const float* bias, float* y, int B, int Ci, int H, int W,
+                          int Co, int KS, int up2, int fmt, float* tile_stats, void* ws, size_t ws_bytes, int b0, int nb,
+                          void* stream) {
   if (int e = check_dims("itcv_conv2d_fwd_bf16p", B, Ci, H, W, Co, KS)) return e;
   ITCV_REQUIRE(xplanes && wp && y && fmt_ok(fmt), "itcv_conv2d_fwd_bf16p");
+  ITCV_REQUIRE(b0 >= 0 && nb >= 1 && b0 + nb <= B && (nb == B || !tile_stats), "itcv_conv2d_fwd_bf16p(image range)");
   const int f16 = fmt == ITCV_PLANES_F16X2, ns = planes_of_fmt(fmt);
   if (tile_stats && (f16 || !itcv_conv2d_fwd_bf16p_stat_tiles(B, Ci, H, W, Co, KS, ns)))
     return fail("%s: tile statistics are not available for this shape / format (see itcv_conv2d_fwd_bf16p_stat_tiles)",
                 "itcv_conv2d_fwd_bf16p_st");
-  const size_t in_plane = (size_t)B * (Ci / 8) * (up2 ? (H / 2) * (W / 2) : H * W);
+  const size_t in_image = (size_t)(Ci / 8) * (up2 ? (H / 2) * (W / 2) : H * W), in_plane = (size_t)B * in_image;
   const u32x4* xp = static_cast<const u32x4*>(xplanes);
   const ScaleRec* xrec = f16 ? reinterpret_cast<const ScaleRec*>(xp + 2 * in_plane) : nullptr;
+  xp += (size_t)b0 * in_image;
+  y += (size_t)b0 * Co * H * W;
   if (!itcv_conv2d_bf16s_supported(Ci, Co, KS))
     return fail("%s: shape not supported by the split-bf16 kernel (Ci %% 32, Co > 32, KS 1/3)", "itcv_conv2d_fwd_bf16p");
   if (up2) ITCV_REQUIRE(H % 2 == 0 && W % 2 == 0, "itcv_conv2d_fwd_bf16p(up2)");
-  const size_t out_elems = (size_t)B * Co * H * W;
-  const FwdPlanP p = plan_fwd_planes(B, Ci, H, W, Co, KS, ns, tile_stats != nullptr);
+  const size_t out_elems = (size_t)nb * Co * H * W;
+  FwdPlanP p = plan_fwd_planes(B, Ci, H, W, Co, KS, ns, tile_stats != nullptr);
   if (int e = check_ws("itcv_conv2d_fwd_bf16p", ws, ws_bytes, p.ws_need)) return e;
+  if (nb != B) {
+    p.nt = (int)(((long long)nb * H * W + p.bn - 1) / p.bn);
+    if (p.path == FwdPath::Band || p.path == FwdPath::BandPersistent) {
+      const int ids = cdiv(p.nt, 8) * 8 * p.mt, pb = g_opt.band_persist_blocks;
+      p.path = (pb > 0 && ids > pb) ? FwdPath::BandPersistent : FwdPath::Band;
+    }
+  }
   const bool split = p.splits > 1;
-  const double flop = 2.0 * B * H * W * (double)Co * Ci * KS * KS;
+  const double flop = 2.0 * nb * H * W * (double)Co * Ci * KS * KS;
   hipStream_t st = S(stream);
   if (p.path != FwdPath::Planes128) {   // band kernels: tap reuse through LDS
     ConvArgsP2 a;
@@ -2678,9 +2693,9 @@ int itcv_conv2d_fwd_bf16p_st(const void* xplanes, const void* wp, const float* b
     a.wp = static_cast<const u32x4*>(wp);
     a.bias = split ? nullptr : bias;
     a.y = split ? static_cast<float*>(ws) : y;
-    a.B = B, a.Ci = Ci, a.H = H, a.Co = Co;
+    a.B = nb, a.Ci = Ci, a.H = H, a.Co = Co;
     a.Mp = p.mt * p.bm;
-    a.N = B * H * W;
+    a.N = nb * H * W;
     a.mt = p.mt, a.nt = p.nt, a.cpt = p.cpt, a.cpt_per_split = p.cps;
     a.SR = p.SR, a.NSEG = p.NSEG, a.NP = p.NP, a.NPC = p.NPC, a.PXB = p.PXB;
     a.h_shift = log2_exact(H);
@@ -2702,9 +2717,9 @@ int itcv_conv2d_fwd_bf16p_st(const void* xplanes, const void* wp, const float* b
     a.wp = static_cast<const u32x4*>(wp);
     a.bias = split ? nullptr : bias;
     a.y = split ? static_cast<float*>(ws) : y;
-    a.B = B, a.Ci = Ci, a.H = H, a.W = W, a.Co = Co;
+    a.B = nb, a.Ci = Ci, a.H = H, a.W = W, a.Co = Co;
     a.Mp = p.mt * p.bm;
-    a.N = B * H * W;
+    a.N = nb * H * W;
     a.mt = p.mt, a.nt = p.nt, a.ktiles = p.ktiles, a.ktiles_per_split = p.kps;
     a.slab_stride = split ? out_elems : 0;
     a.plane_stride = in_plane;
@@ -2719,6 +2734,18 @@ int itcv_conv2d_fwd_bf16p_st(const void* xplanes, const void* wp, const float* b
     ITCV_CHECK_LAUNCH("itcv_conv2d_fwd_bf16p");
   }
   return reduce_fwd_splits("itcv_conv2d_fwd_bf16p(reduce)", ws, bias, y, out_elems, p.splits, H * W, Co, st);
+}
+
+int itcv_conv2d_fwd_bf16p_st(const void* xplanes, const void* wp, const float* bias, float* y, int B, int Ci, int H,
+                             int W, int Co, int KS, int up2, int fmt, float* tile_stats, void* ws, size_t ws_bytes,
+                             void* stream) {
+  return fwd_planes_run(xplanes, wp, bias, y, B, Ci, H, W, Co, KS, up2, fmt, tile_stats, ws, ws_bytes, 0, B, stream);
+}
+
+int itcv_conv2d_fwd_bf16p_sub(const void* xplanes, const void* wp, const float* bias, float* y, int B, int Ci, int H,
+                              int W, int Co, int KS, int up2, int fmt, int b0, int nb, void* ws, size_t ws_bytes,
+                              void* stream) {
+  return fwd_planes_run(xplanes, wp, bias, y, B, Ci, H, W, Co, KS, up2, fmt, nullptr, ws, ws_bytes, b0, nb, stream);
 }
 
 size_t itcv_conv2d_wgrad_workspace(int B, int Ci, int H, int W, int Co, int KS) {

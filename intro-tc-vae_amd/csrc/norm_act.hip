@@ -27,7 +27,12 @@ struct BnGrp {
   size_t ps;    // planes: chunks per group inside one plane
   int cs;       // mean / rstd: C per group (dsums: 2C)
   int G;        // groups walked by the fused statistics kernels (0 or 1 = one)
+  int lv0, lvn; // backward: the live groups [lv0, lv0 + lvn) (lvn = 0: every group); see itcv_bn_train_bwd_live
 };
+// a dead group's upstream gradient is exactly zero by contract: it is never read and nothing is stored for the group
+__device__ __forceinline__ bool bn_dead(const BnGrp& g, uint32_t group) {
+  return g.lvn > 0 && (group < (uint32_t)g.lv0 || group >= (uint32_t)(g.lv0 + g.lvn));
+}
 
 struct BnFinal {   // arguments of the fused single-launch path (splits == 1)
   double count;
@@ -593,10 +598,14 @@ __global__ __launch_bounds__(kRedThreads) void bn_bwd_partial_v4(
   const float mu = mean[c], rs = rstd[c];
   double s1 = 0.0, s2 = 0.0;
   float gmax = 0.f, xmax = 0.f;
+  // dead group (block-uniform): g = 0 without reading dy or skip -- the sums are the +0.0 a zero dy gives; with MX the
+  // walk still reads x for v = max|xhat|, which the tensor-wide scale depends on, and without MX there is no walk
+  const bool dead = bn_dead(grp, FUSED ? (uint32_t)gi : gz);
+  const uint32_t gend = (dead && !MX) ? beg : end;
   // Four iterations' loads are issued before the first is consumed (the accumulation order is that of the plain loop:
   // bitwise the same sums); out-of-range iterations load a valid address and add zeros.  -9..12 % on this kernel.
   constexpr int U = 4;
-  for (uint32_t i0 = beg + threadIdx.x * 4; i0 < end; i0 += kRedThreads * 4 * U) {
+  for (uint32_t i0 = beg + threadIdx.x * 4; i0 < gend; i0 += kRedThreads * 4 * U) {
     float4 xv4[U], g4[U], k4[U];
     bool ok[U];
 #pragma unroll
@@ -608,9 +617,9 @@ __global__ __launch_bounds__(kRedThreads) void bn_bwd_partial_v4(
       const uint32_t h = fdiv(hw, W, w_shift), w = hw - h * W;
       const uint32_t bc = b * C + c;
       xv4[u] = *reinterpret_cast<const float4*>(x + (size_t)bc * HW + hw);
-      g4[u] = upstream4<MODE>(dy, bc, h, w, H, W);
+      g4[u] = dead ? make_float4(0.f, 0.f, 0.f, 0.f) : upstream4<MODE>(dy, bc, h, w, H, W);
     }
-    if (skip) {
+    if (skip && !dead) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const uint32_t iu = i0 + (uint32_t)u * kRedThreads * 4, i = iu < end ? iu : i0;
@@ -627,7 +636,7 @@ __global__ __launch_bounds__(kRedThreads) void bn_bwd_partial_v4(
       float4 g = g4[u];
       const float xh0 = (xv.x - mu) * rs, xh1 = (xv.y - mu) * rs, xh2 = (xv.z - mu) * rs, xh3 = (xv.w - mu) * rs;
       float u0 = xh0 * ga + be, u1 = xh1 * ga + be, u2 = xh2 * ga + be, u3 = xh3 * ga + be;
-      if (skip) u0 += k4[u].x, u1 += k4[u].y, u2 += k4[u].z, u3 += k4[u].w;
+      if (skip) u0 += k4[u].x, u1 += k4[u].y, u2 += k4[u].z, u3 += k4[u].w;   // (dead: k4 = 0 and g = 0 whatever u is)
       if (!(u0 > 0.f)) g.x *= slope;
       if (!(u1 > 0.f)) g.y *= slope;
       if (!(u2 > 0.f)) g.z *= slope;
@@ -769,7 +778,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_planes(
   // ascending order, and on layers whose two tensors exceed the 256 MiB Infinity Cache an ascending second pass finds
   // exactly the lines that were evicted first; descending, it starts on the most recently read ones (c3: +4 % on this
   // kernel; c2's layers fit the cache either way).
-  const uint32_t zg = gridDim.z - 1 - blockIdx.z;     // BatchNorm group (gridDim.z = 1 and a zero `grp` otherwise)
+  // BatchNorm group (gridDim.z = 1 and a zero `grp` otherwise); a live range launches its groups only
+  const uint32_t zg = (uint32_t)grp.lv0 + gridDim.z - 1 - blockIdx.z;
   {
     const size_t g = zg;
     x += g * grp.xs, dy += g * grp.dys, planes += g * grp.ps, mean += g * grp.cs, rstd += g * grp.cs;
@@ -801,10 +811,13 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_planes(
         s_m1[threadIdx.x] = (float)(s1 / count), s_m2[threadIdx.x] = (float)(s2 / count);
         if (g < C8 && g * per_plane >= base) {
           sm.dsums_out[(size_t)gz * 2 * C + c] = s1, sm.dsums_out[(size_t)gz * 2 * C + C + c] = s2;
-          if (gz == 0) {
+          if (gz == (uint32_t)grp.lv0) {
+            for (uint32_t gg = 0; gg < G; ++gg)   // dead groups: no block of their own, their sums are zero
+              if (bn_dead(grp, gg)) sm.dsums_out[(size_t)gg * 2 * C + c] = 0.0, sm.dsums_out[(size_t)gg * 2 * C + C + c] = 0.0;
             float db = (sm.accumulate && sm.dbeta) ? sm.dbeta[c] : 0.f, dg = (sm.accumulate && sm.dgamma) ? sm.dgamma[c] : 0.f;
             db += (float)s1, dg += (float)s2;
-            for (uint32_t gg = 1; gg < G; ++gg) {
+            for (uint32_t gg = 0; gg < G; ++gg) {
+              if (gg == gz) continue;
               const double* pg = sm.part + (size_t)gg * sm.splits * 2 * C;
               db += (float)fold_strided(0.0, pg + c, (size_t)2 * C, sm.splits);
               dg += (float)fold_strided(0.0, pg + C + c, (size_t)2 * C, sm.splits);
@@ -1379,35 +1392,50 @@ int itcv_bn_replay_many(const void* dev_table, int n, int total_blocks, void* st
   return 0;
 }
 
-int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
-                      const float* beta, const float* skip, double* dsums, float* dx, float* dskip, void* dx_planes,
-                      int ns, float* dgamma, float* dbeta, int accumulate, int B, int C, int H, int W, float slope,
-                      int pool, int up2, void* ws, size_t ws_bytes, size_t plane_stride, int groups, void* stream) {
+// itcv_bn_train_bwd with a live-group range: the caller guarantees that dy is exactly zero in every group outside
+// [live0, live0 + nlive).  Live groups: the same launches, arithmetic and results as the full call, on every path.  Dead
+// groups: dy / skip are not read, dx / dskip / planes are not written, dsums = 0.  fp16 planes: the reduce pass still walks
+// a dead group's x for v = max|xhat| (4 of the 20 bytes per element), so the tensor's one scale record -- and with it every
+// live chunk -- is bit for bit that of the full call.
+int itcv_bn_train_bwd_live(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
+                           const float* beta, const float* skip, double* dsums, float* dx, float* dskip, void* dx_planes,
+                           int ns, float* dgamma, float* dbeta, int accumulate, int B, int C, int H, int W, float slope,
+                           int pool, int up2, void* ws, size_t ws_bytes, size_t plane_stride, int groups, int live0,
+                           int nlive, void* stream) {
   ITCV_REQUIRE(x && dy && mean && rstd && gamma && beta && dsums && (dx || dx_planes) && B > 0 && C > 0,
                "itcv_bn_train_bwd");
   ITCV_REQUIRE(!(pool && up2), "itcv_bn_train_bwd(pool and up2 are exclusive)");
+  const int ngroups = groups > 1 ? groups : 1;
+  ITCV_REQUIRE(live0 >= 0 && nlive >= 1 && live0 + nlive <= ngroups, "itcv_bn_train_bwd_live(live range inside the groups)");
+  const bool all_live = nlive == ngroups;
   // roofline leg of bench.py: the apply kernel reads x and dy once more and writes the planes [+ fp32 dx, + dskip]
-  const double bn_el = (double)(groups > 1 ? groups : 1) * B * C * H * W;
+  const double bn_el = (double)nlive * B * C * H * W;
   ProfScope bn_prof(S(stream), kProfBnBwd, ilog2_exact(W) >= 0 ? ilog2_exact(W) : 0, C / 8, pool ? 1 : (up2 ? 2 : 0), dx_planes ? ns : 0,
                     bn_el * 4.0 * (1.0 + (pool ? 0.25 : (up2 ? 4.0 : 1.0)) + (skip ? 1.0 : 0.0)) +
                         bn_el * ((dx_planes ? 4.0 : 0.0) + (dx ? 4.0 : 0.0) + (dskip ? 4.0 : 0.0)));
   if (groups > 1) ITCV_REQUIRE(!dx_planes || plane_stride, "itcv_bn_train_bwd(groups need the plane stride of the whole tensor)");
-  const BnPlan p = bn_plan(true, B, C, H, W, pool, up2, groups, dx_planes != nullptr, ns, plane_stride, ws ? ws_bytes : 0,
-                           false);
+  BnPlan p = bn_plan(true, B, C, H, W, pool, up2, groups, dx_planes != nullptr, ns, plane_stride, ws ? ws_bytes : 0, false);
+  if (!all_live) p.grp.lv0 = live0, p.grp.lvn = nlive, p.agrid.z = nlive;   // (PerGroup: the loop below skips the dead groups)
   const size_t ws_need = p.ws_need;
   if (p.f16 && groups > 1 && (p.path == BnPath::PerGroup || !(ws && ws_bytes >= ws_need)))
     return fail("%s: fp16 gradient planes need the merged group path (W %% 4 == 0, planes, a workspace of itcv_bn_workspace * groups)",
                 "itcv_bn_train_bwd");
   if (p.path == BnPath::PerGroup) {   // the parameter gradients add up over the groups
     const BnGrp& s = p.grp;
-    for (int g = 0; g < groups; ++g)
+    for (int g = 0; g < groups; ++g) {
+      if (g < live0 || g >= live0 + nlive) {   // dead: zero sums, nothing for the parameter gradients to add
+        if (hipMemsetAsync(dsums + (size_t)g * 2 * C, 0, (size_t)2 * C * sizeof(double), S(stream)) != hipSuccess)
+          return fail("%s: clearing a dead group's sums failed", "itcv_bn_train_bwd_live");
+        continue;
+      }
       if (int e = itcv_bn_train_bwd(x + g * s.xs, dy + g * s.dys, mean + (size_t)g * C, rstd + (size_t)g * C, gamma, beta,
                                     skip ? skip + g * s.xs : nullptr, dsums + (size_t)g * 2 * C, dx ? dx + g * s.xs : nullptr,
                                     dskip ? dskip + g * s.xs : nullptr,
                                     dx_planes ? static_cast<u32x4*>(dx_planes) + g * s.ps : nullptr, ns, dgamma, dbeta,
-                                    (accumulate || g > 0) ? 1 : 0, B, C, H, W, slope, pool, up2, ws, ws_bytes, plane_stride,
-                                    1, stream))
+                                    (accumulate || g > live0) ? 1 : 0, B, C, H, W, slope, pool, up2, ws, ws_bytes,
+                                    plane_stride, 1, stream))
         return e;
+    }
     return 0;
   }
   if (p.f16) ITCV_REQUIRE(ws && ws_bytes >= ws_need, "itcv_bn_train_bwd(workspace, fp16 planes)");
@@ -1420,6 +1448,15 @@ int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const 
   const float* mx = p.f16 ? reinterpret_cast<const float*>(static_cast<const double*>(ws) + p.part_doubles) : nullptr;
   return bn_bwd_apply_launch(p, x, dy, mean, rstd, gamma, beta, skip, dsums, (double)B * H * W, dx, dskip, dx_planes, ns, B, C,
                              H, W, slope, fold, mx, S(stream));
+}
+
+int itcv_bn_train_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
+                      const float* beta, const float* skip, double* dsums, float* dx, float* dskip, void* dx_planes,
+                      int ns, float* dgamma, float* dbeta, int accumulate, int B, int C, int H, int W, float slope,
+                      int pool, int up2, void* ws, size_t ws_bytes, size_t plane_stride, int groups, void* stream) {
+  return itcv_bn_train_bwd_live(x, dy, mean, rstd, gamma, beta, skip, dsums, dx, dskip, dx_planes, ns, dgamma, dbeta,
+                                accumulate, B, C, H, W, slope, pool, up2, ws, ws_bytes, plane_stride, groups, 0,
+                                groups > 1 ? groups : 1, stream);
 }
 
 static_assert((int)BnPath::OneBlock == ITCV_BN_PATH_ONE_BLOCK && (int)BnPath::SlicedFold == ITCV_BN_PATH_SLICED_FOLD &&

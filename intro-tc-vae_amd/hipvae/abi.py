@@ -54,6 +54,7 @@ SIGNATURES = {
     "itcv_conv2d_fwd_bf16p": (i32, [p, p, p, p] + [i32] * 8 + [p, sz, p]),
     "itcv_conv2d_fwd_bf16p_stat_tiles": (i32, [i32] * 7),
     "itcv_conv2d_fwd_bf16p_st": (i32, [p, p, p, p] + [i32] * 8 + [p, p, sz, p]),
+    "itcv_conv2d_fwd_bf16p_sub": (i32, [p, p, p, p] + [i32] * 10 + [p, sz, p]),
     "itcv_conv2d_wgrad_bf16p_supported": (i32, [i32] * 6),
     "itcv_conv2d_wgrad_bf16p_workspace": (sz, [i32] * 6),
     "itcv_conv2d_wgrad_bf16p": (i32, [p, p, p] + [i32] * 9 + [p, sz, p]),
@@ -107,6 +108,8 @@ SIGNATURES = {
     "itcv_bn_replay_max_descs": (i32, []),
     "itcv_bn_train_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, p, i32, p, p, i32, i32, i32, i32, i32, f32, i32, i32, p,
                                 sz, sz, i32, p]),
+    "itcv_bn_train_bwd_live": (i32, [p, p, p, p, p, p, p, p, p, p, p, i32, p, p, i32, i32, i32, i32, i32, f32, i32, i32, p,
+                                     sz, sz, i32, i32, i32, p]),
     "itcv_bn_plan_query": (i32, [i32] * 10 + [sz, i32, p, p]),
     "itcv_lrelu_fwd": (i32, [p, p, sz, f32, p]),
     "itcv_lrelu_bwd": (i32, [p, p, p, sz, f32, p]),

@@ -85,6 +85,15 @@ def _grad_target(param):
 #     Conv2dFn / LinearFn / BnActFn.backward whether a backward pass through it may compute and accumulate them (they add
 #     straight into the flat .grad buffers from inside those functions, out of autograd's sight);
 #   * ``input_grad`` False: the first function of the pass does not compute the gradient of the pass's input.
+#   * ``live`` = (g, G): the pass is a batch of G stacked groups and the gradient handed to this backward is exactly zero
+#     outside group g (the intro step's phase E: ``fake`` of dec(noise | z) only feeds constants).  The backward functions
+#     then run the sub-range forms of the kernels on group g's images alone: zero in gives zero out, so nothing is computed
+#     for the other groups, and the dead part of every gradient tensor on the way is never written and never read (NaN in
+#     _POISON mode).  The values of the live images are bit for bit those of the full backward.  It holds only for a
+#     backward with ``param_grads`` off (a weight gradient reads every image), and only for a pass whose functions all
+#     have a sub-range form: the forward calls note what stands in the way in ``live_blockers`` and the pass then runs the
+#     full backward, as a whole.  The chain ends at the first pointwise function in front of a LinearFn, which writes
+#     zeros for the dead rows: the Linear data gradient (a GEMM planned by its batch) runs unchanged.
 _SHARED_PASS = [None]
 
 
@@ -95,6 +104,8 @@ class SharedPass:
     def __init__(self):
         self.param_grads = True
         self.input_grad = True
+        self.live = None
+        self.live_blockers = []
         self.records = []
         self._first = False
         self._pool = {}
@@ -106,6 +117,7 @@ class SharedPass:
         prev, _SHARED_PASS[0] = _SHARED_PASS[0], self
         self.records, self._first = [], True
         self.param_grads = self.input_grad = True
+        self.live, self.live_blockers = None, []
         try:
             yield self
         finally:
@@ -131,6 +143,44 @@ class SharedPass:
 def _shared_ok(ctx, what):
     sp = ctx.shared
     return sp is None or getattr(sp, what)
+
+
+def _block_live(why):
+    """Forward of a function inside SharedPass.record() that has no sub-range backward for this call."""
+    sp = _SHARED_PASS[0]
+    if sp is not None and why not in sp.live_blockers:
+        sp.live_blockers.append(why)
+
+
+def _live_images(ctx, B):
+    """(b0, nb): the images of a B-image gradient this backward has to walk, or None for all of them (see SharedPass)."""
+    sp = getattr(ctx, "shared", None)
+    if sp is None or sp.live is None or sp.param_grads or sp.live_blockers:
+        return None
+    g, G = sp.live
+    if B % G:
+        raise abi.HipExtensionError(f"SharedPass.live: batch {B} is not {G} equal groups")
+    return g * (B // G), B // G
+
+
+def _new_grad(like_or_shape, device=None, live=None):
+    """Gradient tensor of which a live range writes a part only: the rest is never read (NaN in _POISON mode)."""
+    t = torch.empty_like(like_or_shape) if device is None else torch.empty(like_or_shape, dtype=F32, device=device)
+    if live is not None and _POISON[0]:
+        t.fill_(float("nan"))
+    return t
+
+
+def _dgrad_sub_kind(Co, Ci, KS):
+    """How the data gradient of a Ci -> Co conv runs on an image sub-range in the current mode: 'planes' (the planes GEMM
+    with the whole batch's plan, itcv_conv2d_fwd_bf16p_sub), 'small' (the per-image 5x5 kernels: a contiguous batch slice),
+    or None (fp32 / in-kernel-split GEMMs: their K split follows the launched batch)."""
+    ns = _planes_ns(Co, Ci, KS, False)
+    if ns:
+        return None if (_two(ns) and lib.itcv_conv2d_small_cout_bf16p_supported(Co, Ci, KS)) else "planes"
+    if lib.itcv_conv2d_small_cout_supported(Ci, KS):
+        return None
+    return "small" if lib.itcv_conv2d_small_cin_supported(Co, KS) else None
 
 
 def replay_bn_running(records, tables=None):
@@ -359,9 +409,11 @@ def pack_weight_bf16s(w4, for_dgrad, ns):
 _SCIN_MFMA = [True]
 
 
-def conv_apply(x, weight, w4, for_dgrad, bias, B, Ci, H, W, Co, KS, up2):
+def conv_apply(x, weight, w4, for_dgrad, bias, B, Ci, H, W, Co, KS, up2, out=None):
     """Forward-type conv GEMM (forward, or data-gradient with the roles of Ci/Co swapped by the caller)
-    on the kernel selected by set_conv_math()."""
+    on the kernel selected by set_conv_math().  ``out`` (per-image <= 4-reduction-channel kernels only): write there."""
+    if out is not None and (up2 or lib.itcv_conv2d_small_cout_supported(Co, KS) or not lib.itcv_conv2d_small_cin_supported(Ci, KS)):
+        raise abi.HipExtensionError("conv_apply: an output tensor is taken by the small-cin kernels only")
     if not up2 and lib.itcv_conv2d_small_cout_supported(Co, KS):
         # <= 4 output channels: direct fp32 conv on the vector ALUs, reads the raw OIHW weights
         y = torch.empty((B, Co, H, W), dtype=F32, device=x.device)
@@ -371,7 +423,7 @@ def conv_apply(x, weight, w4, for_dgrad, bias, B, Ci, H, W, Co, KS, up2):
         return y
     if not up2 and lib.itcv_conv2d_small_cin_supported(Ci, KS):
         # <= 4 reduction channels: direct fp32 conv, the pixel's input window lives in registers
-        y = torch.empty((B, Co, H, W), dtype=F32, device=x.device)
+        y = out if out is not None else torch.empty((B, Co, H, W), dtype=F32, device=x.device)
         fmt = _NS[_CONV_MATH[0]]
         if _SCIN_MFMA[0] and _two(fmt) and lib.itcv_conv2d_small_cin_bf16x3_supported(Ci, Co, KS, W):
             # fp16 form: the data-gradient's input is a gradient tensor -> scale from its magnitude (device side)
@@ -426,10 +478,19 @@ def split_planes(x, ns, gradient=False):
 _FUSE_STATS = [False]
 
 
-def conv_apply_planes(xp, weight, w4, for_dgrad, bias, B, Ci, H, W, Co, KS, up2, ns, want_stats=False):
+def conv_apply_planes(xp, weight, w4, for_dgrad, bias, B, Ci, H, W, Co, KS, up2, ns, want_stats=False, live=None):
     """conv_apply with the input given as pre-split planes (LDS-DMA kernel, no gather).  ``want_stats``: where the
     kernel can, it also leaves the per-tile channel sums of its output for the BatchNorm that follows
-    (attached to the result as ``_itcv_tile_stats``; BnActFn then skips its own statistics pass)."""
+    (attached to the result as ``_itcv_tile_stats``; BnActFn then skips its own statistics pass).
+    ``live`` = (b0, nb): only these images of the B-image tensors are computed, with the whole batch's launch plan."""
+    if live is not None:
+        wp = packed_weight(weight, w4, for_dgrad, ns)
+        y = _new_grad((B, Co, H, W), xp.device, live)
+        nws = lib.itcv_conv2d_fwd_bf16p_workspace(B, Ci, H, W, Co, KS, ns)
+        ws = _ws(nws, xp.device) if nws else None
+        call("itcv_conv2d_fwd_bf16p_sub", ptr(xp), ptr(wp), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(up2), ns, live[0],
+             live[1], ptr(ws), nws, stream())
+        return y
     if not up2 and _two(ns) and lib.itcv_conv2d_small_cout_bf16p_supported(Ci, Co, KS):
         y = torch.empty((B, Co, H, W), dtype=F32, device=xp.device)
         call("itcv_conv2d_small_cout_fwd_bf16p", ptr(xp), ptr(w4), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(for_dgrad),
@@ -778,6 +839,8 @@ class Conv2dFn(Function):
         ctx.cfg = (B, Ci, H, W, Co, KS, up2, bias is not None, (Hs, Ws))
         ctx.shared = _SHARED_PASS[0]
         ctx.shared_first = ctx.shared is not None and ctx.shared._claim_first()
+        if ctx.shared is not None and _dgrad_sub_kind(Co, Ci, KS) is None:
+            _block_live(f"conv {Ci}->{Co} k{KS}: data gradient without a sub-range form in mode {_CONV_MATH[0]}")
         return y
 
     @staticmethod
@@ -795,16 +858,32 @@ class Conv2dFn(Function):
         wg_planes = need_w and _wgrad_planes_ok(B, Ci, H, W, Co, KS)
         dyp = None
         fmt2 = F16X2 if _NS[_CONV_MATH[0]] == F16X2 else 2       # the two-plane format of the current mode
+        live = _live_images(ctx, B) if need_x else None          # (param_grads is off then: no weight / bias gradient)
+        if live is not None and _dgrad_sub_kind(Co, Ci, KS) is None:
+            raise abi.HipExtensionError("Conv2dFn.backward: conv math mode changed inside a shared pass")
+        if live is not None and ns_d and _tagged_planes(dy, ns_d) is None:
+            # no planes from the producer: the split pass reads the whole tensor, so the dead images become the zeros they stand for
+            full = torch.zeros_like(dy)
+            full[live[0]:live[0] + live[1]] = dy[live[0]:live[0] + live[1]]
+            dy = full
         if ns_d or wg_planes:
             dyp = planes_of(dy, ns_d if ns_d else fmt2, gradient=True)
         if need_x:
             if ns_d:
-                dx = conv_apply_planes(dyp, weight, weight, 1, None, B, Co, H, W, Ci, KS, False, ns_d)
+                dx = conv_apply_planes(dyp, weight, weight, 1, None, B, Co, H, W, Ci, KS, False, ns_d, live=live)
+            elif live is not None:
+                # the per-image 5x5 kernels on the live images (a contiguous slice; the fp16 scale comes from their maximum,
+                # which is the whole tensor's: the rest is zero)
+                r = slice(live[0], live[0] + live[1])
+                dx = _new_grad((B, Ci, H, W), dy.device, live)
+                conv_apply(_require_fp32(dy, "Conv2dFn.backward")[r], weight, weight, 1, None, live[1], Co, H, W, Ci, KS, False,
+                           out=dx[r])
             else:
                 dx = conv_apply(_require_fp32(dy, "Conv2dFn.backward"), weight, weight, 1, None, B, Co, H, W, Ci, KS, False)
             if up2:
-                lo = torch.empty((B, Ci, H // 2, W // 2), dtype=F32, device=dy.device)
-                call("itcv_upsample2_bwd", ptr(dx), ptr(lo), B * Ci, H // 2, W // 2, stream())
+                lo = _new_grad((B, Ci, H // 2, W // 2), dy.device, live)
+                b0, nb = live if live is not None else (0, B)
+                call("itcv_upsample2_bwd", ptr(dx[b0:b0 + nb]), ptr(lo[b0:b0 + nb]), nb * Ci, H // 2, W // 2, stream())
                 dx = lo
         wg5 = _wgrad5_mode(Ci, H, W, Co, KS, up2) if need_w else None
         if wg5 == "predict" and xp is None and x is None:
@@ -911,6 +990,9 @@ class BnActFn(Function):
         dev = x.device
         shared = _SHARED_PASS[0]
         uvar = None
+        if shared is not None and (not training or _world(group) != 1 or skip is not None or G != int(bn_groups)
+                                   or not lib.itcv_bn_act_planes_supported(C, H, W, 0)):
+            _block_live(f"BatchNorm C={C} {H}x{W}: eval / Sync-BN / skip input / a shape the planes kernels do not take")
         if shared is not None and training:
             # mean and the unbiased variance blended into running_var go to the pass's persistent buffer (SharedPass.replay)
             mean, uvar = shared._stats(G, C, dev)
@@ -1006,7 +1088,10 @@ class BnActFn(Function):
             dgamma = torch.empty_like(gamma) if need_g else None
             dbeta = torch.empty_like(beta) if need_b else None
             pg, pb = dgamma, dbeta
-        dx = torch.empty_like(x)
+        live = _live_images(ctx, B) if world == 1 else None
+        if live is not None and (ctx.shared.live[1] != G or skip is not None):
+            raise abi.HipExtensionError("BnActFn.backward: SharedPass.live does not match the BatchNorm groups of the pass")
+        dx = _new_grad(x, live=live)
         dskip = torch.empty_like(x) if (skip is not None and ctx.needs_input_grad[3]) else None
         dxp, pstride = None, 0
         if grad_planes:
@@ -1016,9 +1101,13 @@ class BnActFn(Function):
         if world == 1:
             ws = _ws(nws, dev)
             local = torch.empty((G, 2 * C), dtype=torch.float64, device=dev)
-            call("itcv_bn_train_bwd", ptr(x), ptr(dy), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(skip), ptr(local),
-                 ptr(dx) if write_dx else None, ptr(dskip), ptr(dxp), grad_planes, ptr(pg), ptr(pb), 1 if direct else 0, Bg,
-                 C, H, W, slope, pool, 0, ptr(ws), nws, pstride, G, stream())
+            head = (ptr(x), ptr(dy), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(skip), ptr(local),
+                    ptr(dx) if write_dx else None, ptr(dskip), ptr(dxp), grad_planes, ptr(pg), ptr(pb), 1 if direct else 0, Bg,
+                    C, H, W, slope, pool, 0, ptr(ws), nws, pstride, G)
+            if live is None:
+                call("itcv_bn_train_bwd", *head, stream())
+            else:       # dy is zero outside the live group: no dy read, no apply, no stores there (fp16: the scale still sees x)
+                call("itcv_bn_train_bwd_live", *head, ctx.shared.live[0], 1, stream())
         for g in (range(G) if world != 1 else ()):
             r = slice(g * Bg, (g + 1) * Bg)
             acc = 1 if (direct or g > 0) else 0       # the groups' parameter gradients add up
@@ -1052,6 +1141,7 @@ class LeakyReluFn(Function):
         call("itcv_lrelu_fwd", ptr(x), ptr(y), x.numel(), float(slope), stream())
         ctx.save_for_backward(x)
         ctx.slope = float(slope)
+        ctx.shared = _SHARED_PASS[0]
         return y
 
     @staticmethod
@@ -1059,6 +1149,13 @@ class LeakyReluFn(Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         dy = _f32c(dy)
+        live = _live_images(ctx, x.shape[0]) if x.dim() else None
+        if live is not None:
+            # the live rows; the dead rows get the zeros a zero dy gives: what follows (LinearFn) runs its full form
+            r = slice(live[0], live[0] + live[1])
+            dx = torch.zeros_like(x)
+            call("itcv_lrelu_bwd", ptr(x[r]), ptr(dy[r]), ptr(dx[r]), x[r].numel(), ctx.slope, stream())
+            return dx, None
         dx = torch.empty_like(x)
         call("itcv_lrelu_bwd", ptr(x), ptr(dy), ptr(dx), x.numel(), ctx.slope, stream())
         return dx, None
@@ -1071,6 +1168,7 @@ class SigmoidFn(Function):
         y = torch.empty_like(x)
         call("itcv_sigmoid_fwd", ptr(x), ptr(y), x.numel(), stream())
         ctx.save_for_backward(y)
+        ctx.shared = _SHARED_PASS[0]
         return y
 
     @staticmethod
@@ -1078,8 +1176,10 @@ class SigmoidFn(Function):
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
         dy = _f32c(dy)
-        dx = torch.empty_like(y)
-        call("itcv_sigmoid_bwd", ptr(y), ptr(dy), ptr(dx), y.numel(), stream())
+        live = _live_images(ctx, y.shape[0]) if y.dim() else None
+        dx = _new_grad(y, live=live)
+        r = slice(None) if live is None else slice(live[0], live[0] + live[1])
+        call("itcv_sigmoid_bwd", ptr(y[r]), ptr(dy[r]), ptr(dx[r]), y[r].numel(), stream())
         return dx
 
 
@@ -1090,6 +1190,7 @@ class AvgPool2Fn(Function):
         B, C, H, W = x.shape
         y = torch.empty((B, C, H // 2, W // 2), dtype=F32, device=x.device)
         call("itcv_avgpool2_fwd", ptr(x), ptr(y), B * C, H, W, stream())
+        _block_live("average pool")
         ctx.shape = (B, C, H, W)
         return y
 
@@ -1111,6 +1212,7 @@ class Upsample2Fn(Function):
         y = torch.empty((B, C, 2 * H, 2 * W), dtype=F32, device=x.device)
         call("itcv_upsample2_fwd", ptr(x), ptr(y), B * C, H, W, stream())
         ctx.shape = (B, C, H, W)
+        ctx.shared = _SHARED_PASS[0]
         return y
 
     @staticmethod
@@ -1118,8 +1220,10 @@ class Upsample2Fn(Function):
     def backward(ctx, dy):
         B, C, H, W = ctx.shape
         dy = _f32c(dy)
-        dx = torch.empty((B, C, H, W), dtype=F32, device=dy.device)
-        call("itcv_upsample2_bwd", ptr(dy), ptr(dx), B * C, H, W, stream())
+        live = _live_images(ctx, B)
+        b0, nb = live if live is not None else (0, B)
+        dx = _new_grad((B, C, H, W), dy.device, live)
+        call("itcv_upsample2_bwd", ptr(dy[b0:b0 + nb]), ptr(dx[b0:b0 + nb]), nb * C, H, W, stream())
         return dx
 
 
@@ -1129,6 +1233,7 @@ class AddFn(Function):
         a, b = _f32c(a), _f32c(b)
         out = torch.empty_like(a)
         call("itcv_add", ptr(a), ptr(b), ptr(out), a.numel(), stream())
+        _block_live("residual add")
         return out
 
     @staticmethod

@@ -40,6 +40,13 @@ class IntroSolver(VAESolver):
         # buffers are bitwise those of ``False``, the schedule with the pass issued twice (the tests compare the two).
         # A decoder with forward hooks always takes that schedule: a hook must fire once per pass of the reference.
         self.share_decoder_pass = True
+        # Phase E's backward through the shared pass: ``fake`` only feeds constants there, so the gradient of fake | rec is
+        # exactly zero in its fake half and every kernel of the walk would turn zeros into zeros.  With ``skip_dead_half``
+        # the walk covers the rec group alone (SharedPass.live) -- as the 13-pass schedule, whose model.sample(noise) has no
+        # backward.  Same bits in everything the step returns or updates.  It applies to a single-process pass whose
+        # functions all have a sub-range backward (conv arch, plane conv modes); any other pass runs the full walk, as a
+        # whole (``_shared_pass.live_blockers`` says why).  False: the launch sequence of the full walk.
+        self.skip_dead_half = True
         self._shared_pass = SharedPass()
 
     def _shares_pass(self) -> bool:
@@ -47,6 +54,9 @@ class IntroSolver(VAESolver):
 
     def _schedule_key(self) -> tuple:
         return (bool(self.batch_passes), self._shares_pass())
+
+    def _graph_key_extra(self) -> tuple:
+        return (bool(self.skip_dead_half),)
 
     def _exp_elbo(self, rec_rows: Tensor, kl_rows: Tensor) -> Tensor:
         """intro.py:102-103  mean_j exp(-2 * scale * (rec_j + kl_j))."""
@@ -99,8 +109,10 @@ class IntroSolver(VAESolver):
         # the shared pass: data gradient down to z only -- _clip() below takes its norm over the decoder's STALE gradients
         # (intro.py:113-115), one stray add into them changes norm_E and the encoder update -- and its tape survives
         shared.param_grads = False
+        # rec is group 1 of fake | rec; Sync-BN / data-parallel passes keep the full walk (their BatchNorm calls block it too)
+        shared.live = (1, 2) if (share and self.skip_dead_half and ddp.get() is None) else None
         finish_average = self._backward(loss_e, ("encoder",), defer_average=True, retain_graph=share)
-        shared.param_grads = True
+        shared.param_grads, shared.live = True, None
 
         # ================= update D (encoder frozen) ======================== intro.py:118-160
         self._set_trainable(encoder=False, decoder=True)

@@ -189,7 +189,7 @@ class VAESolver:
         # the optimiser hyper-parameters are scalar kernel arguments frozen into a captured graph: the update specs are
         # part of its key, so a scheduler or manual decay of param_groups[0]["lr"] re-captures instead of being ignored
         # the TC solvers' KL hook ("simple" | "full") selects different kernels: a switch re-captures too
-        key = (tuple(real.shape), real.dtype, self.conv_math) + specs + self._schedule_key() \
+        key = (tuple(real.shape), real.dtype, self.conv_math) + specs + self._graph_key_extra() + self._schedule_key() \
             + (getattr(self, "kl_loss", None),)
         from hipvae.functional import bump_weight_epoch
         graphs = self.__dict__.setdefault("_graphs", {})
@@ -231,6 +231,11 @@ class VAESolver:
 
     def _schedule_key(self) -> tuple:
         """What else selects the kernels of a step (part of the captured graph's key)."""
+        return ()
+
+    def _graph_key_extra(self) -> tuple:
+        """Further kernel-selecting switches of a solver; they sit behind the update specs and in front of the schedule
+        key, so the specs keep their places at the front of the graph key and the schedule key and the KL mode at its end."""
         return ()
 
     # ---- solvers/vae.py:89-136 ---------------------------------------------------------------
