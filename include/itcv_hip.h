@@ -722,6 +722,18 @@ int itcv_fill(float* x, size_t n, float value, void* stream);
 /* Input pipeline (dataset.py:219-224 transforms.RandomHorizontalFlip, moved behind the host -> device copy):
  * y[b] = x[b] mirrored along W where flip[b] != 0, else x[b]; x, y are [B][rows_per_image][W] (rows = C*H), x != y. */
 int itcv_hflip(const float* x, float* y, const unsigned char* flip, int B, int rows_per_image, int W, void* stream);
+/* Device-resident image tables (dataset.py:75-81,141-147: Image.fromarray + ToTensor of one stored uint8 image, for n
+ * images in one launch).  table is planar [num_images][rows_per_image = C*H][W] uint8; out is n dense fp32 images
+ * [n][rows_per_image][W] (the caller offsets out itself to land inside a larger buffer).
+ *   out[j][r][w] = (float)table[idx[j]][r][w'] / 255.0f,   w' = W-1-w where flip != NULL and flip[j] != 0, else w
+ * with the IEEE correctly rounded fp32 division -- torchvision's ToTensor (.float().div(255)) bit for bit; a product with
+ * 1/255.f differs from it for 126 of the 256 byte values and is not used.  An idx[j] outside [0, num_images) writes image
+ * j of out as zeros, reads nothing from the table and ORs bit 0 into flags[0] (int, device memory, cleared by the caller).
+ * Every address is formed in 64 bits (tables are several GB); one image holds fewer than 2^31 bytes.  W % 16 == 0 with
+ * table and out 16-byte aligned takes 16-byte loads and stores, every other shape a scalar form with the same results.
+ * Asynchronous on stream; allocates nothing. */
+int itcv_gather_u8(const unsigned char* table, long long num_images, int rows_per_image, int W, const long long* idx,
+                   int n, const unsigned char* flip, float* out, int* flags, void* stream);
 
 #ifdef __cplusplus
 }

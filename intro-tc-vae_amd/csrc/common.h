@@ -38,6 +38,13 @@ inline size_t align_up(size_t a, size_t b) { return cdivz(a, b) * b; }
 
 constexpr int kWave = 64;
 
+// blocks of 256 threads for a grid-stride streaming kernel over n items, `per_thread` items a thread: at most 2048
+// (8 blocks on each of the 256 CUs), the rest of the range is walked by the stride
+inline int stream_grid(size_t n, int per_thread) {
+  size_t b = cdivz(cdivz(n, per_thread), 256);
+  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
+}
+
 // ---- wave / block reductions (wave = 64 lanes) -------------------------------------------
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {

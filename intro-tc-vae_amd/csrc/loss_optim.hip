@@ -226,10 +226,6 @@ __global__ void fill_kernel(float* __restrict__ x, size_t n, float value) {
     x[i] = value;
 }
 
-static inline int stream_grid(size_t n, int per_thread) {
-  size_t b = cdivz(cdivz(n, per_thread), 256);
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
 constexpr int kSumsqBlocks = 1024;
 
 }  // namespace itcv

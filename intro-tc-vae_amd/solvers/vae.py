@@ -63,6 +63,18 @@ class VAESolver:
         self.scale = 1 / (self.model.cdim * self.model.encoder.image_size ** 2)   # solvers/vae.py:61
         self._flat = {}
 
+    def use_device_dataset(self, table=None, seed=None):
+        """Opt in to device-resident images (hipvae.dataset): build the ``DeviceImageTable`` of ``self.dataset`` (or take
+        ``table``, built earlier for the same dataset) and score through a ``DeviceFactorSampler`` on it, which draws what
+        ``FactorSampler(self.dataset, self.device, seed)`` draws and looks the images up with one kernel launch instead
+        of one ``__getitem__`` each.  Returns the table, so that the training loop can hand the same one to
+        ``hipvae.dataset.DeviceLoader``.  Without this call nothing changes."""
+        from hipvae.dataset import DeviceFactorSampler, DeviceImageTable
+        if table is None:
+            table = DeviceImageTable.from_dataset(self.dataset, self.device)
+        self.latent_generator = DeviceFactorSampler(self.dataset, self.device, seed=seed, table=table)
+        return table
+
     # ---- overridable loss hooks (solvers/vae.py:63-87) -----------------------------------
     def compute_kl_loss(self, z: Optional[Tensor], mu: Tensor, logvar: Tensor, reduce: str = "mean",
                         beta: float = None, write: bool = False) -> Tensor:
