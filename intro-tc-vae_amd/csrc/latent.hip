@@ -733,9 +733,13 @@ static int tc_fwd_impl(const float* z, const float* mu_all, const float* logvar,
   hipStream_t st = S(stream);
 #define ITCV_TC_PART(DL, V, E, W)                                                                               \
   do {                                                                                                          \
-    if (lds > 64 * 1024)                                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tc_fwd_part_kernel<DL, V, E, W>),                 \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
+    if (lds > 64 * 1024) {                                                                                      \
+      const hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(&tc_fwd_part_kernel<DL, V, E, W>), \
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
+      if (e_ != hipSuccess)                                                                                     \
+        return fail("%s: %lld bytes of LDS refused (hipFuncSetAttribute: %lld)", "itcv_tc_fwd", (long long)lds,  \
+                    (long long)e_);                                                                             \
+    }                                                                                                           \
     hipLaunchKernelGGL((tc_fwd_part_kernel<DL, V, E, W>), grid, block, lds, st, z, mu_all, logvar, pmax, psum,   \
                        sjoint, Bt, row_offset, D, nch, c, ldm, ivar);                                           \
   } while (0)

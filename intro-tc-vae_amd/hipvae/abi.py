@@ -290,7 +290,7 @@ def ptr(t):
 
 
 def call(name, *args):
-    check(getattr(lib, name)(*args))
+    check(getattr(lib, name)(*args), HipExtensionError)
 
 
 def bn_plan_query(bwd, B, C, H, W, pool=0, up2=0, groups=1, planes=True, ns=2, ws_bytes=None, tile_stats=False):
