@@ -734,6 +734,25 @@ int itcv_hflip(const float* x, float* y, const unsigned char* flip, int B, int r
  * Asynchronous on stream; allocates nothing. */
 int itcv_gather_u8(const unsigned char* table, long long num_images, int rows_per_image, int W, const long long* idx,
                    int n, const unsigned char* flip, float* out, int* flags, void* stream);
+/* Pillow's 8-bit bicubic resize (dataset.py:78-79,144-145 and load_image: Image.resize(..., Image.BICUBIC) per sample)
+ * of n images of a planar uint8 table [num_images][planes][Hin][Win], bit for bit.  idx as in itcv_gather_u8, or NULL
+ * for images 0..n-1 (n <= num_images).  out is planar [n][planes][Hout][Wout]: uint8, or fp32 byte / 255.0f (correctly
+ * rounded, as itcv_gather_u8) when out_is_f32; image j is written with its columns reversed where flip != NULL and
+ * flip[j] != 0 (the resize of the unmirrored source, mirrored afterwards).
+ * An axis is described by its plan, made on the host in fp64 as Pillow makes it (hipvae/resize.py bicubic_plan):
+ * bounds [out][2] = {first source index, tap count <= k}, coef [out][k] int32 in units of 2^-22, in device memory.  One
+ * pass computes  clamp((2^21 + sum_t src[first + t] * coef[t]) >> 22, 0, 255)  in int32 (arithmetic shift); the
+ * horizontal pass runs first and rounds to uint8, the vertical pass runs on its result.  An axis whose size does not
+ * change has NULL bounds and coef (k ignored) and gets no pass -- Pillow skips it too.  Both NULL is a copy and is
+ * legal for uint8 output only (the fp32 form of that is itcv_gather_u8).  sum |coef| of a row must stay below
+ * (2^31 - 2^21) / 255 (the plan builder checks it), so int32 cannot overflow.
+ * An idx[j] outside [0, num_images) writes image j as zeros and ORs bit 0 into flags[0], as itcv_gather_u8 does; a plan
+ * whose row windows do not fit the image ORs bit 1, reads nothing and writes zeros.  Window starts and counts are
+ * clamped to the source row, so no plan makes the kernel read outside the table.
+ * Asynchronous on stream; allocates nothing. */
+int itcv_resize_u8(const unsigned char* table, long long num_images, int planes, int Hin, int Win, const long long* idx,
+                   int n, const unsigned char* flip, const int* xbounds, const int* xcoef, int kx, const int* ybounds,
+                   const int* ycoef, int ky, int Hout, int Wout, void* out, int out_is_f32, int* flags, void* stream);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,7 @@ SIGNATURES = {
     "itcv_fill": (i32, [p, sz, f32, p]),
     "itcv_hflip": (i32, [p, p, p, i32, i32, i32, p]),
     "itcv_gather_u8": (i32, [p, i64, i32, i32, p, i32, p, p, p, p]),
+    "itcv_resize_u8": (i32, [p, i64, i32, i32, i32, p, i32, p, p, p, i32, p, p, i32, i32, i32, p, i32, p, p]),
 }
 
 TC_VAR_FROM_ROW, TC_EPS_DENSITY, TC_WEIGHTED = 1, 2, 4

@@ -13,22 +13,41 @@ Both tables fit in HBM many times over.  Here
     same factors, same observations, so every ``compute_*`` score runs on it unchanged;
   * ``DeviceLoader`` feeds training from the table: one gather (+ flips) and one label ``index_select`` per batch.
 
-Everything is opt-in (``VAESolver.use_device_dataset``); nothing here is used unless asked for.  Datasets that resize
-(``resize != H``: PIL's bicubic filter) or decode files (UkiyoE) stay on the host path.
+Datasets that resize (``resize != H``: ``Image.resize(..., Image.BICUBIC)`` per sample, dataset.py:78-79,144-145,335) run
+that resize on the device too, bit for bit (``itcv_resize_u8``, csrc/resize.hip, with the plans of hipvae/resize.py):
+either once, into a second table (``resized``), or inside every lookup (``view_resized``, when the resized table would not
+fit).  ``from_dataset(..., device_resize="table" | "gather" | "auto")`` chooses; without the keyword such a dataset is
+refused as before.  Decoding image files (UkiyoE's JPEGs) stays a host job, done once per table
+(``from_image_files``).
+
+Everything is opt-in (``VAESolver.use_device_dataset``); nothing here is used unless asked for.
 """
+import os
+
 import numpy as np
 import torch
 
 from . import abi
 from .disentangle import FactorSampler
+from .resize import ResizePlan
 
-__all__ = ["DeviceImageTable", "DeviceFactorSampler", "DeviceLoader"]
+__all__ = ["DeviceImageTable", "ResizedView", "DeviceFactorSampler", "DeviceLoader"]
 
 UPLOAD_CHUNK_BYTES = 256 << 20
+RESIZE_MODES = (None, "table", "gather", "auto")
+FILE_INPUT_HEIGHT = 256         # UkiyoE.__getitem__ (dataset.py:232-238): load_image(..., input_height=256, ...)
 
 
 def _device(device):
     return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _size_pair(size):
+    """``(Hout, Wout)`` of a ``size`` given as one int (square, as the reference's ``resize``) or as a pair."""
+    pair = tuple(size) if isinstance(size, (tuple, list)) else (size, size)
+    if len(pair) != 2 or not all(isinstance(v, (int, np.integer)) and v >= 1 for v in pair):
+        raise ValueError(f"resize: the size must be a positive int or a pair of them, got {size!r}")
+    return int(pair[0]), int(pair[1])
 
 
 class DeviceImageTable:
@@ -92,26 +111,117 @@ class DeviceImageTable:
         return images_u8
 
     @classmethod
-    def from_dataset(cls, ds, device=None):
+    def from_dataset(cls, ds, device=None, device_resize=None):
         """The table of a reference factor dataset (dataset.py:40-201): ``ds.imgs`` exactly as the class stored it -- the
         ``* 255`` of its constructor included, which wraps modulo 256 on uint8 -- and ``ds.latents_values`` as labels.
         Refuses, before touching the device, what ``__getitem__`` would not turn into ``imgs[i] / 255``: images that are
-        not uint8 (``TypeError``) and a ``resize`` other than the stored height (``NotImplementedError``: the bicubic
-        resize stays on the host path)."""
-        imgs = np.asarray(ds.imgs)
-        if imgs.dtype != np.uint8:
-            raise TypeError(f"from_dataset: {type(ds).__name__}.imgs is {imgs.dtype}, not uint8")
-        imgs = cls._check_arrays(imgs)
+        not uint8 (``TypeError``) and, unless ``device_resize`` opts in, a ``resize`` other than the stored height
+        (``NotImplementedError``).
+
+        ``device_resize`` -- how a dataset that resizes is served: ``"table"`` resizes the whole table once on the device
+        (``resized``), ``"gather"`` keeps the stored size and resizes inside every lookup (``view_resized``), ``"auto"``
+        takes the table when it fits in free device memory next to the source table and the view otherwise; anything
+        else is a ``ValueError``.  With it, a file-backed dataset (``root``, ``entries`` of (file name, label code) and
+        ``resize``, no ``imgs``: UkiyoE) is accepted too: its files are decoded once on the host (``from_image_files``)
+        and its label codes become the label table."""
+        if device_resize not in RESIZE_MODES:
+            raise ValueError(f"from_dataset: device_resize must be one of {RESIZE_MODES}, got {device_resize!r}")
         resize = getattr(ds, "resize", None)
-        if resize is not None and int(resize) != imgs.shape[1]:
-            raise NotImplementedError(f"from_dataset: resize={resize} differs from the stored height {imgs.shape[1]}; "
-                                      "resized datasets stay on the host path")
-        table = cls.from_arrays(imgs, getattr(ds, "latents_values", None), device)
+        if not hasattr(ds, "imgs") and all(hasattr(ds, a) for a in ("root", "entries", "resize")):
+            if device_resize is None:
+                raise NotImplementedError("from_dataset: a dataset that decodes files needs device_resize= (the files are "
+                                          "then decoded once, on the host)")
+            entries = list(ds.entries)
+            table = cls.from_image_files([os.path.join(ds.root, e[0]) for e in entries],
+                                         np.array([e[1] for e in entries]), FILE_INPUT_HEIGHT, None, device)
+        else:
+            imgs = np.asarray(ds.imgs)
+            if imgs.dtype != np.uint8:
+                raise TypeError(f"from_dataset: {type(ds).__name__}.imgs is {imgs.dtype}, not uint8")
+            imgs = cls._check_arrays(imgs)
+            if resize is not None and int(resize) != imgs.shape[1] and device_resize is None:
+                raise NotImplementedError(f"from_dataset: resize={resize} differs from the stored height "
+                                          f"{imgs.shape[1]}; pass device_resize= to resize on the device")
+            table = cls.from_arrays(imgs, getattr(ds, "latents_values", None), device)
         try:        # the base class's properties raise NotImplementedError; a plain image dataset has neither
             table.factor_sizes, table.latent_indices = list(ds.factor_sizes), list(ds.latent_indices)
         except (AttributeError, NotImplementedError):
             table.factor_sizes = table.latent_indices = None
-        return table
+        if device_resize is None or resize is None or (int(resize), int(resize)) == table.image_shape[1:]:
+            return table
+        if device_resize == "gather":
+            return table.view_resized(int(resize))
+        try:
+            return table.resized(int(resize))
+        except MemoryError:
+            if device_resize != "auto":
+                raise
+            return table.view_resized(int(resize))
+
+    @staticmethod
+    def decode_image_files(paths, input_height=FILE_INPUT_HEIGHT):
+        """The host half of ``from_image_files``: uint8 ``[N, input_height, input_height, 3]``, every file decoded once
+        as ``load_image`` (dataset.py:310-320) does before its last line: ``Image.open``, ``convert("RGB")`` unless
+        already RGB, ``resize((input_height, input_height), Image.BICUBIC)`` (which returns a same-size image
+        unchanged)."""
+        from PIL import Image
+        paths = list(paths)
+        if not paths:
+            raise ValueError("decode_image_files: no files")
+        out = np.empty((len(paths), input_height, input_height, 3), dtype=np.uint8)
+        for i, path in enumerate(paths):
+            with Image.open(path) as img:
+                if img.mode != "RGB":
+                    img = img.convert("RGB")
+                out[i] = np.asarray(img.resize((input_height, input_height), Image.BICUBIC))
+        return out
+
+    @classmethod
+    def from_image_files(cls, paths, labels=None, input_height=FILE_INPUT_HEIGHT, resize=None, device=None):
+        """The table of a dataset of image files (UkiyoE, dataset.py:207-240): ``decode_image_files`` on the host, one
+        upload of the ``[N, 3, input_height, input_height]`` table, and ``load_image``'s last line -- the resize to
+        ``resize`` -- on the device (``resized``) when it changes the size.  ``DeviceLoader(table, B, flip_p=0.5)`` is then
+        the dataset's ``RandomHorizontalFlip`` (resize first, mirror after, as the reference)."""
+        table = cls.from_arrays(cls.decode_image_files(paths, input_height), labels, device)
+        return table if resize is None else table.resized(resize)
+
+    # ---- resize ------------------------------------------------------------------------------------------------------
+    def _carry(self, other):
+        other.label_table, other.factor_sizes, other.latent_indices = self.label_table, self.factor_sizes, self.latent_indices
+        return other
+
+    def resized(self, size):
+        """A new materialised uint8 table ``[N, C, Hout, Wout]``: every image through Pillow's bicubic resize, bit for bit
+        (``itcv_resize_u8``, in chunks of at most 256 MiB of output); labels and factor structure are carried over.
+        ``size``: an int (square) or ``(Hout, Wout)``; the table itself when nothing changes.  Raises ``MemoryError`` when
+        the device does not have the room."""
+        Hout, Wout = _size_pair(size)
+        C, H, W = self.image_shape
+        if (Hout, Wout) == (H, W):
+            return self
+        N, per_image = self.num_images, C * Hout * Wout
+        free, _ = torch.cuda.mem_get_info(self.device)
+        if N * per_image > free:
+            raise MemoryError(f"DeviceImageTable: the resized table needs {N * per_image} bytes of device memory, "
+                              f"{free} are free")
+        plan = ResizePlan.get(H, W, Hout, Wout, self.device)
+        out = torch.empty((N, C, Hout, Wout), dtype=torch.uint8, device=self.device)
+        flags = torch.zeros(1, dtype=torch.int32, device=self.device)
+        rows = max(1, min(N, UPLOAD_CHUNK_BYTES // per_image))
+        for a in range(0, N, rows):
+            n = min(rows, N - a)
+            plan.launch(self.images[a:a + n], n, C, None, n, None, out[a:a + n], flags)
+        if flags.item():
+            raise RuntimeError(f"resized: the {H}x{W} -> {Hout}x{Wout} plan was refused by the kernel")
+        return self._carry(DeviceImageTable(out))
+
+    def view_resized(self, size):
+        """A table object over the SAME ``images`` whose ``image_shape`` is ``(C, Hout, Wout)`` and whose ``gather``
+        resizes inside the lookup: what ``resized(size).gather`` returns, bit for bit, without the second table."""
+        Hout, Wout = _size_pair(size)
+        if (Hout, Wout) == self.image_shape[1:]:
+            return self
+        return self._carry(ResizedView(self, Hout, Wout))
 
     # ---- lookup ------------------------------------------------------------------------------------------------------
     def _index(self, idx):
@@ -151,17 +261,23 @@ class DeviceImageTable:
                 raise ValueError("gather: one flip flag per index")
         if self._flags is None:
             self._flags = torch.zeros(1, dtype=torch.int32, device=self.device)
-        C, H, W = self.image_shape
-        abi.call("itcv_gather_u8", abi.ptr(self.images), self.num_images, C * H, W, abi.ptr(idx), n, abi.ptr(flip),
-                 abi.ptr(out), self._flags.data_ptr(), abi.stream())
+        self._launch_gather(idx, n, flip, out)
         if check and not from_host:
             self.check()
         return out
 
+    def _launch_gather(self, idx, n, flip, out):
+        C, H, W = self.image_shape
+        abi.call("itcv_gather_u8", abi.ptr(self.images), self.num_images, C * H, W, abi.ptr(idx), n, abi.ptr(flip),
+                 abi.ptr(out), self._flags.data_ptr(), abi.stream())
+
     def check(self):
         """Read the out-of-range flag of the gathers since the last check (one synchronisation); raises ``IndexError``."""
-        if self._flags is not None and self._flags.item():
+        bits = self._flags.item() if self._flags is not None else 0
+        if bits:
             self._flags.zero_()
+            if bits & 2:
+                raise RuntimeError("a resize plan was refused by the kernel; the images were returned as zeros")
             raise IndexError(f"a device index was outside [0, {self.num_images}); its image was returned as zeros")
 
     def labels(self, idx):
@@ -171,19 +287,45 @@ class DeviceImageTable:
         return self.label_table.index_select(0, self._index(idx)[0])
 
 
+class ResizedView(DeviceImageTable):
+    """``DeviceImageTable.view_resized``: the source table's ``images`` under the resized ``image_shape``.  Everything a
+    sampler or a loader uses (``gather``, ``labels``, ``check``, ``image_shape``, ``num_images``, ``label_table``,
+    ``device``) behaves as on the materialised table; ``gather`` is the fused form of ``itcv_resize_u8``."""
+
+    def __init__(self, source, Hout, Wout):
+        self.images, self.num_images, self.device = source.images, source.num_images, source.device
+        self.source_shape = source.image_shape
+        self.image_shape = (source.image_shape[0], Hout, Wout)
+        self.label_table = self.factor_sizes = self.latent_indices = None
+        self._flags = None
+        self._plan = None
+
+    def _launch_gather(self, idx, n, flip, out):
+        C, H, W = self.source_shape
+        if self._plan is None:
+            self._plan = ResizePlan.get(H, W, self.image_shape[1], self.image_shape[2], self.device)
+        self._plan.launch(self.images, self.num_images, C, idx, n, flip, out, self._flags)
+
+    def resized(self, size):
+        raise ValueError("a resized view is not resized again: resize the source table")
+
+    view_resized = resized
+
+
 class DeviceFactorSampler(FactorSampler):
     """``FactorSampler`` whose observations come from a ``DeviceImageTable``: ``indices_from_factors`` (numpy, the same
     ``RandomState`` draws in the same order), one small host-to-device index copy, one gather.  With equal seeds it
     returns exactly ``FactorSampler``'s factors and observations.  ``dataset_or_table``: a dataset (its table is built
-    with ``from_dataset`` unless ``table`` is given) or a table that carries ``factor_sizes`` / ``latent_indices``."""
+    with ``from_dataset(..., device_resize=device_resize)`` unless ``table`` is given) or a table that carries
+    ``factor_sizes`` / ``latent_indices``."""
 
-    def __init__(self, dataset_or_table, device, seed=None, table=None):
+    def __init__(self, dataset_or_table, device, seed=None, table=None, device_resize=None):
         if isinstance(dataset_or_table, DeviceImageTable):
             table = dataset_or_table
             if table.factor_sizes is None:
                 raise ValueError("DeviceFactorSampler: the table carries no factor_sizes / latent_indices")
         elif table is None:
-            table = DeviceImageTable.from_dataset(dataset_or_table, device)
+            table = DeviceImageTable.from_dataset(dataset_or_table, device, device_resize=device_resize)
         super().__init__(dataset_or_table, device, seed)
         total = int(np.prod(self.factor_sizes, dtype=np.int64))
         if total != table.num_images:

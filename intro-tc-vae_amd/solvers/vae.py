@@ -63,15 +63,16 @@ class VAESolver:
         self.scale = 1 / (self.model.cdim * self.model.encoder.image_size ** 2)   # solvers/vae.py:61
         self._flat = {}
 
-    def use_device_dataset(self, table=None, seed=None):
+    def use_device_dataset(self, table=None, seed=None, device_resize=None):
         """Opt in to device-resident images (hipvae.dataset): build the ``DeviceImageTable`` of ``self.dataset`` (or take
         ``table``, built earlier for the same dataset) and score through a ``DeviceFactorSampler`` on it, which draws what
         ``FactorSampler(self.dataset, self.device, seed)`` draws and looks the images up with one kernel launch instead
         of one ``__getitem__`` each.  Returns the table, so that the training loop can hand the same one to
-        ``hipvae.dataset.DeviceLoader``.  Without this call nothing changes."""
+        ``hipvae.dataset.DeviceLoader``.  ``device_resize`` ("table", "gather" or "auto") lets a dataset that resizes its
+        images do so on the device (``DeviceImageTable.from_dataset``).  Without this call nothing changes."""
         from hipvae.dataset import DeviceFactorSampler, DeviceImageTable
         if table is None:
-            table = DeviceImageTable.from_dataset(self.dataset, self.device)
+            table = DeviceImageTable.from_dataset(self.dataset, self.device, device_resize=device_resize)
         self.latent_generator = DeviceFactorSampler(self.dataset, self.device, seed=seed, table=table)
         return table
 
