@@ -24,11 +24,12 @@ __device__ __forceinline__ float rec_derr(float r, float t) {
   return (r - t) / fmaxf((1.f - r) * r, 1e-12f);  // ATen binary_cross_entropy_backward
 }
 
-// grid (B, splits): partial[b][s] = sum over the slice of row b
+// grid (B, splits): partial[b][s] = sum over the slice of row b; vec4: every row of both operands starts on a 16-byte
+// boundary (P % 4 == 0 and aligned bases, decided by launch_recon_partial), so the slices can be read as float4
 template <int LT>
 __global__ __launch_bounds__(256) void recon_partial_kernel(const float* __restrict__ x,
                                                            const float* __restrict__ recon,
-                                                           double* __restrict__ part, size_t P, int splits) {
+                                                           double* __restrict__ part, size_t P, int splits, int vec4) {
   __shared__ double scratch[4];
   const int b = blockIdx.x, s = blockIdx.y;
   const size_t chunk = ((P + splits - 1) / splits + 3) & ~(size_t)3;
@@ -36,7 +37,7 @@ __global__ __launch_bounds__(256) void recon_partial_kernel(const float* __restr
   const float* xr = x + (size_t)b * P;
   const float* rr = recon + (size_t)b * P;
   double acc = 0.0;
-  if ((P & 3) == 0) {
+  if (vec4) {
     for (size_t i = beg + (size_t)threadIdx.x * 4; i < end; i += 1024) {
       const float4 t = *reinterpret_cast<const float4*>(xr + i);
       const float4 r = *reinterpret_cast<const float4*>(rr + i);
@@ -133,6 +134,23 @@ static inline int recon_splits(int B, size_t P) {
   const size_t maxs = cdivz(P, 2048);
   if ((size_t)s > maxs) s = (int)maxs;
   return s < 1 ? 1 : s;
+}
+// the one launch of recon_partial_kernel; false: unknown loss type.  float4 reads only where every row of both operands
+// is 16-byte aligned: a view that starts inside its storage takes the scalar path (like itcv_sumsq / itcv_scale_by_dev,
+// which refuse such a pointer, but here there is a path to fall to)
+static bool launch_recon_partial(const float* x, const float* recon, double* part, int B, size_t P, int splits,
+                                 int loss_type, hipStream_t st) {
+  const int vec4 = (P & 3) == 0 && (((uintptr_t)x | (uintptr_t)recon) & 15) == 0;
+  dim3 grid(B, splits);
+  if (loss_type == ITCV_LOSS_MSE)
+    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_MSE>, grid, dim3(256), 0, st, x, recon, part, P, splits, vec4);
+  else if (loss_type == ITCV_LOSS_L1)
+    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_L1>, grid, dim3(256), 0, st, x, recon, part, P, splits, vec4);
+  else if (loss_type == ITCV_LOSS_BCE)
+    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_BCE>, grid, dim3(256), 0, st, x, recon, part, P, splits, vec4);
+  else
+    return false;
+  return true;
 }
 
 // ---- optimiser ---------------------------------------------------------------------------
@@ -244,15 +262,8 @@ int itcv_recon_rows_fwd(const float* x, const float* recon, float* rows, int B, 
   const int splits = recon_splits(B, P);
   ITCV_REQUIRE(ws && ws_bytes >= (size_t)B * splits * sizeof(double), "itcv_recon_rows_fwd(workspace)");
   double* part = static_cast<double*>(ws);
-  dim3 grid(B, splits);
   hipStream_t st = S(stream);
-  if (loss_type == ITCV_LOSS_MSE)
-    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_MSE>, grid, dim3(256), 0, st, x, recon, part, P, splits);
-  else if (loss_type == ITCV_LOSS_L1)
-    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_L1>, grid, dim3(256), 0, st, x, recon, part, P, splits);
-  else if (loss_type == ITCV_LOSS_BCE)
-    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_BCE>, grid, dim3(256), 0, st, x, recon, part, P, splits);
-  else
+  if (!launch_recon_partial(x, recon, part, B, P, splits, loss_type, st))
     return fail("%s: unknown loss type %lld", "itcv_recon_rows_fwd", loss_type);
   ITCV_CHECK_LAUNCH("itcv_recon_rows_fwd");
   hipLaunchKernelGGL(recon_combine_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, part, rows, B, splits);
@@ -284,15 +295,8 @@ int itcv_recon_loss_fwd(const float* x, const float* recon, float* out, int B, s
   const int splits = recon_splits(B, P);
   ITCV_REQUIRE(ws && ws_bytes >= (size_t)B * splits * sizeof(double), "itcv_recon_loss_fwd(workspace)");
   double* part = static_cast<double*>(ws);
-  dim3 grid(B, splits);
   hipStream_t st = S(stream);
-  if (loss_type == ITCV_LOSS_MSE)
-    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_MSE>, grid, dim3(256), 0, st, x, recon, part, P, splits);
-  else if (loss_type == ITCV_LOSS_L1)
-    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_L1>, grid, dim3(256), 0, st, x, recon, part, P, splits);
-  else if (loss_type == ITCV_LOSS_BCE)
-    hipLaunchKernelGGL(recon_partial_kernel<ITCV_LOSS_BCE>, grid, dim3(256), 0, st, x, recon, part, P, splits);
-  else
+  if (!launch_recon_partial(x, recon, part, B, P, splits, loss_type, st))
     return fail("%s: unknown loss type %lld", "itcv_recon_loss_fwd", loss_type);
   ITCV_CHECK_LAUNCH("itcv_recon_loss_fwd");
   hipLaunchKernelGGL(recon_finish_kernel, dim3(1), dim3(256), 0, st, part, out, B, splits, reduction, scale);
