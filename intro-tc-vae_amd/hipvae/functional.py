@@ -8,7 +8,11 @@ into Sync-BN (all-reduce of the fp64 channel moments over RCCL) for data-paralle
 with the full-batch reference.
 """
 import contextlib
+import ctypes
+import functools
+import os
 import weakref
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -171,16 +175,18 @@ def _new_grad(like_or_shape, device=None, live=None):
     return t
 
 
-def _dgrad_sub_kind(Co, Ci, KS):
-    """How the data gradient of a Ci -> Co conv runs on an image sub-range in the current mode: 'planes' (the planes GEMM
-    with the whole batch's plan, itcv_conv2d_fwd_bf16p_sub), 'small' (the per-image 5x5 kernels: a contiguous batch slice),
-    or None (fp32 / in-kernel-split GEMMs: their K split follows the launched batch)."""
-    ns = _planes_ns(Co, Ci, KS, False)
-    if ns:
-        return None if (_two(ns) and lib.itcv_conv2d_small_cout_bf16p_supported(Co, Ci, KS)) else "planes"
-    if lib.itcv_conv2d_small_cout_supported(Ci, KS):
-        return None
-    return "small" if lib.itcv_conv2d_small_cin_supported(Co, KS) else None
+def _desc_table(entry, desc_bytes, items, fill, device):
+    """Device-resident descriptor table of a table-driven launch -> (uint8 device tensor, len(items), total blocks).
+    ``fill(slot, item, blocks)`` writes one descriptor through the library's ``entry`` and returns the blocks it
+    adds behind the ``blocks`` of the ones before it (<= 0: the library refused; its message is raised)."""
+    host = (ctypes.c_uint8 * (desc_bytes * len(items)))()
+    blocks = 0
+    for i, item in enumerate(items):
+        got = fill(ctypes.byref(host, i * desc_bytes), item, blocks)
+        if got <= 0:
+            raise abi.HipExtensionError(entry + ": " + abi.last_error())
+        blocks += got
+    return torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device), len(items), blocks
 
 
 def replay_bn_running(records, tables=None):
@@ -189,7 +195,6 @@ def replay_bn_running(records, tables=None):
     forward over the same batch would: ONE launch (itcv_bn_replay_many).  ``tables``: dict that keeps the device tables
     alive, one per sequence of pointers; the caller owns it for as long as a captured graph may replay the launch.
     Without it the table lives for this (eager, stream-ordered) launch only."""
-    import ctypes
     if tables is None:
         tables = {}
     recs = [r for r in records if r[0] is not None or r[1] is not None or r[2] is not None]
@@ -202,21 +207,15 @@ def replay_bn_running(records, tables=None):
     if tab is None:
         if len(recs) > lib.itcv_bn_replay_max_descs():
             raise abi.HipExtensionError("replay_bn_running: more BatchNorm layers than one table holds")
-        nb = lib.itcv_bn_replay_desc_bytes()
-        host = (ctypes.c_uint8 * (nb * len(recs)))()
-        blocks = 0
-        for i, (rm, rv, nbt, mean, uvar, momentum) in enumerate(recs):
-            G, C = mean.shape
-            got = lib.itcv_bn_replay_desc(ctypes.byref(host, i * nb), ptr(rm), ptr(rv), ptr(nbt), ptr(mean), ptr(uvar), C, G,
-                                          float(momentum), blocks)
-            if got <= 0:
-                raise abi.HipExtensionError("itcv_bn_replay_desc: " + abi.last_error())
-            blocks += got
-        # the records keep the tensors the table points at alive with the table
-        tab = tables[key] = (torch.frombuffer(bytearray(host), dtype=torch.uint8).to(recs[0][3].device), len(recs), blocks,
-                             recs)
-    call("itcv_bn_replay_many", ptr(tab[0]), tab[1], tab[2], stream())
+        def fill(slot, rec, blocks):
+            rm, rv, nbt, mean, uvar, momentum = rec
+            return lib.itcv_bn_replay_desc(slot, ptr(rm), ptr(rv), ptr(nbt), ptr(mean), ptr(uvar), mean.shape[1], mean.shape[0],
+                                           float(momentum), blocks)
 
+        # the records keep the tensors the table points at alive with the table
+        tab = tables[key] = _desc_table("itcv_bn_replay_desc", lib.itcv_bn_replay_desc_bytes(), recs, fill,
+                                        recs[0][3].device) + (recs,)
+    call("itcv_bn_replay_many", ptr(tab[0]), tab[1], tab[2], stream())
 
 
 # (Round 1 issued the weight-gradient GEMMs on a second HIP stream; with the batched passes of round 2 they fill the chip
@@ -245,9 +244,7 @@ def bump_weight_epoch(params=None):
 # conv arithmetic -> plane format code of the C ABI (include/itcv_hip.h): 2 / 3 bf16 planes, 4 = two fp16 planes + scale
 _NS = {"fp32": 0, "bf16x3": 2, "bf16x6": 3, "f16x3": 4}
 F16X2 = 4
-import os as _os
-
-_CONV_MATH = [_os.environ.get("ITCV_CONV_MATH", "fp32")]   # the one documented environment override (with ITCV_DDP_GRAPH, ITCV_LIB)
+_CONV_MATH = [os.environ.get("ITCV_CONV_MATH", "fp32")]   # the one documented environment override (with ITCV_DDP_GRAPH, ITCV_LIB)
 assert _CONV_MATH[0] in _NS, "ITCV_CONV_MATH must be one of fp32 / bf16x3 / bf16x6 / f16x3"
 
 
@@ -256,10 +253,10 @@ def _two(ns):
     return ns in (2, F16X2)
 
 
-# Module switches used by the test matrix (never read from the environment):
-_SMALL_PLANES = [True]   # matrix-core form of the 3-output 5x5 convs (tests compare it with the direct fp32 kernels)
-_POISON = [False]        # fill planes-only tensors with NaN (tests: nothing may read an fp32 tensor that was not written)
-_PLANES = [True]         # split-bf16 convs take pre-split operands (tests: planes kernels == gather kernels, bit for bit)
+# Module switch of the test matrix (never read from the environment): fill planes-only tensors with NaN (nothing may read
+# an fp32 tensor that was not written).  The gather kernels the planes kernels are compared with, bit for bit, are
+# reached by calling conv_apply / conv_wgrad_raw directly.
+_POISON = [False]
 
 
 def set_conv_math(mode):
@@ -369,20 +366,11 @@ class _PackGroup:
 
     @staticmethod
     def _build(mem, for_dgrad, ns, device):
-        import ctypes
-
-        nb = lib.itcv_pack_desc_bytes()
-        host = (ctypes.c_uint8 * (nb * len(mem)))()
-        blocks = 0
-        for i, r in enumerate(mem.values()):
+        def fill(slot, r, blocks):
             co, ci, ks = r[1]
-            got = lib.itcv_conv2d_pack_desc_bf16s(ctypes.byref(host, i * nb), r[2], ptr(r[3]), co, ci, ks, int(for_dgrad), ns,
-                                                  blocks)
-            if got <= 0:
-                raise abi.HipExtensionError("itcv_conv2d_pack_desc_bf16s: " + abi.last_error())
-            blocks += got
-        dev_table = torch.frombuffer(bytearray(host), dtype=torch.uint8).to(device)
-        return dev_table, len(mem), blocks
+            return lib.itcv_conv2d_pack_desc_bf16s(slot, r[2], ptr(r[3]), co, ci, ks, int(for_dgrad), ns, blocks)
+
+        return _desc_table("itcv_conv2d_pack_desc_bf16s", lib.itcv_pack_desc_bytes(), list(mem.values()), fill, device)
 
 
 def register_pack_group(params):
@@ -409,43 +397,126 @@ def pack_weight_bf16s(w4, for_dgrad, ns):
 _SCIN_MFMA = [True]
 
 
-def conv_apply(x, weight, w4, for_dgrad, bias, B, Ci, H, W, Co, KS, up2, out=None):
-    """Forward-type conv GEMM (forward, or data-gradient with the roles of Ci/Co swapped by the caller)
-    on the kernel selected by set_conv_math().  ``out`` (per-image <= 4-reduction-channel kernels only): write there."""
-    if out is not None and (up2 or lib.itcv_conv2d_small_cout_supported(Co, KS) or not lib.itcv_conv2d_small_cin_supported(Ci, KS)):
-        raise abi.HipExtensionError("conv_apply: an output tensor is taken by the small-cin kernels only")
+# ---- conv routing: which kernels a conv's three GEMMs run, and in which form they read their operands ----------------
+@functools.lru_cache(maxsize=None)
+def _gemm_kernels(Ci, Co, KS, W, up2, fmt, scin):
+    """(kernel on pre-split planes or None, kernel on the fp32 tensor) of a forward-type conv GEMM Ci -> Co (a forward, or
+    a data gradient with Ci / Co exchanged) in plane format ``fmt`` (0: exact fp32).  Planes are read where a planes kernel
+    exists; the second name is what conv_apply runs when it is handed the fp32 tensor."""
     if not up2 and lib.itcv_conv2d_small_cout_supported(Co, KS):
-        # <= 4 output channels: direct fp32 conv on the vector ALUs, reads the raw OIHW weights
-        y = torch.empty((B, Co, H, W), dtype=F32, device=x.device)
+        direct = "small_cout"        # <= 4 output channels: direct fp32 conv on the vector ALUs, raw OIHW weights
+    elif not up2 and lib.itcv_conv2d_small_cin_supported(Ci, KS):
+        # <= 4 reduction channels: the pixel's input window lives in registers; two-plane modes: on the matrix cores
+        mfma = scin and _two(fmt) and lib.itcv_conv2d_small_cin_bf16x3_supported(Ci, Co, KS, W)
+        direct = "small_cin_mfma" if mfma else "small_cin"
+    elif fmt in (2, 3) and lib.itcv_conv2d_bf16s_supported(Ci, Co, KS):
+        direct = "split"             # gather GEMM that splits its operands in the kernel
+    else:
+        direct = "fp32"
+    if not up2 and _two(fmt) and lib.itcv_conv2d_small_cout_bf16p_supported(Ci, Co, KS):
+        return "small_cout_planes", direct      # the 5x5 predict conv / stem data-gradient on the matrix cores
+    if fmt and direct in ("split", "fp32") and lib.itcv_conv2d_bf16s_supported(Ci, Co, KS):
+        return "planes", direct
+    return None, direct
 
+
+class ConvRoute(NamedTuple):
+    """Everything the host decides for one conv call (stride 1, 'same' padding) in one arithmetic mode.  Kernel names:
+    'planes' (LDS-DMA GEMM on pre-split planes), 'small_cout_planes' (5x5, <= 3 outputs, matrix cores), 'small_cout' /
+    'small_cin' (direct fp32), 'small_cin_mfma', 'split' (in-kernel-split gather GEMM), 'fp32' (exact fp32 GEMM)."""
+    fwd: str                                # kernel of the forward
+    fwd_ns: int                             # plane format in which it reads x (0: reads fp32)
+    fwd_fp32: str                           # kernel conv_apply runs on an fp32 x (tests compare it with the planes kernel)
+    dgrad: str                              # the same three facts for the data gradient (the Co -> Ci conv on dy)
+    dgrad_ns: int
+    dgrad_fp32: str
+    dgrad_sub: Optional[str]                # its image sub-range form (SharedPass.live): 'planes' (the whole batch's plan,
+                                            # itcv_conv2d_fwd_bf16p_sub), 'small' (per-image 5x5 kernels on a batch slice),
+                                            # None (fp32 / in-kernel-split GEMMs: their K split follows the launched batch)
+    wgrad: str                              # 'planes' | 'stem' | 'predict' (5x5 with a <= 3-channel side) | 'raw'
+    keep_xp: bool                           # forward saves x's planes instead of fp32 x
+    in_mode: Tuple[int, bool]               # (ns, fp32_needed) for the producer of x ...
+    grad_mode: Tuple[int, bool]             # ... and of the output gradient
+    in_mode_keep_fp32: Tuple[int, bool]     # the same formats where something else reads the fp32 tensor as well
+    grad_mode_keep_fp32: Tuple[int, bool]   # (skip paths of the residual block, the encoder stem)
+
+
+@functools.lru_cache(maxsize=None)
+def _build_route(B, Ci, H, W, Co, KS, up2, has_bias, needs_input_grad, math, scin):
+    fmt = _NS[math]
+    fwd_p, fwd_d = _gemm_kernels(Ci, Co, KS, W, up2, fmt, scin)
+    dg_p, dg_d = _gemm_kernels(Co, Ci, KS, W, False, fmt, scin)
+    fwd_ns, dgrad_ns = (fmt if fwd_p else 0), (fmt if dg_p else 0)
+    if dg_p:
+        sub = "planes" if dg_p == "planes" else None
+    else:
+        sub = "small" if dg_d in ("small_cin", "small_cin_mfma") else None
+    wg_planes = bool(_two(fmt) and lib.itcv_conv2d_wgrad_bf16p_supported(B, Ci, H, W, Co, KS))
+    wgrad = "planes" if wg_planes else "raw"
+    if not up2 and KS == 5 and _two(fmt):       # the 5x5 weight gradient with a 3-channel side on the matrix cores
+        if Ci <= 3 and lib.itcv_conv2d_wgrad5_bf16p_supported(Ci, Co, H, W):
+            wgrad = "stem"
+        elif Co <= 3 and lib.itcv_conv2d_wgrad5_bf16p_supported(Co, Ci, H, W):
+            wgrad = "predict"
+    keep_xp = _two(fwd_ns) and (wg_planes or wgrad == "predict")
+    # The format of the output gradient's planes is decided by a shape-free rule (it predates the shape-aware hints and
+    # also serves the blocks that always keep fp32): the data gradient's, else the mode's for the layers whose weight
+    # gradient usually runs on planes.  It is NOT wg_planes; the fp32_needed flag below is what the shapes correct.
+    # Changing it changes which planes a BatchNorm backward writes.
+    grad_ns = dgrad_ns if needs_input_grad else 0
+    if not grad_ns and _two(fmt) and (KS == 3 or (KS == 5 and Ci <= 3 and Co == 64)):
+        grad_ns = fmt
+    grad_planes_only = bool(grad_ns and (not needs_input_grad or dgrad_ns == grad_ns) and wg_planes and not has_bias)
+    return ConvRoute(fwd_p or fwd_d, fwd_ns, fwd_d, dg_p or dg_d, dgrad_ns, dg_d, sub, wgrad, keep_xp,
+                     (fwd_ns, not keep_xp), (grad_ns, not grad_planes_only), (fwd_ns, True), (grad_ns, True))
+
+
+def conv_route(B, Ci, H, W, Co, KS, up2=False, has_bias=False, needs_input_grad=True):
+    """The route of a conv whose OUTPUT is [B, Co, H, W] in the current mode (memoised on the full key)."""
+    return _build_route(B, Ci, H, W, Co, KS, up2, has_bias, needs_input_grad, _CONV_MATH[0], _SCIN_MFMA[0])
+
+
+def conv_route_of(conv, B, H, W, up2=False, needs_input_grad=True):
+    """conv_route of an nn.Conv2d-like module: what the BatchNorm passes around it ask for their out_mode / grad_mode."""
+    return conv_route(B, conv.in_channels, H, W, conv.out_channels, conv.kernel_size[0], bool(up2), conv.bias is not None,
+                      bool(needs_input_grad))
+
+
+def missing_operand(fwd, bwd):
+    """(fp32 x, sub-range form): what a backward on route ``bwd`` needs that a forward on route ``fwd`` did not leave --
+    the conv math mode changed in between."""
+    return bwd.wgrad == "raw" and fwd.keep_xp, fwd.dgrad_sub is not None and bwd.dgrad_sub is None
+
+
+def conv_apply(x, weight, w4, for_dgrad, bias, B, Ci, H, W, Co, KS, up2, out=None):
+    """Forward-type conv GEMM (forward, or data-gradient with the roles of Ci/Co swapped by the caller) on the fp32
+    tensor ``x``, on the kernel selected by set_conv_math().  ``out`` (per-image <= 4-reduction-channel kernels only):
+    write there."""
+    fmt = _NS[_CONV_MATH[0]]
+    kernel = _gemm_kernels(Ci, Co, KS, W, bool(up2), fmt, _SCIN_MFMA[0])[1]
+    if out is not None and kernel not in ("small_cin", "small_cin_mfma"):
+        raise abi.HipExtensionError("conv_apply: an output tensor is taken by the small-cin kernels only")
+    if kernel == "fp32":
+        return conv_fwd_raw(x, packed_weight(weight, w4, for_dgrad), bias, B, Ci, H, W, Co, KS, up2)
+    y = out if out is not None else torch.empty((B, Co, H, W), dtype=F32, device=x.device)
+    if kernel == "small_cout":
         call("itcv_conv2d_small_cout_fwd", ptr(x), ptr(w4), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(for_dgrad),
              stream())
-        return y
-    if not up2 and lib.itcv_conv2d_small_cin_supported(Ci, KS):
-        # <= 4 reduction channels: direct fp32 conv, the pixel's input window lives in registers
-        y = out if out is not None else torch.empty((B, Co, H, W), dtype=F32, device=x.device)
-        fmt = _NS[_CONV_MATH[0]]
-        if _SCIN_MFMA[0] and _two(fmt) and lib.itcv_conv2d_small_cin_bf16x3_supported(Ci, Co, KS, W):
-            # fp16 form: the data-gradient's input is a gradient tensor -> scale from its magnitude (device side)
-            amax = absmax_parts(x) if (fmt == F16X2 and for_dgrad) else None
-            call("itcv_conv2d_small_cin_fwd_bf16x3", ptr(x), ptr(w4), ptr(bias), ptr(y), B, Ci, H, W, Co, KS,
-                 int(for_dgrad), fmt, ptr(amax), stream())
-            return y
-
+    elif kernel == "small_cin":
         call("itcv_conv2d_small_cin_fwd", ptr(x), ptr(w4), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(for_dgrad),
              stream())
-        return y
-    ns = _NS[_CONV_MATH[0]]
-    if ns in (2, 3) and lib.itcv_conv2d_bf16s_supported(Ci, Co, KS):
-        wp = packed_weight(weight, w4, for_dgrad, ns)
-        y = torch.empty((B, Co, H, W), dtype=F32, device=x.device)
+    elif kernel == "small_cin_mfma":
+        # fp16 form: the data-gradient's input is a gradient tensor -> scale from its magnitude (device side)
+        amax = absmax_parts(x) if (fmt == F16X2 and for_dgrad) else None
+        call("itcv_conv2d_small_cin_fwd_bf16x3", ptr(x), ptr(w4), ptr(bias), ptr(y), B, Ci, H, W, Co, KS,
+             int(for_dgrad), fmt, ptr(amax), stream())
+    else:
+        wp = packed_weight(weight, w4, for_dgrad, fmt)
         nws = lib.itcv_conv2d_fwd_bf16s_workspace(B, Ci, H, W, Co, KS)
         ws = _ws(nws, x.device) if nws else None
-
-        call("itcv_conv2d_fwd_bf16s", ptr(x), ptr(wp), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(up2), ns, ptr(ws), nws,
+        call("itcv_conv2d_fwd_bf16s", ptr(x), ptr(wp), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(up2), fmt, ptr(ws), nws,
              stream())
-        return y
-    return conv_fwd_raw(x, packed_weight(weight, w4, for_dgrad), bias, B, Ci, H, W, Co, KS, up2)
+    return y
 
 
 def absmax_parts(x):
@@ -483,23 +554,19 @@ def conv_apply_planes(xp, weight, w4, for_dgrad, bias, B, Ci, H, W, Co, KS, up2,
     kernel can, it also leaves the per-tile channel sums of its output for the BatchNorm that follows
     (attached to the result as ``_itcv_tile_stats``; BnActFn then skips its own statistics pass).
     ``live`` = (b0, nb): only these images of the B-image tensors are computed, with the whole batch's launch plan."""
-    if live is not None:
-        wp = packed_weight(weight, w4, for_dgrad, ns)
-        y = _new_grad((B, Co, H, W), xp.device, live)
-        nws = lib.itcv_conv2d_fwd_bf16p_workspace(B, Ci, H, W, Co, KS, ns)
-        ws = _ws(nws, xp.device) if nws else None
-        call("itcv_conv2d_fwd_bf16p_sub", ptr(xp), ptr(wp), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(up2), ns, live[0],
-             live[1], ptr(ws), nws, stream())
-        return y
-    if not up2 and _two(ns) and lib.itcv_conv2d_small_cout_bf16p_supported(Ci, Co, KS):
+    if live is None and _gemm_kernels(Ci, Co, KS, W, bool(up2), ns, _SCIN_MFMA[0])[0] == "small_cout_planes":
         y = torch.empty((B, Co, H, W), dtype=F32, device=xp.device)
         call("itcv_conv2d_small_cout_fwd_bf16p", ptr(xp), ptr(w4), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(for_dgrad),
              ns, stream())
         return y
     wp = packed_weight(weight, w4, for_dgrad, ns)
-    y = torch.empty((B, Co, H, W), dtype=F32, device=xp.device)
+    y = _new_grad((B, Co, H, W), xp.device, live)
     nws = lib.itcv_conv2d_fwd_bf16p_workspace(B, Ci, H, W, Co, KS, ns)
     ws = _ws(nws, xp.device) if nws else None
+    if live is not None:
+        call("itcv_conv2d_fwd_bf16p_sub", ptr(xp), ptr(wp), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(up2), ns, live[0],
+             live[1], ptr(ws), nws, stream())
+        return y
     T = lib.itcv_conv2d_fwd_bf16p_stat_tiles(B, Ci, H, W, Co, KS, ns) if (want_stats and _FUSE_STATS[0]) else 0
     stats = torch.empty((2, Co, T), dtype=F32, device=xp.device) if T else None
     call("itcv_conv2d_fwd_bf16p_st", ptr(xp), ptr(wp), ptr(bias), ptr(y), B, Ci, H, W, Co, KS, int(up2), ns, ptr(stats),
@@ -546,7 +613,6 @@ def flush_wgrad_reduces():
     pend = _DEFER["pending"]
     if not pend:
         return
-    import ctypes
     # group the calls by target (a weight used by several network passes of the backward), keeping call order
     groups = {}
     for ws, dw, co, ci, slabs in pend:
@@ -554,26 +620,24 @@ def flush_wgrad_reduces():
     key = tuple((k, tuple((w.data_ptr(), n) for w, n in g[3])) for k, g in groups.items())
     tab = _DEFER["tables"].get(key)
     if tab is None:
-        nb = lib.itcv_wgrad_reduce_desc_bytes()
-        descs, blocks = [], 0
+        descs = []
         for dw, co, ci, srcs in groups.values():
             for c0 in range(0, len(srcs), 4):          # at most four slab sources per descriptor; later ones accumulate
-                part = srcs[c0:c0 + 4]
-                descs.append((dw, co, ci, part, 1))
-        host = (ctypes.c_uint8 * (nb * len(descs)))()
-        for i, (dw, co, ci, part, acc) in enumerate(descs):
-            sl = (ctypes.c_void_p * len(part))(*[w.data_ptr() for w, _ in part])
-            sp = (ctypes.c_int * len(part))(*[n for _, n in part])
-            got = lib.itcv_wgrad_reduce_desc(ctypes.byref(host, i * nb), sl, sp, len(part), dw.data_ptr(), co, ci, acc, blocks)
-            if got <= 0:
-                raise abi.HipExtensionError("itcv_wgrad_reduce_desc: " + abi.last_error())
-            blocks += got
+                descs.append((dw, co, ci, srcs[c0:c0 + 4]))
         # descriptors of one target that were split into several (> 4 sources) would race inside one launch
         if len(descs) != len(groups):
             raise abi.HipExtensionError("deferred weight-gradient reduce: more than four passes over one weight")
+
+        def fill(slot, desc, blocks):
+            dw, co, ci, part = desc
+            sl = (ctypes.c_void_p * len(part))(*[w.data_ptr() for w, _ in part])
+            sp = (ctypes.c_int * len(part))(*[n for _, n in part])
+            return lib.itcv_wgrad_reduce_desc(slot, sl, sp, len(part), dw.data_ptr(), co, ci, 1, blocks)
+
         if len(_DEFER["tables"]) > 64:
             _DEFER["tables"].clear()
-        tab = _DEFER["tables"][key] = (torch.frombuffer(bytearray(host), dtype=torch.uint8).to(pend[0][1].device), len(descs), blocks)
+        tab = _DEFER["tables"][key] = _desc_table("itcv_wgrad_reduce_desc", lib.itcv_wgrad_reduce_desc_bytes(), descs, fill,
+                                                  pend[0][1].device)
     call("itcv_wgrad_reduce_many", ptr(tab[0]), tab[1], tab[2], stream())
     pend.clear()
 
@@ -634,7 +698,6 @@ class LaunchProfile:
     @classmethod
     def end(cls):
         """-> list of (kernel label, algorithmic FLOP, seconds)."""
-        import ctypes
         n = lib.itcv_profile_end()
         code, flop, ms = ctypes.c_int(), ctypes.c_double(), ctypes.c_float()
         out = []
@@ -727,73 +790,6 @@ def planes_of(t, ns, gradient=False):
     return p if p is not None else split_planes(t, ns, gradient)
 
 
-def conv_input_planes_ns(conv, up2=False):
-    """ns when ``conv`` (an nn.Conv2d-like module) will read its input as planes in the current mode, else 0:
-    tells the producing BatchNorm pass to emit them."""
-    if conv is None:
-        return 0
-    return _planes_ns(conv.in_channels, conv.out_channels, conv.kernel_size[0], up2)
-
-
-def conv_grad_planes_ns(conv, needs_input_grad=True):
-    """ns when the backward of ``conv`` will read its output gradient as planes (data- and/or weight-gradient)."""
-    if conv is None:
-        return 0
-    ks = conv.kernel_size[0]
-    ns = _planes_ns(conv.out_channels, conv.in_channels, ks, False) if needs_input_grad else 0
-    if not ns and _two(_NS[_CONV_MATH[0]]) and _PLANES[0] and (ks == 3 or (ks == 5 and _SMALL_PLANES[0]
-                                                                           and conv.in_channels <= 3
-                                                                           and conv.out_channels == 64)):
-        ns = _NS[_CONV_MATH[0]]    # weight gradient on planes (shape support is re-checked where the planes are consumed)
-    return ns
-
-
-def conv_input_mode(conv, B, H, W, up2=False):
-    """(ns, fp32_needed) for the tensor feeding ``conv`` whose OUTPUT is [B, Co, H, W]: the number of planes its
-    producer should emit, and whether the fp32 tensor itself is still read (fallback kernels)."""
-    ns = conv_input_planes_ns(conv, up2)
-    if not ns:
-        return 0, True
-    ks = conv.kernel_size[0]
-    wg_ok = (_wgrad_planes_ok(B, conv.in_channels, H, W, conv.out_channels, ks)
-             or _wgrad5_mode(conv.in_channels, H, W, conv.out_channels, ks, up2) == "predict")
-    return ns, not (_two(ns) and wg_ok)
-
-
-def conv_grad_mode(conv, B, H, W, needs_input_grad=True):
-    """(ns, fp32_needed) for the gradient of ``conv``'s output [B, Co, H, W]."""
-    ns = conv_grad_planes_ns(conv, needs_input_grad)
-    if not ns:
-        return 0, True
-    ks = conv.kernel_size[0]
-    dgrad_ok = (not needs_input_grad) or _planes_ns(conv.out_channels, conv.in_channels, ks, False) == ns
-    wgrad_ok = _two(ns) and _wgrad_planes_ok(B, conv.in_channels, H, W, conv.out_channels, ks)
-    return ns, not (dgrad_ok and wgrad_ok and conv.bias is None)
-
-
-def _planes_ns(Ci, Co, KS, up2):
-    """Number of bf16 planes when a forward-type conv GEMM (Ci -> Co) runs on pre-split operands, else 0."""
-    ns = _NS[_CONV_MATH[0]]
-    if not ns or not _PLANES[0]:
-        return 0
-    if not up2 and _two(ns) and _SMALL_PLANES[0] and lib.itcv_conv2d_small_cout_bf16p_supported(Ci, Co, KS):
-        return ns    # the 5x5 predict conv / stem data-gradient on the matrix cores (two-plane formats)
-    if not up2 and (lib.itcv_conv2d_small_cout_supported(Co, KS) or lib.itcv_conv2d_small_cin_supported(Ci, KS)):
-        return 0
-    return ns if lib.itcv_conv2d_bf16s_supported(Ci, Co, KS) else 0
-
-
-def _wgrad5_mode(Ci, H, W, Co, KS, up2):
-    """'stem' / 'predict' when the 5x5 weight gradient with a 3-channel side runs on the matrix cores (bf16x3)."""
-    if up2 or KS != 5 or not _two(_NS[_CONV_MATH[0]]) or not (_PLANES[0] and _SMALL_PLANES[0]):
-        return None
-    if Ci <= 3 and lib.itcv_conv2d_wgrad5_bf16p_supported(Ci, Co, H, W):
-        return "stem"
-    if Co <= 3 and lib.itcv_conv2d_wgrad5_bf16p_supported(Co, Ci, H, W):
-        return "predict"
-    return None
-
-
 def conv_wgrad5_planes(small, big_planes, B, Cs, H, W, stem, out=None, accumulate=False, ns=2):
     """5x5 weight gradient with a <= 3-channel side from the planes of the 64-channel side.  fp16 form: the predict
     conv's small side is a gradient tensor and gets a device-side scale; the stem's is the input image (scale 1)."""
@@ -805,10 +801,6 @@ def conv_wgrad5_planes(small, big_planes, B, Cs, H, W, stem, out=None, accumulat
     call("itcv_conv2d_wgrad5_bf16p", ptr(small), ptr(big_planes), ptr(dw), B, Cs, H, W, int(stem), int(ns), ptr(amax),
          int(accumulate), ptr(ws), nws, stream())
     return dw
-
-
-def _wgrad_planes_ok(B, Ci, H, W, Co, KS):
-    return bool(_two(_NS[_CONV_MATH[0]]) and _PLANES[0] and lib.itcv_conv2d_wgrad_bf16p_supported(B, Ci, H, W, Co, KS))
 
 
 class Conv2dFn(Function):
@@ -825,21 +817,20 @@ class Conv2dFn(Function):
         Co, KS = weight.shape[0], weight.shape[2]
         H, W = (Hs * 2, Ws * 2) if up2 else (Hs, Ws)
         b = None if bias is None else _f32c(bias)
-        ns = _planes_ns(Ci, Co, KS, up2)
+        r = conv_route(B, Ci, H, W, Co, KS, bool(up2), bias is not None, ctx.needs_input_grad[0])
         xp = None
-        if ns:
-            xp = planes_of(x, ns)
-            y = conv_apply_planes(xp, weight, weight, 0, b, B, Ci, H, W, Co, KS, up2, ns, want_stats=True)
+        if r.fwd_ns:
+            xp = planes_of(x, r.fwd_ns)
+            y = conv_apply_planes(xp, weight, weight, 0, b, B, Ci, H, W, Co, KS, up2, r.fwd_ns, want_stats=True)
         else:
             y = conv_apply(_require_fp32(x, "Conv2dFn.forward"), weight, weight, 0, b, B, Ci, H, W, Co, KS, up2)
-        wg_planes = _wgrad_planes_ok(B, Ci, H, W, Co, KS)
-        keep_xp = xp if (_two(ns) and (wg_planes or _wgrad5_mode(Ci, H, W, Co, KS, up2) == "predict")) else None
-        ctx.save_for_backward(None if keep_xp is not None else _require_fp32(x, "Conv2dFn.forward (saved input)"),
-                              weight, bias, keep_xp)
+        ctx.save_for_backward(None if r.keep_xp else _require_fp32(x, "Conv2dFn.forward (saved input)"), weight, bias,
+                              xp if r.keep_xp else None)
         ctx.cfg = (B, Ci, H, W, Co, KS, up2, bias is not None, (Hs, Ws))
+        ctx.route = r
         ctx.shared = _SHARED_PASS[0]
         ctx.shared_first = ctx.shared is not None and ctx.shared._claim_first()
-        if ctx.shared is not None and _dgrad_sub_kind(Co, Ci, KS) is None:
+        if ctx.shared is not None and r.dgrad_sub is None:
             _block_live(f"conv {Ci}->{Co} k{KS}: data gradient without a sub-range form in mode {_CONV_MATH[0]}")
         return y
 
@@ -854,30 +845,32 @@ class Conv2dFn(Function):
         need_x = ctx.needs_input_grad[0] and not (ctx.shared_first and not ctx.shared.input_grad)
         need_w = ctx.needs_input_grad[1] and _shared_ok(ctx, "param_grads")
         need_b = ctx.needs_input_grad[2] and _shared_ok(ctx, "param_grads")
-        ns_d = _planes_ns(Co, Ci, KS, False) if need_x else 0
-        wg_planes = need_w and _wgrad_planes_ok(B, Ci, H, W, Co, KS)
-        dyp = None
+        r = conv_route(B, Ci, H, W, Co, KS, bool(up2), has_bias, ctx.needs_input_grad[0])    # of the mode as it is now
+        no_x, no_sub = missing_operand(ctx.route, r)
+        ns_d = r.dgrad_ns if need_x else 0
+        wgrad = r.wgrad if need_w else None
         fmt2 = F16X2 if _NS[_CONV_MATH[0]] == F16X2 else 2       # the two-plane format of the current mode
         live = _live_images(ctx, B) if need_x else None          # (param_grads is off then: no weight / bias gradient)
-        if live is not None and _dgrad_sub_kind(Co, Ci, KS) is None:
+        if live is not None and no_sub:
             raise abi.HipExtensionError("Conv2dFn.backward: conv math mode changed inside a shared pass")
+        if wgrad is not None and no_x:
+            raise abi.HipExtensionError("Conv2dFn.backward: conv math mode changed between forward and backward")
         if live is not None and ns_d and _tagged_planes(dy, ns_d) is None:
             # no planes from the producer: the split pass reads the whole tensor, so the dead images become the zeros they stand for
             full = torch.zeros_like(dy)
             full[live[0]:live[0] + live[1]] = dy[live[0]:live[0] + live[1]]
             dy = full
-        if ns_d or wg_planes:
-            dyp = planes_of(dy, ns_d if ns_d else fmt2, gradient=True)
+        dyp = planes_of(dy, ns_d if ns_d else fmt2, gradient=True) if (ns_d or wgrad == "planes") else None
         if need_x:
             if ns_d:
                 dx = conv_apply_planes(dyp, weight, weight, 1, None, B, Co, H, W, Ci, KS, False, ns_d, live=live)
             elif live is not None:
                 # the per-image 5x5 kernels on the live images (a contiguous slice; the fp16 scale comes from their maximum,
                 # which is the whole tensor's: the rest is zero)
-                r = slice(live[0], live[0] + live[1])
+                sl = slice(live[0], live[0] + live[1])
                 dx = _new_grad((B, Ci, H, W), dy.device, live)
-                conv_apply(_require_fp32(dy, "Conv2dFn.backward")[r], weight, weight, 1, None, live[1], Co, H, W, Ci, KS, False,
-                           out=dx[r])
+                conv_apply(_require_fp32(dy, "Conv2dFn.backward")[sl], weight, weight, 1, None, live[1], Co, H, W, Ci, KS, False,
+                           out=dx[sl])
             else:
                 dx = conv_apply(_require_fp32(dy, "Conv2dFn.backward"), weight, weight, 1, None, B, Co, H, W, Ci, KS, False)
             if up2:
@@ -885,37 +878,26 @@ class Conv2dFn(Function):
                 b0, nb = live if live is not None else (0, B)
                 call("itcv_upsample2_bwd", ptr(dx[b0:b0 + nb]), ptr(lo[b0:b0 + nb]), nb * Ci, H // 2, W // 2, stream())
                 dx = lo
-        wg5 = _wgrad5_mode(Ci, H, W, Co, KS, up2) if need_w else None
-        if wg5 == "predict" and xp is None and x is None:
-            wg5 = None
-        if wg5 is not None:
+        if wgrad is not None:
+            # into .grad where the solvers' flat buffers take it (autograd then gets None), else a fresh tensor
             tgt = _grad_target(weight)
-            if wg5 == "stem":
-                small, big = _require_fp32(x, "Conv2dFn.backward (5x5 weight gradient)"), (dyp if dyp is not None else planes_of(dy, fmt2, gradient=True))
+            into = dict(out=tgt, accumulate=tgt is not None)
+            if wgrad == "stem":
+                big = dyp if dyp is not None else planes_of(dy, fmt2, gradient=True)
+                dw = conv_wgrad5_planes(_require_fp32(x, "Conv2dFn.backward (5x5 weight gradient)"), big, B, Ci, H, W, True,
+                                        ns=fmt2, **into)
+            elif wgrad == "predict":
+                big = xp if xp is not None else split_planes(x, fmt2)
+                dw = conv_wgrad5_planes(_require_fp32(dy, "Conv2dFn.backward (5x5 weight gradient)"), big, B, Co, H, W, False,
+                                        ns=fmt2, **into)
+            elif wgrad == "planes":
+                dw = conv_wgrad_planes(xp if xp is not None else split_planes(x, fmt2), dyp, B, Ci, H, W, Co, KS, up2,
+                                       ns=fmt2, **into)
             else:
-                small, big = _require_fp32(dy, "Conv2dFn.backward (5x5 weight gradient)"), (xp if xp is not None else split_planes(x, fmt2))
-            cs = Ci if wg5 == "stem" else Co
+                dw = conv_wgrad_raw(x, _require_fp32(dy, "Conv2dFn.backward (weight gradient)"), B, Ci, H, W, Co, KS, up2,
+                                    **into)
             if tgt is not None:
-                conv_wgrad5_planes(small, big, B, cs, H, W, wg5 == "stem", out=tgt, accumulate=True, ns=fmt2)
-            else:
-                dw = conv_wgrad5_planes(small, big, B, cs, H, W, wg5 == "stem", ns=fmt2)
-        elif need_w:
-            tgt = _grad_target(weight)
-            if wg_planes and (ns_d in (0, fmt2)):
-                if xp is None:
-                    xp = split_planes(x, fmt2)
-                if tgt is not None:
-                    conv_wgrad_planes(xp, dyp, B, Ci, H, W, Co, KS, up2, out=tgt, accumulate=True, ns=fmt2)
-                else:
-                    dw = conv_wgrad_planes(xp, dyp, B, Ci, H, W, Co, KS, up2, ns=fmt2)
-            else:
-                if x is None:
-                    raise abi.HipExtensionError("Conv2dFn.backward: conv math mode changed between forward and backward")
-                _require_fp32(dy, "Conv2dFn.backward (weight gradient)")
-                if tgt is not None:
-                    conv_wgrad_raw(x, dy, B, Ci, H, W, Co, KS, up2, out=tgt, accumulate=True)
-                else:
-                    dw = conv_wgrad_raw(x, dy, B, Ci, H, W, Co, KS, up2)
+                dw = None
         if has_bias and need_b:
             db = bias_grad_raw(_require_fp32(dy, "Conv2dFn.backward (bias gradient)"), B, Co, H * W, _grad_target(bias))
         return dx, dw, db, None
@@ -1480,7 +1462,6 @@ class LinCombFn(Function):
 
     @staticmethod
     def forward(ctx, weights, *terms):
-        import ctypes
         n = len(terms)
         terms = [_f32c(t) for t in terms]
         if any(t.numel() != 1 for t in terms):
@@ -1496,7 +1477,6 @@ class LinCombFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
-        import ctypes
         n = len(ctx.weights)
         grads = torch.empty((n,), dtype=F32, device=g.device)
         wp = (ctypes.c_float * n)(*ctx.weights)
@@ -1552,7 +1532,6 @@ class TcRowsFn(Function):
 def _bc3(x, mu, logvar):
     """The three operands as (same-storage) views broadcast to one shape of at most three dimensions, with their element
     strides (0 on broadcast dimensions) as ctypes arrays."""
-    import ctypes
     x, mu, logvar = (t if t.dtype == F32 else t.float() for t in (x, mu, logvar))
     xb, mb, lb = torch.broadcast_tensors(x, mu, logvar)
     shape = tuple(xb.shape)
@@ -1713,7 +1692,6 @@ def disent_bins(mu, mn, mx, bins):
 
 
 def _disent_factors(factors, factor_sizes, N, device):
-    import ctypes
     sizes = [int(s) for s in factor_sizes]
     v = factors if isinstance(factors, torch.Tensor) else torch.as_tensor(factors)
     if v.dim() != 2 or v.shape[0] != N or v.shape[1] != len(sizes):
@@ -1741,7 +1719,6 @@ def disent_hist(mu, factors, factor_sizes, mn, mx, bins, flags):
 
 def disent_mi(counts, vcount, N, D, factor_sizes, bins):
     """(MI[D, K], H[K]) in fp64 from the integer tables of ``disent_hist``."""
-    import ctypes
     sizes = [int(s) for s in factor_sizes]
     mi = torch.empty((D, len(sizes)), dtype=torch.float64, device=counts.device)
     h = torch.empty((len(sizes),), dtype=torch.float64, device=counts.device)
@@ -1755,7 +1732,6 @@ F64 = torch.float64
 
 
 def _lr_sizes(class_sizes):
-    import ctypes
     sizes = [int(s) for s in class_sizes]
     return sizes, (ctypes.c_int * max(len(sizes), 1))(*sizes)
 

@@ -186,14 +186,24 @@ class ConvolutionalBlock(nn.Module):
             y = self.relu2(self.bn2(self.conv2(y)))
             return _avgpool2(y) if pool else y
         B, H, W = x.size(0), x.size(2) * (2 if up2 else 1), x.size(3) * (2 if up2 else 1)
-        y = self.bn1(self.conv1(x, up2=up2), slope=LRELU_SLOPE, out_mode=HF.conv_input_mode(self.conv2, B, H, W),
-                     grad_mode=HF.conv_grad_mode(self.conv1, B, H, W, x.requires_grad))
-        Hc, Wc = (H // 2, W // 2) if pool else (H, W)
-        if consumer_up2:
-            Hc, Wc = Hc * 2, Wc * 2
+        y = self.bn1(self.conv1(x, up2=up2), slope=LRELU_SLOPE, out_mode=HF.conv_route_of(self.conv2, B, H, W).in_mode,
+                     grad_mode=HF.conv_route_of(self.conv1, B, H, W, up2, x.requires_grad).grad_mode)
         return self.bn2(self.conv2(y), slope=LRELU_SLOPE, pool=pool,
-                        out_mode=HF.conv_input_mode(consumer, B, Hc, Wc, consumer_up2) if consumer is not None else (0, True),
-                        grad_mode=HF.conv_grad_mode(self.conv2, B, H, W))
+                        out_mode=_consumer_route(consumer, B, H, W, pool, consumer_up2).in_mode,
+                        grad_mode=HF.conv_route_of(self.conv2, B, H, W).grad_mode)
+
+
+class _NoConsumer:
+    """What a BatchNorm pass is told when no conv reads its output: no planes, the fp32 tensor."""
+    in_mode = in_mode_keep_fp32 = (0, True)
+
+
+def _consumer_route(consumer, B, H, W, pool, up2):
+    """Route of the conv module that reads a block's [B, C, H, W] output after its optional pooling / x2 upsampling."""
+    if consumer is None:
+        return _NoConsumer
+    Hc, Wc = (H // 2, W // 2) if pool else (H, W)
+    return HF.conv_route_of(consumer, B, Hc * 2 if up2 else Hc, Wc * 2 if up2 else Wc, up2)
 
 
 def grad_free_parameters(module):
@@ -234,12 +244,13 @@ class ResidualBlock(nn.Module):
         else:
             skip = HF.Upsample2Fn.apply(x) if up2 else x
         # the block output also feeds the next block's skip path and x feeds this one's: fp32 stays everywhere
+        B, H, W = x.size(0), x.size(2) * (2 if up2 else 1), x.size(3) * (2 if up2 else 1)
         y = self.bn1(self.conv1(x, up2=up2), slope=LRELU_SLOPE,
-                     out_mode=(HF.conv_input_planes_ns(self.conv2), True),
-                     grad_mode=(HF.conv_grad_planes_ns(self.conv1, x.requires_grad), True))
+                     out_mode=HF.conv_route_of(self.conv2, B, H, W).in_mode_keep_fp32,
+                     grad_mode=HF.conv_route_of(self.conv1, B, H, W, up2, x.requires_grad).grad_mode_keep_fp32)
         return self.bn2(self.conv2(y), slope=LRELU_SLOPE, pool=pool, skip=skip,
-                        out_mode=(HF.conv_input_planes_ns(consumer, consumer_up2), True),
-                        grad_mode=(HF.conv_grad_planes_ns(self.conv2), True))
+                        out_mode=_consumer_route(consumer, B, H, W, pool, consumer_up2).in_mode_keep_fp32,
+                        grad_mode=HF.conv_route_of(self.conv2, B, H, W).grad_mode_keep_fp32)
 
 
 class Conv2dBatchNorm(nn.Module):
@@ -359,11 +370,11 @@ class Encoder(nn.Module):
         elif self.fused:
             blocks = [getattr(self.main, name) for name, _ in self._stages]
             res_block = not isinstance(blocks[0], ConvolutionalBlock)    # skip paths / branches read the fp32 tensor
-            first = getattr(blocks[0], "conv1", None)
-            mode = HF.conv_input_mode(first, x.size(0), x.size(2) // 2, x.size(3) // 2) if first is not None else (0, True)
+            first = _consumer_route(getattr(blocks[0], "conv1", None), x.size(0), x.size(2), x.size(3), True, False)
+            stem = HF.conv_route_of(self.main[0], x.size(0), x.size(2), x.size(3), False, x.requires_grad)
             y = self.main[1](self.main[0](x), slope=LRELU_SLOPE, pool=True,
-                             out_mode=(mode[0], True) if res_block else mode,
-                             grad_mode=(HF.conv_grad_planes_ns(self.main[0], x.requires_grad), True))
+                             out_mode=first.in_mode_keep_fp32 if res_block else first.in_mode,
+                             grad_mode=stem.grad_mode_keep_fp32)    # (the parent's shape-free hint: fp32 is always written)
             for k, (name, pooled) in enumerate(self._stages):
                 nxt = getattr(blocks[k + 1], "conv1", None) if k + 1 < len(blocks) else None
                 y = blocks[k](y, pool=pooled, consumer=nxt)
