@@ -456,6 +456,22 @@ int itcv_sampling_bwd(const float* g_prodm, const float* g_logqz, const float* l
                       int weighted, void* stream);
 /* ops.py:118-122 for x[m][n] with m == n or m == 1: diag[min(m,n)], off[m][n][n] = x - diag_embed(x) */
 int itcv_on_off_diag(const float* x, float* diag, float* off, int m, int n, void* stream);
+/* Log density of S samples under a mixture of N diagonal Gaussians -- a whole dataset's aggregate posterior -- and under
+ * the product of its marginals, streamed (csrc/aggregate.hip): with lp[j][i][l] = max(log N(z_jl; mu_il, exp(logvar_il)),
+ * -50) (the ops.py:24-29 density with the variance of component i; the clamp per element, inside the sum over l),
+ *   logqz[j]  = logsumexp_i(logw_i + sum_l lp[j][i][l]),      lse[j][l] = logsumexp_i(logw_i + lp[j][i][l]).
+ * logw: N finite log weights, or NULL for -log N each.  1 <= D <= 512, S >= 1, N >= 1; anything else, a null operand or
+ * a short workspace returns non-zero before a launch.  splits: the number of slices the component range is cut into
+ * (each leaves one (max, sum) partial per (row, l) and per row; a second kernel merges them in slice order); 0 lets the
+ * library choose from S, N and D so that the grid fills the 256 CUs; values above min(N, 1024) are lowered to that, and
+ * slices that would be empty are not made.  With s the slice count actually used,
+ *   itcv_aggregate_workspace = 2 * S * s * (D + 1) * sizeof(float)      (s <= 1024: nothing grows with S * N).
+ * No atomics and fixed summation orders: bitwise reproducible, and for a given splits row j's results depend only on
+ * z[j] and the components, not on S or on the other rows of the call. */
+size_t itcv_aggregate_workspace(int64_t S, int64_t N, int D, int splits);
+int itcv_aggregate_logdensity(const float* z, const float* mu, const float* logvar, const float* logw, float* logqz,
+                              float* lse, int64_t S, int64_t N, int D, int splits, void* ws, size_t ws_bytes,
+                              void* stream);
 
 /* ---- disentanglement scores (evaluation/utils.py:245-273,323-335, metrics.py:169-219) -- */
 /* Mutual information between every discretised latent column of mu[N][D] (fp32, row stride ld elements) and every

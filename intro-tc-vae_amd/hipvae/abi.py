@@ -142,6 +142,8 @@ SIGNATURES = {
     "itcv_sampling_fwd": (i32, [p, p, p, p, p, i32, i32, i64, i32, p]),
     "itcv_sampling_bwd": (i32, [p, p, p, p, p, p, p, i32, i32, i64, i32, p]),
     "itcv_on_off_diag": (i32, [p, p, p, i32, i32, p]),
+    "itcv_aggregate_workspace": (sz, [i64, i64, i32, i32]),
+    "itcv_aggregate_logdensity": (i32, [p, p, p, p, p, p, i64, i64, i32, i32, p, sz, p]),
     "itcv_disent_minmax_workspace": (sz, [i32, i32]),
     "itcv_disent_minmax": (i32, [p, sz, i32, i32, p, p, p, p, sz, p]),
     "itcv_disent_bins": (i32, [p, sz, i32, i32, p, p, i32, p, p]),

@@ -1624,6 +1624,31 @@ def diag_logdensity_rows(z, mu, logvar):
     return a, b
 
 
+def aggregate_logdensity(z, mu, logvar, logw=None, splits=0):
+    """``(logqz [S], lse [S, D])`` of the samples ``z`` [S, D] under the mixture of the N diagonal Gaussians
+    ``(mu, logvar)`` [N, D] with log weights ``logw`` [N] (None: -log N each), streamed over the components
+    (itcv_aggregate_logdensity): logqz[j] = logsumexp_i(logw_i + sum_l lp[j, i, l]), lse[j, l] = logsumexp_i(logw_i +
+    lp[j, i, l]) with the ops.py:24-29 density of component i, clamped at -50 per element.  ``splits``: slices of the
+    component range (0: the library's choice); for a given value a row's results do not depend on the other rows."""
+    z, mu, logvar = _f32c(z), _f32c(mu), _f32c(logvar)
+    if z.dim() != 2 or mu.dim() != 2 or mu.shape != logvar.shape or mu.shape[1] != z.shape[1]:
+        raise abi.HipExtensionError(f"aggregate_logdensity: z [S, D] and mu, logvar [N, D] are expected (got "
+                                    f"{tuple(z.shape)}, {tuple(mu.shape)}, {tuple(logvar.shape)})")
+    (S, D), N = z.shape, mu.shape[0]
+    if logw is not None:
+        logw = _f32c(logw)
+        if tuple(logw.shape) != (N,):
+            raise abi.HipExtensionError(f"aggregate_logdensity: logw must have shape ({N},)")
+    dev = z.device
+    logqz = torch.empty((S,), dtype=F32, device=dev)
+    lse = torch.empty((S, D), dtype=F32, device=dev)
+    nws = lib.itcv_aggregate_workspace(S, N, D, int(splits))
+    ws = _ws(nws, dev)
+    call("itcv_aggregate_logdensity", ptr(z), ptr(mu), ptr(logvar), ptr(logw), ptr(logqz), ptr(lse), S, N, D, int(splits),
+         ptr(ws), nws, stream())
+    return logqz, lse
+
+
 class ReconRowsFn(Function):
     """ops.py:219-230: per-sample summed reconstruction error; x is treated as a constant."""
 

@@ -55,10 +55,14 @@ class VAESolver:
         self.device_scores = None
         self.dci_params = None       # ``params`` of hipvae.disentangle.compute_dci_score (None: 100 rounds, depth 6)
         # scores the reference does not have, written from the device on top of the above: a tuple drawn from
-        # {"factor_vae", "sap"}; ``params`` of hipvae.disentangle.compute_factor_vae_score / compute_sap_score
+        # {"factor_vae", "sap", "elbo_decomposition"}; ``params`` of hipvae.disentangle.compute_factor_vae_score /
+        # compute_sap_score; keyword arguments of hipvae.aggregate.compute_elbo_decomposition (None: its defaults, with
+        # this solver's batch size)
         self.extra_scores = ()
         self.factor_vae_params = None
         self.sap_params = None
+        self.elbo_params = None
+        self._device_table = None
         self.recon_loss_type = recon_loss_type
         self.scale = 1 / (self.model.cdim * self.model.encoder.image_size ** 2)   # solvers/vae.py:61
         self._flat = {}
@@ -74,6 +78,7 @@ class VAESolver:
         if table is None:
             table = DeviceImageTable.from_dataset(self.dataset, self.device, device_resize=device_resize)
         self.latent_generator = DeviceFactorSampler(self.dataset, self.device, seed=seed, table=table)
+        self._device_table = table
         return table
 
     # ---- overridable loss hooks (solvers/vae.py:63-87) -----------------------------------
@@ -331,13 +336,32 @@ class VAESolver:
         dci_completeness_score, dci_disentanglement_score} from the device (metrics.py:82-103) and delegates nothing:
         ``evaluation`` is not imported.
         ``extra_scores`` adds, after all of the above and whatever ``device_scores`` says, ``factor_vae`` {train_accuracy,
-        eval_accuracy} and / or ``sap_score`` from the device (hipvae.disentangle; neither is in the reference)."""
-        if self.writer is None or not isinstance(self.dataset, DisentanglementDataset) or cur_iter % self.test_iter:
-            return
+        eval_accuracy} and / or ``sap_score`` from the device (hipvae.disentangle; neither is in the reference), and
+        with "elbo_decomposition" the record ``aggregate_decomp`` {mi, tc, dwkl, kl, kl_analytic}: the decomposition of
+        the aggregate KL over the dataset's aggregate posterior (hipvae.aggregate; ``elbo_params``).  That one needs no
+        factors, so it is written for any dataset, from the device table when ``use_device_dataset`` was called."""
         extras = tuple(self.extra_scores or ())
-        unknown = [e for e in extras if e not in ("factor_vae", "sap")]
+        with_elbo = "elbo_decomposition" in extras
+        factored = isinstance(self.dataset, DisentanglementDataset)
+        if self.writer is None or not (factored or with_elbo) or cur_iter % self.test_iter:
+            return
+        known = ("factor_vae", "sap", "elbo_decomposition")
+        unknown = [e for e in extras if e not in known]
         if unknown:
-            raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: 'factor_vae', 'sap')")
+            raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, known))})")
+        if factored:
+            self._write_factor_scores(cur_iter, num_samples, tuple(e for e in extras if e != "elbo_decomposition"))
+        if with_elbo:
+            from hipvae import aggregate
+            kw = dict(batch_size=self.batch_size)
+            kw.update(self.elbo_params or {})
+            got = aggregate.compute_elbo_decomposition(self.dataset if self._device_table is None else self._device_table,
+                                                       self.model, **kw)
+            self.writer.add_scalars("aggregate_decomp", {k: got[k] for k in ("mi", "tc", "dwkl", "kl", "kl_analytic")},
+                                    global_step=cur_iter)
+
+    def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: tuple):
+        """The factor-based scores of ``write_disentanglemnt_scores`` (a ``DisentanglementDataset``, at a test iteration)."""
         with_dci = isinstance(self.device_scores, str) and self.device_scores == "all+dci"
         M = None
         if not with_dci:
