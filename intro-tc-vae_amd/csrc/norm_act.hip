@@ -569,7 +569,10 @@ struct BnBwdFinal {   // fused single-launch path (splits == 1): the block write
 // mx[idx] / mx[nmx + idx], idx = (group * splits + slice) * C + c.  The apply pass turns their maxima U, V into the
 // tensor's scale: |dx| = |gamma rstd| |g - m1 - xhat m2| <= |gamma rstd| G_c (2 + X_c) <= U (2 + V), because
 // |m1| = |mean g| <= G_c and |m2| = |mean g xhat| <= G_c sqrt(mean xhat^2) <= G_c.
-template <int MODE, bool FUSED, bool MX = false>
+// LIVE: the call has a live range (grp.lvn > 0, itcv_bn_train_bwd_live).  A kernel of its own: with LIVE off the body has
+// no dead-group test, no dead selects and no shortened walk -- sharing one body cost the pool form, which only the encoder
+// runs and which never has a dead group, 4 VGPRs and four more full waits in the loop (27 -> 35 us per launch).
+template <int MODE, bool FUSED, bool MX = false, bool LIVE = false, bool P2 = false>
 __global__ __launch_bounds__(kRedThreads) void bn_bwd_partial_v4(
     const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -600,21 +603,23 @@ __global__ __launch_bounds__(kRedThreads) void bn_bwd_partial_v4(
   float gmax = 0.f, xmax = 0.f;
   // dead group (block-uniform): g = 0 without reading dy or skip -- the sums are the +0.0 a zero dy gives; with MX the
   // walk still reads x for v = max|xhat|, which the tensor-wide scale depends on, and without MX there is no walk
-  const bool dead = bn_dead(grp, FUSED ? (uint32_t)gi : gz);
-  const uint32_t gend = (dead && !MX) ? beg : end;
+  const bool dead = LIVE && bn_dead(grp, FUSED ? (uint32_t)gi : gz);
+  const uint32_t gend = (LIVE && dead && !MX) ? beg : end;
   // Four iterations' loads are issued before the first is consumed (the accumulation order is that of the plain loop:
-  // bitwise the same sums); out-of-range iterations load a valid address and add zeros.  -9..12 % on this kernel.
+  // bitwise the same sums).  A thread's full trips run without bounds tests; its last, ragged trip loads a valid address
+  // for the out-of-range iterations and adds zeros.  P2: H*W and W are powers of two, the index arithmetic is shifts.
   constexpr int U = 4;
-  for (uint32_t i0 = beg + threadIdx.x * 4; i0 < gend; i0 += kRedThreads * 4 * U) {
+  auto trip = [&](const uint32_t i0, auto ragged_c) {
+    constexpr bool RAGGED = decltype(ragged_c)::value != 0;
     float4 xv4[U], g4[U], k4[U];
     bool ok[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t iu = i0 + (uint32_t)u * kRedThreads * 4;
-      ok[u] = iu < end;
+      ok[u] = !RAGGED || iu < end;
       const uint32_t i = ok[u] ? iu : i0;
-      const uint32_t b = fdiv(i, HW, hw_shift), hw = i - b * HW;
-      const uint32_t h = fdiv(hw, W, w_shift), w = hw - h * W;
+      const uint32_t b = P2 ? i >> hw_shift : fdiv(i, HW, hw_shift), hw = i - b * HW;
+      const uint32_t h = P2 ? hw >> w_shift : fdiv(hw, W, w_shift), w = hw - h * W;
       const uint32_t bc = b * C + c;
       xv4[u] = *reinterpret_cast<const float4*>(x + (size_t)bc * HW + hw);
       g4[u] = dead ? make_float4(0.f, 0.f, 0.f, 0.f) : upstream4<MODE>(dy, bc, h, w, H, W);
@@ -622,8 +627,8 @@ __global__ __launch_bounds__(kRedThreads) void bn_bwd_partial_v4(
     if (skip && !dead) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const uint32_t iu = i0 + (uint32_t)u * kRedThreads * 4, i = iu < end ? iu : i0;
-        const uint32_t b = fdiv(i, HW, hw_shift), hw = i - b * HW;
+        const uint32_t iu = i0 + (uint32_t)u * kRedThreads * 4, i = ok[u] ? iu : i0;
+        const uint32_t b = P2 ? i >> hw_shift : fdiv(i, HW, hw_shift), hw = i - b * HW;
         k4[u] = *reinterpret_cast<const float4*>(skip + (size_t)(b * C + c) * HW + hw);
       }
     } else {
@@ -652,7 +657,11 @@ __global__ __launch_bounds__(kRedThreads) void bn_bwd_partial_v4(
         xmax = fmaxf(xmax, ok[u] ? xm : 0.f);
       }
     }
-  }
+  };
+  constexpr uint32_t kStep = kRedThreads * 4 * U;
+  uint32_t i0 = beg + threadIdx.x * 4;
+  for (; i0 + (kStep - kRedThreads * 4) < gend; i0 += kStep) trip(i0, std::integral_constant<int, 0>{});
+  if (i0 < gend) trip(i0, std::integral_constant<int, 1>{});
   s1 = block_sum(s1, scratch);
   s2 = block_sum(s2, scratch);
   if constexpr (MX) {
@@ -1138,9 +1147,14 @@ static int bn_bwd_reduce_launch(const BnPlan& p, const float* x, const float* dy
     }
     pick<2>(fused ? 1 : 0, [&](auto fused_c) {
       pick<2>(p.f16 ? 1 : 0, [&](auto mx_c) {
-        hipLaunchKernelGGL((bn_bwd_partial_v4<MODE, decltype(fused_c)::value != 0, decltype(mx_c)::value != 0>), p.rgrid,
-                           dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta, skip, part, B, C, H, W, slope, p.splits,
-                           ilog2_exact(W), ilog2_exact(H * W), bf, p.grp, mx, p.nmx);
+        pick<2>(p.grp.lvn > 0 ? 1 : 0, [&](auto live_c) {   // a live range is an instantiation of its own
+          pick<2>(ilog2_exact(W) >= 0 && ilog2_exact(H * W) >= 0 ? 1 : 0, [&](auto p2_c) {
+            hipLaunchKernelGGL((bn_bwd_partial_v4<MODE, decltype(fused_c)::value != 0, decltype(mx_c)::value != 0,
+                                                  decltype(live_c)::value != 0, decltype(p2_c)::value != 0>),
+                               p.rgrid, dim3(kRedThreads), 0, st, x, dy, mean, rstd, gamma, beta, skip, part, B, C, H, W, slope,
+                               p.splits, ilog2_exact(W), ilog2_exact(H * W), bf, p.grp, mx, p.nmx);
+          });
+        });
       });
     });
   });
