@@ -664,6 +664,61 @@ int itcv_sap_svc_fit(const float* x, size_t ld, const int* y, int N, int D, int 
 int itcv_sap_svc_score(const float* x, size_t ld, const int* y, int Nt, int D, int K, const int* csize, const int* cvalid,
                        const double* theta, long long* correct, int* pred, int* flags, void* stream);
 
+/* ---- unsupervised scores and IRS (not in the reference; Locatello et al. 2019, Suter et al. 2019) ---------------- */
+/* Fixed rules; all arithmetic is fp64 on fp32 representations x[N][D] (row stride ld elements), every operation rounded
+ * on its own (no fused multiply-add outside the matrix cores), every floating-point reduction in a fixed order that depends
+ * on the shapes alone and never on the grid, no floating-point atomics: same inputs, same bits.
+ *
+ * Covariance.  m[d] = (sum_n x[n][d]) / N;  C[i][j] = (sum_n (x[n][i] - m[i]) (x[n][j] - m[j])) / (N - 1): two passes over
+ *   centred values, as np.cov.  The centred products are accumulated on v_mfma_f64_16x16x4_f64 (D padded to 16 with zero
+ *   columns) per slice of rows; the slice length is a function of N alone and the slices are added in ascending order.  One
+ *   triangle is computed and mirrored: C is symmetric bit for bit.  flags[2] as for itcv_disent_*: [0] a non-finite x.
+ *   Supported: 2 <= N <= 2^24, 1 <= D <= 512.
+ * Gaussian total correlation.  tc = (sum_d log C[d][d] - logdet C) / 2 with logdet C = 2 sum_d log L[d][d], L the Cholesky
+ *   factor of C; both sums in ascending d.  A pivot <= 0 or non-finite sets info[0] and records its dimension in info[1]
+ *   (C must be positive definite; the results are then nan).
+ * Gaussian Wasserstein correlation.  w = 2 tr C - 2 sum_i sqrt(max(lambda_i(S), 0)) with S = D^1/2 C D^1/2, D = diag(C),
+ *   S[i][j] = (sqrt(C[i][i]) C[i][j]) sqrt(C[j][j]) for j <= i, mirrored (S is similar to C o diag(C)[:, None], whose matrix
+ *   square root disentanglement_lib takes); w_norm = w / tr C.  lambda: cyclic Jacobi in fp64 inside one launch.  A sweep is
+ *   Dp - 1 rounds (Dp = D rounded up to even) of the round-robin schedule: round r rotates the disjoint pairs (r, Dp - 1) and
+ *   ((r + k) mod (Dp - 1), (r - k) mod (Dp - 1)), k = 1 .. Dp / 2 - 1, each ordered p < q; a pair with q >= D or with
+ *   S[p][q] == 0 is skipped.  Rotation of (p, q): tau = (S[q][q] - S[p][p]) / (2 S[p][q]), t = sign(tau) / (|tau| +
+ *   sqrt(1 + tau^2)) (sign(0) = +1), c = 1 / sqrt(1 + t^2), s = t c; all rotations of a round are computed from the matrix
+ *   as the round finds it, then rows p, q become (c row_p - s row_q, s row_p + c row_q), then the columns likewise, and the
+ *   2 x 2 block takes its closed form S[p][p] - t S[p][q], S[q][q] + t S[p][q], 0.  Before every sweep: stop when
+ *   off(S)_F <= 1e-14 |S|_F; after 60 sweeps without that, info[2] is set.  lambda_i is the diagonal in index order.
+ *   _gauss: res[5] = {tc, w, w_norm, tr C, logdet C}, eig[D], info[4] = {pivot failed, its dimension (-1), Jacobi did not
+ *   converge, sweeps taken}.  One block; the matrix sits in LDS up to D = itcv_unsup_gauss_lds_dim(), above that in the
+ *   workspace (itcv_unsup_gauss_workspace).  Supported: 1 <= D <= 512.
+ * IRS.  v[N][K] int32 factor values in [0, fsize[k]) (fsize: a HOST array), order[K][N] int32: for every factor the row
+ *   numbers sorted by that factor's value, stable.  mn / mx: the column minima / maxima of itcv_disent_minmax.
+ *   1. d is ACTIVE iff mn[d] < mx[d] (disentanglement_lib tests var > 0, whose result for a constant column depends on
+ *      rounding).  No active dimension: IRS = 0.
+ *   2. maxdev[d] = max_n |x[n][d] - m[d]|, m as above.
+ *   3. For every factor k and every value v PRESENT in the sample, G its rows, n = |G|: e[d] = (sum_G x[g][d]) / n;
+ *      a = |x[g][d] - e[d]| sorted ascending; h = (n - 1) q; lo = floor(h); t = h - lo; hi = min(lo + 1, n - 1);
+ *      Q = a[lo] + (a[hi] - a[lo]) t if t < 0.5, else a[hi] - (a[hi] - a[lo]) (1 - t)       (np.percentile, linear).
+ *      a[lo] and a[hi] are found exactly (a radix select on the bit patterns of the fp64 values).
+ *   4. cum[d][k] = (sum_v Q, ascending v) / #present values;  M[d][k] = 1 - cum[d][k] / maxdev[d] (0 for an inactive d);
+ *      score[d] = max_k M[d][k], parent[d] its first arg-max;
+ *      IRS = (sum_d score[d] maxdev[d]) / (sum_d maxdev[d]) over the active d in ascending order.
+ *   flags[2] as for itcv_disent_*: [1] a factor value outside its range (or a row number of `order` outside [0, N)).
+ *   _irs: maxdev[D], cum[D][K], M[D][K], score[D] fp64; parent[D], active[D] int32; res[2] = {IRS, number of active d}.
+ *   A fixed number of launches whatever the groups; workspace itcv_irs_workspace(N, D, K, fsum).
+ *   Supported: 1 <= N <= 2^24, 1 <= D <= 512, 1 <= K <= 16, 1 <= fsize[k] <= 256, 0 <= q <= 1.
+ * Anything unsupported returns non-zero before a launch. */
+size_t itcv_unsup_cov_workspace(int N, int D);
+int itcv_unsup_cov(const float* x, size_t ld, int N, int D, double* mean, double* cov, int* flags, void* ws,
+                   size_t ws_bytes, void* stream);
+int itcv_unsup_gauss_lds_dim(void);
+size_t itcv_unsup_gauss_workspace(int D);
+int itcv_unsup_gauss(const double* cov, int D, double* res, double* eig, int* info, void* ws, size_t ws_bytes,
+                     void* stream);
+size_t itcv_irs_workspace(int N, int D, int K, int fsum);
+int itcv_irs(const float* x, size_t ld, const int* v, const int* order, int N, int D, int K, const int* fsize, double q,
+             const float* mn, const float* mx, double* maxdev, double* cum, double* M, double* score, int* parent,
+             int* active, double* res, int* flags, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- reconstruction loss (ops.py:188-236) --------------------------------------------- */
 #define ITCV_LOSS_MSE 0
 #define ITCV_LOSS_L1 1

@@ -175,6 +175,13 @@ SIGNATURES = {
     "itcv_sap_svc_workspace": (sz, [i32] * 4),
     "itcv_sap_svc_fit": (i32, [p, sz, p, i32, i32, i32, p, f64, f64, i32, p, p, p, p, p, p, sz, p]),
     "itcv_sap_svc_score": (i32, [p, sz, p, i32, i32, i32, p, p, p, p, p, p, p]),
+    "itcv_unsup_cov_workspace": (sz, [i32, i32]),
+    "itcv_unsup_cov": (i32, [p, sz, i32, i32, p, p, p, p, sz, p]),
+    "itcv_unsup_gauss_lds_dim": (i32, []),
+    "itcv_unsup_gauss_workspace": (sz, [i32]),
+    "itcv_unsup_gauss": (i32, [p, i32, p, p, p, p, sz, p]),
+    "itcv_irs_workspace": (sz, [i32] * 4),
+    "itcv_irs": (i32, [p, sz, p, p, i32, i32, i32, p, f64] + [p] * 10 + [p, sz, p]),
     "itcv_recon_workspace": (sz, [i32, sz]),
     "itcv_recon_rows_fwd": (i32, [p, p, p, i32, sz, i32, p, sz, p]),
     "itcv_recon_rows_bwd": (i32, [p, p, p, p, i32, sz, i32, p]),

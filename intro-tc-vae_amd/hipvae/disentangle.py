@@ -40,6 +40,30 @@ usual seven-metric table.  Both are fixed rules (include/itcv_hip.h, csrc/extra_
 classifier on integer vote tables, one wave per group of images with one factor held fixed; SAP's default form fits
 ``D x sum(sizes)`` two-parameter squared-hinge classifiers (liblinear's ``LinearSVC(C=0.01, class_weight="balanced")``
 objective, whose optimum is unique) to convergence in one launch and counts correct test predictions as integers.
+
+The unsupervised scores and IRS (disentanglement_lib's ``unsupervised_metrics`` and ``irs``; not in the reference) are
+fixed rules too (include/itcv_hip.h, csrc/unsup_scores.hip), all in fp64 on the fp32 representations ``x[N][D]``, every
+reduction in a fixed order, no floating-point atomics, the same bits from run to run:
+
+* covariance: ``m[d] = (sum_n x[n][d]) / N``, ``C[i][j] = sum_n (x[n][i] - m[i]) (x[n][j] - m[j]) / (N - 1)`` (two passes
+  over centred values as ``np.cov``; the products on the f64 matrix cores; one triangle mirrored);  N >= 2, D <= 512.
+* Gaussian total correlation ``tc = (sum_d log C[d][d] - logdet C) / 2``, ``logdet C = 2 sum_d log L[d][d]`` from the
+  Cholesky factor.  C must be positive definite: a pivot <= 0 raises ``ValueError`` naming the dimension (the library
+  returns nan or inf there).
+* Gaussian Wasserstein correlation ``w = 2 tr C - 2 sum_i sqrt(max(lambda_i(S), 0))``, ``S = D^1/2 C D^1/2``, ``D =
+  diag(C)`` (similar to the matrix whose ``sqrtm`` the library takes); ``lambda`` by a cyclic Jacobi iteration with a
+  fixed round-robin rotation order, stopped at ``off(S)_F <= 1e-14 |S|_F``, ``RuntimeError`` after 60 sweeps;
+  ``w_norm = w / tr C``.
+* mutual information score: every column in 20 bins by ``discretize``; ``MI[i][j]`` in nats between the bin numbers of
+  columns i and j (the existing histogram and MI kernels, 16 columns a call; the upper triangle mirrored); the score is
+  ``sum_{i != j} MI[i][j] / (D^2 - D)``, ``nan`` for D = 1 as in the library.
+* IRS: active dimensions are those with min < max (the library tests var > 0, whose result for a constant column depends
+  on rounding); ``maxdev[d] = max_n |x[n][d] - m[d]|``; for every factor k and every value v present in the sample, with
+  G its rows and n = |G|: ``e[d]`` the mean of the group, ``a`` the ascending sort of ``|x[g][d] - e[d]|``, ``h = (n - 1)
+  q`` (q = 0.99), ``lo = floor(h)``, ``t = h - lo``, ``hi = min(lo + 1, n - 1)``, ``Q = a[lo] + (a[hi] - a[lo]) t`` if
+  ``t < 0.5`` else ``a[hi] - (a[hi] - a[lo]) (1 - t)`` (``np.percentile``, bit for bit; the two order statistics are
+  selected exactly); ``cum[d][k] = (sum_v Q) / #present``; ``M = 1 - cum / maxdev``; ``score[d] = max_k M[d][k]``,
+  ``parent[d]`` its first arg-max; ``IRS = sum_d score[d] maxdev[d] / sum_d maxdev[d]``; no active dimension: 0.0.
 """
 import numpy as np
 import torch
@@ -53,7 +77,9 @@ __all__ = ["discretize", "factor_counts", "mutual_info", "mig_score", "modularit
            "fit_softmax", "factor_change_accuracy", "explicitness", "factor_change_rows", "compute_bvae_score",
            "compute_explicitness_score", "compute_mod_expl_score", "fit_boosted_trees", "dci_completeness",
            "dci_disentanglement", "dci", "compute_dci_score", "factor_vae_votes", "factor_vae_score",
-           "compute_factor_vae_score", "fit_sap_classifiers", "sap_score_matrix", "sap_score", "compute_sap_score"]
+           "compute_factor_vae_score", "fit_sap_classifiers", "sap_score_matrix", "sap_score", "compute_sap_score",
+           "covariance", "unsupervised_scores", "gaussian_scores", "compute_unsupervised_scores", "irs_score_matrix",
+           "irs_score", "compute_irs_score"]
 
 
 def _raise_on(flags):
@@ -636,3 +662,123 @@ def compute_sap_score(latent_generator, model, num_train=10000, num_test=5000, b
     xte, yte = factor_representations(latent_generator, model, int(params.get("num_test", num_test)), bs)
     return sap_score(xtr, ytr, xte, yte, _latent_sizes(latent_generator), params.get("continuous_factors", False),
                      params.get("C", 0.01), params.get("gtol", 1e-10), params.get("max_iter", 100))
+
+
+# ---- unsupervised scores: Gaussian total correlation, Gaussian Wasserstein correlation, mutual information ----------
+_MI_BINS = 20          # disentanglement_lib's unsupervised_metrics discretises every latent into 20 bins
+_MI_CHUNK = 16         # factors per call of the histogram / MI kernels (kDisMaxK)
+
+
+def covariance(mu):
+    """``(mean [D], cov [D, D])`` as fp64 device tensors: the ddof = 1 covariance of ``mu [N >= 2, D <= 512]`` (``np.cov``'s
+    two passes over centred values; rule: include/itcv_hip.h), symmetric bit for bit."""
+    flags = HF.disent_flags(mu.device)
+    mean, cov = HF.unsup_cov(mu, flags)
+    _raise_on(flags.tolist())
+    return mean, cov
+
+
+def _mutual_info_matrix(mu, flags):
+    """fp64 ``MI [D, D]``: the mutual information in nats of the bin numbers of every pair of columns.  The bin numbers
+    minus 1 are handed to the histogram and MI kernels as "factors" of size 20, 16 columns a call; the upper triangle is
+    kept and mirrored."""
+    N, D = mu.shape
+    mn, mx = HF.disent_minmax(mu, flags)
+    b = HF.disent_bins(mu, mn, mx, _MI_BINS) - 1
+    cols = []
+    for c0 in range(0, D, _MI_CHUNK):
+        f = b[:, c0:c0 + _MI_CHUNK].contiguous()
+        sizes = [_MI_BINS] * f.shape[1]
+        counts, vcount = HF.disent_hist(mu, f, sizes, mn, mx, _MI_BINS, flags)
+        cols.append(HF.disent_mi(counts, vcount, N, D, sizes, _MI_BINS)[0])
+    mi = torch.cat(cols, 1)
+    return torch.triu(mi) + torch.triu(mi, 1).t()
+
+
+def unsupervised_scores(mu):
+    """The unsupervised scores of ``mu [N >= 2, D <= 512]`` (disentanglement_lib's ``unsupervised_metrics``; rules:
+    include/itcv_hip.h): the floats ``gaussian_total_correlation``, ``gaussian_wasserstein_correlation``,
+    ``gaussian_wasserstein_correlation_norm`` and ``mutual_info_score`` (``nan`` for D = 1), and the fp64 device tensors
+    ``covariance [D, D]``, ``eigenvalues [D]`` (of S = D^1/2 C D^1/2, ascending) and ``mutual_info_matrix [D, D]``.  The
+    covariance must be positive definite: a Cholesky pivot <= 0 (a constant column, two identical columns) raises
+    ``ValueError`` naming the dimension, where the library returns nan or inf.  One host read-back."""
+    flags = HF.disent_flags(mu.device)
+    _, cov = HF.unsup_cov(mu, flags)
+    res, eig, info = HF.unsup_gauss(cov)
+    mi = _mutual_info_matrix(mu, flags)
+    D = mu.shape[1]
+    off = mi.masked_fill(torch.eye(D, dtype=torch.bool, device=mi.device), 0.0)
+    mis = off.sum() / torch.full((), float(D * D - D), dtype=torch.float64, device=mi.device)
+    out = torch.cat([res, mis.reshape(1), info.to(torch.float64), flags.to(torch.float64)]).tolist()
+    _raise_on(out[10:12])
+    _raise_on_gauss(out[6:10])
+    return dict(gaussian_total_correlation=out[0], gaussian_wasserstein_correlation=out[1],
+                gaussian_wasserstein_correlation_norm=out[2], mutual_info_score=out[5], covariance=cov,
+                eigenvalues=torch.sort(eig).values, mutual_info_matrix=mi)
+
+
+def _raise_on_gauss(info):
+    if info[0]:
+        raise ValueError(f"unsupervised scores: the covariance is not positive definite (the Cholesky pivot of dimension "
+                         f"{int(info[1])} is not positive: a constant column, or one that depends linearly on the ones "
+                         "before it)")
+    if info[2]:
+        raise RuntimeError("unsupervised scores: the Jacobi iteration did not converge in 60 sweeps")
+
+
+def gaussian_scores(cov):
+    """``(tc, w, w_norm, eigenvalues)`` of a given symmetric fp64 device ``cov [D, D]``: the Cholesky / Jacobi launch
+    alone (the eigenvalues of S in the kernel's index order, a device tensor)."""
+    res, eig, info = HF.unsup_gauss(cov)
+    out = torch.cat([res, info.to(torch.float64)]).tolist()
+    _raise_on_gauss(out[5:9])
+    return out[0], out[1], out[2], eig
+
+
+def compute_unsupervised_scores(source, model, num_train=10000, batch_size=64, seed=0):
+    """``unsupervised_scores`` of the mean representations of ``num_train`` images of ``source`` (a ``DeviceImageTable``
+    or a dataset; no factors are needed): the images ``np.sort(RandomState(seed).choice(len(source), num_train,
+    replace=False))``, or all of them when ``num_train >= len(source)``, encoded by ``hipvae.aggregate.
+    dataset_posteriors`` in eval mode without gradients.  torch's generators, the BatchNorm buffers and the training flag
+    are left as found."""
+    from . import aggregate
+    n = len(source)
+    if int(num_train) >= n:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.RandomState(seed).choice(n, int(num_train), replace=False)).astype(np.int64)
+    mu, _ = aggregate.dataset_posteriors(source, model, idx, batch_size)
+    return unsupervised_scores(mu)
+
+
+# ---- IRS: interventional robustness score ----------------------------------------------------------------------------
+def irs_score_matrix(mu, factors, factor_sizes, diff_quantile=0.99):
+    """Everything the IRS is made of (Suter et al. 2019; disentanglement_lib's ``irs.scalable_disentanglement_score`` on the
+    active dimensions; rule: include/itcv_hip.h): ``avg_score`` (the IRS, a float), ``num_active_dims`` (int) and, over the
+    active dimensions only, the device tensors ``disentanglement_scores [A]``, ``parents [A]`` (int64), ``IRS_matrix
+    [A, K]``, ``max_deviations [A]``, ``cum_deviations [A, K]``; ``active_dims [A]`` lists them.  A dimension is active iff
+    its minimum is below its maximum (the library tests var > 0, whose result for a constant column depends on rounding).
+    No active dimension: ``avg_score`` 0.0."""
+    flags = HF.disent_flags(mu.device)
+    mn, mx = HF.disent_minmax(mu, flags)
+    got = HF.irs(mu, factors, factor_sizes, mn, mx, flags, diff_quantile)
+    out = torch.cat([got["res"], flags.to(torch.float64)]).tolist()
+    _raise_on(out[2:])
+    act = got["active"].nonzero().reshape(-1)
+    return dict(avg_score=out[0], num_active_dims=int(out[1]), disentanglement_scores=got["score"][act],
+                parents=got["parent"][act].long(), IRS_matrix=got["M"][act], max_deviations=got["maxdev"][act],
+                cum_deviations=got["cum"][act], active_dims=act)
+
+
+def irs_score(mu, factors, factor_sizes, diff_quantile=0.99):
+    """The IRS alone, a Python float."""
+    return irs_score_matrix(mu, factors, factor_sizes, diff_quantile)["avg_score"]
+
+
+def compute_irs_score(latent_generator, model, num_train=10000, batch_size=64, params=None):
+    """``irs_score_matrix`` of ``num_train`` sampled images encoded in eval mode (``factor_representations``); ``params``
+    may override ``num_train`` / ``batch_size`` and carry ``diff_quantile``.  The IRS is ``["avg_score"]``."""
+    params = params or {}
+    mu, v = factor_representations(latent_generator, model, int(params.get("num_train", num_train)),
+                                   int(params.get("batch_size", batch_size)))
+    return irs_score_matrix(mu, v, _latent_sizes(latent_generator), params.get("diff_quantile", 0.99))

@@ -2045,3 +2045,63 @@ def sap_svc_score(x, y, class_sizes, cvalid, theta, flags, with_pred=False):
     call("itcv_sap_svc_score", x.data_ptr(), x.stride(0), ptr(y), Nt, D, K, csizes, ptr(cvalid), ptr(theta), ptr(correct),
          ptr(pred), ptr(flags), stream())
     return (correct, pred) if with_pred else correct
+
+
+# ------------------------------------------------------------------ unsupervised scores and IRS (csrc/unsup_scores.hip)
+def unsup_cov(x, flags):
+    """fp64 ``(mean [D], cov [D, D])`` of x[N, D], N >= 2: the ddof = 1 covariance of the centred values, symmetric bit
+    for bit; sets flags[0] on a non-finite element."""
+    if x.dim() == 2 and x.shape[0] < 2:
+        raise ValueError(f"covariance: at least 2 rows are needed (got {x.shape[0]})")
+    x = _disent_mu(x)
+    N, D = x.shape
+    mean = torch.empty((D,), dtype=F64, device=x.device)
+    cov = torch.empty((D, D), dtype=F64, device=x.device)
+    nws = lib.itcv_unsup_cov_workspace(N, D)                            # 0 for what the call below refuses
+    ws = _ws(nws, x.device)
+    call("itcv_unsup_cov", x.data_ptr(), x.stride(0), N, D, ptr(mean), ptr(cov), ptr(flags), ptr(ws), nws, stream())
+    return mean, cov
+
+
+def unsup_gauss_lds_dim():
+    """Largest D whose matrix itcv_unsup_gauss keeps in LDS (above: in its global workspace)."""
+    return lib.itcv_unsup_gauss_lds_dim()
+
+
+def unsup_gauss(cov):
+    """``(res [5] fp64 = tc, w, w_norm, tr C, logdet C; eig [D] fp64; info [4] int32 = pivot failed, its dimension, Jacobi
+    did not converge, sweeps)`` of a symmetric fp64 ``cov [D, D]``: one launch, nothing is read back."""
+    cov = _gbt_dense(cov, F64, "cov")
+    if cov.dim() != 2 or cov.shape[0] != cov.shape[1] or cov.shape[0] < 1:
+        raise abi.HipExtensionError(f"unsup: the covariance must be a square [D, D] tensor (got {tuple(cov.shape)})")
+    D = cov.shape[0]
+    res = torch.empty((5,), dtype=F64, device=cov.device)
+    eig = torch.empty((D,), dtype=F64, device=cov.device)
+    info = torch.empty((4,), dtype=torch.int32, device=cov.device)
+    nws = lib.itcv_unsup_gauss_workspace(D)
+    ws = _ws(nws, cov.device)
+    call("itcv_unsup_gauss", ptr(cov), D, ptr(res), ptr(eig), ptr(info), ptr(ws), nws, stream())
+    return res, eig, info
+
+
+def irs(x, factors, factor_sizes, mn, mx, flags, diff_quantile=0.99):
+    """The IRS rule of include/itcv_hip.h on x[N, D] / factors[N, K]: a dict of device tensors ``maxdev [D]``, ``cum
+    [D, K]``, ``M [D, K]``, ``score [D]`` (fp64), ``parent [D]``, ``active [D]`` (int32) and ``res [2]`` (IRS, number of
+    active dimensions).  The rows of every factor value are made contiguous by one stable device sort of the factor
+    columns; sets flags[1] on a factor value outside its range."""
+    x = _disent_mu(x)
+    N, D = x.shape
+    v, sizes, csizes = _disent_factors(factors, factor_sizes, N, x.device)
+    K, fsum = len(sizes), sum(sizes)
+    order = torch.sort(v.t().contiguous(), dim=1, stable=True).indices.to(torch.int32).contiguous() if K else v
+    dev = x.device
+    out = dict(maxdev=torch.empty((D,), dtype=F64, device=dev), cum=torch.empty((D, max(K, 1)), dtype=F64, device=dev),
+               M=torch.empty((D, max(K, 1)), dtype=F64, device=dev), score=torch.empty((D,), dtype=F64, device=dev),
+               parent=torch.empty((D,), dtype=torch.int32, device=dev),
+               active=torch.empty((D,), dtype=torch.int32, device=dev), res=torch.empty((2,), dtype=F64, device=dev))
+    nws = lib.itcv_irs_workspace(N, D, K, fsum)                         # 0 for what the call below refuses
+    ws = _ws(nws, dev)
+    call("itcv_irs", x.data_ptr(), x.stride(0), ptr(v), ptr(order), N, D, K, csizes, float(diff_quantile), ptr(mn), ptr(mx),
+         ptr(out["maxdev"]), ptr(out["cum"]), ptr(out["M"]), ptr(out["score"]), ptr(out["parent"]), ptr(out["active"]),
+         ptr(out["res"]), ptr(flags), ptr(ws), nws, stream())
+    return out

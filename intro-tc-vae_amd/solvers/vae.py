@@ -55,13 +55,16 @@ class VAESolver:
         self.device_scores = None
         self.dci_params = None       # ``params`` of hipvae.disentangle.compute_dci_score (None: 100 rounds, depth 6)
         # scores the reference does not have, written from the device on top of the above: a tuple drawn from
-        # {"factor_vae", "sap", "elbo_decomposition"}; ``params`` of hipvae.disentangle.compute_factor_vae_score /
-        # compute_sap_score; keyword arguments of hipvae.aggregate.compute_elbo_decomposition (None: its defaults, with
-        # this solver's batch size)
+        # {"factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised"}; ``params`` of
+        # hipvae.disentangle.compute_factor_vae_score / compute_sap_score / compute_irs_score; keyword arguments of
+        # hipvae.aggregate.compute_elbo_decomposition / hipvae.disentangle.compute_unsupervised_scores (None: their
+        # defaults, with this solver's batch size)
         self.extra_scores = ()
         self.factor_vae_params = None
         self.sap_params = None
         self.elbo_params = None
+        self.irs_params = None
+        self.unsupervised_params = None
         self._device_table = None
         self.recon_loss_type = recon_loss_type
         self.scale = 1 / (self.model.cdim * self.model.encoder.image_size ** 2)   # solvers/vae.py:61
@@ -339,18 +342,24 @@ class VAESolver:
         eval_accuracy} and / or ``sap_score`` from the device (hipvae.disentangle; neither is in the reference), and
         with "elbo_decomposition" the record ``aggregate_decomp`` {mi, tc, dwkl, kl, kl_analytic}: the decomposition of
         the aggregate KL over the dataset's aggregate posterior (hipvae.aggregate; ``elbo_params``).  That one needs no
-        factors, so it is written for any dataset, from the device table when ``use_device_dataset`` was called."""
+        factors, so it is written for any dataset, from the device table when ``use_device_dataset`` was called.
+        "irs" is a factor score: the record ``irs`` {IRS, num_active_dims} (``irs_params``).  "unsupervised" needs no
+        factors either and is read like the decomposition: the record ``unsupervised`` {gaussian_total_correlation,
+        gaussian_wasserstein_correlation, gaussian_wasserstein_correlation_norm, mutual_info_score}
+        (``unsupervised_params``)."""
         extras = tuple(self.extra_scores or ())
         with_elbo = "elbo_decomposition" in extras
+        with_unsup = "unsupervised" in extras
         factored = isinstance(self.dataset, DisentanglementDataset)
-        if self.writer is None or not (factored or with_elbo) or cur_iter % self.test_iter:
+        if self.writer is None or not (factored or with_elbo or with_unsup) or cur_iter % self.test_iter:
             return
-        known = ("factor_vae", "sap", "elbo_decomposition")
+        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised")
         unknown = [e for e in extras if e not in known]
         if unknown:
             raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, known))})")
         if factored:
-            self._write_factor_scores(cur_iter, num_samples, tuple(e for e in extras if e != "elbo_decomposition"))
+            self._write_factor_scores(cur_iter, num_samples,
+                                      tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised")))
         if with_elbo:
             from hipvae import aggregate
             kw = dict(batch_size=self.batch_size)
@@ -359,6 +368,15 @@ class VAESolver:
                                                        self.model, **kw)
             self.writer.add_scalars("aggregate_decomp", {k: got[k] for k in ("mi", "tc", "dwkl", "kl", "kl_analytic")},
                                     global_step=cur_iter)
+        if with_unsup:
+            from hipvae import disentangle
+            kw = dict(batch_size=self.batch_size)
+            kw.update(self.unsupervised_params or {})
+            got = disentangle.compute_unsupervised_scores(self.dataset if self._device_table is None else self._device_table,
+                                                          self.model, **kw)
+            self.writer.add_scalars("unsupervised", {k: got[k] for k in (
+                "gaussian_total_correlation", "gaussian_wasserstein_correlation", "gaussian_wasserstein_correlation_norm",
+                "mutual_info_score")}, global_step=cur_iter)
 
     def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: tuple):
         """The factor-based scores of ``write_disentanglemnt_scores`` (a ``DisentanglementDataset``, at a test iteration)."""
@@ -410,6 +428,11 @@ class VAESolver:
         if "sap" in extras:
             self.writer.add_scalar("sap_score", disentangle.compute_sap_score(
                 self.latent_generator, self.model, batch_size=self.batch_size, params=self.sap_params), global_step=cur_iter)
+        if "irs" in extras:
+            got = disentangle.compute_irs_score(self.latent_generator, self.model, batch_size=self.batch_size,
+                                                params=self.irs_params)
+            self.writer.add_scalars("irs", dict(IRS=got["avg_score"], num_active_dims=got["num_active_dims"]),
+                                    global_step=cur_iter)
         if was_training:
             self.model.train()
 
