@@ -719,6 +719,46 @@ int itcv_irs(const float* x, size_t ld, const int* v, const int* order, int N, i
              const float* mn, const float* mx, double* maxdev, double* cum, double* M, double* score, int* parent,
              int* active, double* res, int* flags, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- UDR: tie-averaged ranks and the Lasso matrix (not in the reference; Duan et al. 2020) ------------------------ */
+/* The two device primitives of the Unsupervised Disentanglement Ranking (disentanglement_lib's `udr`); fixed rules, no
+ * floating-point atomics, nothing depends on the grid: same inputs, same bits.
+ *
+ * Ranks.  x[N][D] fp32 (row stride ld elements; nothing left of a strided view is read), r2[N][D] fp32 dense:
+ *   r2[n][d] = L + H + 1,  L = #{m : x[m][d] < x[n][d]},  H = #{m : x[m][d] <= x[n][d]},
+ *   twice scipy.stats.rankdata's average rank: an integer <= 2 N, exact in fp32 up to N = 2^23 (rounded to nearest above).
+ *   The comparison is numeric: -0.0 equals +0.0, denormals are ordinary values.  A non-finite element sets flags[0] as in
+ *   itcv_unsup_cov; r2 is then unspecified.  One block per column: every value becomes a monotone uint32 key (u = bits of
+ *   x, +-0 -> 0; key = ~u if the sign bit is set, else u | 2^31), the keys of the column are sorted in place (a bitonic
+ *   network whose exchanges all point upwards, so any N needs no padding), and every row finds L and H by two binary
+ *   searches.  The sorted keys sit in LDS up to N = itcv_udr_rank_lds_rows() (32768 keys = 128 KiB of the 160 KiB; the
+ *   in-place sort needs nothing else), above that in the workspace (itcv_udr_ranks_workspace: N D uint32, else 0).
+ *   Supported: 2 <= N <= 2^24, 1 <= D <= 512 (the limits of itcv_unsup_cov).
+ * Lasso.  cov: the fp64 covariance [(Da + Db)][(Da + Db)] of the concatenated columns [a | b] as itcv_unsup_cov writes it.
+ *   1. R[k][l] = C[k][l] / sqrt(C[k][k] C[l][l]); a column with C[k][k] == 0 (exactly what the covariance's two centred
+ *      passes give for a constant fp32 column) has row and column k of R equal to 0, the diagonal included.  This is
+ *      StandardScaler followed by sklearn.linear_model.Lasso(alpha) with its intercept: the 1 / n factors cancel.
+ *   2. For every target column t of b: G = R[:Da][:Da], c = R[:Da][Da + t], w_t = argmin 1/2 w'Gw - c'w + alpha |w|_1 by
+ *      cyclic coordinate descent in index order from w = 0:
+ *        w[k] <- S(c[k] - sum_{l != k} G[k][l] w[l], alpha) / G[k][k],   S(r, a) = r - a if r > a, r + a if r < -a, else 0;
+ *      a coordinate with G[k][k] == 0 stays 0.  The sum is taken by one wave: lane i adds its terms l = i, i + 64, ... in
+ *      ascending l, the 64 partial sums are folded by the xor butterfly (32, 16, .., 1).
+ *   3. After every sweep: g = G w - c (the same sum, l == k included),
+ *        v = max_k (w[k] != 0 ? |g[k] + alpha sign(w[k])| : max(|g[k]| - alpha, 0)).
+ *      Stop at v <= gtol (a nan never stops); otherwise stop after max_sweeps sweeps.
+ *   4. W[Da][Db] fp64, W[k][t] = |w_t[k]| (rows of a, columns of b: the library's transpose(abs(coef_))).
+ *      info[3] = {some target did not reach gtol, how many, the largest number of sweeps any target took}.
+ *   One wave per target, eight targets a block, one launch; G sits in LDS up to Da = 128, above that its rows are read
+ *   from the normalised copy in the workspace (itcv_udr_lasso_workspace).  All arithmetic is fp64, every operation rounded
+ *   on its own.  Supported: Da, Db >= 1, Da + Db <= 512, alpha >= 0 finite, gtol >= 0, max_sweeps >= 1.
+ * Anything unsupported returns non-zero before a launch; the workspace queries return 0 for it. */
+int itcv_udr_rank_lds_rows(void);
+size_t itcv_udr_ranks_workspace(int N, int D);
+int itcv_udr_ranks(const float* x, size_t ld, int N, int D, float* r2, int* flags, void* ws, size_t ws_bytes,
+                   void* stream);
+size_t itcv_udr_lasso_workspace(int Da, int Db);
+int itcv_udr_lasso(const double* cov, int Da, int Db, double alpha, double gtol, int max_sweeps, double* W, int* info,
+                   void* ws, size_t ws_bytes, void* stream);
+
 /* ---- reconstruction loss (ops.py:188-236) --------------------------------------------- */
 #define ITCV_LOSS_MSE 0
 #define ITCV_LOSS_L1 1

@@ -182,6 +182,11 @@ SIGNATURES = {
     "itcv_unsup_gauss": (i32, [p, i32, p, p, p, p, sz, p]),
     "itcv_irs_workspace": (sz, [i32] * 4),
     "itcv_irs": (i32, [p, sz, p, p, i32, i32, i32, p, f64] + [p] * 10 + [p, sz, p]),
+    "itcv_udr_rank_lds_rows": (i32, []),
+    "itcv_udr_ranks_workspace": (sz, [i32, i32]),
+    "itcv_udr_ranks": (i32, [p, sz, i32, i32, p, p, p, sz, p]),
+    "itcv_udr_lasso_workspace": (sz, [i32, i32]),
+    "itcv_udr_lasso": (i32, [p, i32, i32, f64, f64, i32, p, p, p, sz, p]),
     "itcv_recon_workspace": (sz, [i32, sz]),
     "itcv_recon_rows_fwd": (i32, [p, p, p, i32, sz, i32, p, sz, p]),
     "itcv_recon_rows_bwd": (i32, [p, p, p, p, i32, sz, i32, p]),

@@ -64,6 +64,21 @@ reduction in a fixed order, no floating-point atomics, the same bits from run to
   ``t < 0.5`` else ``a[hi] - (a[hi] - a[lo]) (1 - t)`` (``np.percentile``, bit for bit; the two order statistics are
   selected exactly); ``cum[d][k] = (sum_v Q) / #present``; ``M = 1 - cum / maxdev``; ``score[d] = max_k M[d][k]``,
   ``parent[d]`` its first arg-max; ``IRS = sum_d score[d] maxdev[d] / sum_d maxdev[d]``; no active dimension: 0.0.
+
+The Unsupervised Disentanglement Ranking (Duan et al. 2020; disentanglement_lib's ``udr``; not in the reference) needs no
+factors: M >= 2 models encode the same N images, and a model ranks high when each of its informative latents matches
+exactly one latent of every other model.  Fixed rules (include/itcv_hip.h, csrc/udr.hip):
+
+* ``kl_d = mean_n (mu^2 + exp(logvar) - logvar - 1) / 2`` per model and dimension in fp64; a dimension is informative iff
+  ``kl_d > kl_filter_threshold`` (0.01).
+* the similarity of the latents of models i and j, a matrix ``[D_i, D_j]``: in the Spearman form ``|R|`` of the cross block
+  of the covariance of the doubled tie-averaged ranks ``[r2(a) | r2(b)]`` (``r2 = L + H + 1``, exact integers),
+  ``R_kl = C_kl / sqrt(C_kk C_ll)`` with the row and column of a constant column set to 0; in the Lasso form (the library's
+  default) ``|w|`` of the Lasso (alpha = 0.1) that predicts each standardised latent of j from the standardised latents of
+  i, solved by cyclic coordinate descent on the same normalised covariance until the subgradient condition holds to 1e-12.
+* ``relative_strength``: ``sx = mean_j (max_i c_ij)^2 / sum_i c_ij`` over the informative rows and columns, ``sy`` the same
+  over rows, a term whose sum is 0 counts as 0, the result ``(sx + sy) / 2``; all sums in index order.
+* ``model_scores[i]``: the median over ``j != i`` of the non-nan ``pairwise[j, i]``.
 """
 import numpy as np
 import torch
@@ -79,7 +94,8 @@ __all__ = ["discretize", "factor_counts", "mutual_info", "mig_score", "modularit
            "dci_disentanglement", "dci", "compute_dci_score", "factor_vae_votes", "factor_vae_score",
            "compute_factor_vae_score", "fit_sap_classifiers", "sap_score_matrix", "sap_score", "compute_sap_score",
            "covariance", "unsupervised_scores", "gaussian_scores", "compute_unsupervised_scores", "irs_score_matrix",
-           "irs_score", "compute_irs_score"]
+           "irs_score", "compute_irs_score", "spearman_matrix", "lasso_matrix", "relative_strength", "udr_scores",
+           "compute_udr_score"]
 
 
 def _raise_on(flags):
@@ -782,3 +798,197 @@ def compute_irs_score(latent_generator, model, num_train=10000, batch_size=64, p
     mu, v = factor_representations(latent_generator, model, int(params.get("num_train", num_train)),
                                    int(params.get("batch_size", batch_size)))
     return irs_score_matrix(mu, v, _latent_sizes(latent_generator), params.get("diff_quantile", 0.99))
+
+
+# ---- UDR: unsupervised disentanglement ranking -----------------------------------------------------------------------
+def _ordered_sum(t, dim):
+    """The sum of ``t`` along ``dim`` taken slice by slice in index order, so that the bits are defined (as ``_sap``)."""
+    parts = t.unbind(dim)
+    tot = parts[0]
+    for part in parts[1:]:
+        tot = tot + part
+    return tot
+
+
+def _correlation_of(cov):
+    """``R_kl = C_kl / sqrt(C_kk C_ll)`` of a covariance; the row and column of a column with ``C_kk == 0`` are 0."""
+    d = torch.diagonal(cov)
+    live = (d != 0)[:, None] & (d != 0)[None, :]
+    return torch.where(live, cov / torch.sqrt(d[:, None] * d[None, :]), torch.zeros_like(cov))
+
+
+def _spearman(a, b, flags):
+    cols = torch.cat([HF.udr_ranks(a, flags), HF.udr_ranks(b, flags)], 1)
+    _, cov = HF.unsup_cov(cols, flags)
+    return _correlation_of(cov)[:a.shape[1], a.shape[1]:].abs().contiguous()
+
+
+def _same_rows(a, b):
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"udr: the representations must be [N, D_i] tensors of the same N inputs (got {tuple(a.shape)} "
+                         f"and {tuple(b.shape)})")
+    if a.shape[1] + b.shape[1] > 512:
+        raise ValueError(f"udr: the two models have {a.shape[1]} + {b.shape[1]} latents, more than 512 together")
+
+
+def spearman_matrix(a, b):
+    """fp64 device ``[Da, Db]``: ``|rho|`` of Spearman's rank correlation (ties averaged, as ``scipy.stats.spearmanr``)
+    between every column of ``a [N, Da]`` and every column of ``b [N, Db]``; a constant column gives zeros.  Exact ranks by
+    ``itcv_udr_ranks``, their covariance by ``itcv_unsup_cov``."""
+    _same_rows(a, b)
+    flags = HF.disent_flags(a.device)
+    out = _spearman(a, b, flags)
+    _raise_on(flags.tolist())
+    return out
+
+
+def _raise_on_lasso(info):
+    if info[0]:
+        raise RuntimeError(f"udr: the Lasso coordinate descent did not converge for {int(info[1])} target(s) in "
+                           f"{int(info[2])} sweeps (raise max_sweeps or gtol)")
+
+
+def lasso_matrix(a, b, alpha=0.1, gtol=1e-12, max_sweeps=1000):
+    """fp64 device ``[Da, Db]``: column t holds ``|w|`` of the Lasso that predicts the standardised column t of ``b`` from
+    the standardised columns of ``a`` (``StandardScaler`` + ``sklearn.linear_model.Lasso(alpha)``, the library's
+    ``transpose(abs(coef_))``), solved to ``gtol`` in the subgradient condition; ``RuntimeError`` when ``max_sweeps``
+    sweeps do not reach it."""
+    _same_rows(a, b)
+    flags = HF.disent_flags(a.device)
+    _, cov = HF.unsup_cov(torch.cat([HF._disent_mu(a), HF._disent_mu(b)], 1), flags)
+    W, info = HF.udr_lasso(cov, a.shape[1], b.shape[1], alpha, gtol, max_sweeps)
+    out = torch.cat([flags, info]).tolist()
+    _raise_on(out[:2])
+    _raise_on_lasso(out[2:])
+    return W
+
+
+def _relative_strength(corr, rows, cols):
+    """``relative_strength`` of ``corr[rows][:, cols]`` (boolean device masks) without compacting it: a masked entry enters
+    the ordered sums as +0, which changes no bit of a sum of non-negative terms, and never wins a maximum.  Leading
+    dimensions are a batch: ``corr [..., Da, Db]``, ``rows [..., Da]``, ``cols [..., Db]`` give one score each from the same
+    elementwise operations, so the bits do not depend on the batch."""
+    zero = torch.zeros((), dtype=torch.float64, device=corr.device)
+    c = torch.where(rows[..., :, None] & cols[..., None, :], corr, zero)
+
+    def side(c, keep, n):
+        top, tot = c.max(dim=-2).values, _ordered_sum(c, -2)
+        term = torch.where(keep & (tot != 0), top * top / tot, zero)
+        return _ordered_sum(term, -1) / n
+
+    nr, nc = rows.sum(-1).to(torch.float64), cols.sum(-1).to(torch.float64)
+    score = (side(c, cols, nc) + side(c.transpose(-1, -2), rows, nr)) / 2.0
+    return torch.where((nr > 0) & (nc > 0), score, torch.full_like(zero, float("nan")))
+
+
+def relative_strength(corr):
+    """0-dim fp64 device tensor: ``(sx + sy) / 2`` with ``sx = mean_j (max_i c_ij)^2 / sum_i c_ij`` and ``sy`` the same
+    over rows (disentanglement_lib's ``relative_strength_disentanglement``); a term whose sum is 0 counts as 0, a matrix
+    with no rows or no columns gives nan.  The sums run in index order."""
+    if corr.dim() != 2 or corr.dtype != torch.float64 or not corr.is_cuda:
+        raise HF.abi.HipExtensionError("udr: relative_strength needs an fp64 [Da, Db] device tensor; there is no CPU path")
+    if corr.shape[0] == 0 or corr.shape[1] == 0:
+        return torch.full((), float("nan"), dtype=torch.float64, device=corr.device)
+    return _relative_strength(corr, torch.ones(corr.shape[0], dtype=torch.bool, device=corr.device),
+                              torch.ones(corr.shape[1], dtype=torch.bool, device=corr.device))
+
+
+def _median(values):
+    v = sorted(values)
+    n = len(v)
+    if not n:
+        return float("nan")
+    return v[n // 2] if n % 2 else (v[n // 2 - 1] + v[n // 2]) / 2.0
+
+
+def udr_scores(mus, logvars=None, correlation="lasso", kl_filter_threshold=0.01, alpha=0.1):
+    """The Unsupervised Disentanglement Ranking of M >= 2 models from their mean representations ``mus[i] [N, D_i]`` (and
+    ``logvars[i]``) of the same N inputs.  A dict: ``model_scores`` (M floats: the median over the other models j of the
+    non-nan ``pairwise[j, i]``, nan if there is none), ``pairwise_disentanglement_scores`` (fp64 numpy ``[M, M]``, nan on the
+    diagonal: ``relative_strength`` of the similarity matrix of (i, j) restricted to the informative dimensions of both),
+    ``raw_correlations`` ((i, j) -> the unrestricted fp64 device matrix ``[D_i, D_j]``), ``kl_masks`` (bool numpy arrays,
+    ``kl_divergence > kl_filter_threshold``; everything when ``logvars`` is None) and ``kl_divergence`` (fp64 numpy arrays,
+    None without ``logvars``).  ``correlation``: "lasso" (the library's default) or "spearman".  One covariance per
+    unordered pair, one host read-back."""
+    if correlation not in ("lasso", "spearman"):
+        raise ValueError(f"udr: correlation must be 'lasso' or 'spearman' (got {correlation!r})")
+    mus = [HF._disent_mu(m) for m in mus]
+    M = len(mus)
+    if M < 2:
+        raise ValueError(f"udr: at least two models are needed (got {M})")
+    if logvars is not None and (len(logvars) != M or any(lv.shape != m.shape for lv, m in zip(logvars, mus))):
+        raise ValueError("udr: logvars must match mus, one [N, D_i] tensor per model")
+    for m in mus[1:]:
+        _same_rows(mus[0], m)
+    dev = mus[0].device
+    flags = HF.disent_flags(dev)
+    if logvars is None:
+        kls = None
+        masks = [torch.ones(m.shape[1], dtype=torch.bool, device=dev) for m in mus]
+    else:
+        kls = []
+        for m, lv in zip(mus, logvars):
+            m64, lv64 = m.to(torch.float64), lv.detach().to(torch.float64)
+            kls.append((0.5 * (m64 * m64 + torch.exp(lv64) - lv64 - 1.0)).mean(0))
+        masks = [k > kl_filter_threshold for k in kls]
+    raw, infos = {}, []
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    pair = [[nan] * M for _ in range(M)]
+    for i in range(M):
+        for j in range(i + 1, M):
+            Di, Dj = mus[i].shape[1], mus[j].shape[1]
+            if correlation == "spearman":
+                raw[i, j] = _spearman(mus[i], mus[j], flags)
+                raw[j, i] = raw[i, j].t().contiguous()
+            else:
+                _, cov = HF.unsup_cov(torch.cat([mus[i], mus[j]], 1), flags)
+                raw[i, j], info = HF.udr_lasso(cov, Di, Dj, alpha)
+                infos.append(info)
+                # the covariance of [b | a] is the same matrix with its blocks swapped
+                raw[j, i], info = HF.udr_lasso(cov.roll((Dj, Dj), (0, 1)).contiguous(), Dj, Di, alpha)
+                infos.append(info)
+    shapes = {}                                                         # matrices of one shape are scored as one batch
+    for key, mat in raw.items():
+        shapes.setdefault(tuple(mat.shape), []).append(key)
+    for keys in shapes.values():
+        got = _relative_strength(torch.stack([raw[k] for k in keys]), torch.stack([masks[k[0]] for k in keys]),
+                                 torch.stack([masks[k[1]] for k in keys]))
+        for n, (i, j) in enumerate(keys):
+            pair[i][j] = got[n]
+    worst = torch.stack(infos).max(0).values if infos else torch.zeros(3, dtype=torch.int32, device=dev)
+    head = torch.cat([torch.stack([p for row in pair for p in row]), flags.to(torch.float64), worst.to(torch.float64)])
+    out = torch.cat([head] + (kls or [])).cpu().numpy()                 # the one read-back
+    _raise_on(out[M * M:M * M + 2])
+    _raise_on_lasso(out[M * M + 2:M * M + 5])
+    pairwise = out[:M * M].reshape(M, M).copy()
+    scores = [_median([float(pairwise[j, i]) for j in range(M) if j != i and not np.isnan(pairwise[j, i])])
+              for i in range(M)]
+    kl_np, kl_masks, at = None, [np.ones(m.shape[1], dtype=bool) for m in mus], M * M + 5
+    if kls is not None:
+        kl_np = []
+        for m in mus:
+            kl_np.append(out[at:at + m.shape[1]].copy())
+            at += m.shape[1]
+        kl_masks = [k > kl_filter_threshold for k in kl_np]
+    return dict(model_scores=scores, pairwise_disentanglement_scores=pairwise, raw_correlations=raw, kl_masks=kl_masks,
+                kl_divergence=kl_np)
+
+
+def compute_udr_score(source, models, num_train=10000, batch_size=64, seed=0, params=None):
+    """``udr_scores`` of ``models`` (M >= 2 networks with the same input) on ``num_train`` images of ``source`` (a
+    ``DeviceImageTable`` or a dataset; no factors are needed): the images of ``compute_unsupervised_scores`` (``np.sort(
+    RandomState(seed).choice(len(source), num_train, replace=False))``, or all of them), encoded once per model by
+    ``hipvae.aggregate.dataset_posteriors`` in eval mode without gradients.  torch's generators, the BatchNorm buffers
+    and the training flags are left as found.  ``params`` may carry ``correlation``, ``kl_filter_threshold``, ``alpha``
+    and ``num_train``."""
+    from . import aggregate
+    params = params or {}
+    num_train = int(params.get("num_train", num_train))
+    n = len(source)
+    if num_train >= n:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.RandomState(seed).choice(n, num_train, replace=False)).astype(np.int64)
+    post = [aggregate.dataset_posteriors(source, model, idx, batch_size) for model in models]
+    return udr_scores([p[0] for p in post], [p[1] for p in post], params.get("correlation", "lasso"),
+                      params.get("kl_filter_threshold", 0.01), params.get("alpha", 0.1))

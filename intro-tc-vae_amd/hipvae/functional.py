@@ -2105,3 +2105,42 @@ def irs(x, factors, factor_sizes, mn, mx, flags, diff_quantile=0.99):
          ptr(out["maxdev"]), ptr(out["cum"]), ptr(out["M"]), ptr(out["score"]), ptr(out["parent"]), ptr(out["active"]),
          ptr(out["res"]), ptr(flags), ptr(ws), nws, stream())
     return out
+
+
+# ------------------------------------------------------------------ UDR: ranks and the Lasso matrix (csrc/udr.hip)
+def udr_rank_lds_rows():
+    """Largest N whose sorted keys itcv_udr_ranks keeps in LDS (above: in its global workspace)."""
+    return lib.itcv_udr_rank_lds_rows()
+
+
+def udr_ranks(x, flags):
+    """fp32 ``r2 [N, D]``: twice the tie-averaged rank (``2 * scipy.stats.rankdata``) of every column of x[N >= 2, D], an
+    exact integer; sets flags[0] on a non-finite element (the ranks are then unspecified)."""
+    if x.dim() == 2 and x.shape[0] < 2:
+        raise ValueError(f"udr ranks: at least 2 rows are needed (got {x.shape[0]})")
+    x = _disent_mu(x)
+    N, D = x.shape
+    r2 = torch.empty((N, D), dtype=F32, device=x.device)
+    nws = lib.itcv_udr_ranks_workspace(N, D)                            # 0 in LDS, and for what the call below refuses
+    ws = _ws(nws, x.device)
+    call("itcv_udr_ranks", x.data_ptr(), x.stride(0), N, D, ptr(r2), ptr(flags), ptr(ws), nws, stream())
+    return r2
+
+
+def udr_lasso(cov, Da, Db, alpha=0.1, gtol=1e-12, max_sweeps=1000):
+    """``(W [Da, Db] fp64, info [3] int32)`` of the fp64 covariance ``cov [Da + Db, Da + Db]`` of the columns [a | b]:
+    ``W[k, t] = |w_t[k]|``, the Lasso of include/itcv_hip.h that predicts the standardised column t of b from the
+    standardised columns of a; ``info`` = (a target did not reach gtol, how many, the largest sweep count).  Nothing is read
+    back."""
+    cov = _gbt_dense(cov, F64, "cov")
+    Da, Db = int(Da), int(Db)
+    if cov.dim() != 2 or cov.shape[0] != cov.shape[1] or cov.shape[0] != Da + Db:
+        raise abi.HipExtensionError(f"udr: the covariance must be a square [Da + Db, Da + Db] tensor (got "
+                                    f"{tuple(cov.shape)} for Da = {Da}, Db = {Db})")
+    W = torch.empty((max(Da, 0), max(Db, 0)), dtype=F64, device=cov.device)
+    info = torch.empty((3,), dtype=torch.int32, device=cov.device)
+    nws = lib.itcv_udr_lasso_workspace(Da, Db)                          # 0 for what the call below refuses
+    ws = _ws(nws, cov.device)
+    call("itcv_udr_lasso", ptr(cov), Da, Db, float(alpha), float(gtol), int(max_sweeps), ptr(W), ptr(info), ptr(ws), nws,
+         stream())
+    return W, info

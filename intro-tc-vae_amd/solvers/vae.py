@@ -55,7 +55,7 @@ class VAESolver:
         self.device_scores = None
         self.dci_params = None       # ``params`` of hipvae.disentangle.compute_dci_score (None: 100 rounds, depth 6)
         # scores the reference does not have, written from the device on top of the above: a tuple drawn from
-        # {"factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised"}; ``params`` of
+        # {"factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr"}; ``params`` of
         # hipvae.disentangle.compute_factor_vae_score / compute_sap_score / compute_irs_score; keyword arguments of
         # hipvae.aggregate.compute_elbo_decomposition / hipvae.disentangle.compute_unsupervised_scores (None: their
         # defaults, with this solver's batch size)
@@ -65,6 +65,10 @@ class VAESolver:
         self.elbo_params = None
         self.irs_params = None
         self.unsupervised_params = None
+        # "udr" ranks this model against ``udr_peers``: models trained from other seeds on the same data (a sequence of
+        # networks; required by that score); ``udr_params``: ``params`` of hipvae.disentangle.compute_udr_score
+        self.udr_peers = None
+        self.udr_params = None
         self._device_table = None
         self.recon_loss_type = recon_loss_type
         self.scale = 1 / (self.model.cdim * self.model.encoder.image_size ** 2)   # solvers/vae.py:61
@@ -346,20 +350,22 @@ class VAESolver:
         "irs" is a factor score: the record ``irs`` {IRS, num_active_dims} (``irs_params``).  "unsupervised" needs no
         factors either and is read like the decomposition: the record ``unsupervised`` {gaussian_total_correlation,
         gaussian_wasserstein_correlation, gaussian_wasserstein_correlation_norm, mutual_info_score}
-        (``unsupervised_params``)."""
+        (``unsupervised_params``).  "udr" needs no factors either: the record ``udr`` {model_score, mean_pairwise}, the
+        Unsupervised Disentanglement Ranking of this model among ``[self.model, *self.udr_peers]`` (``udr_params``)."""
         extras = tuple(self.extra_scores or ())
         with_elbo = "elbo_decomposition" in extras
         with_unsup = "unsupervised" in extras
+        with_udr = "udr" in extras
         factored = isinstance(self.dataset, DisentanglementDataset)
-        if self.writer is None or not (factored or with_elbo or with_unsup) or cur_iter % self.test_iter:
+        if self.writer is None or not (factored or with_elbo or with_unsup or with_udr) or cur_iter % self.test_iter:
             return
-        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised")
+        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr")
         unknown = [e for e in extras if e not in known]
         if unknown:
             raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, known))})")
         if factored:
             self._write_factor_scores(cur_iter, num_samples,
-                                      tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised")))
+                                      tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised", "udr")))
         if with_elbo:
             from hipvae import aggregate
             kw = dict(batch_size=self.batch_size)
@@ -377,6 +383,18 @@ class VAESolver:
             self.writer.add_scalars("unsupervised", {k: got[k] for k in (
                 "gaussian_total_correlation", "gaussian_wasserstein_correlation", "gaussian_wasserstein_correlation_norm",
                 "mutual_info_score")}, global_step=cur_iter)
+        if with_udr:
+            from hipvae import disentangle
+            if not self.udr_peers:
+                raise ValueError('extra_scores: "udr" compares this model with models trained from other seeds: set '
+                                 "udr_peers to a sequence of them")
+            got = disentangle.compute_udr_score(self.dataset if self._device_table is None else self._device_table,
+                                                [self.model, *self.udr_peers], batch_size=self.batch_size,
+                                                params=self.udr_params)
+            mine = [float(v) for v in got["pairwise_disentanglement_scores"][1:, 0] if v == v]
+            self.writer.add_scalars("udr", dict(model_score=got["model_scores"][0],
+                                                mean_pairwise=sum(mine) / len(mine) if mine else float("nan")),
+                                    global_step=cur_iter)
 
     def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: tuple):
         """The factor-based scores of ``write_disentanglemnt_scores`` (a ``DisentanglementDataset``, at a test iteration)."""
