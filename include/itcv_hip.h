@@ -433,6 +433,29 @@ int itcv_tc_full_bwd(const float* g, const float* z, const float* mu_all, const 
 int itcv_kl_loss_fwd(const float* logvar, const float* mu, float* out, int B, int D, int reduction, float scale, void* stream);
 int itcv_kl_loss_bwd(const float* g, const float* logvar, const float* mu, float* dlogvar, float* dmu, int B, int D,
                      int reduction, float scale, void* stream);
+/* The KL hook of DIP-VAE-I (kind 1) / DIP-VAE-II (kind 2) (Kumar et al. 2018; disentanglement_lib's dip_vae) with its
+ * gradient (csrc/dip.hip).  mu_all / logvar_all [Bt][D] fp32 are the whole global batch, row stride ld = D, or ld = 2D for
+ * the two halves of one packed [Bt][2D] all-gather read in place; this rank's rows are row_offset .. row_offset+Bl-1.
+ *   m = mean_b mu_all[b], X = mu_all - m, C = X^T X / Bt (centred two-pass form, fp64; divisor Bt),
+ *   kind 2: C += diag(mean_b exp(logvar_all[b]));
+ *   out[0]   = coef_kl * mean_{local rows} kl_j (ops.py:161-163) + lambda_od sum_{i != j} C_ij^2 + lambda_d sum_i (C_ii - 1)^2
+ *   terms[3] = {mean kl_j, the lambda_od term, the lambda_d term}
+ *   W[D][D]  = 2 lambda_od offdiag(C) + diag(2 lambda_d (C_ii - 1)) (fp32, symmetric), mean[D] = m (fp64): kept for _bwd.
+ * coef_kl == 0 leaves the KL out of out[0] and of the gradients whatever its value.  Workspace: itcv_dip_kl_workspace (the
+ * fp64 loss partials of the 32 x 32 tiles of C).  2 launches: the tiles over a grid, then a one-block finish.
+ * _bwd, ONE launch: g[1]; dmu_all / dlogvar_all [Bt][D] with row stride ld (every element written):
+ *   dmu_all = g ((2 / Bt) X W + (coef_kl / Bl) mu on the local rows)
+ *   dlogvar_all = g (exp(logvar_all) diag(W) / Bt [kind 2] + (coef_kl / Bl) (-1/2)(1 - exp(logvar)) on the local rows).
+ * Every sum is fp64 in a fixed order, there are no atomics: results are bitwise reproducible and do not depend on the grid.
+ * Refused before any launch: a NULL pointer, Bt outside 2..2^24, D outside 1..512, rows outside the global batch, another
+ * kind, a negative or non-finite lambda, a non-finite coef_kl, a row stride that is neither D nor 2D. */
+size_t itcv_dip_kl_workspace(int Bt, int D);
+int itcv_dip_kl_fwd(const float* mu_all, const float* logvar_all, int ld, float* out, float* terms, float* W, double* mean,
+                    int Bl, int Bt, int row_offset, int D, int kind, double lambda_od, double lambda_d, double coef_kl,
+                    void* ws, size_t ws_bytes, void* stream);
+int itcv_dip_kl_bwd(const float* g, const float* mu_all, const float* logvar_all, int ld, const float* W, const double* mean,
+                    float* dmu_all, float* dlogvar_all, int Bl, int Bt, int row_offset, int D, int kind, double coef_kl,
+                    void* stream);
 /* solvers/tc.py:104-121: per-sample log q(z|x) (ops.py:24-29 density, own mu/logvar) and log p(z) */
 int itcv_diag_logdensity_rows(const float* z, const float* mu, const float* logvar, float* logq_cx,
                               float* logpz, int B, int D, void* stream);

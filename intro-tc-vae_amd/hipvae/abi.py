@@ -136,6 +136,9 @@ SIGNATURES = {
     "itcv_tc_full_bwd": (i32, [p, p, p, p, i32] + [p] * 7 + [i32, i32, i32, i32, i64, f32, f32, f32, i32, p, sz, p]),
     "itcv_kl_loss_fwd": (i32, [p, p, p, i32, i32, i32, f32, p]),
     "itcv_kl_loss_bwd": (i32, [p, p, p, p, p, i32, i32, i32, f32, p]),
+    "itcv_dip_kl_workspace": (sz, [i32, i32]),
+    "itcv_dip_kl_fwd": (i32, [p, p, i32, p, p, p, p, i32, i32, i32, i32, i32, f64, f64, f64, p, sz, p]),
+    "itcv_dip_kl_bwd": (i32, [p, p, p, i32, p, p, p, p, i32, i32, i32, i32, i32, f64, p]),
     "itcv_diag_logdensity_rows": (i32, [p, p, p, p, p, i32, i32, p]),
     "itcv_gauss_logdensity_fwd": (i32, [p, p, p, p, p, p, p, p, i32, p]),
     "itcv_gauss_logdensity_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, i32, p]),

@@ -1407,6 +1407,66 @@ class TcFullFn(Function):
         return dz, dmu, dlv, None, None, None, None, None, None
 
 
+def dip_kl_forward(mu_all, logvar_all, Bl, row_offset, kind, lambda_od, lambda_d, coef_kl):
+    """itcv_dip_kl_fwd on a [Bt, D] pair in either layout (two dense tensors, or the halves of one packed [Bt, 2D] tensor,
+    read in place; anything else is copied dense).  Returns (mu_all, logvar_all, ld) as read and (out, terms [3], W [D, D],
+    mean [D] fp64).  No gradient: ``DipKlFn`` is the differentiable form."""
+    if not (mu_all.is_cuda and logvar_all.is_cuda):
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    if mu_all.dim() != 2 or mu_all.shape != logvar_all.shape:
+        raise ValueError(f"mu_all / logvar_all must share one [Bt, D] shape (got {tuple(mu_all.shape)}, "
+                         f"{tuple(logvar_all.shape)})")
+    ld = _packed_pair(mu_all, logvar_all)
+    if ld is None or ld == mu_all.shape[1]:
+        mu_all, logvar_all = _f32c(mu_all), _f32c(logvar_all)
+        ld = mu_all.shape[1]
+    Bt, D = mu_all.shape
+    dev = mu_all.device
+    out = torch.empty((), dtype=F32, device=dev)
+    terms = torch.empty((3,), dtype=F32, device=dev)
+    W = torch.empty((D, D), dtype=F32, device=dev)
+    mean = torch.empty((D,), dtype=torch.float64, device=dev)
+    nws = lib.itcv_dip_kl_workspace(Bt, D)
+    ws = _ws(nws, dev)
+    call("itcv_dip_kl_fwd", mu_all.data_ptr(), logvar_all.data_ptr(), ld, ptr(out), ptr(terms), ptr(W), ptr(mean),
+         int(Bl), Bt, int(row_offset), D, int(kind), float(lambda_od), float(lambda_d), float(coef_kl), ptr(ws), nws,
+         stream())
+    return mu_all, logvar_all, ld, out, terms, W, mean
+
+
+class DipKlFn(Function):
+    """coef_kl * mean KL of this rank's rows + the DIP-VAE covariance regulariser of the whole global batch
+    (include/itcv_hip.h: itcv_dip_kl_fwd; ``kind`` 1 = DIP-VAE-I, 2 = DIP-VAE-II): two launches forward, one backward.
+    ``mu_all`` / ``logvar_all``: [Bt, D], two dense tensors or the halves of one packed [Bt, 2D] tensor (their gradients
+    then come back as the halves of one packed tensor too); this rank's rows are ``row_offset .. row_offset + Bl - 1``.
+    Second output: (mean KL, off-diagonal term, diagonal term) [3], no gradient.  Kept for the backward: the two inputs,
+    W [D, D] and the fp64 column means the forward centred with."""
+
+    @staticmethod
+    def forward(ctx, mu_all, logvar_all, Bl, row_offset, kind, lambda_od, lambda_d, coef_kl):
+        mu_all, logvar_all, ld, out, terms, W, mean = dip_kl_forward(mu_all, logvar_all, Bl, row_offset, kind, lambda_od,
+                                                                     lambda_d, coef_kl)
+        ctx.save_for_backward(mu_all, logvar_all, W, mean)
+        ctx.cfg = (int(Bl), int(row_offset), int(kind), float(coef_kl), ld)
+        ctx.mark_non_differentiable(terms)
+        return out, terms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_terms):
+        mu_all, logvar_all, W, mean = ctx.saved_tensors
+        Bl, off, kind, coef_kl, ld = ctx.cfg
+        Bt, D = mu_all.shape
+        if ld == D:
+            dmu, dlv = torch.empty((Bt, D), dtype=F32, device=W.device), torch.empty((Bt, D), dtype=F32, device=W.device)
+        else:                               # one packed [Bt, 2D] gradient: the gather's adjoint reduce-scatters it in place
+            dpk = torch.empty((Bt, 2 * D), dtype=F32, device=W.device)
+            dmu, dlv = dpk[:, :D], dpk[:, D:]
+        call("itcv_dip_kl_bwd", ptr(_f32c(g)), mu_all.data_ptr(), logvar_all.data_ptr(), ld, ptr(W), ptr(mean),
+             dmu.data_ptr(), dlv.data_ptr(), Bl, Bt, off, D, kind, coef_kl, stream())
+        return dmu, dlv, None, None, None, None, None, None
+
+
 class ReconLossFn(Function):
     """scale * ops.reconstruction_loss(x, recon, loss_type, reduction) (ops.py:188-236 + the hook's beta): two launches
     forward, one backward; x is a constant."""

@@ -153,6 +153,36 @@ def _tc_full(z, mu, logvar, dataset_size, alpha, beta, gamma, reduce, mu_all=Non
                              float(gamma), 2 if reduce == "mean" else 0)
 
 
+DIP_KINDS = {"i": 1, "ii": 2}
+
+
+def dip_kl_loss(mu, logvar, beta, lambda_od, lambda_d, kind="i", mu_all=None, logvar_all=None, row_offset=0,
+                with_terms=False):
+    """The KL hook of DIP-VAE-I / DIP-VAE-II (Kumar et al. 2018; disentanglement_lib's ``dip_vae`` with ``dip_type``
+    "i" / "ii"; not in the reference): beta * kl_divergence(logvar, mu, "mean") + lambda_od * sum_{i != j} C_ij^2 +
+    lambda_d * sum_i (C_ii - 1)^2, with C the covariance (divisor Bt) of the means of the whole batch, plus
+    diag(mean_b exp(logvar)) for kind "ii" -- two launches forward, one backward, bitwise reproducible.
+    ``mu_all`` / ``logvar_all`` / ``row_offset``: the data-parallel extension, as in ``tc_full_loss`` (the regulariser is
+    that of the global batch, the KL that of this rank's ``mu.shape[0]`` rows of it; the local ``mu`` / ``logvar`` are
+    then not read).  ``with_terms``: also return the device vector (mean KL, off-diagonal term, diagonal term), no
+    gradient."""
+    if kind not in DIP_KINDS:
+        raise ValueError(f"kind must be one of {tuple(DIP_KINDS)} (got {kind!r})")
+    if (mu_all is None) != (logvar_all is None):
+        raise ValueError("mu_all and logvar_all are given together")
+    if mu_all is None:
+        mu_all, logvar_all = mu, logvar
+    out, terms = HF.DipKlFn.apply(mu_all, logvar_all, int(mu.shape[0]), int(row_offset), DIP_KINDS[kind], float(lambda_od),
+                                  float(lambda_d), float(beta))
+    return (out, terms) if with_terms else out
+
+
+def dip_regularizer(mu, logvar, lambda_od, lambda_d, kind="i", mu_all=None, logvar_all=None, row_offset=0,
+                    with_terms=False):
+    """``dip_kl_loss`` without its KL term (beta = 0): the covariance regulariser alone."""
+    return dip_kl_loss(mu, logvar, 0.0, lambda_od, lambda_d, kind, mu_all, logvar_all, row_offset, with_terms)
+
+
 def tc_components(z, mu, logvar, dataset_size, *, var_from_row=True, eps_density=True, weighted=False):
     """Fused ops.py:80-84 + :92-115: returns (logqz_prodmarginals [B], log_qz [B]) of the stratified
     (default) or weighted sampler, for either density flavour / variance orientation.  No grad."""
