@@ -456,6 +456,38 @@ int itcv_dip_kl_fwd(const float* mu_all, const float* logvar_all, int ld, float*
 int itcv_dip_kl_bwd(const float* g, const float* mu_all, const float* logvar_all, int ld, const float* W, const double* mean,
                     float* dmu_all, float* dlogvar_all, int Bl, int Bt, int row_offset, int D, int kind, double coef_kl,
                     void* stream);
+/* The KL hook of InfoVAE / MMD-VAE (Zhao et al. 2017) and WAE-MMD (Tolstikhin et al. 2018) with its gradient
+ * (csrc/mmd.hip).  z_all [Bt][D] fp32: the reparameterised samples of the whole global batch (the gradient flows to it);
+ * prior [P][D] fp32: draws from N(0, I), a constant; mu / logvar [Bl][D] fp32: this rank's rows, read for the KL only.
+ * All four are dense (row stride D).
+ *   d2(a, b) = sum_l (a_l - b_l)^2 in fp64 from the fp32 inputs (difference form); bandwidth h > 0;
+ *   kernel 1 "rbf": k = exp(-d2 / h), k' = -k / h;
+ *   kernel 2 "imq": k = sum_s C_s / (C_s + d2), k' = -sum_s C_s / (C_s + d2)^2, C_s = s h, s in (.1, .2, .5, 1, 2, 5, 10);
+ *   S_zz = sum_{i != j} k(d2(z_i, z_j)) / (Bt (Bt - 1)), S_pp = sum_{i != j} k(d2(p_i, p_j)) / (P (P - 1)),
+ *   S_zp = sum_{i, j} k(d2(z_i, p_j)) / (Bt P), MMD^2 = S_zz + S_pp - 2 S_zp (the unbiased U-statistic; may be negative);
+ *   out[0]   = coef_kl * mean_{b < Bl} kl_b (ops.py:161-163) + lambda_mmd * MMD^2
+ *   terms[5] = {mean kl_b, MMD^2, S_zz, S_pp, S_zp}
+ *   Wt[Bt][Bt + P] = (A | C) (fp32), A_ij = k'(d2(z_i, z_j)) 2 / (Bt (Bt - 1)) (A_ii = 0; symmetric bit for bit),
+ *   C_ij = k'(d2(z_i, p_j)) (-2) / (Bt P); rs[Bt] (fp64) = the row sums of (A | C), accumulated from the fp64 values in a
+ *   fixed order: both kept for _bwd.
+ * coef_kl == 0 leaves the KL out of out[0] and of the gradients whatever its value.  Workspace: itcv_mmd_kl_workspace (one
+ * fp64 partial per 32 x 32 tile of the pair matrix of [z_all ; prior] and one fp64 row sum per strip of 32 points and row
+ * of z_all: at most 8.5 MiB).  2 launches: the upper tiles over a grid (zz upper tiles mirrored, zp in full, pp sums only),
+ * then a finish whose first block folds the partials and the KL and whose other blocks fold rs.
+ * _bwd, ONE launch: g[1]; every element of dz_all [Bt][D], dmu and dlogvar [Bl][D] is written:
+ *   dz_all = g lambda_mmd 2 (rs o z_all - Wt [z_all ; prior]) (fp64 accumulation, fp32 store)
+ *   dmu = g (coef_kl / Bl) mu, dlogvar = g (coef_kl / Bl) (-1/2)(1 - exp(logvar)).
+ * Every sum is fp64 in a fixed order, there are no atomics: results are bitwise reproducible and do not depend on the grid.
+ * Refused before any launch: a NULL pointer, Bt or P outside 2..4096, Bl outside 1..2^24, D outside 1..512, another
+ * kernel id, h not finite or <= 0, a negative or non-finite lambda_mmd, a non-finite coef_kl, a workspace that is too
+ * small.  The limits bound Wt at 4096 x 8192 x 4 bytes = 128 MiB. */
+size_t itcv_mmd_kl_workspace(int Bt, int P);
+int itcv_mmd_kl_fwd(const float* z_all, const float* prior, const float* mu, const float* logvar, float* out, float* terms,
+                    float* Wt, double* rs, int Bl, int Bt, int P, int D, int kernel, double h, double lambda_mmd,
+                    double coef_kl, void* ws, size_t ws_bytes, void* stream);
+int itcv_mmd_kl_bwd(const float* g, const float* z_all, const float* prior, const float* mu, const float* logvar,
+                    const float* Wt, const double* rs, float* dz_all, float* dmu, float* dlogvar, int Bl, int Bt, int P,
+                    int D, double lambda_mmd, double coef_kl, void* stream);
 /* solvers/tc.py:104-121: per-sample log q(z|x) (ops.py:24-29 density, own mu/logvar) and log p(z) */
 int itcv_diag_logdensity_rows(const float* z, const float* mu, const float* logvar, float* logq_cx,
                               float* logpz, int B, int D, void* stream);

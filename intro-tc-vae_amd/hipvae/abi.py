@@ -139,6 +139,9 @@ SIGNATURES = {
     "itcv_dip_kl_workspace": (sz, [i32, i32]),
     "itcv_dip_kl_fwd": (i32, [p, p, i32, p, p, p, p, i32, i32, i32, i32, i32, f64, f64, f64, p, sz, p]),
     "itcv_dip_kl_bwd": (i32, [p, p, p, i32, p, p, p, p, i32, i32, i32, i32, i32, f64, p]),
+    "itcv_mmd_kl_workspace": (sz, [i32, i32]),
+    "itcv_mmd_kl_fwd": (i32, [p] * 8 + [i32, i32, i32, i32, i32, f64, f64, f64, p, sz, p]),
+    "itcv_mmd_kl_bwd": (i32, [p] * 10 + [i32, i32, i32, i32, f64, f64, p]),
     "itcv_diag_logdensity_rows": (i32, [p, p, p, p, p, i32, i32, p]),
     "itcv_gauss_logdensity_fwd": (i32, [p, p, p, p, p, p, p, p, i32, p]),
     "itcv_gauss_logdensity_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, i32, p]),

@@ -1467,6 +1467,65 @@ class DipKlFn(Function):
         return dmu, dlv, None, None, None, None, None, None
 
 
+MMD_KERNELS = {"rbf": 1, "imq": 2}
+
+
+def mmd_kl_forward(z_all, prior, mu, logvar, kernel, h, lambda_mmd, coef_kl):
+    """itcv_mmd_kl_fwd on z_all [Bt, D], prior [P, D] and this rank's mu / logvar [Bl, D] (made fp32-contiguous: a strided
+    view is copied dense).  Returns (out, terms [5], Wt [Bt, Bt + P], rs [Bt] fp64).  No gradient: ``MmdKlFn`` is the
+    differentiable form."""
+    return _mmd_kl_forward(z_all, prior, mu, logvar, kernel, h, lambda_mmd, coef_kl)[4:]
+
+
+def _mmd_kl_forward(z_all, prior, mu, logvar, kernel, h, lambda_mmd, coef_kl):
+    if not (z_all.is_cuda and prior.is_cuda and mu.is_cuda and logvar.is_cuda):
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    if z_all.dim() != 2 or prior.dim() != 2 or z_all.shape[1] != prior.shape[1]:
+        raise ValueError(f"z_all [Bt, D] and prior [P, D] must share D (got {tuple(z_all.shape)}, {tuple(prior.shape)})")
+    if mu.dim() != 2 or mu.shape != logvar.shape or mu.shape[1] != z_all.shape[1]:
+        raise ValueError(f"mu / logvar must share one [Bl, D] shape with the D of z_all (got {tuple(mu.shape)}, "
+                         f"{tuple(logvar.shape)}, D = {z_all.shape[1]})")
+    z_all, prior, mu, logvar = _f32c(z_all), _f32c(prior), _f32c(mu), _f32c(logvar)
+    (Bt, D), P, Bl = z_all.shape, prior.shape[0], mu.shape[0]
+    dev = z_all.device
+    out = torch.empty((), dtype=F32, device=dev)
+    terms = torch.empty((5,), dtype=F32, device=dev)
+    Wt = torch.empty((Bt, Bt + P), dtype=F32, device=dev)
+    rs = torch.empty((Bt,), dtype=torch.float64, device=dev)
+    nws = lib.itcv_mmd_kl_workspace(Bt, P)
+    ws = _ws(nws, dev)
+    call("itcv_mmd_kl_fwd", ptr(z_all), ptr(prior), ptr(mu), ptr(logvar), ptr(out), ptr(terms), ptr(Wt), ptr(rs), Bl, Bt, P,
+         D, int(kernel), float(h), float(lambda_mmd), float(coef_kl), ptr(ws), nws, stream())
+    return z_all, prior, mu, logvar, out, terms, Wt, rs
+
+
+class MmdKlFn(Function):
+    """coef_kl * mean KL of this rank's rows + lambda_mmd * the unbiased MMD^2 between the sampled latents of the whole
+    global batch and draws from the prior (include/itcv_hip.h: itcv_mmd_kl_fwd; ``kernel`` 1 = rbf, 2 = imq with
+    bandwidth ``h``): two launches forward, one backward.  Second output: (mean KL, MMD^2, S_zz, S_pp, S_zp) [5], no
+    gradient.  ``prior`` is a constant.  Kept for the backward: the four inputs, Wt [Bt, Bt + P] and its fp64 row sums."""
+
+    @staticmethod
+    def forward(ctx, z_all, prior, mu, logvar, kernel, h, lambda_mmd, coef_kl):
+        z_all, prior, mu, logvar, out, terms, Wt, rs = _mmd_kl_forward(z_all, prior, mu, logvar, kernel, h, lambda_mmd,
+                                                                       coef_kl)
+        ctx.save_for_backward(z_all, prior, mu, logvar, Wt, rs)
+        ctx.cfg = (float(lambda_mmd), float(coef_kl))
+        ctx.mark_non_differentiable(terms)
+        return out, terms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_terms):
+        z_all, prior, mu, logvar, Wt, rs = ctx.saved_tensors
+        lambda_mmd, coef_kl = ctx.cfg
+        (Bt, D), P, Bl = z_all.shape, prior.shape[0], mu.shape[0]
+        dz, dmu, dlv = torch.empty_like(z_all), torch.empty_like(mu), torch.empty_like(logvar)
+        call("itcv_mmd_kl_bwd", ptr(_f32c(g)), ptr(z_all), ptr(prior), ptr(mu), ptr(logvar), ptr(Wt), ptr(rs), ptr(dz),
+             ptr(dmu), ptr(dlv), Bl, Bt, P, D, lambda_mmd, coef_kl, stream())
+        return dz, None, dmu, dlv, None, None, None, None
+
+
 class ReconLossFn(Function):
     """scale * ops.reconstruction_loss(x, recon, loss_type, reduction) (ops.py:188-236 + the hook's beta): two launches
     forward, one backward; x is a constant."""

@@ -183,6 +183,48 @@ def dip_regularizer(mu, logvar, lambda_od, lambda_d, kind="i", mu_all=None, logv
     return dip_kl_loss(mu, logvar, 0.0, lambda_od, lambda_d, kind, mu_all, logvar_all, row_offset, with_terms)
 
 
+MMD_KERNELS = HF.MMD_KERNELS
+
+
+def mmd_kl_loss(z, mu, logvar, prior, beta, lambda_mmd, kernel="imq", bandwidth=None, z_all=None, prior_all=None,
+                with_terms=False):
+    """The KL hook of InfoVAE / MMD-VAE (Zhao, Song and Ermon 2017) and WAE-MMD (Tolstikhin et al. 2018; not in the
+    reference): beta * kl_divergence(logvar, mu, "mean") + lambda_mmd * MMD^2(z, prior), the unbiased U-statistic
+
+        MMD^2 = sum_{i != j} k(z_i, z_j) / (B (B - 1)) + sum_{i != j} k(p_i, p_j) / (P (P - 1)) - 2 sum_{i, j} k(z_i, p_j) / (B P)
+
+    (it may be negative) between the sampled latents ``z`` [B, D] and ``prior`` [P, D], draws from N(0, I) that receive
+    no gradient.  With d2 = |a - b|^2 (fp64, difference form) and the bandwidth h (``bandwidth``; None: 2 D, WAE's Cbase
+    for a unit-variance prior): ``kernel`` "rbf" is k = exp(-d2 / h); "imq" is WAE's multi-scale inverse multiquadric
+    k = sum_s s h / (s h + d2), s in (0.1, 0.2, 0.5, 1, 2, 5, 10).  Two launches forward, one backward, fp64 throughout,
+    bitwise reproducible.  ``z_all`` / ``prior_all``: the data-parallel extension -- the samples and prior draws of the
+    whole global batch (given together); the statistic is then that of the global batch, the KL that of this rank's
+    ``mu`` / ``logvar``, and the local ``z`` / ``prior`` are not read.  ``with_terms``: also return the device vector
+    (mean KL, MMD^2, S_zz, S_pp, S_zp), no gradient."""
+    if kernel not in MMD_KERNELS:
+        raise ValueError(f"kernel must be one of {tuple(MMD_KERNELS)} (got {kernel!r})")
+    if (z_all is None) != (prior_all is None):
+        raise ValueError("z_all and prior_all are given together")
+    if z_all is None:
+        z_all, prior_all = z, prior
+    D = z_all.shape[-1]
+    if z_all.dim() != 2 or prior_all.dim() != 2 or prior_all.shape[1] != D or mu.shape != logvar.shape \
+            or mu.dim() != 2 or mu.shape[1] != D:
+        raise ValueError(f"z, prior, mu and logvar must be matrices that share D (got {tuple(z_all.shape)}, "
+                         f"{tuple(prior_all.shape)}, {tuple(mu.shape)}, {tuple(logvar.shape)})")
+    h = 2.0 * D if bandwidth is None else float(bandwidth)
+    out, terms = HF.MmdKlFn.apply(z_all, prior_all.detach(), mu, logvar, MMD_KERNELS[kernel], h, float(lambda_mmd),
+                                  float(beta))
+    return (out, terms) if with_terms else out
+
+
+def mmd_regularizer(z, prior, lambda_mmd, kernel="imq", bandwidth=None, with_terms=False):
+    """``mmd_kl_loss`` without its KL term (beta = 0): lambda_mmd * MMD^2(z, prior) alone.  There is no ``mu`` /
+    ``logvar`` to read: ``z`` stands in for both, and with beta = 0 their values do not reach the result."""
+    zd = z.detach()
+    return mmd_kl_loss(z, zd, zd, prior, 0.0, lambda_mmd, kernel, bandwidth, with_terms=with_terms)
+
+
 def tc_components(z, mu, logvar, dataset_size, *, var_from_row=True, eps_density=True, weighted=False):
     """Fused ops.py:80-84 + :92-115: returns (logqz_prodmarginals [B], log_qz [B]) of the stratified
     (default) or weighted sampler, for either density flavour / variance orientation.  No grad."""

@@ -1,2 +1,3 @@
 from .vae import VAESolver
 from .intro import IntroSolver
+from .mmd import MMDSolver, IntroMMDSolver
