@@ -164,6 +164,19 @@ int itcv_linear_dgrad(const float* dy, const float* w, float* dx, int B, int K, 
                       void* stream);
 int itcv_linear_wgrad(const float* dy, const float* x, float* dw, int B, int K, int N, int accumulate, void* ws,
                       size_t ws_bytes, void* stream);
+/* The hidden layers of the FactorVAE discriminator: the same GEMMs (same arithmetic, same plan, same deterministic
+ * split-K, itcv_linear_workspace) with LeakyReLU(slope) in the epilogue of the GEMM or, under split-K, of its slab
+ * reduce: no pointwise launch and no pre-activation in memory.
+ *   _lrelu_fwd  : y[B][N] = lrelu(x[B][K] w[N][K]^T + bias)          x has row stride ldx >= K, bias may be NULL
+ *   _dgrad_lrelu: dx[B][K] = (dy[B][N] w[N][K]) o lrelu'(y_prev[B][K])  dy / y_prev have row strides lddy >= N, ldy >= K
+ * y_prev is the OUTPUT of the activation whose input gradient is wanted: y_prev > 0 <=> its input > 0 for slope > 0, and
+ * an element that is exactly zero takes the derivative `slope`, as torch's leaky_relu does.  w, y and dx are dense.
+ * Refused before any launch: a NULL x / dy / w / y / dx / y_prev, B, K or N < 1, a row stride below the row length,
+ * slope <= 0 or not finite, a workspace that is too small. */
+int itcv_linear_lrelu_fwd(const float* x, size_t ldx, const float* w, const float* bias, float* y, int B, int K, int N,
+                          float slope, void* ws, size_t ws_bytes, void* stream);
+int itcv_linear_dgrad_lrelu(const float* dy, size_t lddy, const float* w, const float* y_prev, size_t ldy, float* dx,
+                            int B, int K, int N, float slope, void* ws, size_t ws_bytes, void* stream);
 /* 5x5 weight gradients with a <= 3-channel side (stem 3 -> 64: stem = 1, small = x, big_planes = planes of dy;
  * predict 64 -> 3: stem = 0, small = dy, big_planes = planes of x), bf16x3 on the matrix cores: rows (small channel,
  * filter column), pixel reduction through the transposing LDS read.  W in {32, 64}.  Deterministic slab reduce. */
@@ -488,6 +501,27 @@ int itcv_mmd_kl_fwd(const float* z_all, const float* prior, const float* mu, con
 int itcv_mmd_kl_bwd(const float* g, const float* z_all, const float* prior, const float* mu, const float* logvar,
                     const float* Wt, const double* rs, float* dz_all, float* dmu, float* dlogvar, int Bl, int Bt, int P,
                     int D, double lambda_mmd, double coef_kl, void* stream);
+/* The FactorVAE objective (Kim & Mnih 2018; disentanglement_lib's `factor_vae`), csrc/factor.hip.
+ * itcv_permute_dims, ONE launch (a block per column): out[r][d] = z[i][d] where r is the rank of keys[i][d] in column d
+ * of keys[B][D] -- ascending in the monotone uint32 image of the float's bits (the sign-flip map of itcv_udr_ranks, +0 and
+ * -0 share one image), then in the row index i.  The result is a permutation of every column for ANY keys (ties, +-0,
+ * +-inf, NaN).  z and keys have row strides ldz, ldk >= D; out is dense; zcopy (may be NULL) receives the dense copy of z
+ * in the same launch.  Keys and indices are sorted in LDS.  Refused: a NULL z / keys / out, B outside 1..4096, D outside
+ * 1..512, a row stride below D.
+ * itcv_disc_head_fwd, ONE launch: logits[R][2] (dense), the first R0 rows labelled 0 and the rest 1; d_i = l_i0 - l_i1:
+ *   out[0] = tc     = mean_{i < R0} d_i
+ *   out[1] = d_loss = 0.5 mean_{i < R0} softplus(-d_i) + 0.5 mean_{i >= R0} softplus(d_i)   (cross entropy; the second
+ *            term is 0 when R == R0), softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ *   out[2] = d_acc  = the share of the R rows whose argmax (the first of two equal logits) is their label.
+ * itcv_disc_head_bwd, ONE launch, g[1] on the device: mode 0 writes the R0 rows dlogits[i] = (+w, -w), w = g / R0 (the
+ * gradient of tc); mode 1 (needs R0 < R) writes all R rows, w = -g sigmoid(-d_i) / (2 R0) for i < R0 and
+ * w = g sigmoid(d_i) / (2 (R - R0)) for the others (the gradient of d_loss).
+ * Every sum is fp64 in a fixed order, there are no atomics; both are finite for any finite logits.  Refused: a NULL
+ * pointer, R0 outside 1..R, R above 2^24, another mode. */
+int itcv_permute_dims(const float* z, size_t ldz, const float* keys, size_t ldk, float* out, float* zcopy, int B, int D,
+                      void* stream);
+int itcv_disc_head_fwd(const float* logits, int R, int R0, float* out, void* stream);
+int itcv_disc_head_bwd(const float* g, const float* logits, float* dlogits, int R, int R0, int mode, void* stream);
 /* solvers/tc.py:104-121: per-sample log q(z|x) (ops.py:24-29 density, own mu/logvar) and log p(z) */
 int itcv_diag_logdensity_rows(const float* z, const float* mu, const float* logvar, float* logq_cx,
                               float* logpz, int B, int D, void* stream);

@@ -22,6 +22,8 @@
 // half-wave (conflict free); operand fragments are double-buffered in registers across the
 // K-steps.  Global->register->LDS software pipeline with two LDS buffers and one barrier per
 // K-tile.  blockIdx -> tile mapping keeps tiles that share an im2col panel on one XCD.
+#include <float.h>
+
 #include "conv_shared.h"
 
 namespace itcv {
@@ -237,9 +239,15 @@ struct GemmArgs {
   int mt, nt, ktiles, ktiles_per_split;
   size_t slab_stride;
   int accumulate;
+  const float* mask;   // EPI 2: the activation's output at (m, n), row stride ldm
+  long long ldm;
+  float slope;         // EPI 1, 2
 };
 
-template <bool A_KC, bool B_KC>   // is the operand's k index the contiguous one in memory?
+// EPI: what the kernel does to a value it writes to C itself (never to a split-K slab: gemm64_reduce_epi does it then).
+// 0: nothing (nn.Linear of the VAE); 1: LeakyReLU(slope) after the bias; 2: times LeakyReLU'(mask), read from the
+// activation's OUTPUT (mask > 0 <=> its input > 0 for slope > 0; exactly zero takes the slope, as in torch).
+template <bool A_KC, bool B_KC, int EPI = 0>   // A_KC / B_KC: is the operand's k index the contiguous one in memory?
 __global__ __launch_bounds__(256) void gemm64_kernel(GemmArgs a) {
   constexpr int BM = 64, BN = 64, BK = 32, PA = BM + 1, PB = BN + 1;
   __shared__ float As[2][BK * PA];
@@ -312,7 +320,9 @@ __global__ __launch_bounds__(256) void gemm64_kernel(GemmArgs a) {
     const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
     if (m < a.M) {
       float* q = out + (size_t)m * a.N + n;
-      const float v = acc[0][0][r] + bv;
+      float v = acc[0][0][r] + bv;
+      if constexpr (EPI == 1) v = v > 0.f ? v : v * a.slope;
+      if constexpr (EPI == 2) v *= a.mask[(long long)m * a.ldm + n] > 0.f ? 1.f : a.slope;
       *q = a.accumulate ? *q + v : v;
     }
   }
@@ -325,6 +335,20 @@ __global__ void gemm64_reduce(const float* __restrict__ slab, const float* __res
     float s = fold_strided(0.f, slab + i, total, splits);
     if (bias) s += bias[i % N];
     C[i] = accumulate ? C[i] + s : s;
+  }
+}
+
+// the same fold with the epilogue of gemm64_kernel<.., EPI> (1, 2) behind it
+template <int EPI>
+__global__ void gemm64_reduce_epi(const float* __restrict__ slab, const float* __restrict__ bias, float* __restrict__ C,
+                                  size_t total, int N, int splits, const float* __restrict__ mask, long long ldm,
+                                  float slope) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    float s = fold_strided(0.f, slab + i, total, splits);
+    if (bias) s += bias[i % N];
+    if constexpr (EPI == 1) s = s > 0.f ? s : s * slope;
+    if constexpr (EPI == 2) s *= mask[(long long)(i / N) * ldm + (long long)(i % N)] > 0.f ? 1.f : slope;
+    C[i] = s;
   }
 }
 
@@ -2939,7 +2963,8 @@ static size_t gemm64_ws(int M, int N, int K) {
 }
 static int run_gemm64(const char* name, const float* A, const float* B, const float* bias, float* C, int M, int N,
                       int K, long long sam, long long sak, long long sbk, long long sbn, int accumulate, void* ws,
-                      size_t ws_bytes, hipStream_t st) {
+                      size_t ws_bytes, hipStream_t st, int epi = 0, const float* mask = nullptr, long long ldm = 0,
+                      float slope = 0.f) {
   const GemmPlan p = plan_gemm64(M, N, K);
   const size_t need = p.splits > 1 ? (size_t)p.splits * M * N * sizeof(float) : 0;
   if (need && (!ws || ws_bytes < need)) return fail("%s: workspace too small (need %lld bytes)", name, (long long)need);
@@ -2951,14 +2976,28 @@ static int run_gemm64(const char* name, const float* A, const float* B, const fl
   a.mt = p.mt, a.nt = p.nt, a.ktiles = p.ktiles, a.ktiles_per_split = p.kps;
   a.slab_stride = p.splits > 1 ? (size_t)M * N : 0;
   a.accumulate = p.splits > 1 ? 0 : accumulate;
+  a.mask = mask, a.ldm = ldm, a.slope = slope;
   dim3 grid(p.mt * p.nt, p.splits), blk(256);
   const bool akc = sak == 1, bkc = sbk == 1;
-  if (akc && bkc) hipLaunchKernelGGL((gemm64_kernel<true, true>), grid, blk, 0, st, a);
+  // the fused epilogues exist for the two layouts the discriminator's layers have; a split-K launch writes plain slabs
+  if (epi == 1 && p.splits == 1) hipLaunchKernelGGL((gemm64_kernel<true, true, 1>), grid, blk, 0, st, a);
+  else if (epi == 2 && p.splits == 1) hipLaunchKernelGGL((gemm64_kernel<true, false, 2>), grid, blk, 0, st, a);
+  else if (akc && bkc) hipLaunchKernelGGL((gemm64_kernel<true, true>), grid, blk, 0, st, a);
   else if (akc) hipLaunchKernelGGL((gemm64_kernel<true, false>), grid, blk, 0, st, a);
   else if (bkc) hipLaunchKernelGGL((gemm64_kernel<false, true>), grid, blk, 0, st, a);
   else hipLaunchKernelGGL((gemm64_kernel<false, false>), grid, blk, 0, st, a);
   ITCV_CHECK_LAUNCH(name);
-  if (p.splits > 1) {
+  if (p.splits > 1 && epi) {
+    const size_t total = (size_t)M * N;
+    const dim3 rgrid((int)(cdivz(total, 256) < 1024 ? cdivz(total, 256) : 1024));
+    if (epi == 1)
+      hipLaunchKernelGGL(gemm64_reduce_epi<1>, rgrid, dim3(256), 0, st, static_cast<const float*>(ws), bias, C, total, N,
+                         p.splits, mask, ldm, slope);
+    else
+      hipLaunchKernelGGL(gemm64_reduce_epi<2>, rgrid, dim3(256), 0, st, static_cast<const float*>(ws), bias, C, total, N,
+                         p.splits, mask, ldm, slope);
+    ITCV_CHECK_LAUNCH(name);
+  } else if (p.splits > 1) {
     const size_t total = (size_t)M * N;
     hipLaunchKernelGGL(gemm64_reduce, dim3((int)(cdivz(total, 256) < 1024 ? cdivz(total, 256) : 1024)), dim3(256), 0, st,
                        static_cast<const float*>(ws), bias, C, total, N, p.splits, accumulate);
@@ -2994,6 +3033,23 @@ int itcv_linear_wgrad(const float* dy, const float* x, float* dw, int B, int K, 
                       size_t ws_bytes, void* stream) {
   ITCV_REQUIRE(dy && x && dw && B > 0 && K > 0 && N > 0, "itcv_linear_wgrad");
   return run_gemm64("itcv_linear_wgrad", dy, x, nullptr, dw, N, K, B, 1, N, K, 1, accumulate, ws, ws_bytes, S(stream));
+}
+
+// The discriminator's hidden layers (FactorVAE): the same GEMMs with LeakyReLU in the epilogue of the kernel or, under
+// split-K, of the slab reduce -- no pointwise launch, no pre-activation in memory.  x / dy / y_prev may be row-strided.
+int itcv_linear_lrelu_fwd(const float* x, size_t ldx, const float* w, const float* bias, float* y, int B, int K, int N,
+                          float slope, void* ws, size_t ws_bytes, void* stream) {
+  ITCV_REQUIRE(x && w && y && B > 0 && K > 0 && N > 0, "itcv_linear_lrelu_fwd");
+  ITCV_REQUIRE(ldx >= (size_t)K && slope > 0.f && slope <= FLT_MAX, "itcv_linear_lrelu_fwd");
+  return run_gemm64("itcv_linear_lrelu_fwd", x, w, bias, y, B, N, K, (long long)ldx, 1, 1, K, 0, ws, ws_bytes, S(stream), 1,
+                    nullptr, 0, slope);
+}
+int itcv_linear_dgrad_lrelu(const float* dy, size_t lddy, const float* w, const float* y_prev, size_t ldy, float* dx,
+                            int B, int K, int N, float slope, void* ws, size_t ws_bytes, void* stream) {
+  ITCV_REQUIRE(dy && w && y_prev && dx && B > 0 && K > 0 && N > 0, "itcv_linear_dgrad_lrelu");
+  ITCV_REQUIRE(lddy >= (size_t)N && ldy >= (size_t)K && slope > 0.f && slope <= FLT_MAX, "itcv_linear_dgrad_lrelu");
+  return run_gemm64("itcv_linear_dgrad_lrelu", dy, w, nullptr, dx, B, K, N, (long long)lddy, 1, K, 1, 0, ws, ws_bytes,
+                    S(stream), 2, y_prev, (long long)ldy, slope);
 }
 
 // ---- 5x5 weight gradient with a 3-channel side, from planes of the 64-channel side (bf16x3) -------------------

@@ -67,6 +67,8 @@ SIGNATURES = {
     "itcv_linear_fwd": (i32, [p, p, p, p, i32, i32, i32, p, sz, p]),
     "itcv_linear_dgrad": (i32, [p, p, p, i32, i32, i32, p, sz, p]),
     "itcv_linear_wgrad": (i32, [p, p, p, i32, i32, i32, i32, p, sz, p]),
+    "itcv_linear_lrelu_fwd": (i32, [p, sz, p, p, p, i32, i32, i32, f32, p, sz, p]),
+    "itcv_linear_dgrad_lrelu": (i32, [p, sz, p, p, sz, p, i32, i32, i32, f32, p, sz, p]),
     "itcv_conv2d_wgrad5_bf16p_supported": (i32, [i32] * 4),
     "itcv_conv2d_wgrad5_bf16p_workspace": (sz, [i32, i32]),
     "itcv_conv2d_wgrad5_bf16p": (i32, [p, p, p] + [i32] * 6 + [p, i32, p, sz, p]),
@@ -142,6 +144,9 @@ SIGNATURES = {
     "itcv_mmd_kl_workspace": (sz, [i32, i32]),
     "itcv_mmd_kl_fwd": (i32, [p] * 8 + [i32, i32, i32, i32, i32, f64, f64, f64, p, sz, p]),
     "itcv_mmd_kl_bwd": (i32, [p] * 10 + [i32, i32, i32, i32, f64, f64, p]),
+    "itcv_permute_dims": (i32, [p, sz, p, sz, p, p, i32, i32, p]),
+    "itcv_disc_head_fwd": (i32, [p, i32, i32, p, p]),
+    "itcv_disc_head_bwd": (i32, [p, p, p, i32, i32, i32, p]),
     "itcv_diag_logdensity_rows": (i32, [p, p, p, p, p, i32, i32, p]),
     "itcv_gauss_logdensity_fwd": (i32, [p, p, p, p, p, p, p, p, i32, p]),
     "itcv_gauss_logdensity_bwd": (i32, [p, p, p, p, p, p, p, p, p, p, i32, p]),

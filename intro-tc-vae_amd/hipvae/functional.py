@@ -1526,6 +1526,168 @@ class MmdKlFn(Function):
         return dz, None, dmu, dlv, None, None, None, None
 
 
+# ------------------------------------------------------------------ FactorVAE: permutation + discriminator
+# None of this reads or claims _SHARED_PASS: the discriminator is no part of a recorded network pass, and the Soft-Intro
+# bookkeeping (param_grads / input_grad / live) must not steer its two walks.  That is why LinearFn is not reused.
+PERMUTE_MAX_B, PERMUTE_MAX_D = 4096, 512
+
+
+def _rows_f32(t, what):
+    """A 2-D fp32 device tensor as (tensor, row stride in elements): a view with unit column stride is passed as it is."""
+    if not t.is_cuda:
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    if t.dtype != F32:
+        raise abi.HipExtensionError(f"HIP path is fp32 only (got {t.dtype})")
+    if t.dim() != 2:
+        raise ValueError(f"{what} must be a matrix (got {tuple(t.shape)})")
+    B, D = t.shape
+    if B == 1 and t.stride(1) == 1:
+        return t, D
+    if t.stride(1) != 1 or t.stride(0) < D:
+        t = t.contiguous()
+    return t, t.stride(0)
+
+
+def permute_dims(z, keys, out=None, zcopy=None):
+    """FactorVAE's per-dimension batch permutation in one launch (include/itcv_hip.h: itcv_permute_dims):
+    ``out[r, d] = z[i, d]`` with r the rank of ``keys[i, d]`` in column d (ties by row index), i.e.
+    ``z[argsort(keys[:, d], stable), d]``.  z, keys [B, D] fp32 (row-strided views are read in place), B <= 4096,
+    D <= 512.  ``out`` / ``zcopy``: dense [B, D] tensors to write the result / a copy of z into.  No gradient."""
+    z, keys = z.detach(), keys.detach()
+    if z.dim() != 2 or z.shape != keys.shape:
+        raise ValueError(f"z and keys must share one [B, D] shape (got {tuple(z.shape)}, {tuple(keys.shape)})")
+    (z, ldz), (keys, ldk) = _rows_f32(z, "z"), _rows_f32(keys, "keys")
+    B, D = z.shape
+    if not (1 <= B <= PERMUTE_MAX_B and 1 <= D <= PERMUTE_MAX_D):
+        raise ValueError(f"permute_dims takes 1 <= B <= {PERMUTE_MAX_B} and 1 <= D <= {PERMUTE_MAX_D} (got {B}, {D})")
+    if out is None:
+        out = torch.empty((B, D), dtype=F32, device=z.device)
+    for t in (out, zcopy):
+        if t is not None and (tuple(t.shape) != (B, D) or t.dtype != F32 or t.device != z.device):
+            raise ValueError("out / zcopy must be fp32 [B, D] tensors on z's device")
+    call("itcv_permute_dims", z.data_ptr(), ldz, keys.data_ptr(), ldk, ptr(out), ptr(zcopy), B, D, stream())
+    return out
+
+
+class DiscPass:
+    """One forward of the discriminator MLP over R stacked rows, the first R0 labelled 0 ("from q(z)") and the rest 1
+    ("from the product of the marginals"): the input ``x`` [R, zdim], the hidden activations, the logits [R, 2], the
+    device vector ``stats`` = (tc, d_loss, d_acc) of itcv_disc_head_fwd and the weights it ran with.  ``DiscTcFn`` and
+    ``DiscLossFn`` walk it backwards, each on its own."""
+    __slots__ = ("x", "acts", "logits", "stats", "weights", "biases", "slope", "R", "R0")
+
+
+def _linear_ws(shapes, device):
+    nws = max(lib.itcv_linear_workspace(B, K, N) for B, K, N in shapes)
+    return (_ws(nws, device) if nws else None), nws
+
+
+def disc_forward(x, weights, biases, slope, R0):
+    """x [R, zdim] (dense fp32) through Linear + LeakyReLU(slope) for all but the last (weight, bias) pair -- one fused
+    launch per layer, two when its K is split -- the plain Linear for the last (2 logits) and the head.  No gradient."""
+    x = _f32c(x.detach())
+    if not x.is_cuda:
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    R = x.shape[0]
+    dp = DiscPass()
+    dp.weights = [_f32c(w.detach()) for w in weights]
+    dp.biases = [None if b is None else _f32c(b.detach()) for b in biases]
+    if x.dim() != 2 or dp.weights[0].shape[1] != x.shape[1] or dp.weights[-1].shape[0] != 2 or not 1 <= R0 <= R:
+        raise ValueError(f"discriminator: x {tuple(x.shape)}, first weight {tuple(dp.weights[0].shape)}, last weight "
+                         f"{tuple(dp.weights[-1].shape)}, R0 = {R0}")
+    dp.x, dp.slope, dp.R, dp.R0 = x, float(slope), R, int(R0)
+    dev = x.device
+    ws, nws = _linear_ws([(R, w.shape[1], w.shape[0]) for w in dp.weights], dev)
+    dp.acts, h = [], x
+    for w, b in zip(dp.weights[:-1], dp.biases[:-1]):
+        N, K = w.shape
+        y = torch.empty((R, N), dtype=F32, device=dev)
+        call("itcv_linear_lrelu_fwd", ptr(h), K, ptr(w), ptr(b), ptr(y), R, K, N, dp.slope, ptr(ws), nws, stream())
+        dp.acts.append(y)
+        h = y
+    w, b = dp.weights[-1], dp.biases[-1]
+    dp.logits = torch.empty((R, 2), dtype=F32, device=dev)
+    call("itcv_linear_fwd", ptr(h), ptr(w), ptr(b), ptr(dp.logits), R, w.shape[1], 2, ptr(ws), nws, stream())
+    dp.stats = torch.empty((3,), dtype=F32, device=dev)
+    call("itcv_disc_head_fwd", ptr(dp.logits), R, dp.R0, ptr(dp.stats), stream())
+    return dp
+
+
+class DiscTcFn(Function):
+    """tc = mean_{i < R0} (l_i0 - l_i1) of a ``DiscPass`` as a function of ``z``, its first R0 input rows.  The backward
+    is the VAE walk: the data-gradient chain of those rows only (head, then one itcv_linear_dgrad_lrelu per hidden layer
+    and the plain data gradient of the first).  The discriminator's parameters are constants here: no weight or bias
+    gradient is computed and no ``.grad`` is touched."""
+
+    @staticmethod
+    def forward(ctx, z, dp):
+        if tuple(z.shape) != (dp.R0, dp.x.shape[1]):
+            raise ValueError(f"z {tuple(z.shape)} is not the first {dp.R0} rows of the pass {tuple(dp.x.shape)}")
+        ctx.dp = dp
+        return dp.stats[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        dp = ctx.dp
+        B, dev = dp.R0, dp.x.device
+        dy = torch.empty((B, 2), dtype=F32, device=dev)
+        call("itcv_disc_head_bwd", ptr(_f32c(g)), ptr(dp.logits), ptr(dy), dp.R, B, 0, stream())
+        ws, nws = _linear_ws([(B, w.shape[1], w.shape[0]) for w in dp.weights], dev)
+        for l in range(len(dp.weights) - 1, 0, -1):
+            N, K = dp.weights[l].shape
+            dx = torch.empty((B, K), dtype=F32, device=dev)
+            call("itcv_linear_dgrad_lrelu", ptr(dy), N, ptr(dp.weights[l]), ptr(dp.acts[l - 1]), K, ptr(dx), B, K, N, dp.slope,
+                 ptr(ws), nws, stream())
+            dy = dx
+        N, K = dp.weights[0].shape
+        dz = torch.empty((B, K), dtype=F32, device=dev)
+        call("itcv_linear_dgrad", ptr(dy), ptr(dp.weights[0]), ptr(dz), B, K, N, ptr(ws), nws, stream())
+        return dz, None
+
+
+class DiscLossFn(Function):
+    """d_loss = 0.5 mean CE(l_i, 0) over the first R0 rows + 0.5 mean CE(l_i, 1) over the others of a ``DiscPass`` as a
+    function of the discriminator's parameters (w_0, b_0, w_1, b_1, ...: those the pass ran with).  The backward is the
+    discriminator's walk: weight and bias gradients from all R rows (added straight into the flat ``.grad`` buffers inside
+    ``direct_grad_accumulation``), the data gradient from layer to layer but not of the first: the input rows are
+    constants, nothing flows to the encoder."""
+
+    @staticmethod
+    def forward(ctx, dp, *params):
+        if dp.R0 >= dp.R:
+            raise ValueError("the discriminator's loss needs rows of both labels (R0 < R)")
+        ctx.dp, ctx.params = dp, params
+        return dp.stats[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        dp, params = ctx.dp, ctx.params
+        R, dev = dp.R, dp.x.device
+        dy = torch.empty((R, 2), dtype=F32, device=dev)
+        call("itcv_disc_head_bwd", ptr(_f32c(g)), ptr(dp.logits), ptr(dy), R, dp.R0, 1, stream())
+        ws, nws = _linear_ws([(R, w.shape[1], w.shape[0]) for w in dp.weights], dev)
+        grads = [None] * len(params)
+        for l in range(len(dp.weights) - 1, -1, -1):
+            N, K = dp.weights[l].shape
+            x = dp.acts[l - 1] if l else dp.x
+            if ctx.needs_input_grad[1 + 2 * l]:
+                tgt = _grad_target(params[2 * l])
+                dw = None if tgt is not None else torch.empty((N, K), dtype=F32, device=dev)
+                call("itcv_linear_wgrad", ptr(dy), ptr(x), ptr(tgt if tgt is not None else dw), R, K, N,
+                     int(tgt is not None), ptr(ws), nws, stream())
+                grads[2 * l] = dw
+            if params[2 * l + 1] is not None and ctx.needs_input_grad[2 + 2 * l]:
+                grads[2 * l + 1] = bias_grad_raw(dy, R, N, 1, _grad_target(params[2 * l + 1]))
+            if l:
+                dx = torch.empty((R, K), dtype=F32, device=dev)
+                call("itcv_linear_dgrad_lrelu", ptr(dy), N, ptr(dp.weights[l]), ptr(x), K, ptr(dx), R, K, N, dp.slope, ptr(ws),
+                     nws, stream())
+                dy = dx
+        return (None, *grads)
+
+
 class ReconLossFn(Function):
     """scale * ops.reconstruction_loss(x, recon, loss_type, reduction) (ops.py:188-236 + the hook's beta): two launches
     forward, one backward; x is a constant."""

@@ -463,3 +463,43 @@ class SoftIntroVAE(nn.Module):
     def set_fused(self, flag):
         self.encoder.fused = self.decoder.fused = bool(flag)
         return self
+
+
+class Discriminator(nn.Sequential):
+    """The FactorVAE discriminator (Kim & Mnih 2018; disentanglement_lib's ``factor_vae``; not in the reference): the MLP
+    ``zdim -> hidden (x layers) -> 2`` with LeakyReLU(slope) behind every hidden layer, which tells samples of q(z) (class
+    0) from samples of the product of its marginals (class 1).  An ``nn.Sequential`` of ``nn.Linear`` / ``nn.LeakyReLU``
+    for its parameters, torch's default initialisation and its state-dict keys (``0.weight``, ``0.bias``, ``2.weight``,
+    ...): a plain torch ``nn.Sequential`` of the same layers loads its ``state_dict``.
+
+    ``forward(z)`` returns the logits [B, 2] from the fused layer kernels (hipvae.functional.disc_forward), WITHOUT a
+    gradient: the objective's two walks are ``ops.factor_tc`` (gradient to z only) and ``ops.factor_disc_loss`` (gradient
+    to these parameters only).  There is no CPU path: a CPU tensor raises ``HipExtensionError``."""
+
+    def __init__(self, zdim, hidden=1000, layers=6, slope=LRELU_SLOPE):
+        if not (isinstance(layers, int) and layers >= 1 and zdim >= 1 and hidden >= 1):
+            raise ValueError(f"Discriminator(zdim={zdim!r}, hidden={hidden!r}, layers={layers!r}): positive integers")
+        if not (isinstance(slope, (int, float)) and 0 < slope < float("inf")):
+            raise ValueError(f"slope must be a finite number > 0 (got {slope!r}): the layer kernels read the activation "
+                             "mask from the layer's output")
+        mods, width = [], zdim
+        for _ in range(layers):
+            mods += [nn.Linear(width, hidden), nn.LeakyReLU(slope)]
+            width = hidden
+        super().__init__(*mods, nn.Linear(width, 2))
+        self.zdim, self.hidden, self.layers, self.slope = zdim, hidden, layers, float(slope)
+
+    def linears(self):
+        return [m for m in self if isinstance(m, nn.Linear)]
+
+    def flat_parameters(self):
+        """(w_0, b_0, w_1, b_1, ...), the order of ``parameters()``."""
+        return [p for m in self.linears() for p in (m.weight, m.bias)]
+
+    def run(self, x, R0=None):
+        """The ``DiscPass`` of the stacked rows ``x`` [R, zdim], the first ``R0`` (None: all) labelled 0."""
+        lin = self.linears()
+        return HF.disc_forward(x, [m.weight for m in lin], [m.bias for m in lin], self.slope, x.shape[0] if R0 is None else R0)
+
+    def forward(self, z):
+        return self.run(z).logits

@@ -269,3 +269,62 @@ def entropy(x, base=None, axis=0, eps=1e-9):
     prob = shifted / shifted.sum(axis=axis, keepdims=True)
     h = -(prob * np.log(prob + eps)).sum(axis=axis)
     return h if base is None else h / math.log(base + eps)
+
+
+# ---------------------------------------------------------------------------- FactorVAE
+def permute_dims(z, keys=None):
+    """FactorVAE's ``shuffle_codes``: every column of ``z`` [B, D] permuted over the batch on its own, in one launch:
+    ``out[:, d] = z[argsort(keys[:, d], stable), d]``.  ``keys`` None: one N(0, 1) draw per element from ``noise`` (the
+    project's noise source, so recorded draws and graph capture work as for ``reparameterize``): argsort of i.i.d.
+    continuous keys is a uniform random permutation.  Any keys give a permutation (ties go by row index).  The result
+    carries no gradient.  B <= 4096, D <= 512."""
+    if not z.is_cuda:
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    if keys is None:
+        keys = noise(z.shape, z.device)
+    return HF.permute_dims(z, keys)
+
+
+def factor_pass(z, discriminator, z_perm=None, keys=None, permute=True):
+    """ONE forward of ``discriminator`` (models.Discriminator) over the 2B stacked rows [z; z_perm], both detached, for
+    ``factor_tc`` and ``factor_disc_loss`` to share (``shared=``): both then see the same weights and the same z.
+    ``z_perm`` None: ``permute_dims(z, keys)``, written straight into the stacked buffer together with the copy of z (one
+    launch).  ``permute=False``: the B rows of z alone, enough for ``factor_tc``."""
+    if not z.is_cuda:
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    if z.dim() != 2 or z.shape[1] != discriminator.zdim:
+        raise ValueError(f"z must be [B, {discriminator.zdim}] (got {tuple(z.shape)})")
+    B, D = z.shape
+    if not permute and z_perm is None:
+        return discriminator.run(z.detach(), B)
+    if z_perm is not None:
+        if z_perm.shape != z.shape:
+            raise ValueError(f"z_perm {tuple(z_perm.shape)} must have z's shape {tuple(z.shape)}")
+        return discriminator.run(torch.cat([z.detach(), z_perm.detach()]), B)
+    if keys is None:
+        keys = noise(z.shape, z.device)
+    x = torch.empty((2 * B, D), dtype=torch.float32, device=z.device)
+    HF.permute_dims(z, keys, out=x[B:], zcopy=x[:B])
+    return discriminator.run(x, B)
+
+
+def factor_tc(z, discriminator, with_terms=False, shared=None):
+    """FactorVAE's density-ratio estimate of the total correlation of q(z): tc = mean_i (l_i0 - l_i1), l = D(z) the
+    discriminator's logits; differentiable in ``z`` ONLY (the data-gradient chain of the fused layers; the
+    discriminator's parameters are constants and their ``.grad`` is not touched).  ``shared``: a ``factor_pass`` of this
+    z to read the logits from (None: the forward runs here, over z alone).  ``with_terms``: also the device vector
+    (tc, d_loss, d_acc) of the pass, no gradient."""
+    dp = factor_pass(z, discriminator, permute=False) if shared is None else shared
+    tc = HF.DiscTcFn.apply(z, dp)
+    return (tc, dp.stats) if with_terms else tc
+
+
+def factor_disc_loss(z, discriminator, z_perm=None, keys=None, with_terms=False, shared=None):
+    """The discriminator's loss 0.5 mean_i CE(D(z_i), 0) + 0.5 mean_i CE(D(z_perm_i), 1), differentiable in the
+    discriminator's parameters ONLY: z and z_perm are detached, the first layer's data gradient is not computed.  CE is
+    the stable softplus of the logit difference.  ``z_perm`` / ``keys`` / ``shared``: as in ``factor_pass``.
+    ``with_terms``: also the device vector (tc, d_loss, d_acc), no gradient; d_acc is the share of the 2B rows the
+    discriminator classifies correctly."""
+    dp = factor_pass(z, discriminator, z_perm, keys) if shared is None else shared
+    loss = HF.DiscLossFn.apply(dp, *discriminator.flat_parameters())
+    return (loss, dp.stats) if with_terms else loss
