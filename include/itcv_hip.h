@@ -501,6 +501,37 @@ int itcv_mmd_kl_fwd(const float* z_all, const float* prior, const float* mu, con
 int itcv_mmd_kl_bwd(const float* g, const float* z_all, const float* prior, const float* mu, const float* logvar,
                     const float* Wt, const double* rs, float* dz_all, float* dmu, float* dlogvar, int Bl, int Bt, int P,
                     int D, double lambda_mmd, double coef_kl, void* stream);
+/* The latent op of Ada-GVAE / Ada-ML-VAE (Locatello et al. 2020; disentanglement_lib's `weak` module: GroupVAEBase with
+ * aggregate_argmax) with its gradient (csrc/ada.hip).  mu, logvar, eps [2B][D] fp32 with unit column stride and row strides
+ * ld_mu, ld_logvar, ld_eps >= D (mu and logvar may be the halves of one [2B][2D] tensor); rows b and B + b are a pair
+ * (m1, l1), (m2, l2).  Per pair and dimension d, in fp64 from the fp32 inputs:
+ *   delta = exp(l1 - l2) + (m2 - m1)^2 exp(-l2) - 1 + l2 - l1        (the library's compute_kl: one direction, no 1/2)
+ *   tau   = (min_d delta + max_d delta) / 2,   own = delta >= tau    (D = 1 or all-equal delta: every dimension is own);
+ *           own_in [B][D] uint8 (may be NULL), when given, replaces the threshold: own = own_in != 0
+ *   averaging 1 "gvae":  mb = (m1 + m2) / 2, vb = (e^l1 + e^l2) / 2
+ *   averaging 2 "mlvae": vb = 2 e^l1 e^l2 / (e^l1 + e^l2), mb = vb (m1 e^-l1 + m2 e^-l2) / 2
+ *   (mt_i, lt_i) = own ? (m_i, l_i) : (mb, log vb);   z_i = mt_i + eps_i exp(lt_i / 2)
+ *   part[r] = -1/2 sum_d (1 + lt - mt^2 - e^lt) for r < 2B (the KL of adapted row r), part[2B + b] = the number of shared
+ *           (not own) dimensions of pair b: part [3B] fp64 is the op's workspace
+ *   out[0]   = beta * mean_{r < 2B} part[r];  terms[2] = {that mean, mean_b part[2B + b]}
+ * z [2B][D] fp32 and own [B][D] uint8 are dense and written in full.  2 launches: a wave per pair (four pairs a block, the
+ * blocks stride over the pairs), then a one-block finish that adds the partials in row order.
+ * _bwd, ONE launch, the mask a constant: dz [2B][D] (row stride ld_dz >= D) and g[1] are the gradients of z and out[0];
+ * every element of the dense dmu, dlogvar [2B][D] is written.  With g_k = g beta / (2B):
+ *   own:    dm_i = dz_i + g_k m_i,  dl_i = dz_i eps_i e^(l_i / 2) / 2 + g_k (e^l_i - 1) / 2
+ *   shared: G_m = dz_1 + dz_2 + 2 g_k mb,  G_l = sqrt(vb) (dz_1 eps_1 + dz_2 eps_2) / 2 + g_k (vb - 1)
+ *     gvae:  dm_i = G_m / 2,  dl_i = G_l e^l_i / (e^l1 + e^l2)
+ *     mlvae: w_i = e^-l_i / (e^-l1 + e^-l2):  dm_i = G_m w_i,  dl_i = G_l w_i + G_m w_i (mb - m_i)
+ * beta == 0 leaves the KL out of out[0] and of the gradients whatever its value.  Every sum is fp64 in a fixed order, there
+ * are no atomics: results are bitwise reproducible and do not depend on the grid.  Refused before any launch: a NULL
+ * pointer (own_in excepted), B outside 1..2^30, D outside 1..512, another averaging, a non-finite beta, a row stride
+ * below D. */
+int itcv_ada_group_fwd(const float* mu, size_t ld_mu, const float* logvar, size_t ld_logvar, const float* eps,
+                       size_t ld_eps, const uint8_t* own_in, float* z, uint8_t* own, double* part, float* out,
+                       float* terms, int B, int D, int averaging, double beta, void* stream);
+int itcv_ada_group_bwd(const float* dz, size_t ld_dz, const float* g, const float* mu, size_t ld_mu, const float* logvar,
+                       size_t ld_logvar, const float* eps, size_t ld_eps, const uint8_t* own, float* dmu, float* dlogvar,
+                       int B, int D, int averaging, double beta, void* stream);
 /* The FactorVAE objective (Kim & Mnih 2018; disentanglement_lib's `factor_vae`), csrc/factor.hip.
  * itcv_permute_dims, ONE launch (a block per column): out[r][d] = z[i][d] where r is the rank of keys[i][d] in column d
  * of keys[B][D] -- ascending in the monotone uint32 image of the float's bits (the sign-flip map of itcv_udr_ranks, +0 and

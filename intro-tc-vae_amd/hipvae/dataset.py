@@ -11,7 +11,9 @@ Both tables fit in HBM many times over.  Here
     ``gather(idx)`` returns ``table[idx] / 255`` as fp32 -- ``ToTensor``'s ``.float().div(255)`` bit for bit;
   * ``DeviceFactorSampler`` is ``disentangle.FactorSampler`` with the image lookup replaced by one gather: same draws,
     same factors, same observations, so every ``compute_*`` score runs on it unchanged;
-  * ``DeviceLoader`` feeds training from the table: one gather (+ flips) and one label ``index_select`` per batch.
+  * ``DeviceLoader`` feeds training from the table: one gather (+ flips) and one label ``index_select`` per batch;
+  * ``DevicePairLoader`` feeds the weakly-supervised pair objective (solvers/ada.py): pairs of images that differ in a
+    few factors, drawn on the device (``pair_factors``) and looked up with two gathers into one ``[2B, C, H, W]`` batch.
 
 Datasets that resize (``resize != H``: ``Image.resize(..., Image.BICUBIC)`` per sample, dataset.py:78-79,144-145,335) run
 that resize on the device too, bit for bit (``itcv_resize_u8``, csrc/resize.hip, with the plans of hipvae/resize.py):
@@ -31,7 +33,8 @@ from . import abi
 from .disentangle import FactorSampler
 from .resize import ResizePlan
 
-__all__ = ["DeviceImageTable", "ResizedView", "DeviceFactorSampler", "DeviceLoader"]
+__all__ = ["DeviceImageTable", "ResizedView", "DeviceFactorSampler", "DeviceLoader", "DevicePairLoader", "pair_factors",
+           "factor_bases"]
 
 UPLOAD_CHUNK_BYTES = 256 << 20
 RESIZE_MODES = (None, "table", "gather", "auto")
@@ -385,4 +388,104 @@ class DeviceLoader:
             x = t.gather(idx, flip=flip, check=False)
             y = t.label_table.index_select(0, idx) if t.label_table is not None else idx
             yield self.func(x, y) if self.func is not None else (x, y)
+        t.check()
+
+
+# ---- pairs for the weakly-supervised objective -------------------------------------------------------------------------
+def factor_bases(factor_sizes):
+    """Place value of every factor in the image index (the first factor most significant), as ``FactorSampler``'s."""
+    sizes = [int(s) for s in factor_sizes]
+    return [int(np.prod(sizes[i + 1:], dtype=np.int64)) for i in range(len(sizes))]
+
+
+def _uniform_ints(sizes, rows, generator, device):
+    """int64 ``[rows, len(sizes)]``, column j uniform in ``[0, sizes[j])``: ONE fp64 draw, scaled and floored."""
+    sz = torch.tensor(sizes, dtype=torch.float64, device=device)
+    u = torch.rand((rows, len(sizes)), dtype=torch.float64, generator=generator, device=device)
+    return torch.minimum((u * sz).floor(), sz - 1).to(torch.int64)
+
+
+def pair_factors(factor_sizes, latent_indices, batch_size, k=1, generator=None, device=None):
+    """The factors of ``batch_size`` pairs of images as Locatello et al. (2020) draw them (disentanglement_lib's
+    ``weak`` module): ``(first, second, changed)``, int64 ``[B, num_factors]`` twice and bool ``[B, num_latents]``.
+
+      * ``first``: every factor uniform over its values -- the factors that do not vary included, which both images of a
+        pair share;
+      * per pair ``k`` latent factors chosen without replacement (``k = -1``: first a number uniform in
+        ``1 .. num_latents - 1`` per pair); ``changed`` marks them, in the order of ``latent_indices``;
+      * ``second``: ``first`` with the chosen factors drawn again, uniformly (a redrawn value may equal the old one, as in
+        the library).
+
+    Integer torch ops on ``device`` (any device) with the draws of ``generator`` in a fixed order: the first factors, the
+    per-pair counts (``k = -1`` only), the choice, the redrawn values."""
+    sizes, lat = [int(s) for s in factor_sizes], [int(i) for i in latent_indices]
+    F, L, B = len(sizes), len(lat), int(batch_size)
+    if B < 1:
+        raise ValueError("batch_size must be positive")
+    if not lat or len(set(lat)) != L or min(lat) < 0 or max(lat) >= F or min(sizes) < 1:
+        raise ValueError(f"pair_factors: latent_indices {lat} do not name distinct factors of sizes {sizes}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not (k == -1 or 1 <= k <= L):
+        raise ValueError(f"k must be -1 or in 1 .. {L}, the number of latent factors (got {k!r})")
+    if k == -1 and L < 2:
+        raise ValueError("k = -1 draws a number in 1 .. num_latents - 1: it needs at least two latent factors")
+    first = _uniform_ints(sizes, B, generator, device)
+    if k == -1:
+        count = torch.randint(1, L, (B, 1), generator=generator, device=device)
+    else:
+        count = torch.full((B, 1), int(k), dtype=torch.int64, device=device)
+    # the rank of an i.i.d. uniform score among its row: the `count` smallest are a uniform choice without replacement
+    rank = torch.rand((B, L), generator=generator, device=device).argsort(dim=1).argsort(dim=1)
+    changed = rank < count
+    redrawn = _uniform_ints([sizes[i] for i in lat], B, generator, device)
+    lat_t = torch.tensor(lat, dtype=torch.int64, device=device)
+    second = first.clone()
+    second[:, lat_t] = torch.where(changed, redrawn, first[:, lat_t])
+    return first, second, changed
+
+
+class DevicePairLoader:
+    """Batches ``(x, changed)`` of image PAIRS from a ``DeviceImageTable`` that carries ``factor_sizes`` /
+    ``latent_indices`` (any other table: ``ValueError``): ``x`` fp32 ``[2B, C, H, W]`` on the device, rows ``b`` and
+    ``B + b`` a pair that differs in (at most) the ``k`` latent factors ``changed[b]`` marks (bool ``[B, num_latents]``);
+    ``pre_process(x, changed)`` when given.  ``pair_factors`` draws the factors from a private device generator seeded
+    with ``seed`` -- the same seed repeats the same epochs, torch's global RNG streams are untouched -- the table's bases
+    turn both factor tuples into indices, and two gathers fill the halves of one buffer: no host round trip per image.
+    ``factors`` holds the ``(first, second)`` factor tensors of the batch yielded last.  ``len()``: ``steps_per_epoch``,
+    or ``num_images // (2 * batch_size)``.  The table's index flag is checked once, at the end of the epoch."""
+
+    def __init__(self, table, batch_size, k=1, device=None, seed=0, steps_per_epoch=None, pre_process=None):
+        if not isinstance(table, DeviceImageTable) or table.factor_sizes is None or table.latent_indices is None:
+            raise ValueError("DevicePairLoader: the table carries no factor_sizes / latent_indices")
+        total = int(np.prod(table.factor_sizes, dtype=np.int64))
+        if total != table.num_images:
+            raise ValueError(f"DevicePairLoader: the factors index {total} images, the table holds {table.num_images}")
+        if device is not None and torch.device(device) != table.device:
+            raise ValueError(f"DevicePairLoader: the table lives on {table.device}, not on {device}")
+        if steps_per_epoch is not None and steps_per_epoch < 0:
+            raise ValueError("steps_per_epoch must not be negative")
+        # the remaining arguments are checked by the function that uses them (a throw-away host generator: the global
+        # streams stay untouched), before the first batch
+        pair_factors(table.factor_sizes, table.latent_indices, batch_size, k, torch.Generator(), "cpu")
+        self.table, self.batch_size, self.k = table, int(batch_size), int(k)
+        self.seed, self.steps_per_epoch, self.func = int(seed), steps_per_epoch, pre_process
+        self.factors = None
+        self._gen = self._bases = None
+
+    def __len__(self):
+        if self.steps_per_epoch is not None:
+            return int(self.steps_per_epoch)
+        return self.table.num_images // (2 * self.batch_size)
+
+    def __iter__(self):
+        t, B = self.table, self.batch_size
+        if self._gen is None:
+            self._gen = torch.Generator(device=t.device).manual_seed(self.seed)
+            self._bases = torch.tensor(factor_bases(t.factor_sizes), dtype=torch.int64, device=t.device)
+        for _ in range(len(self)):
+            first, second, changed = pair_factors(t.factor_sizes, t.latent_indices, B, self.k, self._gen, t.device)
+            x = torch.empty((2 * B,) + t.image_shape, dtype=torch.float32, device=t.device)
+            t.gather((first * self._bases).sum(1), out=x[:B], check=False)
+            t.gather((second * self._bases).sum(1), out=x[B:], check=False)
+            self.factors = (first, second)
+            yield self.func(x, changed) if self.func is not None else (x, changed)
         t.check()

@@ -1569,6 +1569,62 @@ def permute_dims(z, keys, out=None, zcopy=None):
     return out
 
 
+# ------------------------------------------------------------------ Ada-GVAE / Ada-ML-VAE: the pair op
+ADA_AVERAGINGS = {"gvae": 1, "mlvae": 2}
+ADA_MAX_D = 512
+
+
+class AdaGroupFn(Function):
+    """The latent op of Ada-GVAE / Ada-ML-VAE on 2B stacked rows, rows b and B + b a pair (include/itcv_hip.h:
+    itcv_ada_group_fwd; ``averaging`` 1 = gvae, 2 = mlvae): two launches forward, one backward.  ``mu`` / ``logvar`` /
+    ``eps`` [2B, D]: fp32 views with unit column stride are read in place (the halves of one packed [2B, 2D] tensor too).
+    ``own_in``: None (the adaptive threshold) or a [B, D] mask (non-zero: the dimension keeps its own posterior).  Outputs:
+    z [2B, D] and the scalar beta * mean KL, both differentiable in ``mu`` and ``logvar``; the mask as used [B, D] uint8
+    and (mean KL, mean shared dimensions per pair) [2], no gradient.  The mask is a constant of the backward pass."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, own_in, averaging, beta):
+        if mu.dim() != 2 or mu.shape != logvar.shape or mu.shape != eps.shape:
+            raise ValueError(f"mu, logvar and eps must share one [2B, D] shape (got {tuple(mu.shape)}, "
+                             f"{tuple(logvar.shape)}, {tuple(eps.shape)})")
+        R, D = mu.shape
+        if R < 2 or R % 2:
+            raise ValueError(f"the rows are pairs (b, B + b): an even, positive number of them (got {R})")
+        if not 1 <= D <= ADA_MAX_D:
+            raise ValueError(f"the pair op takes 1 <= D <= {ADA_MAX_D} (got {D})")
+        B, dev = R // 2, mu.device
+        if own_in is not None and tuple(own_in.shape) != (B, D):
+            raise ValueError(f"own must be a [B, D] = {(B, D)} mask (got {tuple(own_in.shape)})")
+        (mu, ldm), (logvar, ldl), (eps, lde) = _rows_f32(mu, "mu"), _rows_f32(logvar, "logvar"), _rows_f32(eps, "eps")
+        if own_in is not None:
+            if not own_in.is_cuda:
+                raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+            own_in = (own_in != 0).to(torch.uint8).contiguous()
+        z = torch.empty((R, D), dtype=F32, device=dev)
+        own = torch.empty((B, D), dtype=torch.uint8, device=dev)
+        part = torch.empty((3 * B,), dtype=torch.float64, device=dev)
+        out = torch.empty((), dtype=F32, device=dev)
+        terms = torch.empty((2,), dtype=F32, device=dev)
+        call("itcv_ada_group_fwd", mu.data_ptr(), ldm, logvar.data_ptr(), ldl, eps.data_ptr(), lde, ptr(own_in), ptr(z),
+             ptr(own), ptr(part), ptr(out), ptr(terms), B, D, int(averaging), float(beta), stream())
+        ctx.save_for_backward(mu, logvar, eps, own)
+        ctx.cfg = (int(averaging), float(beta), ldm, ldl, lde)
+        ctx.mark_non_differentiable(own, terms)
+        return z, out, own, terms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, g, _g_own, _g_terms):
+        mu, logvar, eps, own = ctx.saved_tensors
+        averaging, beta, ldm, ldl, lde = ctx.cfg
+        R, D = mu.shape
+        dz, ldz = _rows_f32(dz, "dz")
+        dmu, dlv = torch.empty((R, D), dtype=F32, device=mu.device), torch.empty((R, D), dtype=F32, device=mu.device)
+        call("itcv_ada_group_bwd", dz.data_ptr(), ldz, ptr(_f32c(g)), mu.data_ptr(), ldm, logvar.data_ptr(), ldl,
+             eps.data_ptr(), lde, ptr(own), ptr(dmu), ptr(dlv), R // 2, D, averaging, beta, stream())
+        return dmu, dlv, None, None, None, None
+
+
 class DiscPass:
     """One forward of the discriminator MLP over R stacked rows, the first R0 labelled 0 ("from q(z)") and the rest 1
     ("from the product of the marginals"): the input ``x`` [R, zdim], the hidden activations, the logits [R, 2], the

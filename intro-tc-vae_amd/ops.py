@@ -225,6 +225,49 @@ def mmd_regularizer(z, prior, lambda_mmd, kernel="imq", bandwidth=None, with_ter
     return mmd_kl_loss(z, zd, zd, prior, 0.0, lambda_mmd, kernel, bandwidth, with_terms=with_terms)
 
 
+ADA_AVERAGINGS = HF.ADA_AVERAGINGS
+
+
+def ada_group(mu, logvar, beta, averaging="gvae", own=None, eps=None, with_terms=False):
+    """The latent op of Ada-GVAE / Ada-ML-VAE (Locatello et al. 2020, "Weakly-Supervised Disentanglement Without
+    Compromises"; disentanglement_lib's ``weak`` module, ``GroupVAEBase`` with ``aggregate_argmax``; not in the
+    reference) on ``B`` pairs stacked as ``2B`` rows, rows ``b`` and ``B + b`` a pair (m1, l1), (m2, l2):
+
+        delta = exp(l1 - l2) + (m2 - m1)^2 exp(-l2) - 1 + l2 - l1,   tau = (min_d delta + max_d delta) / 2,
+        own   = delta >= tau                  (D = 1 or all-equal delta: every dimension keeps its own posterior)
+        "gvae":  mb = (m1 + m2) / 2, vb = (e^l1 + e^l2) / 2;   "mlvae": vb = 2 e^l1 e^l2 / (e^l1 + e^l2),
+                 mb = vb (m1 e^-l1 + m2 e^-l2) / 2
+        z_i   = mt_i + eps_i exp(lt_i / 2) with (mt_i, lt_i) = (m_i, l_i) where own, (mb, log vb) elsewhere
+        loss  = beta * mean over the 2B rows of -1/2 sum_d (1 + lt - mt^2 - e^lt)
+
+    Returns ``(z [2B, D], loss)``, both differentiable in ``mu`` and ``logvar`` (the mask is a constant of the backward
+    pass, as with ``tf.where``); with ``with_terms`` also the mask as used (uint8 [B, D]) and the device vector (mean KL,
+    mean number of shared dimensions per pair), no gradient.  ``own`` [B, D] replaces the threshold (non-zero: own) --
+    GVAE / ML-VAE with known groups.  ``eps`` None: ONE draw ``noise(mu.shape, mu.device)``, so recorded draws and graph
+    capture work as for ``reparameterize``.  Two launches forward, one backward, fp64 inside, bitwise reproducible;
+    1 <= D <= 512."""
+    if averaging not in ADA_AVERAGINGS:
+        raise ValueError(f"averaging must be one of {tuple(ADA_AVERAGINGS)} (got {averaging!r})")
+    if mu.dim() != 2 or mu.shape != logvar.shape:
+        raise ValueError(f"mu and logvar must share one [2B, D] shape (got {tuple(mu.shape)}, {tuple(logvar.shape)})")
+    R, D = mu.shape
+    if R < 2 or R % 2:
+        raise ValueError(f"the rows are pairs (b, B + b): an even, positive number of them (got {R})")
+    if not 1 <= D <= HF.ADA_MAX_D:
+        raise ValueError(f"ada_group takes 1 <= D <= {HF.ADA_MAX_D} (got {D})")
+    if own is not None and tuple(own.shape) != (R // 2, D):
+        raise ValueError(f"own must be a [B, D] = {(R // 2, D)} mask (got {tuple(own.shape)})")
+    if eps is not None and eps.shape != mu.shape:
+        raise ValueError(f"eps must have mu's shape {tuple(mu.shape)} (got {tuple(eps.shape)})")
+    if not (mu.is_cuda and logvar.is_cuda):
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    if eps is None:
+        eps = noise(mu.shape, mu.device)
+    z, loss, mask, terms = HF.AdaGroupFn.apply(mu, logvar, eps.detach(), None if own is None else own.detach(),
+                                               ADA_AVERAGINGS[averaging], float(beta))
+    return (z, loss, mask, terms) if with_terms else (z, loss)
+
+
 def tc_components(z, mu, logvar, dataset_size, *, var_from_row=True, eps_density=True, weighted=False):
     """Fused ops.py:80-84 + :92-115: returns (logqz_prodmarginals [B], log_qz [B]) of the stratified
     (default) or weighted sampler, for either density flavour / variance orientation.  No grad."""
