@@ -328,6 +328,142 @@ __global__ __launch_bounds__(256) void gemm64_kernel(GemmArgs a) {
   }
 }
 
+// The same GEMM -- the same LDS tiles, K order, MFMA sequence and per-element epilogue arithmetic, so the same bits -- for
+// operands that can be read in 16-byte pieces (run_gemm64 checks: the contiguous index has stride 1 and an extent that is
+// a multiple of 4, the other stride is a multiple of 4, the bases are 16-byte aligned; N % 4 == 0 for C).  A thread
+// brings two float4 of A and two of B per K-tile (16 scalar loads in gemm64_kernel), along k where k is the contiguous
+// index and along m / n where that one is.  Four register sets form a ring: the loads of K-tiles kt + 1 .. kt + 4 are in
+// flight while tile kt is multiplied, and storing tile kt + 1 to LDS waits for that tile's loads alone (a block of the
+// encoder fc forward owns 8 K-tiles: 8 exposed round trips with one tile of prefetch).  Loads past the block's last tile
+// re-read that tile -- unconditional, so that the counted waits stay counted.  The epilogue goes through LDS: a thread
+// owns four consecutive n of a row, all reads of C (accumulate) and of the mask are issued before the first use, and C is
+// read and written as float4 (under the `if (m < M)` of the scalar form every read-modify-write of the weight gradient was
+// a dependent round trip, sixteen per thread behind two K-tiles of work).
+template <bool A_KC, bool B_KC, int EPI = 0>
+__global__ __launch_bounds__(256) void gemm64_vec_kernel(GemmArgs a) {
+  constexpr int BM = 64, BN = 64, BK = 32, PA = BM + 1, PB = BN + 1, NS = 4;
+  static_assert(2 * BK * PA >= BM * PB, "the C tile is staged in As");
+  __shared__ float As[2][BK * PA];
+  __shared__ float Bs[2][BK * PB];
+  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int wm = wid >> 1, wn = wid & 1, l31 = lane & 31, half = lane >> 5;
+  const int tile_m = blockIdx.x % a.mt, tile_n = blockIdx.x / a.mt, sk = blockIdx.y;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const int kt0 = sk * a.ktiles_per_split, kt1 = min(a.ktiles, kt0 + a.ktiles_per_split);
+  // piece i = 0, 1 of a thread: k-contiguous operand -> row (t >> 3) + 32 i, k = 4 (t & 7) .. + 3;
+  //                             otherwise            -> k = (t >> 4) + 16 i, rows 4 (t & 15) .. + 3
+  const int ak = A_KC ? (t & 7) * 4 : (t >> 4), am = A_KC ? (t >> 3) : (t & 15) * 4;
+  const int bk = B_KC ? (t & 7) * 4 : (t >> 4), bn = B_KC ? (t >> 3) : (t & 15) * 4;
+  constexpr int AKI = A_KC ? 0 : 16, AMI = A_KC ? 32 : 0, BKI = B_KC ? 0 : 16, BNI = B_KC ? 32 : 0;
+
+  float4 ra[NS][2], rb[NS][2];
+  auto load_tile = [&](int kt, float4 (&pa)[2], float4 (&pb)[2]) {   // clamped (always valid) addresses
+    const int kb = kt * BK;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int k = kb + ak + i * AKI, m = m0 + am + i * AMI;
+      const float* p = A_KC ? a.A + (long long)min(m, a.M - 1) * a.sam + min(k, a.K - 4)
+                            : a.A + (long long)min(k, a.K - 1) * a.sak + min(m, a.M - 4);
+      pa[i] = *reinterpret_cast<const float4*>(p);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int k = kb + bk + i * BKI, n = n0 + bn + i * BNI;
+      const float* p = B_KC ? a.B + (long long)min(n, a.N - 1) * a.sbn + min(k, a.K - 4)
+                            : a.B + (long long)min(k, a.K - 1) * a.sbk + min(n, a.N - 4);
+      pb[i] = *reinterpret_cast<const float4*>(p);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x020, 4, 0);      // the 4 VMEM reads together, ahead of everything else
+  };
+  auto store_tile = [&](int buf, int kt, const float4 (&pa)[2], const float4 (&pb)[2]) {   // bounds applied here
+    const int kb = kt * BK;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int k = ak + i * AKI, m = am + i * AMI;
+      const bool ok = m0 + m < a.M && kb + k < a.K;           // a piece is inside or outside as a whole
+      const float v[4] = {ok ? pa[i].x : 0.f, ok ? pa[i].y : 0.f, ok ? pa[i].z : 0.f, ok ? pa[i].w : 0.f};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) As[buf][A_KC ? (k + j) * PA + m : k * PA + m + j] = v[j];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int k = bk + i * BKI, n = bn + i * BNI;
+      const bool ok = n0 + n < a.N && kb + k < a.K;
+      const float v[4] = {ok ? pb[i].x : 0.f, ok ? pb[i].y : 0.f, ok ? pb[i].z : 0.f, ok ? pb[i].w : 0.f};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) Bs[buf][B_KC ? (k + j) * PB + n : k * PB + n + j] = v[j];
+    }
+  };
+  f32x16 acc[1][1];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[0][0][r] = 0.f;
+  if (kt0 < kt1) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) load_tile(min(kt0 + s, kt1 - 1), ra[s], rb[s]);
+    store_tile(0, kt0, ra[0], rb[0]);
+    __syncthreads();
+    int cur = 0, kt = kt0;
+    auto step = [&](auto sc) {                               // set s held tile kt (now in LDS) and takes tile kt + NS
+      constexpr int s = decltype(sc)::value;
+      load_tile(min(kt + NS, kt1 - 1), ra[s], rb[s]);
+      mfma_tile<BK, PA, PB, 1, 1>(&As[cur][half * PA + wm * 32 + l31], &Bs[cur][half * PB + wn * 32 + l31], acc);
+      if (kt + 1 < kt1) store_tile(cur ^ 1, kt + 1, ra[(s + 1) % NS], rb[(s + 1) % NS]);
+      __syncthreads();
+      cur ^= 1;
+      return ++kt < kt1;
+    };
+    // every exit leaves from the step that ran last: no path on which a later step sees fewer loads behind its own
+    while (step(std::integral_constant<int, 0>{}) && step(std::integral_constant<int, 1>{}) &&
+           step(std::integral_constant<int, 2>{}) && step(std::integral_constant<int, 3>{})) {
+    }
+    static_assert(NS == 4, "the ring is walked by four written-out steps");
+  }
+  // ---- epilogue through LDS: Cs[m][n], then four consecutive n of a row per thread ----
+  float* Cs = &As[0][0];
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    Cs[(wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * half) * PB + wn * 32 + l31] = acc[0][0][r];
+  __syncthreads();
+  float* out = a.C + (size_t)sk * a.slab_stride;
+  const int n = n0 + (t & 15) * 4, nc = min(n, a.N - 4);
+  float bv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (a.bias && !a.slab_stride) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bv[j] = a.bias[nc + j];
+  }
+  float4 old[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) old[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (a.accumulate) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      old[i] = *reinterpret_cast<const float4*>(out + (size_t)min(m0 + (t >> 4) + 16 * i, a.M - 1) * a.N + nc);
+  }
+  float mk[4][4];
+  if constexpr (EPI == 2) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) mk[i][j] = a.mask[(long long)min(m0 + (t >> 4) + 16 * i, a.M - 1) * a.ldm + nc + j];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = (t >> 4) + 16 * i, m = m0 + row;
+    if (m < a.M && n < a.N) {
+      const float o4[4] = {old[i].x, old[i].y, old[i].z, old[i].w};
+      float v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[j] = Cs[row * PB + (t & 15) * 4 + j] + bv[j];
+        if constexpr (EPI == 1) v[j] = v[j] > 0.f ? v[j] : v[j] * a.slope;
+        if constexpr (EPI == 2) v[j] *= mk[i][j] > 0.f ? 1.f : a.slope;
+        if (a.accumulate) v[j] = o4[j] + v[j];
+      }
+      *reinterpret_cast<float4*>(out + (size_t)m * a.N + n) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  }
+}
+
 // C (+)= bias[n] + sum_s slab[s]
 __global__ void gemm64_reduce(const float* __restrict__ slab, const float* __restrict__ bias, float* __restrict__ C,
                               size_t total, int N, int splits, int accumulate) {
@@ -1953,60 +2089,83 @@ __device__ __forceinline__ void wgrad_reduce_tile(const WgReduceDesc& d, int til
 }
 
 // Layers with MANY slices (the 64-channel layers: a 147-KB weight, 170 slices): a thread walking all slices of its elements
-// is a chain of ~85 dependent memory round trips, the critical path of the whole launch (157 against 84 us).  "Fine" tiles
-// own 16 elements x 9 taps and split the slice range SIXTEEN ways (lane = (slice group, element), 4 groups per wave);
-// the partial sums meet in LDS and are folded in group order, the 144 results leave as one contiguous run.  Only for
-// >= 64 slices: at 8 / 16 slices fine tiles took 195 / 126 us for the same launch (tools/reduce_bench.py).
+// is a chain of ~85 dependent memory round trips, the critical path of the whole launch (157 against 84 us).  "Fine" tile
+// numbers stand for 16 elements x 9 taps whose slice range is split SIXTEEN ways, the group sums folded in group order.
+// Only for >= 64 slices: at 8 / 16 slices fine tiles took 195 / 126 us for the same launch (tools/reduce_bench.py).
+//
+// A block takes kWgFineTiles consecutive tile numbers together (64 elements): lane = (slice group, four elements), 4 groups
+// per wave, so a load instruction covers 256 contiguous bytes per (slice, tap) -- two whole cache lines -- where a block
+// per tile number read 64-byte segments whose other halves were fetched again by other blocks once the slabs no longer sat
+// in a cache.  Up to four slices (36 float4) are in flight per thread.  The group sums meet in LDS in dw's own order
+// ([group][element][tap]), every thread folds them for two or three of the 576 outputs, and those leave as one contiguous
+// run of dw.  Per (element, tap) the additions and their order are those of one tile number on its own.
 constexpr int kWgFineSplits = 64;   // a descriptor is "fine" when any of its sources has at least this many slices
-__device__ __forceinline__ void wgrad_reduce_tile_fine(const WgReduceDesc& d, int tile, float* part /* [16][9][16] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, el = lane & 15, sg = wave * 4 + (lane >> 4);
-  const int e0 = tile * 16, e = e0 + el;
+constexpr int kWgFineTiles = 4;     // tile numbers per block
+constexpr int kWgFineElems = 16 * kWgFineTiles, kWgFineOut = 9 * kWgFineElems;
+constexpr int kWgPartFloats = 16 * kWgFineOut;   // 36 KB of LDS
+static_assert(kWgFineElems == 64 && kWgFineOut <= 3 * 256, "lane mapping of wgrad_reduce_tile_fine");
+
+template <int U>   // acc += slices sl .. sl + U - 1, in that order, all their loads issued first
+__device__ __forceinline__ void wgrad_fine_add(float (&acc)[36], const float* p, int sl, size_t stride, size_t plane) {
+  float4 v[U][9];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int tp = 0; tp < 9; ++tp) v[u][tp] = *reinterpret_cast<const float4*>(p + (size_t)(sl + u) * stride + (size_t)tp * plane);
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int tp = 0; tp < 9; ++tp)
+      acc[tp] += v[u][tp].x, acc[9 + tp] += v[u][tp].y, acc[18 + tp] += v[u][tp].z, acc[27 + tp] += v[u][tp].w;
+}
+
+__device__ __forceinline__ void wgrad_reduce_tile_fine(const WgReduceDesc& d, int item, float* part /* [16][64][9] */) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, el4 = lane & 15, sg = wave * 4 + (lane >> 4);
+  const int e0 = item * kWgFineElems, e = e0 + el4 * 4;      // Co * Ci % 4 == 0
   const bool live = e < d.coci;
   const size_t plane = (size_t)d.coci, stride = 9 * plane;
-  const int o = threadIdx.x;                          // outputs 0..143 = (element, tap) of this tile
-  const bool oo = o < 144 && e0 * 9 + o < d.coci * 9;
-  float tot = (d.accumulate && oo) ? d.dw[(size_t)e0 * 9 + o] : 0.f;
+  const int nout = min(kWgFineOut, (d.coci - e0) * 9);       // outputs (element, tap) of this block: dw[e0 * 9 + o]
+  float* dwp = d.dw + (size_t)e0 * 9;
+  float tot[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int o = (int)threadIdx.x + 256 * r;
+    tot[r] = (d.accumulate && o < nout) ? dwp[o] : 0.f;
+  }
   for (int k = 0; k < d.nsrc; ++k) {
     const int q = (d.splits[k] + 15) >> 4;
     const int s0 = sg * q, s1 = min(s0 + q, d.splits[k]);
-    float acc[9];
+    float acc[36];                                           // [element][tap]
 #pragma unroll
-    for (int tp = 0; tp < 9; ++tp) acc[tp] = 0.f;
+    for (int f = 0; f < 36; ++f) acc[f] = 0.f;
     if (live) {
       const float* p = d.slab[k] + e;
       int sl = s0;
-      for (; sl + 4 <= s1; sl += 4) {
-        float v[4][9];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int tp = 0; tp < 9; ++tp) v[u][tp] = p[(size_t)(sl + u) * stride + (size_t)tp * plane];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int tp = 0; tp < 9; ++tp) acc[tp] += v[u][tp];
-      }
-      for (; sl < s1; ++sl) {
-        float v[9];
-#pragma unroll
-        for (int tp = 0; tp < 9; ++tp) v[tp] = p[(size_t)sl * stride + (size_t)tp * plane];
-#pragma unroll
-        for (int tp = 0; tp < 9; ++tp) acc[tp] += v[tp];
-      }
+      for (; sl + 4 <= s1; sl += 4) wgrad_fine_add<4>(acc, p, sl, stride, plane);
+      if (sl + 2 <= s1) wgrad_fine_add<2>(acc, p, sl, stride, plane), sl += 2;
+      if (sl < s1) wgrad_fine_add<1>(acc, p, sl, stride, plane);
     }
     if (k) __syncthreads();
+    float4* pw = reinterpret_cast<float4*>(part + sg * kWgFineOut + el4 * 36);
 #pragma unroll
-    for (int tp = 0; tp < 9; ++tp) part[(sg * 9 + tp) * 16 + el] = acc[tp];
+    for (int c = 0; c < 9; ++c) pw[c] = make_float4(acc[4 * c], acc[4 * c + 1], acc[4 * c + 2], acc[4 * c + 3]);
     __syncthreads();
-    if (o < 144) {
-      const int el2 = o / 9, tp = o - el2 * 9;
-      float sum = 0.f;
 #pragma unroll
-      for (int g = 0; g < 16; ++g) sum += part[(g * 9 + tp) * 16 + el2];
-      tot += sum;
+    for (int r = 0; r < 3; ++r) {
+      const int o = (int)threadIdx.x + 256 * r;
+      if (o < kWgFineOut) {
+        float sum = 0.f;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) sum += part[g * kWgFineOut + o];
+        tot[r] += sum;
+      }
     }
   }
-  if (oo) d.dw[(size_t)e0 * 9 + o] = tot;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int o = (int)threadIdx.x + 256 * r;
+    if (o < nout) dwp[o] = tot[r];
+  }
 }
 static inline bool wgrad_reduce_fine(const int* splits, int nsrc) {
   for (int k = 0; k < nsrc; ++k)
@@ -2017,37 +2176,66 @@ static inline int wgrad_reduce_blocks(int coci, bool fine) { return fine ? cdiv(
 
 __global__ __launch_bounds__(256) void wgrad_p_reduce(const float* __restrict__ slab, float* __restrict__ dw, int CoCi,
                                                      int splits, int accumulate, int fine) {
-  __shared__ float part[4][9][64];
+  __shared__ __attribute__((aligned(16))) float part[kWgPartFloats];
   WgReduceDesc d;
   d.slab[0] = slab, d.dw = dw, d.splits[0] = splits, d.nsrc = 1, d.coci = CoCi, d.accumulate = accumulate;
-  if (fine) wgrad_reduce_tile_fine(d, blockIdx.x, &part[0][0][0]);
+  if (fine) wgrad_reduce_tile_fine(d, blockIdx.x, part);   // grid: one block per kWgFineTiles tile numbers
   else wgrad_reduce_tile(d, blockIdx.x);
 }
 
 // The same reduce for MANY layers in one launch (a backward pass's weight gradients, folded when the pass is over): a
 // device-resident table of descriptors, every layer owns a contiguous range of tile numbers; a layer whose weight took
-// part in several network passes of the backward lists their slabs in call order.  Persistent blocks: each copies the
-// table into LDS once and walks tiles blockIdx.x, + gridDim.x, ... -- with one block per tile every block began with two
-// dependent global round trips (find the descriptor, load it) in front of a tile that needs one.
+// part in several network passes of the backward lists their slabs in call order.  Each block copies the table into LDS
+// once (one global round trip in front of its work, not two: find the descriptor, load it).
+//
+// What a block takes at a time is a work item: one wide tile number, or kWgFineTiles fine ones.  Items differ in cost by
+// more than ten (1024 elements x 20 slices against 1024 x 2), so they are not walked in table order: every block ranks the
+// descriptors by the bytes one of their items reads, heaviest first (ties in table order), and block b takes items b,
+// b + gridDim.x, ... of that order -- the heavy items start first and the light ones fill in behind them.
 constexpr int kWgMaxDesc = 96;
-__global__ __launch_bounds__(256) void wgrad_p_reduce_many(const WgReduceDesc* __restrict__ tab, int n, int tile0, int tile1) {
-  __shared__ float part[4][9][64];
+__device__ __forceinline__ int wgrad_desc_items(const WgReduceDesc& d) {
+  return d.fine ? (d.nblocks + kWgFineTiles - 1) / kWgFineTiles : d.nblocks;
+}
+__global__ __launch_bounds__(256) void wgrad_p_reduce_many(const WgReduceDesc* __restrict__ tab, int n) {
+  __shared__ __attribute__((aligned(16))) float part[kWgPartFloats];
   __shared__ WgReduceDesc s_desc[kWgMaxDesc];
+  __shared__ int s_cost[kWgMaxDesc], s_items[kWgMaxDesc], s_ord[kWgMaxDesc], s_first[kWgMaxDesc + 1];
+  const int tid = threadIdx.x;
   {
     const int* src = reinterpret_cast<const int*>(tab);
     int* dst = reinterpret_cast<int*>(s_desc);
-    for (int i = threadIdx.x; i < n * (int)(sizeof(WgReduceDesc) / 4); i += blockDim.x) dst[i] = src[i];
+    for (int i = tid; i < n * (int)(sizeof(WgReduceDesc) / 4); i += blockDim.x) dst[i] = src[i];
   }
   __syncthreads();
-  int di = 0;
-  for (int t = tile0 + (int)blockIdx.x; t < tile1; t += (int)gridDim.x) {
-    while (di + 1 < n && s_desc[di + 1].block0 <= t) ++di;
-    const WgReduceDesc d = s_desc[di];
+  if (tid < n) {
+    const WgReduceDesc& d = s_desc[tid];
+    int slices = 0;
+    for (int k = 0; k < d.nsrc; ++k) slices += d.splits[k];
+    s_cost[tid] = slices * (d.fine ? kWgFineElems : 1024);
+    s_items[tid] = wgrad_desc_items(d);
+  }
+  __syncthreads();
+  if (tid < n) {
+    const int mine = s_cost[tid];
+    int rank = 0, first = 0;
+    for (int j = 0; j < n; ++j) {
+      const int cj = s_cost[j];
+      if (cj > mine || (cj == mine && j < tid)) ++rank, first += s_items[j];
+    }
+    s_ord[rank] = tid, s_first[rank] = first;
+    if (rank == n - 1) s_first[n] = first + s_items[tid];
+  }
+  __syncthreads();
+  const int total = s_first[n];
+  int r = 0;
+  for (int w = (int)blockIdx.x; w < total; w += (int)gridDim.x) {
+    while (s_first[r + 1] <= w) ++r;
+    const WgReduceDesc& d = s_desc[s_ord[r]];
     if (d.fine) {
-      wgrad_reduce_tile_fine(d, t - d.block0, &part[0][0][0]);
-      __syncthreads();                                // `part` is reused by the next tile
+      wgrad_reduce_tile_fine(d, w - s_first[r], part);
+      __syncthreads();                                // `part` is reused by the next item
     } else {
-      wgrad_reduce_tile(d, t - d.block0);
+      wgrad_reduce_tile(d, w - s_first[r]);
     }
   }
 }
@@ -2891,7 +3079,8 @@ int itcv_conv2d_wgrad_bf16p(const void* xplanes, const void* dyplanes, float* dw
   if (accumulate == 2) return 0;     // deferred: the slabs stay in `ws` for itcv_wgrad_reduce_many
   const int coci = Co * Ci;
   const bool fine = wgrad_reduce_fine(&p.slabs, 1);
-  hipLaunchKernelGGL(wgrad_p_reduce, dim3(wgrad_reduce_blocks(coci, fine)), dim3(256), 0, st, static_cast<const float*>(ws),
+  const int rblocks = fine ? cdiv(wgrad_reduce_blocks(coci, true), kWgFineTiles) : wgrad_reduce_blocks(coci, false);
+  hipLaunchKernelGGL(wgrad_p_reduce, dim3(rblocks), dim3(256), 0, st, static_cast<const float*>(ws),
                      dw, coci, p.slabs, accumulate, fine ? 1 : 0);
   ITCV_CHECK_LAUNCH("itcv_conv2d_wgrad_bf16p(reduce)");
   return 0;
@@ -2928,9 +3117,9 @@ int itcv_wgrad_reduce_max_descs(void) { return kWgMaxDesc; }
 int itcv_wgrad_reduce_many(const void* dev_table, int n, int total_blocks, void* stream) {
   ITCV_REQUIRE(dev_table && n > 0 && total_blocks > 0, "itcv_wgrad_reduce_many");
   if (n > kWgMaxDesc) return fail("%s: at most %d descriptors per table (itcv_wgrad_reduce_max_descs)", "itcv_wgrad_reduce_many", kWgMaxDesc);
-  const int grid = total_blocks < 2048 ? total_blocks : 2048;            // 8 blocks per CU, persistent
-  hipLaunchKernelGGL(wgrad_p_reduce_many, dim3(grid), dim3(256), 0, S(stream), static_cast<const WgReduceDesc*>(dev_table), n, 0,
-                     total_blocks);
+  // total_blocks (the table's tile count) bounds the number of work items from above; the kernel counts the items itself
+  const int grid = total_blocks < 2048 ? total_blocks : 2048;
+  hipLaunchKernelGGL(wgrad_p_reduce_many, dim3(grid), dim3(256), 0, S(stream), static_cast<const WgReduceDesc*>(dev_table), n);
   ITCV_CHECK_LAUNCH("itcv_wgrad_reduce_many");
   return 0;
 }
@@ -2979,8 +3168,19 @@ static int run_gemm64(const char* name, const float* A, const float* B, const fl
   a.mask = mask, a.ldm = ldm, a.slope = slope;
   dim3 grid(p.mt * p.nt, p.splits), blk(256);
   const bool akc = sak == 1, bkc = sbk == 1;
+  // gemm64_vec_kernel: every operand readable in aligned 16-byte pieces that are inside or outside the matrix as a whole
+  const auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  const bool vec = al16(A) && al16(B) && al16(a.C) && N % 4 == 0 &&
+                   (akc ? (K % 4 == 0 && sam % 4 == 0) : (sam == 1 && M % 4 == 0 && sak % 4 == 0)) &&
+                   (bkc ? (K % 4 == 0 && sbn % 4 == 0) : (sbn == 1 && sbk % 4 == 0));
   // the fused epilogues exist for the two layouts the discriminator's layers have; a split-K launch writes plain slabs
-  if (epi == 1 && p.splits == 1) hipLaunchKernelGGL((gemm64_kernel<true, true, 1>), grid, blk, 0, st, a);
+  if (vec && epi == 1 && p.splits == 1) hipLaunchKernelGGL((gemm64_vec_kernel<true, true, 1>), grid, blk, 0, st, a);
+  else if (vec && epi == 2 && p.splits == 1) hipLaunchKernelGGL((gemm64_vec_kernel<true, false, 2>), grid, blk, 0, st, a);
+  else if (vec && akc && bkc) hipLaunchKernelGGL((gemm64_vec_kernel<true, true>), grid, blk, 0, st, a);
+  else if (vec && akc) hipLaunchKernelGGL((gemm64_vec_kernel<true, false>), grid, blk, 0, st, a);
+  else if (vec && bkc) hipLaunchKernelGGL((gemm64_vec_kernel<false, true>), grid, blk, 0, st, a);
+  else if (vec) hipLaunchKernelGGL((gemm64_vec_kernel<false, false>), grid, blk, 0, st, a);
+  else if (epi == 1 && p.splits == 1) hipLaunchKernelGGL((gemm64_kernel<true, true, 1>), grid, blk, 0, st, a);
   else if (epi == 2 && p.splits == 1) hipLaunchKernelGGL((gemm64_kernel<true, false, 2>), grid, blk, 0, st, a);
   else if (akc && bkc) hipLaunchKernelGGL((gemm64_kernel<true, true>), grid, blk, 0, st, a);
   else if (akc) hipLaunchKernelGGL((gemm64_kernel<true, false>), grid, blk, 0, st, a);

@@ -281,6 +281,7 @@ struct TcGrad {
   float coef_tc, coef_kl;
 };
 __device__ __forceinline__ float tc_g(const TcGrad& t, int j) { return t.bcast ? t.g[0] : t.g[j]; }
+constexpr int kTcBwdU = 16;   // columns (rows) per wave whose loads are in flight together: 64 x 64 is one batch per wave
 
 __global__ __launch_bounds__(256) void tc_bwd_rows_kernel(
     TcGrad tg, const float* __restrict__ z, const float* __restrict__ mu_all,
@@ -296,19 +297,34 @@ __global__ __launch_bounds__(256) void tc_bwd_rows_kernel(
   const float var = expf(lvj), vh = fmaxf(var, kVarEps), lvh = logf(vh), ivh = 1.f / vh;
   const float ls = act ? lse[(size_t)j * D + l] : 0.f;
   float az = 0.f, av = 0.f;
-#pragma unroll 4
-  for (int i = wid; i < Bt; i += 4) {                  // wave-uniform i: sjoint / log_iw are scalar work
-    const float liw = log_iw(c, jg, i);
-    const float q = gj * expf(sjoint[(size_t)j * Bt + i] - lq);
-    if (blockIdx.y == 0 && lane == 0) wq[(size_t)j * Bt + i] = q;
-    if (act) {
-      const float d = zj - mu_all[(size_t)i * D + l];
-      const float lp = -(0.5f * (lvh + d * d * ivh) + kHalfLog2Pi);
-      if (lp >= kFloor) {                              // clamp(min=-50) passes the gradient where lp >= -50
-        const float G = q - gj * expf(lp + liw - ls);
-        const float dv = d * ivh;
-        az -= G * dv;
-        av -= G * 0.5f * (ivh - dv * dv);              // d lp / d var at the clamped value (straight-through)
+  // A wave's columns i = wid, wid + 4, ... are taken kTcBwdU at a time: the loads of a whole batch (from clamped, always
+  // valid addresses) are issued before the first expf chain that depends on one of them -- with the loads inside the
+  // `if (act)` every column was a dependent round trip.  The terms and their order are unchanged; `act`, the column
+  // bound and the clamp only decide whether a term is added.
+  const int lc = min(l, D - 1);
+  for (int i0 = wid; i0 < Bt; i0 += 4 * kTcBwdU) {     // wave-uniform i: sjoint / log_iw are scalar work
+    float mv[kTcBwdU], sv[kTcBwdU];
+#pragma unroll
+    for (int u = 0; u < kTcBwdU; ++u) {
+      const int ic = min(i0 + 4 * u, Bt - 1);
+      mv[u] = mu_all[(size_t)ic * D + lc];
+      sv[u] = sjoint[(size_t)j * Bt + ic];
+    }
+#pragma unroll
+    for (int u = 0; u < kTcBwdU; ++u) {
+      const int i = i0 + 4 * u;
+      if (i < Bt) {
+        const float liw = log_iw(c, jg, i);
+        const float q = gj * expf(sv[u] - lq);
+        if (blockIdx.y == 0 && lane == 0) wq[(size_t)j * Bt + i] = q;
+        const float d = zj - mv[u];
+        const float lp = -(0.5f * (lvh + d * d * ivh) + kHalfLog2Pi);
+        if (act && lp >= kFloor) {                     // clamp(min=-50) passes the gradient where lp >= -50
+          const float G = q - gj * expf(lp + liw - ls);
+          const float dv = d * ivh;
+          az -= G * dv;
+          av -= G * 0.5f * (ivh - dv * dv);            // d lp / d var at the clamped value (straight-through)
+        }
       }
     }
   }
@@ -333,14 +349,28 @@ __global__ __launch_bounds__(256) void tc_bwd_cols_kernel(
   const bool act = l < D;
   const float mi = act ? mu_all[(size_t)i * D + l] : 0.f;
   float acc = 0.f;
-#pragma unroll 2
-  for (int j = wid; j < Bl; j += 4) {
-    const float gj = tg.coef_tc * tc_g(tg, j), q = wq[(size_t)j * Bt + i], liw = log_iw(c, row_offset + j, i);
-    if (act) {
-      const float vh = fmaxf(expf(logvar[(size_t)j * D + l]), kVarEps), ivh = 1.f / vh;
-      const float d = z[(size_t)j * D + l] - mi;
-      const float lp = -(0.5f * (logf(vh) + d * d * ivh) + kHalfLog2Pi);
-      if (lp >= kFloor) acc += (q - gj * expf(lp + liw - lse[(size_t)j * D + l])) * d * ivh;
+  const int lc = min(l, D - 1);
+  for (int j0 = wid; j0 < Bl; j0 += 4 * kTcBwdU) {     // a batch of rows: all its loads first (see tc_bwd_rows_kernel)
+    float lvv[kTcBwdU], zv[kTcBwdU], lsv[kTcBwdU], qv[kTcBwdU], gv[kTcBwdU];
+#pragma unroll
+    for (int u = 0; u < kTcBwdU; ++u) {
+      const int jc = min(j0 + 4 * u, Bl - 1);
+      lvv[u] = logvar[(size_t)jc * D + lc];
+      zv[u] = z[(size_t)jc * D + lc];
+      lsv[u] = lse[(size_t)jc * D + lc];
+      qv[u] = wq[(size_t)jc * Bt + i];
+      gv[u] = tg.g[tg.bcast ? 0 : jc];
+    }
+#pragma unroll
+    for (int u = 0; u < kTcBwdU; ++u) {
+      const int j = j0 + 4 * u;
+      if (j < Bl) {
+        const float gj = tg.coef_tc * gv[u], q = qv[u], liw = log_iw(c, row_offset + j, i);
+        const float vh = fmaxf(expf(lvv[u]), kVarEps), ivh = 1.f / vh;
+        const float d = zv[u] - mi;
+        const float lp = -(0.5f * (logf(vh) + d * d * ivh) + kHalfLog2Pi);
+        if (act && lp >= kFloor) acc += (q - gj * expf(lp + liw - lsv[u])) * d * ivh;
+      }
     }
   }
   racc[wid][lane] = acc;
