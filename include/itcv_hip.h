@@ -532,6 +532,43 @@ int itcv_ada_group_fwd(const float* mu, size_t ld_mu, const float* logvar, size_
 int itcv_ada_group_bwd(const float* dz, size_t ld_dz, const float* g, const float* mu, size_t ld_mu, const float* logvar,
                        size_t ld_logvar, const float* eps, size_t ld_eps, const uint8_t* own, float* dmu, float* dlogvar,
                        int B, int D, int averaging, double beta, void* stream);
+/* The latent op of JointVAE (Dupont 2018, "Learning Disentangled Joint Continuous and Discrete Representations") and, with
+ * n_disc = 0, of AnnealedVAE (Burgess et al. 2018; disentanglement_lib's `annealed_vae`) with its gradient (csrc/joint.hip).
+ * mu, logvar [B][D] fp32, D = n_cont + n_disc, unit column stride and row strides ld_mu, ld_logvar >= D (they may be the
+ * halves of one [B][2D] tensor).  Columns [0, n_cont) are the continuous posterior; columns [n_cont, D) of mu are the LOGITS
+ * a of G categorical variables laid side by side, and the same columns of logvar are never read.  eps [B][n_cont] ~ N(0, 1)
+ * (ld_eps >= n_cont), u [B][n_disc] ~ U[0, 1) (ld_u >= n_disc).  seg [n_disc][2] int32 on the device: the first and the
+ * one-past-last column of the group of discrete column j, both counted from the first discrete column (the kernels hold
+ * them inside 0 <= first <= j < last <= n_disc).  cap [2] fp64 ON THE DEVICE = (C_z, C_c), read by the second launch when it
+ * runs: a captured graph replays with whatever it holds then.  In fp64 from the fp32 inputs, every sum in column order:
+ *   z_d   = m + eps exp(l / 2),   part[b] = -1/2 sum_d (1 + l - m^2 - e^l)                                   (d < n_cont)
+ *   per group of K columns: log alpha = a - logsumexp(a),  u' = u > 0 ? u : 2^-25,  g = -log(-log u'),
+ *           y = softmax((a + g) / tau) -> z,   part[B + b] = sum over the groups of (log K + sum_k alpha_k log alpha_k)
+ *   KL_z = mean_b part[b], KL_c = mean_b part[B + b]                     (part [2B] fp64 is the op's workspace)
+ *   out[0] = beta (gamma_cont |KL_z - C_z| + gamma_disc |KL_c - C_c|),  sgn[2] = the signs of the two differences (0 at 0),
+ *   terms[4] = {KL_z, KL_c, C_z, C_c}
+ * z [B][D] fp32 is dense and written in full.  2 launches: a wave per row (four rows a block, the blocks stride over the
+ * rows), then a one-block finish that adds the partials in row order.
+ * hard != 0, ONE launch, the deterministic code: z_d = mu_d bit for bit (d < n_cont) and, per group, the one-hot of the FIRST
+ * maximum of the fp32 logits (an exact comparison; ties take the lowest column).  Only mu, seg and z are touched then; every
+ * other pointer may be NULL and tau, the gammas and beta are not looked at.
+ * _bwd, ONE launch: dz [B][D] (row stride ld_dz >= D) and g[1] are the gradients of z and out[0], sgn the forward's; every
+ * element of the dense dmu, dlogvar [B][D] is written.  With k_z = g beta gamma_cont sgn[0] / B, k_c = g beta gamma_disc
+ * sgn[1] / B:
+ *   d < n_cont:  dm = dz + k_z m,   dl = dz eps e^(l / 2) / 2 + k_z (e^l - 1) / 2
+ *   per group:   da_k = y_k (dz_k - sum_j y_j dz_j) / tau + k_c alpha_k (log alpha_k - sum_j alpha_j log alpha_j),  dl = 0
+ * Every sum is fp64 in a fixed order, there are no atomics: results are bitwise reproducible and do not depend on the grid.
+ * Refused before any launch: a NULL pointer that the call needs (eps / logvar with n_cont = 0, u / seg with n_disc = 0 are
+ * not needed), B outside 1..2^30, a negative n_cont or n_disc, D outside 1..512, a temperature that is not finite and above
+ * 0, a gamma that is negative or not finite, a non-finite beta, a row stride below its width. */
+int itcv_joint_latent_fwd(const float* mu, size_t ld_mu, const float* logvar, size_t ld_logvar, const float* eps,
+                          size_t ld_eps, const float* u, size_t ld_u, const int* seg, const double* cap, float* z,
+                          double* part, float* out, float* sgn, float* terms, int B, int n_cont, int n_disc, int hard,
+                          double tau, double gamma_cont, double gamma_disc, double beta, void* stream);
+int itcv_joint_latent_bwd(const float* dz, size_t ld_dz, const float* g, const float* sgn, const float* mu, size_t ld_mu,
+                          const float* logvar, size_t ld_logvar, const float* eps, size_t ld_eps, const float* u,
+                          size_t ld_u, const int* seg, float* dmu, float* dlogvar, int B, int n_cont, int n_disc,
+                          double tau, double gamma_cont, double gamma_disc, double beta, void* stream);
 /* The FactorVAE objective (Kim & Mnih 2018; disentanglement_lib's `factor_vae`), csrc/factor.hip.
  * itcv_permute_dims, ONE launch (a block per column): out[r][d] = z[i][d] where r is the rank of keys[i][d] in column d
  * of keys[B][D] -- ascending in the monotone uint32 image of the float's bits (the sign-flip map of itcv_udr_ranks, +0 and

@@ -146,6 +146,10 @@ SIGNATURES = {
     "itcv_mmd_kl_bwd": (i32, [p] * 10 + [i32, i32, i32, i32, f64, f64, p]),
     "itcv_ada_group_fwd": (i32, [p, sz, p, sz, p, sz, p, p, p, p, p, p, i32, i32, i32, f64, p]),
     "itcv_ada_group_bwd": (i32, [p, sz, p, p, sz, p, sz, p, sz, p, p, p, i32, i32, i32, f64, p]),
+    "itcv_joint_latent_fwd": (i32, [p, sz, p, sz, p, sz, p, sz, p, p, p, p, p, p, p, i32, i32, i32, i32, f64, f64, f64, f64,
+                                    p]),
+    "itcv_joint_latent_bwd": (i32, [p, sz, p, p, p, sz, p, sz, p, sz, p, sz, p, p, p, i32, i32, i32, f64, f64, f64, f64,
+                                    p]),
     "itcv_permute_dims": (i32, [p, sz, p, sz, p, p, i32, i32, p]),
     "itcv_disc_head_fwd": (i32, [p, i32, i32, p, p]),
     "itcv_disc_head_bwd": (i32, [p, p, p, i32, i32, i32, p]),

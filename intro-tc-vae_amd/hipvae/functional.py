@@ -1625,6 +1625,103 @@ class AdaGroupFn(Function):
         return dmu, dlv, None, None, None, None
 
 
+# ------------------------------------------------------------------ JointVAE / AnnealedVAE: the capacity-controlled latent op
+JOINT_MAX_D = 512
+
+
+def _joint_device(*tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+
+
+def _row_ptr(t):
+    """Device pointer of what ``_rows_f32`` returned (a row-strided view is passed as it is), or NULL for None."""
+    return None if t is None else t.data_ptr()
+
+
+class JointLatentFn(Function):
+    """The latent op of JointVAE / AnnealedVAE (include/itcv_hip.h: itcv_joint_latent_fwd): two launches forward, one
+    backward.  ``mu`` / ``logvar`` [B, n_cont + n_disc]: fp32 views with unit column stride are read in place (the halves of
+    one packed [B, 2D] tensor too); ``eps`` [B, n_cont] and ``u`` [B, n_disc] (None where the block is empty); ``seg``
+    [n_disc, 2] int32: the group of every discrete column; ``capacity`` [2] fp64 on the device, read when the kernel runs.
+    Outputs: z [B, D] and the scalar beta (gamma_cont |KL_z - C_z| + gamma_disc |KL_c - C_c|), both differentiable in
+    ``mu`` and ``logvar``, and (KL_z, KL_c, C_z, C_c) [4], no gradient.  The signs of the two differences are kept for the
+    backward pass, so it does not read ``capacity`` again."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, u, seg, capacity, n_cont, n_disc, tau, gamma_cont, gamma_disc, beta):
+        if mu.dim() != 2 or mu.shape != logvar.shape:
+            raise ValueError(f"mu and logvar must share one [B, D] shape (got {tuple(mu.shape)}, {tuple(logvar.shape)})")
+        B, D = mu.shape
+        if n_cont < 0 or n_disc < 0 or n_cont + n_disc != D:
+            raise ValueError(f"n_cont + n_disc = {n_cont} + {n_disc} is not D = {D}")
+        if B < 1 or not 1 <= D <= JOINT_MAX_D:
+            raise ValueError(f"the joint op takes B >= 1 and 1 <= D <= {JOINT_MAX_D} (got {(B, D)})")
+        if n_cont and (eps is None or tuple(eps.shape) != (B, n_cont)):
+            raise ValueError(f"eps must be [B, n_cont] = {(B, n_cont)}")
+        if n_disc and (u is None or tuple(u.shape) != (B, n_disc) or seg is None or tuple(seg.shape) != (n_disc, 2)
+                       or seg.dtype != torch.int32):
+            raise ValueError(f"u must be [B, n_disc] = {(B, n_disc)} and seg an int32 [n_disc, 2] table")
+        if tuple(capacity.shape) != (2,) or capacity.dtype != torch.float64:
+            raise ValueError(f"capacity must be a [2] float64 tensor (got {tuple(capacity.shape)}, {capacity.dtype})")
+        _joint_device(capacity, seg)
+        (mu, ldm), (logvar, ldl) = _rows_f32(mu, "mu"), _rows_f32(logvar, "logvar")
+        (eps, lde) = _rows_f32(eps, "eps") if n_cont else (None, 0)
+        (u, ldu) = _rows_f32(u, "u") if n_disc else (None, 0)
+        seg = seg.contiguous() if n_disc else None
+        dev = mu.device
+        z = torch.empty((B, D), dtype=F32, device=dev)
+        part = torch.empty((2 * B,), dtype=torch.float64, device=dev)
+        out = torch.empty((), dtype=F32, device=dev)
+        sgn = torch.empty((2,), dtype=F32, device=dev)
+        terms = torch.empty((4,), dtype=F32, device=dev)
+        call("itcv_joint_latent_fwd", mu.data_ptr(), ldm, logvar.data_ptr(), ldl, _row_ptr(eps), lde, _row_ptr(u), ldu,
+             ptr(seg), ptr(capacity.contiguous()), ptr(z), ptr(part), ptr(out), ptr(sgn), ptr(terms), B, int(n_cont),
+             int(n_disc), 0, float(tau), float(gamma_cont), float(gamma_disc), float(beta), stream())
+        ctx.save_for_backward(mu, logvar, eps, u, seg, sgn)
+        ctx.cfg = (int(n_cont), int(n_disc), float(tau), float(gamma_cont), float(gamma_disc), float(beta), ldm, ldl, lde,
+                   ldu)
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)         # no zero tensor is filled for ``terms`` (or an unused z / loss) per backward
+        return z, out, terms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, g, _g_terms):
+        mu, logvar, eps, u, seg, sgn = ctx.saved_tensors
+        n_cont, n_disc, tau, gamma_cont, gamma_disc, beta, ldm, ldl, lde, ldu = ctx.cfg
+        B, D = mu.shape
+        if dz is None:                           # z unused: the loss alone is differentiated
+            dz = torch.zeros((B, D), dtype=F32, device=mu.device)
+        if g is None:
+            g = torch.zeros((), dtype=F32, device=mu.device)
+        dz, ldz = _rows_f32(dz, "dz")
+        dmu, dlv = torch.empty((B, D), dtype=F32, device=mu.device), torch.empty((B, D), dtype=F32, device=mu.device)
+        call("itcv_joint_latent_bwd", dz.data_ptr(), ldz, ptr(_f32c(g)), ptr(sgn), mu.data_ptr(), ldm, logvar.data_ptr(),
+             ldl, _row_ptr(eps), lde, _row_ptr(u), ldu, ptr(seg), ptr(dmu), ptr(dlv), B, n_cont, n_disc, tau, gamma_cont,
+             gamma_disc, beta, stream())
+        return (dmu, dlv) + (None,) * 10
+
+
+def joint_latent_hard(mu, seg, n_cont, n_disc):
+    """The deterministic code of ``JointLatentFn``'s model, one launch, no gradient: the continuous columns of ``mu`` bit
+    for bit, and per group the one-hot of the first maximum of the fp32 logits."""
+    if mu.dim() != 2 or n_cont < 0 or n_disc < 0 or n_cont + n_disc != mu.size(1):
+        raise ValueError(f"mu must be [B, n_cont + n_disc] (got {tuple(mu.shape)} for {n_cont} + {n_disc})")
+    B, D = mu.shape
+    if B < 1 or not 1 <= D <= JOINT_MAX_D:
+        raise ValueError(f"the joint op takes B >= 1 and 1 <= D <= {JOINT_MAX_D} (got {(B, D)})")
+    if n_disc and (seg is None or tuple(seg.shape) != (n_disc, 2) or seg.dtype != torch.int32):
+        raise ValueError("seg must be an int32 [n_disc, 2] table")
+    _joint_device(seg)
+    mu, ldm = _rows_f32(mu.detach(), "mu")
+    z = torch.empty((B, D), dtype=F32, device=mu.device)
+    call("itcv_joint_latent_fwd", mu.data_ptr(), ldm, None, 0, None, 0, None, 0, ptr(seg.contiguous() if n_disc else None),
+         None, ptr(z), None, None, None, None, B, int(n_cont), int(n_disc), 1, 1.0, 0.0, 0.0, 0.0, stream())
+    return z
+
+
 class DiscPass:
     """One forward of the discriminator MLP over R stacked rows, the first R0 labelled 0 ("from q(z)") and the rest 1
     ("from the product of the marginals"): the input ``x`` [R, zdim], the hidden activations, the logits [R, 2], the

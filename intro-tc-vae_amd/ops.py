@@ -56,6 +56,21 @@ def noise(shape, device):
     return torch.randn(shape, device=device)
 
 
+def uniform_noise(shape, device):
+    """U[0, 1) draws (``torch.rand``: fp32 multiples of 2^-24) from the same source as ``noise``: the device generator,
+    the host's in "host" mode, or the next recorded tensor inside a ``noise_queue`` block."""
+    q = _noise["queue"]
+    if q is not None:
+        if not q:
+            raise RuntimeError("noise_queue exhausted")
+        t = q.pop(0)
+        assert tuple(t.shape) == tuple(shape), (t.shape, shape)
+        return t.to(device=device, dtype=torch.float32)
+    if _noise["mode"] == "host":
+        return torch.rand(shape).to(device)
+    return torch.rand(shape, device=device)
+
+
 # ---------------------------------------------------------------------------- ops surface
 def reparameterize(mu, logvar):
     """ops.py:166-185."""
@@ -266,6 +281,105 @@ def ada_group(mu, logvar, beta, averaging="gvae", own=None, eps=None, with_terms
     z, loss, mask, terms = HF.AdaGroupFn.apply(mu, logvar, eps.detach(), None if own is None else own.detach(),
                                                ADA_AVERAGINGS[averaging], float(beta))
     return (z, loss, mask, terms) if with_terms else (z, loss)
+
+
+_JOINT_SEG = {}
+
+
+def joint_spec(n_cont, disc_sizes, D=None):
+    """``(n_cont, disc_sizes as a tuple of ints, n_disc)`` of a latent spec, checked: n_cont >= 0, every K_i >= 2,
+    1 <= n_cont + sum K_i <= 512 and, when ``D`` is given, equal to it."""
+    disc = tuple(disc_sizes)
+    if isinstance(n_cont, bool) or int(n_cont) != n_cont or n_cont < 0:
+        raise ValueError(f"n_cont must be a non-negative integer (got {n_cont!r})")
+    if any(isinstance(k, bool) or int(k) != k or k < 2 for k in disc):
+        raise ValueError(f"every discrete variable needs K >= 2 categories (got {disc})")
+    n_cont, disc = int(n_cont), tuple(int(k) for k in disc)
+    n_disc = sum(disc)
+    if not 1 <= n_cont + n_disc <= HF.JOINT_MAX_D:
+        raise ValueError(f"joint_latent takes 1 <= D <= {HF.JOINT_MAX_D} (got n_cont + sum K = {n_cont + n_disc})")
+    if D is not None and n_cont + n_disc != D:
+        raise ValueError(f"n_cont + sum K = {n_cont} + {n_disc} is not D = {D}")
+    return n_cont, disc, n_disc
+
+
+def joint_segments(disc_sizes, device):
+    """The device table [n_disc, 2] int32 of a discrete block: per column the first and the one-past-last column of its
+    group, counted from the first discrete column.  Built once per (sizes, device) and kept."""
+    key = (tuple(disc_sizes), torch.device(device))
+    seg = _JOINT_SEG.get(key)
+    if seg is None:
+        ends = np.cumsum(key[0])
+        rows = [(e - k, e) for k, e in zip(key[0], ends) for _ in range(k)]
+        seg = _JOINT_SEG[key] = torch.tensor(rows, dtype=torch.int32).reshape(-1, 2).to(device)
+    return seg
+
+
+def joint_latent(mu, logvar, n_cont, disc_sizes, capacity, gamma_cont, gamma_disc, beta=1.0, temperature=0.67, eps=None,
+                 u=None, hard=False, with_terms=False):
+    """The latent op of JointVAE (Dupont 2018, "Learning Disentangled Joint Continuous and Discrete Representations") and,
+    with ``disc_sizes=()``, of AnnealedVAE (Burgess et al. 2018; disentanglement_lib's ``annealed_vae``); neither is in
+    the reference.  ``mu``, ``logvar`` [B, D] with D = n_cont + sum K_i: columns [0, n_cont) are the continuous posterior,
+    the rest of ``mu`` the logits ``a`` of G categorical variables with K_1 .. K_G categories side by side; the same
+    columns of ``logvar`` are never read and get an exactly zero gradient.
+
+        z_cont = m + eps exp(l / 2),                            KL_z = mean_b -1/2 sum_d (1 + l - m^2 - e^l)
+        per group: log alpha = a - logsumexp(a),  g = -log(-log u)  (u = 0 is taken as 2^-25),
+                   y = softmax((a + g) / temperature),          KL_c = sum_i mean_b (log K_i + sum_k alpha_k log alpha_k)
+        loss = beta (gamma_cont |KL_z - C_z| + gamma_disc |KL_c - C_c|),   (C_z, C_c) = capacity
+
+    ``capacity`` is a [2] float64 DEVICE tensor that the kernel reads when it runs: a captured step replays with the
+    value it holds then.  Returns ``(z [B, D] = [z_cont | y_1 | .. | y_G], loss)``, both differentiable in ``mu`` and
+    ``logvar``; with ``with_terms`` also the device vector (KL_z, KL_c, C_z, C_c), no gradient.  ``eps`` None: a draw
+    ``noise((B, n_cont))``, then ``u`` None: a draw ``uniform_noise((B, n_disc))`` -- in this order, and none for an
+    empty block -- so recorded draws and graph capture work as for ``reparameterize``.  ``hard=True`` returns the
+    deterministic code alone: z_cont = mu bit for bit and per group the one-hot of the first maximum of the logits; no
+    loss, no gradient, one launch (``capacity`` and the weights are not looked at).  Two launches forward, one backward,
+    fp64 inside, bitwise reproducible; 1 <= D <= 512, every K_i >= 2."""
+    if mu.dim() != 2 or mu.shape != logvar.shape:
+        raise ValueError(f"mu and logvar must share one [B, D] shape (got {tuple(mu.shape)}, {tuple(logvar.shape)})")
+    B, D = mu.shape
+    if B < 1:
+        raise ValueError("joint_latent needs at least one row")
+    n_cont, disc, n_disc = joint_spec(n_cont, disc_sizes, D)
+    if hard:
+        if not mu.is_cuda:
+            raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+        return HF.joint_latent_hard(mu, joint_segments(disc, mu.device) if n_disc else None, n_cont, n_disc)
+    temperature, gamma_cont, gamma_disc, beta = float(temperature), float(gamma_cont), float(gamma_disc), float(beta)
+    if not (0.0 < temperature < math.inf):
+        raise ValueError(f"temperature must be a finite number above 0 (got {temperature})")
+    if not (0.0 <= gamma_cont < math.inf and 0.0 <= gamma_disc < math.inf):
+        raise ValueError(f"gamma_cont and gamma_disc must be finite and not negative (got {gamma_cont}, {gamma_disc})")
+    if not math.isfinite(beta):
+        raise ValueError(f"beta must be finite (got {beta})")
+    if eps is not None and tuple(eps.shape) != (B, n_cont):
+        raise ValueError(f"eps must be [B, n_cont] = {(B, n_cont)} (got {tuple(eps.shape)})")
+    if u is not None and tuple(u.shape) != (B, n_disc):
+        raise ValueError(f"u must be [B, n_disc] = {(B, n_disc)} (got {tuple(u.shape)})")
+    if not (mu.is_cuda and logvar.is_cuda):
+        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    if not isinstance(capacity, torch.Tensor) or tuple(capacity.shape) != (2,) or capacity.dtype != torch.float64 \
+            or not capacity.is_cuda:
+        raise ValueError("capacity must be a [2] float64 device tensor (C_z, C_c): the kernel reads it when it runs")
+    if n_cont and eps is None:
+        eps = noise((B, n_cont), mu.device)
+    if n_disc and u is None:
+        u = uniform_noise((B, n_disc), mu.device)
+    z, loss, terms = HF.JointLatentFn.apply(mu, logvar, eps.detach() if n_cont else None, u.detach() if n_disc else None,
+                                            joint_segments(disc, mu.device) if n_disc else None, capacity.detach(),
+                                            n_cont, n_disc, temperature, gamma_cont, gamma_disc, beta)
+    return (z, loss, terms) if with_terms else (z, loss)
+
+
+def joint_prior_sample(n, n_cont, disc_sizes, device):
+    """``n`` draws [n, n_cont + sum K_i] of the JointVAE prior: standard normal columns, then per discrete variable the
+    one-hot of a uniformly drawn category.  Plain torch; not on the hot path."""
+    n_cont, disc, _ = joint_spec(n_cont, disc_sizes)
+    cols = [torch.randn((n, n_cont), device=device)]
+    for k in disc:
+        cols.append(torch.nn.functional.one_hot(torch.randint(k, (n,), device=device), k).to(torch.float32))
+    return torch.cat(cols, dim=1)
 
 
 def tc_components(z, mu, logvar, dataset_size, *, var_from_row=True, eps_density=True, weighted=False):
