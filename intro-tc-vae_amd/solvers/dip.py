@@ -6,14 +6,13 @@ moment-matching counterpart of beta-TC, the baseline its disentanglement scores 
     hook = beta * KL + lambda_od * sum_{i != j} C_ij^2 + lambda_d * sum_i (C_ii - 1)^2
 
 in the fused launches of ``ops.dip_kl_loss`` (two forward, one backward)."""
-import math
-import numbers
 from typing import Optional
 
 from torch import Tensor
 
 import ops
 from hipvae import ddp
+from solvers.hyper import Choice, Number
 from solvers.intro import IntroSolver
 from solvers.vae import VAESolver
 from utils import SingletonWriter
@@ -21,48 +20,13 @@ from utils import SingletonWriter
 DIP_TYPES = ("i", "ii")
 
 
-class DipType:
-    """The ``dip_type`` attribute of the DIP solvers: "i" or "ii".  Checked on every assignment; part of the captured
-    graph's key, so a change re-captures."""
-
-    def __get__(self, obj, cls=None):
-        return self if obj is None else obj.__dict__.get("_dip_type", "i")
-
-    def __set__(self, obj, value):
-        if value not in DIP_TYPES:
-            raise ValueError(f"dip_type must be one of {DIP_TYPES} (got {value!r})")
-        obj.__dict__["_dip_type"] = value
-
-
-class DipLambda:
-    """``lambda_od`` / ``lambda_d``: a finite number >= 0, checked on every assignment; a scalar kernel argument frozen
-    into a captured step and therefore part of the graph's key.  ``lambda_d`` may also be None: the sweep convention of
-    disentanglement_lib, 10 * lambda_od for "i" and lambda_od for "ii", followed at every read."""
-
-    def __init__(self, name, optional=False):
-        self.name, self.optional = name, optional
-
-    def __get__(self, obj, cls=None):
-        if obj is None:
-            return self
-        v = obj.__dict__.get("_" + self.name)
-        if v is None and self.optional:
-            return (10.0 if obj.dip_type == "i" else 1.0) * obj.lambda_od
-        return v
-
-    def __set__(self, obj, value):
-        if value is None and self.optional:
-            obj.__dict__["_" + self.name] = None
-            return
-        if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value) or value < 0:
-            raise ValueError(f"{self.name} must be a finite number >= 0 (got {value!r})")
-        obj.__dict__["_" + self.name] = float(value)
-
-
-class DIPSolver(VAESolver):
-    dip_type = DipType()
-    lambda_od = DipLambda("lambda_od")
-    lambda_d = DipLambda("lambda_d", optional=True)
+class DipHook:
+    """The DIP hyperparameters, KL hook and graph-key entries, mixed in front of ``VAESolver`` or ``IntroSolver``.
+    ``lambda_d`` None follows the sweep convention of disentanglement_lib at every read: 10 * lambda_od for "i",
+    lambda_od for "ii"."""
+    dip_type = Choice(DIP_TYPES, "i")
+    lambda_od = Number()
+    lambda_d = Number(optional=True, fallback=lambda s: (10.0 if s.dip_type == "i" else 1.0) * s.lambda_od)
 
     def __init__(self, *args, dip_type: str = "i", lambda_od: float = 10.0, lambda_d: Optional[float] = None, **kwargs):
         self.dip_type = dip_type
@@ -102,23 +66,11 @@ class DIPSolver(VAESolver):
         return super()._graph_key_extra() + (self.dip_type, self.lambda_od, self.lambda_d)
 
 
-class IntroDIPSolver(IntroSolver):
+class DIPSolver(DipHook, VAESolver):
+    """The VAE step with the DIP hook."""
+
+
+class IntroDIPSolver(DipHook, IntroSolver):
     """The Soft-Intro step with the DIP hook: every ``reduce="mean"`` call of the step (the real batch, and the decoder
     phase's reconstructions and fakes) carries the regulariser; the per-sample soft-exp terms (``reduce="none"``,
     ``beta_neg``) stay plain KL."""
-    dip_type = DipType()
-    lambda_od = DipLambda("lambda_od")
-    lambda_d = DipLambda("lambda_d", optional=True)
-
-    def __init__(self, *args, dip_type: str = "i", lambda_od: float = 10.0, lambda_d: Optional[float] = None, **kwargs):
-        self.dip_type = dip_type
-        self.lambda_od = lambda_od
-        self.lambda_d = lambda_d
-        super().__init__(*args, **kwargs)
-
-    def compute_kl_loss(self, z: Optional[Tensor], mu: Tensor, logvar: Tensor, reduce: str = "mean",
-                        beta: float = None, write: bool = False) -> Tensor:
-        return DIPSolver.compute_kl_loss(self, z, mu, logvar, reduce, beta, write)
-
-    def _graph_key_extra(self) -> tuple:
-        return super()._graph_key_extra() + (self.dip_type, self.lambda_od, self.lambda_d)

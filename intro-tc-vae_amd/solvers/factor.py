@@ -25,37 +25,19 @@ rows per rank) and D's gradients are averaged over the ranks like the others.
 
 Not here: a Soft-Intro variant.  The intro step's shared decoder pass makes three mean-KL calls a step, and when D should
 be updated among them needs a design of its own."""
-import math
-import numbers
 from typing import Optional
 
-import torch
 from torch import Tensor
 
 import ops
-from hipvae import ddp
-from hipvae.flat import FlatGroup, fused_update
+from hipvae.flat import fused_update
+from solvers.hyper import Number
 from solvers.vae import VAESolver
 
 
-class FactorNumber:
-    """``gamma`` (a finite number >= 0): checked on every assignment; a scalar kernel argument frozen into a captured
-    step and therefore part of the graph's key."""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __get__(self, obj, cls=None):
-        return self if obj is None else obj.__dict__.get("_" + self.name)
-
-    def __set__(self, obj, value):
-        if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value) or value < 0:
-            raise ValueError(f"{self.name} must be a finite number >= 0 (got {value!r})")
-        obj.__dict__["_" + self.name] = float(value)
-
-
 class FactorSolver(VAESolver):
-    gamma = FactorNumber("gamma")
+    gamma = Number()
+    _updates = ("encoder", "decoder", "discriminator")
 
     def __init__(self, *args, discriminator, optimizer_disc, gamma: float = 10.0, **kwargs):
         self.gamma = gamma
@@ -65,35 +47,11 @@ class FactorSolver(VAESolver):
         super().__init__(*args, **kwargs)
 
     # ---- the third parameter group ----------------------------------------------------------------------------------
-    def _params(self, part):
-        if part != "discriminator":
-            return super()._params(part)
-        mod = self.discriminator
-        ent = self.__dict__.setdefault("_plists", {}).get(part)
-        if ent is None or ent[0] is not mod:
-            ent = self._plists[part] = (mod, list(mod.parameters()))
-        return ent[1]
+    def _module(self, part):
+        return self.discriminator if part == "discriminator" else super()._module(part)
 
-    def _group(self, part) -> FlatGroup:
-        if part != "discriminator":
-            return super()._group(part)
-        params = self._params(part)
-        g = self._flat.get(part)
-        if g is None or not g.owns(params):
-            g = self._flat[part] = FlatGroup(params, inherit=g)
-        return g
-
-    def _step(self, part):
-        if part != "discriminator":
-            return super()._step(part)
-        opt = self.optimizer_disc
-        spec = fused_update(opt)
-        if spec is None:
-            opt.step()
-        else:
-            g = self._group(part)
-            g.bind_optimizer(opt, spec)
-            g.fused_step(spec)
+    def _optimizer(self, part):
+        return self.optimizer_disc if part == "discriminator" else super()._optimizer(part)
 
     def _graph_ok(self, specs=None):
         return super()._graph_ok(specs) and fused_update(self.optimizer_disc) is not None
@@ -119,40 +77,18 @@ class FactorSolver(VAESolver):
             return kl                     # the discriminator still trains; the VAE's loss and walk are the plain ones
         return self._lincomb((1.0, self.gamma), kl, ops.factor_tc(z, self.discriminator, shared=dp))
 
-    # ---- the step ----------------------------------------------------------------------------------------------------
-    def _device_step(self, real: Tensor) -> Tensor:
-        self._set_trainable(True, True)
-        mu, logvar, z, rec = self.model(real)
-        loss_rec = self.compute_rec_loss(real, rec, reduction="mean", write=True)
-        loss_kl = self.compute_kl_loss(z, mu, logvar, write=True)
-        loss = self._lincomb((self.scale, self.scale), loss_rec, loss_kl)
-        dp, self._disc_pass = self._disc_pass, None
-        self._backward(loss, ("decoder", "encoder"))
-        d_loss = ops.factor_disc_loss(z, self.discriminator, shared=dp)
-        self._backward(d_loss, ("discriminator",))
-        norm = self._clip()
-        self._step("encoder")
-        self._step("decoder")
-        self._step("discriminator")
-        stats = torch.cat([torch.stack([loss.detach(), loss_kl.detach(), loss_rec.detach()]), dp.stats])
-        ddp.mean_scalars_(stats)
-        return torch.cat([stats, norm if norm is not None else stats.new_zeros(1)])
+    # ---- the step: the plain forward, then D's own loss and walk from the pass the hook kept ------------------------------
+    def _losses(self, real: Tensor):
+        z, loss_rec, loss_kl, _ = super()._losses(real)
+        return z, loss_rec, loss_kl, self._disc_pass.stats
 
-    def train_step(self, batch: Tensor, cur_iter: int) -> dict:
-        if batch.dim() == 3:
-            batch = batch.unsqueeze(0)
-        real = batch.to(self.device)
-        v_loss, v_kl, v_rec, v_tc, v_disc, v_acc, v_norm = self._run(real).tolist()     # the step's only host read-back
-        if v_loss != v_loss:
-            raise RuntimeError
-        if self.writer:
-            self.write_scalars(cur_iter, losses=dict(r_loss=v_rec, kl_loss=v_kl))
-            self.writer.add_scalars("factor", dict(tc=v_tc, d_loss=v_disc, d_acc=v_acc), global_step=cur_iter)
-            if self.clip:
-                self.writer.add_scalar("total_norm", v_norm, global_step=cur_iter)
-            self.write_gradient_norm(cur_iter)
-            self._write_images_helper(real, cur_iter)
-            self.write_disentanglemnt_scores(cur_iter)
-            self.writer.flush()
-        return {"loss_enc": v_loss, "loss_dec": v_loss, "loss_kl": v_kl, "loss_rec": v_rec,
-                "L2": v_norm if self.clip else None, "loss_tc": v_tc, "loss_disc": v_disc, "disc_acc": v_acc}
+    def _side_walk(self, z: Tensor):
+        dp, self._disc_pass = self._disc_pass, None
+        self._backward(ops.factor_disc_loss(z, self.discriminator, shared=dp), ("discriminator",))
+
+    def _write_losses(self, cur_iter, v_kl, v_rec, v_tc, v_disc, v_acc):
+        super()._write_losses(cur_iter, v_kl, v_rec)
+        self.writer.add_scalars("factor", dict(tc=v_tc, d_loss=v_disc, d_acc=v_acc), global_step=cur_iter)
+
+    def _extra_results(self, v_tc, v_disc, v_acc) -> dict:
+        return {"loss_tc": v_tc, "loss_disc": v_disc, "disc_acc": v_acc}

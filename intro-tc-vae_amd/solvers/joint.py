@@ -27,7 +27,7 @@ import torch
 from torch import Tensor
 
 import ops
-from hipvae import ddp
+from solvers.hyper import Number
 from solvers.vae import VAESolver
 
 
@@ -42,36 +42,6 @@ def _capacity(value, what):
     if not (math.isfinite(iters) and iters > 0):
         raise ValueError(f"{what}: iters must be a positive number of steps (got {iters})")
     return (lo, hi, iters), gamma
-
-
-class _Gamma:
-    """A capacity weight of the solver: finite and not negative.  Checked on every assignment; part of the captured
-    graph's key, so a change re-captures."""
-
-    def __init__(self, name):
-        self.name = name
-
-    def __get__(self, obj, cls=None):
-        return self if obj is None else obj.__dict__["_" + self.name]
-
-    def __set__(self, obj, value):
-        v = float(value)
-        if not (0.0 <= v < math.inf):
-            raise ValueError(f"{self.name} must be finite and not negative (got {value!r})")
-        obj.__dict__["_" + self.name] = v
-
-
-class _Temperature:
-    """The Gumbel-softmax temperature: finite and above 0.  Checked on every assignment; part of the graph key."""
-
-    def __get__(self, obj, cls=None):
-        return self if obj is None else obj.__dict__["_temperature"]
-
-    def __set__(self, obj, value):
-        v = float(value)
-        if not (0.0 < v < math.inf):
-            raise ValueError(f"temperature must be a finite number above 0 (got {value!r})")
-        obj.__dict__["_temperature"] = v
 
 
 class _LatentSpec:
@@ -94,9 +64,9 @@ class _LatentSpec:
 
 class JointVAESolver(VAESolver):
     latent_spec = _LatentSpec()
-    temperature = _Temperature()
-    gamma_cont = _Gamma("gamma_cont")
-    gamma_disc = _Gamma("gamma_disc")
+    temperature = Number(positive=True)          # of the Gumbel-softmax
+    gamma_cont = Number()                        # the capacity weights
+    gamma_disc = Number()
 
     def __init__(self, *args, latent_spec=None, cont_capacity=(0.0, 5.0, 25000, 30.0),
                  disc_capacity=(0.0, 5.0, 25000, 30.0), temperature: float = 0.67, **kwargs):
@@ -125,50 +95,30 @@ class JointVAESolver(VAESolver):
         return super()._graph_key_extra() + (self._latent_spec, self.temperature, self.gamma_cont, self.gamma_disc,
                                              self._cap.data_ptr())
 
-    def _device_step(self, real: Tensor) -> Tensor:
-        self._set_trainable(True, True)
+    def _run(self, real: Tensor) -> Tensor:
+        # outside the captured region: a replay reads what is written here
+        self._cap.copy_(torch.tensor(self.capacity_at(self.steps_taken), dtype=torch.float64))
+        stats = super()._run(real)
+        self.steps_taken += 1
+        return stats
+
+    def _losses(self, real: Tensor):
         cont, disc = self._latent_spec
         mu, logvar = self.model.encode(real)
         z, loss_kl, terms = ops.joint_latent(mu, logvar, cont, disc, self._cap, self.gamma_cont, self.gamma_disc,
                                              beta=self.beta_kl, temperature=self.temperature, with_terms=True)
-        rec = self.model.decode(z)
-        loss_rec = self.compute_rec_loss(real, rec, reduction="mean", write=True)
-        loss = self._lincomb((self.scale, self.scale), loss_rec, loss_kl)      # scale * (loss_rec + loss_kl)
-        self._backward(loss, ("decoder", "encoder"))
-        norm = self._clip()
-        self._step("encoder")
-        self._step("decoder")
-        stats = torch.cat([torch.stack([loss.detach(), loss_kl.detach(), loss_rec.detach()]), terms])
-        ddp.mean_scalars_(stats)
-        return torch.cat([stats, norm if norm is not None else stats.new_zeros(1)])
+        loss_rec = self.compute_rec_loss(real, self.model.decode(z), reduction="mean", write=True)
+        return z, loss_rec, loss_kl, terms
 
-    def train_step(self, batch: Tensor, cur_iter: int) -> dict:
-        """Returns the ``VAESolver`` dict (``loss_kl``: the weighted capacity loss) plus ``kl_cont``, ``kl_disc`` (the
-        two batch-mean KLs) and ``cap_cont``, ``cap_disc`` (the capacities this step was held to)."""
-        if batch.dim() == 3:
-            batch = batch.unsqueeze(0)
-        real = batch.to(self.device)
-        # outside the captured region: a replay reads what is written here
-        self._cap.copy_(torch.tensor(self.capacity_at(self.steps_taken), dtype=torch.float64))
-        stats = self._run(real)
-        self.steps_taken += 1
-        v_loss, v_kl, v_rec, v_klz, v_klc, v_cz, v_cc, v_norm = stats.tolist()      # the step's only host read-back
-        if v_loss != v_loss:
-            raise RuntimeError
-        if self.writer:
-            self.writer.add_scalar("kl_loss_unscaled", v_klz + v_klc, global_step=cur_iter)
-            self.write_scalars(cur_iter, losses=dict(r_loss=v_rec, kl_loss=v_kl))
-            self.writer.add_scalars("joint", dict(kl_cont=v_klz, kl_disc=v_klc, cap_cont=v_cz, cap_disc=v_cc),
-                                    global_step=cur_iter)
-            if self.clip:
-                self.writer.add_scalar("total_norm", v_norm, global_step=cur_iter)
-            self.write_gradient_norm(cur_iter)
-            self._write_images_helper(real, cur_iter)
-            self.write_disentanglemnt_scores(cur_iter)
-            self.writer.flush()
-        return {"loss_enc": v_loss, "loss_dec": v_loss, "loss_kl": v_kl, "loss_rec": v_rec,
-                "L2": v_norm if self.clip else None, "kl_cont": v_klz, "kl_disc": v_klc, "cap_cont": v_cz,
-                "cap_disc": v_cc}
+    def _write_losses(self, cur_iter, v_kl, v_rec, *terms):
+        self.writer.add_scalar("kl_loss_unscaled", terms[0] + terms[1], global_step=cur_iter)
+        super()._write_losses(cur_iter, v_kl, v_rec)
+        self.writer.add_scalars("joint", self._extra_results(*terms), global_step=cur_iter)
+
+    def _extra_results(self, v_klz, v_klc, v_cz, v_cc) -> dict:
+        """``train_step`` returns the ``VAESolver`` dict (``loss_kl``: the weighted capacity loss) plus ``kl_cont``,
+        ``kl_disc`` (the two batch-mean KLs) and ``cap_cont``, ``cap_disc`` (the capacities this step was held to)."""
+        return dict(kl_cont=v_klz, kl_disc=v_klc, cap_cont=v_cz, cap_disc=v_cc)
 
     # ---- images: fakes from the joint prior, reconstructions from the deterministic code --------------------------------
     def _write_images_helper(self, batch, cur_iter):

@@ -11,8 +11,6 @@ inverse multiquadric) or "rbf", ``mmd_bandwidth`` the bandwidth h (None: 2 * zdi
 
 InfoVAE's objective  rec + (1 - alpha) KL + (alpha + lambda - 1) MMD^2  maps to ``beta_kl = 1 - alpha`` and
 ``lambda_mmd = alpha + lambda - 1``; MMD-VAE (alpha = 1) is ``beta_kl = 0``, ``lambda_mmd = lambda``."""
-import math
-import numbers
 from typing import Optional
 
 import torch
@@ -20,6 +18,7 @@ from torch import Tensor
 
 import ops
 from hipvae import ddp
+from solvers.hyper import Choice, Number
 from solvers.intro import IntroSolver
 from solvers.vae import VAESolver
 from utils import SingletonWriter
@@ -27,45 +26,12 @@ from utils import SingletonWriter
 MMD_KERNELS = ("imq", "rbf")
 
 
-class MmdKernel:
-    """The ``mmd_kernel`` attribute of the MMD solvers: "imq" or "rbf".  Checked on every assignment; part of the captured
-    graph's key, so a change re-captures."""
-
-    def __get__(self, obj, cls=None):
-        return self if obj is None else obj.__dict__.get("_mmd_kernel", "imq")
-
-    def __set__(self, obj, value):
-        if value not in MMD_KERNELS:
-            raise ValueError(f"mmd_kernel must be one of {MMD_KERNELS} (got {value!r})")
-        obj.__dict__["_mmd_kernel"] = value
-
-
-class MmdNumber:
-    """``lambda_mmd`` (a finite number >= 0) / ``mmd_bandwidth`` (a finite number > 0, or None: 2 * D at every call):
-    checked on every assignment; scalar kernel arguments frozen into a captured step and therefore part of the graph's
-    key."""
-
-    def __init__(self, name, positive=False, optional=False):
-        self.name, self.positive, self.optional = name, positive, optional
-
-    def __get__(self, obj, cls=None):
-        return self if obj is None else obj.__dict__.get("_" + self.name)
-
-    def __set__(self, obj, value):
-        if value is None and self.optional:
-            obj.__dict__["_" + self.name] = None
-            return
-        bad = isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value)
-        if bad or value < 0 or (self.positive and value == 0):
-            raise ValueError(f"{self.name} must be a finite number {'> 0' if self.positive else '>= 0'}"
-                             f"{' or None' if self.optional else ''} (got {value!r})")
-        obj.__dict__["_" + self.name] = float(value)
-
-
-class MMDSolver(VAESolver):
-    lambda_mmd = MmdNumber("lambda_mmd")
-    mmd_kernel = MmdKernel()
-    mmd_bandwidth = MmdNumber("mmd_bandwidth", positive=True, optional=True)
+class MmdHook:
+    """The MMD hyperparameters, KL hook and graph-key entries, mixed in front of ``VAESolver`` or ``IntroSolver``.
+    ``mmd_bandwidth`` None: 2 * D at every call."""
+    lambda_mmd = Number()
+    mmd_kernel = Choice(MMD_KERNELS, "imq")
+    mmd_bandwidth = Number(positive=True, optional=True)
 
     def __init__(self, *args, lambda_mmd: float = 10.0, mmd_kernel: str = "imq", mmd_bandwidth: Optional[float] = None,
                  **kwargs):
@@ -113,24 +79,11 @@ class MMDSolver(VAESolver):
         return super()._graph_key_extra() + (self.lambda_mmd, self.mmd_kernel, self.mmd_bandwidth)
 
 
-class IntroMMDSolver(IntroSolver):
+class MMDSolver(MmdHook, VAESolver):
+    """The VAE step with the MMD hook: two draws a step."""
+
+
+class IntroMMDSolver(MmdHook, IntroSolver):
     """The Soft-Intro step with the MMD hook: every ``reduce="mean"`` call of the step (the real batch, and the decoder
     phase's reconstructions and fakes: three prior draws a step) carries the statistic; the per-sample soft-exp terms
     (``reduce="none"``, ``beta_neg``) stay plain KL."""
-    lambda_mmd = MmdNumber("lambda_mmd")
-    mmd_kernel = MmdKernel()
-    mmd_bandwidth = MmdNumber("mmd_bandwidth", positive=True, optional=True)
-
-    def __init__(self, *args, lambda_mmd: float = 10.0, mmd_kernel: str = "imq", mmd_bandwidth: Optional[float] = None,
-                 **kwargs):
-        self.lambda_mmd = lambda_mmd
-        self.mmd_kernel = mmd_kernel
-        self.mmd_bandwidth = mmd_bandwidth
-        super().__init__(*args, **kwargs)
-
-    def compute_kl_loss(self, z: Optional[Tensor], mu: Tensor, logvar: Tensor, reduce: str = "mean",
-                        beta: float = None, write: bool = False) -> Tensor:
-        return MMDSolver.compute_kl_loss(self, z, mu, logvar, reduce, beta, write)
-
-    def _graph_key_extra(self) -> tuple:
-        return super()._graph_key_extra() + (self.lambda_mmd, self.mmd_kernel, self.mmd_bandwidth)

@@ -9,28 +9,18 @@ from torch import Tensor
 import ops
 from hipvae import ddp
 from ops import kl_divergence, tc_decomposition, tc_kl_loss, total_correlation
+from solvers.hyper import Choice
 from solvers.vae import VAESolver
 from utils import SingletonWriter
 
 KL_LOSSES = ("simple", "full")
 
 
-class KlLossMode:
-    """The ``kl_loss`` attribute of the TC solvers: which hook ``compute_kl_loss`` runs, "simple" (tc.py:69-89, the
-    reference's) or "full" (tc.py:91-144).  Checked on every assignment; part of the captured graph's key
-    (solvers/vae.py), so a change re-captures."""
-
-    def __get__(self, obj, cls=None):
-        return self if obj is None else obj.__dict__.get("_kl_loss", "simple")
-
-    def __set__(self, obj, value):
-        if value not in KL_LOSSES:
-            raise ValueError(f"kl_loss must be one of {KL_LOSSES} (got {value!r})")
-        obj.__dict__["_kl_loss"] = value
-
-
-class TCSovler(VAESolver):
-    kl_loss = KlLossMode()
+class TcHook:
+    """The beta-TC KL hooks, mixed in front of ``VAESolver`` or ``IntroSolver``.  ``kl_loss`` says which one
+    ``compute_kl_loss`` runs: "simple" (tc.py:69-89, the reference's) or "full" (tc.py:91-144); it selects kernels, and
+    the captured graph's key ends with it (solvers/vae.py)."""
+    kl_loss = Choice(KL_LOSSES, "simple")
 
     def __init__(self, *args, kl_loss: str = "simple", **kwargs):
         self.kl_loss = kl_loss
@@ -39,8 +29,8 @@ class TCSovler(VAESolver):
     def compute_kl_loss(self, z: Optional[Tensor], mu: Tensor, logvar: Tensor, reduce: str = "mean",
                         beta: float = None, write: bool = False) -> Tensor:
         if getattr(self, "kl_loss", "simple") == "full":
-            return TCSovler._compute_kl_loss_full(self, z, mu, logvar, reduce, beta, write)
-        return TCSovler._compute_kl_loss_simple(self, z, mu, logvar, reduce, beta, write)
+            return TcHook._compute_kl_loss_full(self, z, mu, logvar, reduce, beta, write)
+        return TcHook._compute_kl_loss_simple(self, z, mu, logvar, reduce, beta, write)
 
     def _compute_kl_loss_simple(self, z, mu, logvar, reduce="mean", beta=None, write=False) -> Tensor:
         """tc.py:69-89.  In a data-parallel run the estimator sees the whole global batch: the means
@@ -97,3 +87,7 @@ class TCSovler(VAESolver):
         mu_all, logvar_all = ddp.all_gather_mu_logvar(mu.detach(), logvar.detach())
         return tc_decomposition(z, mu, logvar, len(self.dataset), mu_all=mu_all, logvar_all=logvar_all,
                                 row_offset=ddp.row_offset(mu.shape[0]))
+
+
+class TCSovler(TcHook, VAESolver):
+    """The VAE step with the beta-TC hook."""

@@ -117,10 +117,17 @@ class VAESolver:
         return sum(w * t for w, t in zip(weights, terms))
 
     # ---- optimiser tail shared by all solvers ----------------------------------------------
+    def _module(self, part):
+        """The module of a parameter group; with ``_optimizer`` all a solver with a further group overrides."""
+        return getattr(self.model, part)
+
+    def _optimizer(self, part):
+        return self.optimizer_e if part == "encoder" else self.optimizer_d
+
     def _params(self, part):
-        """Parameter list of one model half, walked once per (solver, module) -- ``module.parameters()`` re-walks the
+        """Parameter list of one group, walked once per (solver, module) -- ``module.parameters()`` re-walks the
         module tree on every call (~1.5 ms of host time per step over the handful of calls a step makes)."""
-        mod = getattr(self.model, part)
+        mod = self._module(part)
         ent = self.__dict__.setdefault("_plists", {}).get(part)
         if ent is None or ent[0] is not mod:
             ent = self._plists[part] = (mod, list(mod.parameters()))
@@ -133,7 +140,7 @@ class VAESolver:
             # ownership lost (model.to() / .float() / load_state_dict(assign=True) after the first step): the new group
             # inherits the optimiser state and step count instead of restarting them
             g = self._flat[part] = FlatGroup(params, inherit=g,
-                                             grad_free=grad_free_parameters(getattr(self.model, part)))
+                                             grad_free=grad_free_parameters(self._module(part)))
         return g
 
     def _set_trainable(self, encoder: bool, decoder: bool):
@@ -169,7 +176,7 @@ class VAESolver:
         return clip_grad_norm([self._group("encoder"), self._group("decoder")], self.clip)
 
     def _step(self, part):
-        opt = self.optimizer_e if part == "encoder" else self.optimizer_d
+        opt = self._optimizer(part)
         spec = fused_update(opt)
         if spec is None:
             opt.step()                       # an optimiser config without a fused update: torch's own
@@ -264,29 +271,52 @@ class VAESolver:
         return ()
 
     # ---- solvers/vae.py:89-136 ---------------------------------------------------------------
-    def _device_step(self, real: Tensor) -> Tensor:
-        self._set_trainable(True, True)
+    # The one VAE step.  An objective supplies what differs: ``_losses`` (how z and the two loss terms come out of the
+    # batch, and its further device scalars), ``_batch`` (the batch check), ``_write_losses`` / ``_extra_results`` (what
+    # it logs and returns for those scalars); FactorVAE also ``_side_walk`` and ``_updates`` for its third group.
+    _updates = ("encoder", "decoder")
+
+    def _losses(self, real: Tensor):
+        """(z, loss_rec, loss_kl, extra): ``extra`` a device vector of further scalars for the stats, or None."""
         mu, logvar, z, rec = self.model(real)
         loss_rec = self.compute_rec_loss(real, rec, reduction="mean", write=True)
-        loss_kl = self.compute_kl_loss(z, mu, logvar, write=True)
+        return z, loss_rec, self.compute_kl_loss(z, mu, logvar, write=True), None
+
+    def _side_walk(self, z: Tensor):
+        """Between the VAE's backward and the clip: a further loss and walk over a group of its own."""
+
+    def _device_step(self, real: Tensor) -> Tensor:
+        """Returns the stats vector [loss, loss_kl, loss_rec, *extra, norm]."""
+        self._set_trainable(True, True)
+        z, loss_rec, loss_kl, extra = self._losses(real)
         loss = self._lincomb((self.scale, self.scale), loss_rec, loss_kl)      # scale * (loss_rec + loss_kl), vae.py:106
         self._backward(loss, ("decoder", "encoder"))
+        self._side_walk(z)
         norm = self._clip()
-        self._step("encoder")
-        self._step("decoder")
+        for part in self._updates:
+            self._step(part)
         stats = torch.stack([loss.detach(), loss_kl.detach(), loss_rec.detach()])
+        if extra is not None:
+            stats = torch.cat([stats, extra])
         ddp.mean_scalars_(stats)
         return torch.cat([stats, norm if norm is not None else stats.new_zeros(1)])
 
+    def _batch(self, batch: Tensor) -> Tensor:
+        return batch.unsqueeze(0) if batch.dim() == 3 else batch
+
+    def _write_losses(self, cur_iter: int, v_kl: float, v_rec: float, *extra):
+        self.write_scalars(cur_iter, losses=dict(r_loss=v_rec, kl_loss=v_kl))
+
+    def _extra_results(self, *extra) -> dict:
+        return {}
+
     def train_step(self, batch: Tensor, cur_iter: int) -> dict:
-        if batch.dim() == 3:
-            batch = batch.unsqueeze(0)
-        real = batch.to(self.device)
-        v_loss, v_kl, v_rec, v_norm = self._run(real).tolist()     # the step's only host read-back
+        real = self._batch(batch).to(self.device)
+        v_loss, v_kl, v_rec, *extra, v_norm = self._run(real).tolist()     # the step's only host read-back
         if v_loss != v_loss:
             raise RuntimeError
         if self.writer:
-            self.write_scalars(cur_iter, losses=dict(r_loss=v_rec, kl_loss=v_kl))
+            self._write_losses(cur_iter, v_kl, v_rec, *extra)
             if self.clip:
                 self.writer.add_scalar("total_norm", v_norm, global_step=cur_iter)
             self.write_gradient_norm(cur_iter)
@@ -295,7 +325,7 @@ class VAESolver:
             self.writer.flush()
         # the reference leaves L2 unbound when clip is falsy (vae.py:135); None is returned instead
         return {"loss_enc": v_loss, "loss_dec": v_loss, "loss_kl": v_kl, "loss_rec": v_rec,
-                "L2": v_norm if self.clip else None}
+                "L2": v_norm if self.clip else None, **self._extra_results(*extra)}
 
     # ---- TensorBoard side channel (solvers/vae.py:138-254); all no-ops without a writer ------
     def _write_images_helper(self, batch, cur_iter):
