@@ -243,7 +243,7 @@ def bump_weight_epoch(params=None):
 
 # conv arithmetic -> plane format code of the C ABI (include/itcv_hip.h): 2 / 3 bf16 planes, 4 = two fp16 planes + scale
 _NS = {"fp32": 0, "bf16x3": 2, "bf16x6": 3, "f16x3": 4}
-F16X2 = 4
+F16X2 = abi.DEFINES["ITCV_PLANES_F16X2"]
 _CONV_MATH = [os.environ.get("ITCV_CONV_MATH", "fp32")]   # the one documented environment override (with ITCV_DDP_GRAPH, ITCV_LIB)
 assert _CONV_MATH[0] in _NS, "ITCV_CONV_MATH must be one of fp32 / bf16x3 / bf16x6 / f16x3"
 
@@ -1346,6 +1346,25 @@ def _packed_pair(a, b):
     return None
 
 
+def _pair_in(mu_all, logvar_all):
+    """(mu_all, logvar_all, ld) as the kernels read a [Bt, D] pair: the halves of one packed [Bt, 2D] tensor in place at
+    ld = 2D, any other layout as two dense fp32 tensors at ld = D."""
+    ld = _packed_pair(mu_all, logvar_all)
+    if ld is None or ld == mu_all.shape[1]:
+        mu_all, logvar_all = _f32c(mu_all), _f32c(logvar_all)
+        ld = mu_all.shape[1]
+    return mu_all, logvar_all, ld
+
+
+def _pair_grads(Bt, D, ld, device):
+    """(dmu, dlv) [Bt, D] in the layout ``_pair_in`` read the pair in."""
+    if ld == D:
+        return torch.empty((Bt, D), dtype=F32, device=device), torch.empty((Bt, D), dtype=F32, device=device)
+    # one packed [Bt, 2D] gradient: the gather's adjoint reduce-scatters it in place
+    dpk = torch.empty((Bt, 2 * D), dtype=F32, device=device)
+    return dpk[:, :D], dpk[:, D:]
+
+
 class TcFullFn(Function):
     """Per sample alpha*(logqcx - logqz) + beta*(logqz - prodm) + gamma*(prodm - logpz): the full decomposition loss of
     solvers/tc.py:91-144 (ops.py:24-29 density, variance of component i, stratified sampler) with the reduction,
@@ -1357,12 +1376,8 @@ class TcFullFn(Function):
     @staticmethod
     def forward(ctx, z, mu_all, logvar_all, dataset_size, row_offset, alpha, beta, gamma, reduction):
         z = _f32c(z)
-        if not (mu_all.is_cuda and logvar_all.is_cuda):
-            raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
-        ld = _packed_pair(mu_all, logvar_all)
-        if ld is None or ld == mu_all.shape[1]:
-            mu_all, logvar_all = _f32c(mu_all), _f32c(logvar_all)
-            ld = mu_all.shape[1]
+        abi.need_device(mu_all, logvar_all)
+        mu_all, logvar_all, ld = _pair_in(mu_all, logvar_all)
         Bl, D = z.shape
         Bt = mu_all.shape[0]
         if tuple(mu_all.shape) != (Bt, D) or tuple(logvar_all.shape) != (Bt, D):
@@ -1394,11 +1409,7 @@ class TcFullFn(Function):
         Bl, D = z.shape
         Bt = mu_all.shape[0]
         dz = torch.empty_like(z)
-        if ld == D:
-            dmu, dlv = torch.empty((Bt, D), dtype=F32, device=z.device), torch.empty((Bt, D), dtype=F32, device=z.device)
-        else:                               # one packed [Bt, 2D] gradient: the gather's adjoint reduce-scatters it in place
-            dpk = torch.empty((Bt, 2 * D), dtype=F32, device=z.device)
-            dmu, dlv = dpk[:, :D], dpk[:, D:]
+        dmu, dlv = _pair_grads(Bt, D, ld, z.device)
         nws = lib.itcv_tc_full_bwd_workspace(Bl, Bt)
         ws = _ws(nws, z.device)
         call("itcv_tc_full_bwd", ptr(_f32c(g)), ptr(z), mu_all.data_ptr(), logvar_all.data_ptr(), ld, ptr(logqz), ptr(lse),
@@ -1411,15 +1422,11 @@ def dip_kl_forward(mu_all, logvar_all, Bl, row_offset, kind, lambda_od, lambda_d
     """itcv_dip_kl_fwd on a [Bt, D] pair in either layout (two dense tensors, or the halves of one packed [Bt, 2D] tensor,
     read in place; anything else is copied dense).  Returns (mu_all, logvar_all, ld) as read and (out, terms [3], W [D, D],
     mean [D] fp64).  No gradient: ``DipKlFn`` is the differentiable form."""
-    if not (mu_all.is_cuda and logvar_all.is_cuda):
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    abi.need_device(mu_all, logvar_all)
     if mu_all.dim() != 2 or mu_all.shape != logvar_all.shape:
         raise ValueError(f"mu_all / logvar_all must share one [Bt, D] shape (got {tuple(mu_all.shape)}, "
                          f"{tuple(logvar_all.shape)})")
-    ld = _packed_pair(mu_all, logvar_all)
-    if ld is None or ld == mu_all.shape[1]:
-        mu_all, logvar_all = _f32c(mu_all), _f32c(logvar_all)
-        ld = mu_all.shape[1]
+    mu_all, logvar_all, ld = _pair_in(mu_all, logvar_all)
     Bt, D = mu_all.shape
     dev = mu_all.device
     out = torch.empty((), dtype=F32, device=dev)
@@ -1457,11 +1464,7 @@ class DipKlFn(Function):
         mu_all, logvar_all, W, mean = ctx.saved_tensors
         Bl, off, kind, coef_kl, ld = ctx.cfg
         Bt, D = mu_all.shape
-        if ld == D:
-            dmu, dlv = torch.empty((Bt, D), dtype=F32, device=W.device), torch.empty((Bt, D), dtype=F32, device=W.device)
-        else:                               # one packed [Bt, 2D] gradient: the gather's adjoint reduce-scatters it in place
-            dpk = torch.empty((Bt, 2 * D), dtype=F32, device=W.device)
-            dmu, dlv = dpk[:, :D], dpk[:, D:]
+        dmu, dlv = _pair_grads(Bt, D, ld, W.device)
         call("itcv_dip_kl_bwd", ptr(_f32c(g)), mu_all.data_ptr(), logvar_all.data_ptr(), ld, ptr(W), ptr(mean),
              dmu.data_ptr(), dlv.data_ptr(), Bl, Bt, off, D, kind, coef_kl, stream())
         return dmu, dlv, None, None, None, None, None, None
@@ -1478,8 +1481,7 @@ def mmd_kl_forward(z_all, prior, mu, logvar, kernel, h, lambda_mmd, coef_kl):
 
 
 def _mmd_kl_forward(z_all, prior, mu, logvar, kernel, h, lambda_mmd, coef_kl):
-    if not (z_all.is_cuda and prior.is_cuda and mu.is_cuda and logvar.is_cuda):
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    abi.need_device(z_all, prior, mu, logvar)
     if z_all.dim() != 2 or prior.dim() != 2 or z_all.shape[1] != prior.shape[1]:
         raise ValueError(f"z_all [Bt, D] and prior [P, D] must share D (got {tuple(z_all.shape)}, {tuple(prior.shape)})")
     if mu.dim() != 2 or mu.shape != logvar.shape or mu.shape[1] != z_all.shape[1]:
@@ -1532,10 +1534,17 @@ class MmdKlFn(Function):
 PERMUTE_MAX_B, PERMUTE_MAX_D = 4096, 512
 
 
+def _unit_cols(t):
+    """A 2-D tensor as the kernels take rows: a view with unit column stride and a row stride >= D as it is (its row
+    stride goes to the kernel), anything else copied dense."""
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
+
+
 def _rows_f32(t, what):
     """A 2-D fp32 device tensor as (tensor, row stride in elements): a view with unit column stride is passed as it is."""
-    if not t.is_cuda:
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    abi.need_device(t)
     if t.dtype != F32:
         raise abi.HipExtensionError(f"HIP path is fp32 only (got {t.dtype})")
     if t.dim() != 2:
@@ -1543,8 +1552,7 @@ def _rows_f32(t, what):
     B, D = t.shape
     if B == 1 and t.stride(1) == 1:
         return t, D
-    if t.stride(1) != 1 or t.stride(0) < D:
-        t = t.contiguous()
+    t = _unit_cols(t)
     return t, t.stride(0)
 
 
@@ -1597,8 +1605,7 @@ class AdaGroupFn(Function):
             raise ValueError(f"own must be a [B, D] = {(B, D)} mask (got {tuple(own_in.shape)})")
         (mu, ldm), (logvar, ldl), (eps, lde) = _rows_f32(mu, "mu"), _rows_f32(logvar, "logvar"), _rows_f32(eps, "eps")
         if own_in is not None:
-            if not own_in.is_cuda:
-                raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+            abi.need_device(own_in)
             own_in = (own_in != 0).to(torch.uint8).contiguous()
         z = torch.empty((R, D), dtype=F32, device=dev)
         own = torch.empty((B, D), dtype=torch.uint8, device=dev)
@@ -1627,12 +1634,6 @@ class AdaGroupFn(Function):
 
 # ------------------------------------------------------------------ JointVAE / AnnealedVAE: the capacity-controlled latent op
 JOINT_MAX_D = 512
-
-
-def _joint_device(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
 
 
 def _row_ptr(t):
@@ -1665,7 +1666,7 @@ class JointLatentFn(Function):
             raise ValueError(f"u must be [B, n_disc] = {(B, n_disc)} and seg an int32 [n_disc, 2] table")
         if tuple(capacity.shape) != (2,) or capacity.dtype != torch.float64:
             raise ValueError(f"capacity must be a [2] float64 tensor (got {tuple(capacity.shape)}, {capacity.dtype})")
-        _joint_device(capacity, seg)
+        abi.need_device(capacity, seg)
         (mu, ldm), (logvar, ldl) = _rows_f32(mu, "mu"), _rows_f32(logvar, "logvar")
         (eps, lde) = _rows_f32(eps, "eps") if n_cont else (None, 0)
         (u, ldu) = _rows_f32(u, "u") if n_disc else (None, 0)
@@ -1714,7 +1715,7 @@ def joint_latent_hard(mu, seg, n_cont, n_disc):
         raise ValueError(f"the joint op takes B >= 1 and 1 <= D <= {JOINT_MAX_D} (got {(B, D)})")
     if n_disc and (seg is None or tuple(seg.shape) != (n_disc, 2) or seg.dtype != torch.int32):
         raise ValueError("seg must be an int32 [n_disc, 2] table")
-    _joint_device(seg)
+    abi.need_device(seg)
     mu, ldm = _rows_f32(mu.detach(), "mu")
     z = torch.empty((B, D), dtype=F32, device=mu.device)
     call("itcv_joint_latent_fwd", mu.data_ptr(), ldm, None, 0, None, 0, None, 0, ptr(seg.contiguous() if n_disc else None),
@@ -1739,8 +1740,7 @@ def disc_forward(x, weights, biases, slope, R0):
     """x [R, zdim] (dense fp32) through Linear + LeakyReLU(slope) for all but the last (weight, bias) pair -- one fused
     launch per layer, two when its K is split -- the plain Linear for the last (2 logits) and the head.  No gradient."""
     x = _f32c(x.detach())
-    if not x.is_cuda:
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    abi.need_device(x)
     R = x.shape[0]
     dp = DiscPass()
     dp.weights = [_f32c(w.detach()) for w in weights]
@@ -1984,9 +1984,7 @@ class GaussLogDensityFn(Function):
     def forward(ctx, x, mu, logvar, eps_density):
         shape, views, dims, sx, sm, sl = _bc3(x, mu, logvar)
         out = torch.empty(tuple(views[0].shape), dtype=F32, device=views[0].device)
-        for v in views:
-            if not v.is_cuda:
-                raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+        abi.need_device(*views)
         call("itcv_gauss_logdensity_fwd", views[0].data_ptr(), views[1].data_ptr(), views[2].data_ptr(), ptr(out), dims, sx,
              sm, sl, int(eps_density), stream())
         ctx.save_for_backward(x, mu, logvar)
@@ -2117,12 +2115,8 @@ def _disent_mu(mu):
         raise abi.HipExtensionError(f"disent: representations must be a non-empty [N, D] tensor (got {tuple(mu.shape)})")
     if mu.dtype != F32:
         raise abi.HipExtensionError(f"HIP path is fp32 only (got {mu.dtype})")
-    if not mu.is_cuda:
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
-    mu = mu.detach()
-    if mu.stride(1) != 1 or mu.stride(0) < mu.shape[1]:
-        mu = mu.contiguous()
-    return mu
+    abi.need_device(mu)
+    return _unit_cols(mu.detach())
 
 
 def disent_flags(device):
@@ -2275,7 +2269,7 @@ def zdiff_row(a, b, out):
 
 
 # ------------------------------------------------------------------ boosted trees for DCI (csrc/gbt.hip)
-GBT_NODES = 127          # ITCV_GBT_TREE_NODES: heap slots of one tree
+GBT_NODES = abi.DEFINES["ITCV_GBT_TREE_NODES"]          # heap slots of one tree
 U8, I64 = torch.uint8, torch.int64
 
 

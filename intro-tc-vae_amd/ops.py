@@ -274,8 +274,7 @@ def ada_group(mu, logvar, beta, averaging="gvae", own=None, eps=None, with_terms
         raise ValueError(f"own must be a [B, D] = {(R // 2, D)} mask (got {tuple(own.shape)})")
     if eps is not None and eps.shape != mu.shape:
         raise ValueError(f"eps must have mu's shape {tuple(mu.shape)} (got {tuple(eps.shape)})")
-    if not (mu.is_cuda and logvar.is_cuda):
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    abi.need_device(mu, logvar)
     if eps is None:
         eps = noise(mu.shape, mu.device)
     z, loss, mask, terms = HF.AdaGroupFn.apply(mu, logvar, eps.detach(), None if own is None else own.detach(),
@@ -343,8 +342,7 @@ def joint_latent(mu, logvar, n_cont, disc_sizes, capacity, gamma_cont, gamma_dis
         raise ValueError("joint_latent needs at least one row")
     n_cont, disc, n_disc = joint_spec(n_cont, disc_sizes, D)
     if hard:
-        if not mu.is_cuda:
-            raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+        abi.need_device(mu)
         return HF.joint_latent_hard(mu, joint_segments(disc, mu.device) if n_disc else None, n_cont, n_disc)
     temperature, gamma_cont, gamma_disc, beta = float(temperature), float(gamma_cont), float(gamma_disc), float(beta)
     if not (0.0 < temperature < math.inf):
@@ -357,8 +355,7 @@ def joint_latent(mu, logvar, n_cont, disc_sizes, capacity, gamma_cont, gamma_dis
         raise ValueError(f"eps must be [B, n_cont] = {(B, n_cont)} (got {tuple(eps.shape)})")
     if u is not None and tuple(u.shape) != (B, n_disc):
         raise ValueError(f"u must be [B, n_disc] = {(B, n_disc)} (got {tuple(u.shape)})")
-    if not (mu.is_cuda and logvar.is_cuda):
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    abi.need_device(mu, logvar)
     if not isinstance(capacity, torch.Tensor) or tuple(capacity.shape) != (2,) or capacity.dtype != torch.float64 \
             or not capacity.is_cuda:
         raise ValueError("capacity must be a [2] float64 device tensor (C_z, C_c): the kernel reads it when it runs")
@@ -435,8 +432,7 @@ def permute_dims(z, keys=None):
     project's noise source, so recorded draws and graph capture work as for ``reparameterize``): argsort of i.i.d.
     continuous keys is a uniform random permutation.  Any keys give a permutation (ties go by row index).  The result
     carries no gradient.  B <= 4096, D <= 512."""
-    if not z.is_cuda:
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    abi.need_device(z)
     if keys is None:
         keys = noise(z.shape, z.device)
     return HF.permute_dims(z, keys)
@@ -447,8 +443,7 @@ def factor_pass(z, discriminator, z_perm=None, keys=None, permute=True):
     ``factor_tc`` and ``factor_disc_loss`` to share (``shared=``): both then see the same weights and the same z.
     ``z_perm`` None: ``permute_dims(z, keys)``, written straight into the stacked buffer together with the copy of z (one
     launch).  ``permute=False``: the B rows of z alone, enough for ``factor_tc``."""
-    if not z.is_cuda:
-        raise abi.HipExtensionError("HIP kernels need device tensors (got a CPU tensor); there is no CPU path")
+    abi.need_device(z)
     if z.dim() != 2 or z.shape[1] != discriminator.zdim:
         raise ValueError(f"z must be [B, {discriminator.zdim}] (got {tuple(z.shape)})")
     B, D = z.shape
