@@ -569,6 +569,41 @@ int itcv_joint_latent_bwd(const float* dz, size_t ld_dz, const float* g, const f
                           const float* logvar, size_t ld_logvar, const float* eps, size_t ld_eps, const float* u,
                           size_t ld_u, const int* seg, float* dmu, float* dlogvar, int B, int n_cont, int n_disc,
                           double tau, double gamma_cont, double gamma_disc, double beta, void* stream);
+/* The label regulariser of the semi-supervised S2 objectives (Locatello et al. 2020, "Disentangling Factors of Variation
+ * Using Few Labels"; disentanglement_lib's `semi_supervised_vae`: supervised_regularizer_xent / _l2 / _cov) with its gradient
+ * (csrc/sup.hip).  mu [B][D] fp32: the encoder means of the B labelled rows, unit column stride and a row stride ld_mu >= D
+ * (read in place: a row slice of a wider tensor, half of a packed [.][2D] tensor).  y [B][F] fp32 holding the integer factor
+ * values, row stride ld_y >= F.  1 <= F <= min(D, 64), D <= 512.  All three forms are SUMS over the labelled batch, not means,
+ * as the library defines them.  In fp64 from the fp32 inputs:
+ *   form 1 "xent": t = y_bf / sizes[f];  sup = sum_b sum_{f<F} (max(m, 0) - m t + log1p(exp(-|m|))),  m = mu[b][f]
+ *                  d sup / d m = sigmoid(m) - t.  sizes [F] int32 ON THE DEVICE; min_size is its smallest entry as the host
+ *                  that built it knows it (only this form reads either).
+ *   form 2 "l2":   sup = sum_b sum_{f<F} (scale mu[b][f] - y_bf)^2;   d sup / d m = 2 scale (scale m - y)
+ *   form 3 "cov":  C = (1 / B) sum_b (mu[b] - mean)(y_b - ybar)^T  [D][F];  W = C with W_ii = 0 (i < min(D, F));
+ *                  sup = sum_ij W_ij^2;   d sup / d mu[b][i] = (2 / B) sum_j W_ij (y_bj - ybar_j)
+ * Columns >= F of mu get an exactly zero gradient under xent and l2 (they are not read); under cov every column counts.
+ * gamma: gamma_dev, when not NULL, is a [1] fp64 value ON THE DEVICE that the second launch reads when it runs (a captured
+ * graph replays with whatever it holds then) and the scalar argument gamma is not looked at; with gamma_dev NULL the scalar
+ * is used.  out[0] = gamma * sup;  terms[2] = {sup, gamma};  keep [1 + F] fp64: keep[0] = the gamma that was used, and under
+ * cov keep[1 + j] = ybar_j.  Wt [F][D] fp64 (cov only, may be NULL otherwise): Wt[j][i] = W_ij, so that the backward is the
+ * row-major product (2 / B) Y_c Wt.  ws: itcv_sup_workspace(B, D, F, form) bytes (B fp64 row partials, or one per 32 x 32
+ * tile of C; 0 for shapes the op refuses).
+ * 2 launches forward: xent / l2 a wave per row (four rows a block, the blocks stride over the rows), cov a 32 x 32 tile of
+ * C per block (column means first, then the rows in staged chunks of 64); then a one-block finish that adds the partials in
+ * index order.
+ * _bwd, ONE launch: g[1] is the gradient of out[0]; every element of the dense dmu [B][D] fp32 is written:
+ * g keep[0] d sup / d mu.  It reads keep and Wt of the forward, not gamma_dev again.  gamma == 0 gives out[0] = 0 and an all-zero
+ * dmu whatever sup is.  Every sum is fp64 in a fixed order, there are no atomics: results are bitwise reproducible and do
+ * not depend on the grid.  Refused before any launch: a NULL pointer that the form needs, B outside 1..2^24, D outside
+ * 1..512, F outside 1..64, F > D, another form, min_size < 1 under xent, a gamma (gamma_dev NULL) or scale that is not
+ * finite, a row stride below its width, a workspace that is too small. */
+size_t itcv_sup_workspace(int B, int D, int F, int form);
+int itcv_sup_fwd(const float* mu, size_t ld_mu, const float* y, size_t ld_y, const int* sizes, int min_size,
+                 const double* gamma_dev, double gamma, double scale, float* out, float* terms, double* Wt, double* keep,
+                 void* ws, size_t ws_bytes, int B, int D, int F, int form, void* stream);
+int itcv_sup_bwd(const float* g, const float* mu, size_t ld_mu, const float* y, size_t ld_y, const int* sizes, int min_size,
+                 double scale, const double* Wt, const double* keep, float* dmu, int B, int D, int F, int form,
+                 void* stream);
 /* The FactorVAE objective (Kim & Mnih 2018; disentanglement_lib's `factor_vae`), csrc/factor.hip.
  * itcv_permute_dims, ONE launch (a block per column): out[r][d] = z[i][d] where r is the rank of keys[i][d] in column d
  * of keys[B][D] -- ascending in the monotone uint32 image of the float's bits (the sign-flip map of itcv_udr_ranks, +0 and

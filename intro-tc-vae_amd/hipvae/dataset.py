@@ -13,7 +13,9 @@ Both tables fit in HBM many times over.  Here
     same factors, same observations, so every ``compute_*`` score runs on it unchanged;
   * ``DeviceLoader`` feeds training from the table: one gather (+ flips) and one label ``index_select`` per batch;
   * ``DevicePairLoader`` feeds the weakly-supervised pair objective (solvers/ada.py): pairs of images that differ in a
-    few factors, drawn on the device (``pair_factors``) and looked up with two gathers into one ``[2B, C, H, W]`` batch.
+    few factors, drawn on the device (``pair_factors``) and looked up with two gathers into one ``[2B, C, H, W]`` batch;
+  * ``DeviceLabelledLoader`` feeds the semi-supervised S2 objectives (solvers/semi.py): unlabelled rows from an epoch
+    permutation plus a few rows of a fixed labelled subset, with their integer factor values (``index_factors``).
 
 Datasets that resize (``resize != H``: ``Image.resize(..., Image.BICUBIC)`` per sample, dataset.py:78-79,144-145,335) run
 that resize on the device too, bit for bit (``itcv_resize_u8``, csrc/resize.hip, with the plans of hipvae/resize.py):
@@ -34,7 +36,7 @@ from .disentangle import FactorSampler
 from .resize import ResizePlan
 
 __all__ = ["DeviceImageTable", "ResizedView", "DeviceFactorSampler", "DeviceLoader", "DevicePairLoader", "pair_factors",
-           "factor_bases"]
+           "factor_bases", "DeviceLabelledLoader", "index_factors"]
 
 UPLOAD_CHUNK_BYTES = 256 << 20
 RESIZE_MODES = (None, "table", "gather", "auto")
@@ -488,4 +490,77 @@ class DevicePairLoader:
             t.gather((second * self._bases).sum(1), out=x[B:], check=False)
             self.factors = (first, second)
             yield self.func(x, changed) if self.func is not None else (x, changed)
+        t.check()
+
+
+# ---- a few labels for the semi-supervised objectives ---------------------------------------------------------------------
+def index_factors(idx, factor_sizes, columns=None):
+    """int64 ``[n, len(columns)]``: the factor values of the images ``idx`` (an int64 tensor on any device) of a table
+    ordered by its factors, ``(idx // base_f) % size_f`` with ``factor_bases`` -- integers derived from the index, not the
+    float ``latents_values`` of a label table.  ``columns`` None: every factor."""
+    sizes = [int(s) for s in factor_sizes]
+    cols = list(range(len(sizes))) if columns is None else [int(c) for c in columns]
+    bases = torch.tensor([factor_bases(sizes)[c] for c in cols], dtype=torch.int64, device=idx.device)
+    size_t = torch.tensor([sizes[c] for c in cols], dtype=torch.int64, device=idx.device)
+    return (idx.reshape(-1, 1) // bases) % size_t
+
+
+class DeviceLabelledLoader:
+    """Batches ``(x, y)`` for the semi-supervised S2 solvers (solvers/semi.py) from a ``DeviceImageTable`` that carries
+    ``factor_sizes`` / ``latent_indices`` (any other table: ``ValueError``): ``x`` fp32 ``[B + B_l, C, H, W]`` on the
+    device whose first ``B`` rows are unlabelled and whose LAST ``B_l = labelled_batch_size`` (None: ``batch_size``) rows
+    are labelled, ``y`` fp32 ``[B_l, F]`` the labelled rows' integer factor values (``index_factors``: derived from the
+    image index); ``pre_process(x, y)`` when given.  The label columns are the table's ``latent_indices``, or the subset
+    ``factors`` of them; ``.factor_sizes`` holds their sizes, for the solver's constructor.
+
+    The unlabelled rows come from one ``torch.randperm`` per epoch, as ``DeviceLoader`` draws them (``len()`` and the batch
+    sizes are its too).  The labelled subset of ``num_labelled`` image indices is drawn ONCE, before the first epoch, and
+    never changes (``.labelled_indices``); every batch draws ``B_l`` of them uniformly with replacement.  All draws come
+    from a private device generator seeded with ``seed`` -- the same seed repeats the same epochs, torch's global RNG
+    streams are untouched.  One buffer, two gathers, no host round trip; the table's index flag is checked once, at the
+    end of the epoch."""
+
+    def __init__(self, table, batch_size, labelled_batch_size=None, num_labelled=1000, factors=None, seed=0,
+                 drop_last=True, pre_process=None):
+        if not isinstance(table, DeviceImageTable) or table.factor_sizes is None or table.latent_indices is None:
+            raise ValueError("DeviceLabelledLoader: the table carries no factor_sizes / latent_indices")
+        total = int(np.prod(table.factor_sizes, dtype=np.int64))
+        if total != table.num_images:
+            raise ValueError(f"DeviceLabelledLoader: the factors index {total} images, the table holds {table.num_images}")
+        Bl = batch_size if labelled_batch_size is None else labelled_batch_size
+        if batch_size < 1 or Bl < 1:
+            raise ValueError("batch_size and labelled_batch_size must be positive")
+        if not 1 <= num_labelled <= table.num_images:
+            raise ValueError(f"num_labelled must lie in 1 .. {table.num_images}, the table's images (got {num_labelled})")
+        lat = [int(i) for i in table.latent_indices]
+        cols = lat if factors is None else [int(i) for i in factors]
+        if not cols or len(set(cols)) != len(cols) or not set(cols) <= set(lat):
+            raise ValueError(f"factors must name distinct latent factors out of {lat} (got {factors!r})")
+        self.table, self.batch_size, self.labelled_batch_size = table, int(batch_size), int(Bl)
+        self.num_labelled, self.columns, self.seed = int(num_labelled), tuple(cols), int(seed)
+        self.drop_last, self.func = bool(drop_last), pre_process
+        self.factor_sizes = tuple(int(table.factor_sizes[c]) for c in cols)
+        self.labelled_indices = None
+        self._gen = None
+
+    def __len__(self):
+        return len(DeviceLoader.batch_sizes(self.table.num_images, self.batch_size, self.drop_last))
+
+    def __iter__(self):
+        t, Bl = self.table, self.labelled_batch_size
+        if self._gen is None:
+            self._gen = torch.Generator(device=t.device).manual_seed(self.seed)
+            self.labelled_indices = torch.randperm(t.num_images, generator=self._gen, device=t.device)[:self.num_labelled]
+        order = torch.randperm(t.num_images, generator=self._gen, device=t.device)
+        row = 0
+        for n in DeviceLoader.batch_sizes(t.num_images, self.batch_size, self.drop_last):
+            idx = order[row:row + n]
+            row += n
+            pick = torch.randint(self.num_labelled, (Bl,), generator=self._gen, device=t.device)
+            lab = self.labelled_indices.index_select(0, pick)
+            x = torch.empty((n + Bl,) + t.image_shape, dtype=torch.float32, device=t.device)
+            t.gather(idx, out=x[:n], check=False)
+            t.gather(lab, out=x[n:], check=False)
+            y = index_factors(lab, t.factor_sizes, self.columns).to(torch.float32)
+            yield self.func(x, y) if self.func is not None else (x, y)
         t.check()

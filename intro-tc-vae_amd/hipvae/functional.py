@@ -1723,6 +1723,68 @@ def joint_latent_hard(mu, seg, n_cont, n_disc):
     return z
 
 
+# ------------------------------------------------------------------ semi-supervised S2 objectives: the label regulariser
+SUP_KINDS = {"xent": 1, "l2": 2, "cov": 3}
+SUP_MAX_D = 512
+SUP_MAX_F = 64
+_SUP_SIZES = {}
+
+
+def sup_sizes(factor_sizes, device):
+    """The device table [F] int32 of the factor sizes.  Built once per (sizes, device) and kept."""
+    key = (tuple(int(k) for k in factor_sizes), torch.device(device))
+    t = _SUP_SIZES.get(key)
+    if t is None:
+        t = _SUP_SIZES[key] = torch.tensor(key[0], dtype=torch.int32).to(device)
+    return t
+
+
+class SupRegFn(Function):
+    """gamma * the label regulariser of the S2 objectives (include/itcv_hip.h: itcv_sup_fwd; ``kind`` 1 = xent, 2 = l2,
+    3 = cov): two launches forward, one backward.  ``mu`` [B_l, D] and ``y`` [B_l, F]: fp32 views with unit column stride
+    are read in place.  ``factor_sizes``: a tuple of F ints (xent) or None.  ``gamma``: a float, or a [1] float64 device
+    tensor read when the kernel runs.  Outputs: the scalar, differentiable in ``mu``, and (sup, gamma) [2], no gradient.
+    Kept for the backward: the two inputs, the gamma that was used and, under cov, W and the fp64 column means of y."""
+
+    @staticmethod
+    def forward(ctx, mu, y, kind, factor_sizes, gamma, scale):
+        (mu, ldm), (y, ldy) = _rows_f32(mu, "mu"), _rows_f32(y, "labels")
+        (B, D), F = mu.shape, y.shape[1]
+        dev = mu.device
+        sizes = sup_sizes(factor_sizes, dev) if factor_sizes is not None else None
+        min_size = min(int(k) for k in factor_sizes) if factor_sizes is not None else 0
+        on_device = isinstance(gamma, torch.Tensor)
+        if on_device:
+            abi.need_device(gamma)
+        out = torch.empty((), dtype=F32, device=dev)
+        terms = torch.empty((2,), dtype=F32, device=dev)
+        keep = torch.empty((1 + F,), dtype=torch.float64, device=dev)
+        Wt = torch.empty((F, D), dtype=torch.float64, device=dev) if kind == SUP_KINDS["cov"] else None
+        nws = lib.itcv_sup_workspace(B, D, F, int(kind))
+        ws = _ws(nws, dev)
+        call("itcv_sup_fwd", mu.data_ptr(), ldm, y.data_ptr(), ldy, ptr(sizes), min_size, ptr(gamma) if on_device else None,
+             0.0 if on_device else float(gamma), float(scale), ptr(out), ptr(terms), ptr(Wt), ptr(keep), ptr(ws), nws, B, D,
+             F, int(kind), stream())
+        ctx.save_for_backward(mu, y, sizes, Wt, keep)
+        ctx.cfg = (int(kind), min_size, float(scale), ldm, ldy)
+        ctx.mark_non_differentiable(terms)
+        ctx.set_materialize_grads(False)
+        return out, terms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_terms):
+        mu, y, sizes, Wt, keep = ctx.saved_tensors
+        kind, min_size, scale, ldm, ldy = ctx.cfg
+        (B, D), F = mu.shape, y.shape[1]
+        if g is None:
+            return (None,) * 6
+        dmu = torch.empty((B, D), dtype=F32, device=mu.device)
+        call("itcv_sup_bwd", ptr(_f32c(g)), mu.data_ptr(), ldm, y.data_ptr(), ldy, ptr(sizes), min_size, scale, ptr(Wt),
+             ptr(keep), ptr(dmu), B, D, F, kind, stream())
+        return dmu, None, None, None, None, None
+
+
 class DiscPass:
     """One forward of the discriminator MLP over R stacked rows, the first R0 labelled 0 ("from q(z)") and the rest 1
     ("from the product of the marginals"): the input ``x`` [R, zdim], the hidden activations, the logits [R, 2], the

@@ -379,6 +379,67 @@ def joint_prior_sample(n, n_cont, disc_sizes, device):
     return torch.cat(cols, dim=1)
 
 
+SUP_KINDS = HF.SUP_KINDS
+
+
+def supervised_regularizer(mu, labels, kind="xent", factor_sizes=None, gamma=1.0, scale=1.0, with_terms=False):
+    """The label term of the semi-supervised S2 objectives (Locatello et al. 2020, "Disentangling Factors of Variation
+    Using Few Labels"; disentanglement_lib's ``semi_supervised_vae``, ``supervised_regularizer_xent`` / ``_l2`` /
+    ``_cov``; not in the reference).  ``mu`` [B_l, D]: the encoder means of the labelled rows (a row-strided view is read
+    in place); ``labels`` [B_l, F]: their factor values, fp32 holding integers; 1 <= F <= min(D, 64), D <= 512.  The first
+    F latent means are tied to the F factors.  All three forms are SUMS over the labelled batch, not means: the library
+    defines them so, and published ``gamma_sup`` values assume it.
+
+        "xent": t = y_bf / K_f,  sup = sum_b sum_{f<F} (max(m, 0) - m t + log1p(exp(-|m|))),  m = mu[b, f]
+                (``factor_sizes`` = (K_1, .., K_F), required)
+        "l2":   sup = sum_b sum_{f<F} (scale mu[b, f] - y_bf)^2         (``scale`` a fixed number)
+        "cov":  C = (1 / B_l) sum_b (mu_b - mean)(y_b - ybar)^T [D, F],  W = C with W_ii = 0,  sup = sum_ij W_ij^2
+
+    Columns >= F of ``mu`` receive an exactly zero gradient under xent and l2; under cov they are penalised, because all
+    of C off the zeroed diagonal counts.  ``logvar`` is not an input.  Returns ``gamma * sup``, differentiable in ``mu``;
+    with ``with_terms`` also the device vector (sup, gamma), no gradient.  ``gamma``: a Python float, or a [1] float64
+    DEVICE tensor that the kernel reads when it runs, so that a captured step replays with the value it holds then.
+    Two launches forward, one backward, fp64 inside, bitwise reproducible.  Launched eagerly the term costs 50 - 75 us
+    forward + backward on an MI355X, bound by the host's launch rate.
+
+    Out of scope: the library's ``embed`` form and l2's learnable scale (both add parameters outside the encoder's and the
+    decoder's flat groups), and its label-noise transformations (permuted / noisy / binned labels)."""
+    if kind not in SUP_KINDS:
+        raise ValueError(f"kind must be one of {tuple(SUP_KINDS)} (got {kind!r})")
+    if not isinstance(mu, torch.Tensor) or mu.dim() != 2 or mu.shape[0] < 1:
+        raise ValueError(f"mu must be a [B_l, D] matrix with B_l >= 1 (got {tuple(getattr(mu, 'shape', ()))})")
+    B, D = mu.shape
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] < 1:
+        raise ValueError(f"labels must be a [B_l, F] = [{B}, F] tensor on the device "
+                         f"(got {tuple(getattr(labels, 'shape', ()))})")
+    F = labels.shape[1]
+    if F > D or F > HF.SUP_MAX_F or D > HF.SUP_MAX_D:
+        raise ValueError(f"supervised_regularizer takes 1 <= F <= min(D, {HF.SUP_MAX_F}) and D <= {HF.SUP_MAX_D} "
+                         f"(got F = {F}, D = {D})")
+    sizes = None
+    if kind == "xent":
+        if factor_sizes is None:
+            raise ValueError('kind "xent" needs factor_sizes = (K_1, .., K_F): its targets are y / K')
+        sizes = tuple(factor_sizes)
+        if len(sizes) != F or any(isinstance(k, bool) or int(k) != k or k < 1 for k in sizes):
+            raise ValueError(f"factor_sizes must be {F} integers >= 1, one per label column (got {sizes})")
+        sizes = tuple(int(k) for k in sizes)
+    if isinstance(gamma, torch.Tensor):
+        if tuple(gamma.shape) != (1,) or gamma.dtype != torch.float64:
+            raise ValueError(f"gamma must be a number or a [1] float64 device tensor (got {tuple(gamma.shape)}, "
+                             f"{gamma.dtype})")
+        gamma = gamma.detach()
+    elif not math.isfinite(float(gamma)):
+        raise ValueError(f"gamma must be finite (got {gamma})")
+    if not math.isfinite(float(scale)):
+        raise ValueError(f"scale must be finite (got {scale})")
+    abi.need_device(mu)
+    if not labels.is_cuda or labels.device != mu.device:
+        raise ValueError(f"labels must be a [B_l, F] = [{B}, F] tensor on the device (got one on {labels.device})")
+    out, terms = HF.SupRegFn.apply(mu, labels.detach(), SUP_KINDS[kind], sizes, gamma, float(scale))
+    return (out, terms) if with_terms else out
+
+
 def tc_components(z, mu, logvar, dataset_size, *, var_from_row=True, eps_density=True, weighted=False):
     """Fused ops.py:80-84 + :92-115: returns (logqz_prodmarginals [B], log_qz [B]) of the stratified
     (default) or weighted sampler, for either density flavour / variance orientation.  No grad."""

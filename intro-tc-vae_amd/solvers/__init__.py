@@ -7,6 +7,9 @@ from .mmd import MMDSolver, IntroMMDSolver
 from .factor import FactorSolver
 from .ada import AdaGVAESolver
 from .joint import JointVAESolver, AnnealedVAESolver
+# the semi-supervised family takes (x, y) batches: imported by name (``from solvers import S2VAESolver``); ``__all__``
+# stays the twelve solvers that train from images alone
+from .semi import S2VAESolver, S2TCSolver, S2DIPSolver, S2FactorSolver
 
 __all__ = ["VAESolver", "IntroSolver", "TCSovler", "IntroTCSovler", "DIPSolver", "IntroDIPSolver", "MMDSolver",
            "IntroMMDSolver", "FactorSolver", "AdaGVAESolver", "JointVAESolver", "AnnealedVAESolver"]
