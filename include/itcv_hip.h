@@ -604,6 +604,62 @@ int itcv_sup_fwd(const float* mu, size_t ld_mu, const float* y, size_t ld_y, con
 int itcv_sup_bwd(const float* g, const float* mu, size_t ld_mu, const float* y, size_t ld_y, const int* sizes, int min_size,
                  double scale, const double* Wt, const double* keep, float* dmu, int B, int D, int F, int form,
                  void* stream);
+/* The importance-weighted bound (Burda, Grosse and Salakhutdinov 2016, "Importance Weighted Autoencoders") as a training
+ * objective and as a streaming estimate of log p(x), with the gradient estimators of Roeder et al. 2017 ("sticking the
+ * landing") and Tucker et al. 2019 (doubly reparameterised), csrc/iwae.hip.  K samples of each of B images: row r = k B + b is
+ * sample k of image b, so slab k = 0 is the plain batch.  1 <= K <= 1024, B K <= 2^24, 1 <= D <= 512.  fp64 arithmetic from
+ * the fp32 inputs; every sum in a fixed order, no atomics: results are bitwise reproducible and do not depend on the grid.
+ * mu, logvar [B][D] fp32 with unit column stride and row strides ld_mu, ld_logvar >= D (read in place); eps [K B][D], row
+ * stride ld_eps >= D.
+ * itcv_iwae_sample_fwd, ONE launch (a wave per row): with s = exp(logvar / 2)
+ *   z[r][d] = mu[b][d] + s eps[r][d]  (dense [K B][D] fp32),   lat[r] = 1/2 sum_d (z^2 - eps^2 - logvar)  ([K B] fp64)
+ * lat is log q(z | x) - log p(z) of the sample; no clamp and no variance floor; it is formed from the fp64 z.
+ * itcv_iwae_sample_bwd, ONE launch (a thread per element of [B][D], the K samples walked in k order): dz [K B][D] (row stride
+ * ld_dz >= D) is the gradient of z, h [K B] fp64 that of lat, wt [K B] fp64 the normalised weights of itcv_iwae_combine_fwd
+ * (read under estimator 2 only; may be NULL otherwise).  Every element of the dense dmu, dlogvar [B][D] fp32 is written:
+ *   estimator 0 "iwae": t = dz + h z;                  dmu = sum_k t,  dlogvar = sum_k (t eps s / 2 - h / 2)
+ *   estimator 1 "stl":  p = dz + h (z - eps / s);      dmu = sum_k p,  dlogvar = sum_k p eps s / 2
+ *   estimator 2 "dreg": p as under 1, times wt[r]
+ * (1 and 2 drop the direct dependence of log q on mu and logvar and keep the path through z.)
+ * itcv_iwae_rows_fwd, 2 launches, the broadcast reconstruction rows: rows[r] = sum_p err(recon[r][p], x[r mod B][p]) for
+ * x [B][P] and recon [K B][P], both dense; x is never copied K times.  A block takes one slice of one image and a k-strided
+ * set of its rows, so the slice of x comes from HBM once.  err, the slicing and the order of every row's sum are those of
+ * itcv_recon_rows_fwd at K B rows: with x repeated K times the two entries give the same bits (float4 reads under the same
+ * condition: P % 4 == 0 and 16-byte aligned bases).  ws: itcv_iwae_rows_workspace(B, K, P) bytes (0 for refused shapes).
+ * itcv_iwae_rows_bwd, ONE launch: drecon[r][p] = g[r] err'(recon[r][p], x[r mod B][p]), g [K B] fp32; the bits of
+ * itcv_recon_rows_bwd on the repeated x.
+ * itcv_iwae_combine_fwd, 2 launches (a wave per image, lanes striding over k; then a one-block finish that adds the per-image
+ * values in image order): logw_r = -(beta_rec rows[r] + beta_kl lat[r]), m_b = max_k logw,
+ *   wt[r] = e^(logw_r - m_b) / sum_k e^(logw - m_b)                                               ([K B] fp64)
+ *   img [4][B] fp64 = {bound_b = m_b + log sum_k e^(logw - m_b) - log K,  ess_b = (sum_k e)^2 / sum_k e^2,
+ *                      sum_k wt rows,  sum_k wt lat}
+ *   out[0] = -mean_b bound_b,  terms[4] = {beta_rec mean_b sum_k wt rows, beta_kl mean_b sum_k wt lat, mean_b bound_b, mean_b ess_b}
+ * K = 1 gives bound_b = logw, wt = 1 and ess = 1 exactly; K equal weights give ess = K exactly.
+ * itcv_iwae_combine_bwd, ONE launch: with a_r = g[0] wt[r] / B, g_rows[r] = (float)(beta_rec a_r), g_lat[r] = beta_kl a_r (fp64).
+ * itcv_iwae_accumulate, ONE launch, the streaming form: one chunk's rows, lat of K samples of B images is merged into
+ * state [5][B] fp64 = {running max m, sum e^(logw - m), sum e^(2 (logw - m)), sum logw, count}; a count of 0 marks an empty
+ * state (a zero-filled buffer is one).  The number of samples is unbounded across calls.  itcv_iwae_finalize, ONE launch:
+ *   log_px[b] = m + log sum e - log count,  elbo[b] = sum logw / count,  ess[b] = (sum e)^2 / sum e^2     (all [B] fp64)
+ * Refused before any launch, with every output untouched: a NULL pointer that the call needs, B < 1, K outside 1..1024,
+ * B K above 2^24, D outside 1..512, a row stride below its width, P < 1, an unknown loss type or estimator, a beta that is
+ * not finite, a workspace that is too small. */
+int itcv_iwae_sample_fwd(const float* mu, size_t ld_mu, const float* logvar, size_t ld_logvar, const float* eps,
+                         size_t ld_eps, float* z, double* lat, int B, int K, int D, void* stream);
+int itcv_iwae_sample_bwd(const float* dz, size_t ld_dz, const double* h, const double* wt, const float* mu, size_t ld_mu,
+                         const float* logvar, size_t ld_logvar, const float* eps, size_t ld_eps, float* dmu, float* dlogvar,
+                         int B, int K, int D, int estimator, void* stream);
+size_t itcv_iwae_rows_workspace(int B, int K, size_t P);
+int itcv_iwae_rows_fwd(const float* x, const float* recon, float* rows, int B, int K, size_t P, int loss_type, void* ws,
+                       size_t ws_bytes, void* stream);
+int itcv_iwae_rows_bwd(const float* x, const float* recon, const float* g, float* drecon, int B, int K, size_t P,
+                       int loss_type, void* stream);
+int itcv_iwae_combine_fwd(const float* rows, const double* lat, double beta_rec, double beta_kl, double* wt, double* img,
+                          float* out, float* terms, int B, int K, void* stream);
+int itcv_iwae_combine_bwd(const float* g, const double* wt, double beta_rec, double beta_kl, float* g_rows, double* g_lat,
+                          int B, int K, void* stream);
+int itcv_iwae_accumulate(const float* rows, const double* lat, double beta_rec, double beta_kl, double* state, int B, int K,
+                         void* stream);
+int itcv_iwae_finalize(const double* state, double* log_px, double* elbo, double* ess, int B, void* stream);
 /* The FactorVAE objective (Kim & Mnih 2018; disentanglement_lib's `factor_vae`), csrc/factor.hip.
  * itcv_permute_dims, ONE launch (a block per column): out[r][d] = z[i][d] where r is the rank of keys[i][d] in column d
  * of keys[B][D] -- ascending in the monotone uint32 image of the float's bits (the sign-flip map of itcv_udr_ranks, +0 and

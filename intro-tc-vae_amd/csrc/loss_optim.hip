@@ -4,25 +4,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "recon_rows.h"
 
 namespace itcv {
-
-template <int LT>
-__device__ __forceinline__ float rec_err(float r, float t) {
-  if (LT == ITCV_LOSS_MSE) {
-    const float d = r - t;
-    return d * d;
-  }
-  if (LT == ITCV_LOSS_L1) return fabsf(r - t);
-  // F.binary_cross_entropy clamps both log terms at -100
-  return -(t * fmaxf(logf(r), -100.f) + (1.f - t) * fmaxf(logf(1.f - r), -100.f));
-}
-template <int LT>
-__device__ __forceinline__ float rec_derr(float r, float t) {
-  if (LT == ITCV_LOSS_MSE) return 2.f * (r - t);
-  if (LT == ITCV_LOSS_L1) return r > t ? 1.f : (r < t ? -1.f : 0.f);
-  return (r - t) / fmaxf((1.f - r) * r, 1e-12f);  // ATen binary_cross_entropy_backward
-}
 
 // grid (B, splits): partial[b][s] = sum over the slice of row b; vec4: every row of both operands starts on a 16-byte
 // boundary (P % 4 == 0 and aligned bases, decided by launch_recon_partial), so the slices can be read as float4
@@ -32,21 +16,9 @@ __global__ __launch_bounds__(256) void recon_partial_kernel(const float* __restr
                                                            double* __restrict__ part, size_t P, int splits, int vec4) {
   __shared__ double scratch[4];
   const int b = blockIdx.x, s = blockIdx.y;
-  const size_t chunk = ((P + splits - 1) / splits + 3) & ~(size_t)3;
-  const size_t beg = (size_t)s * chunk, end = beg + chunk < P ? beg + chunk : P;
-  const float* xr = x + (size_t)b * P;
-  const float* rr = recon + (size_t)b * P;
-  double acc = 0.0;
-  if (vec4) {
-    for (size_t i = beg + (size_t)threadIdx.x * 4; i < end; i += 1024) {
-      const float4 t = *reinterpret_cast<const float4*>(xr + i);
-      const float4 r = *reinterpret_cast<const float4*>(rr + i);
-      acc += (double)(rec_err<LT>(r.x, t.x) + rec_err<LT>(r.y, t.y)) +
-             (double)(rec_err<LT>(r.z, t.z) + rec_err<LT>(r.w, t.w));
-    }
-  } else {
-    for (size_t i = beg + threadIdx.x; i < end; i += 256) acc += (double)rec_err<LT>(rr[i], xr[i]);
-  }
+  size_t beg, end;
+  recon_slice(P, splits, s, beg, end);
+  double acc = recon_slice_acc<LT>(x + (size_t)b * P, recon + (size_t)b * P, beg, end, vec4);
   acc = block_sum(acc, scratch);
   if (threadIdx.x == 0) part[(size_t)b * splits + s] = acc;
 }
@@ -129,12 +101,6 @@ __global__ void lincomb_bwd_kernel(const float* __restrict__ g, LinComb a, float
   if (k < a.n) grads[k] = g[0] * a.weight[k];
 }
 
-static inline int recon_splits(int B, size_t P) {
-  int s = cdiv(1024, B);
-  const size_t maxs = cdivz(P, 2048);
-  if ((size_t)s > maxs) s = (int)maxs;
-  return s < 1 ? 1 : s;
-}
 // the one launch of recon_partial_kernel; false: unknown loss type.  float4 reads only where every row of both operands
 // is 16-byte aligned: a view that starts inside its storage takes the scalar path (like itcv_sumsq / itcv_scale_by_dev,
 // which refuse such a pointer, but here there is a path to fall to)

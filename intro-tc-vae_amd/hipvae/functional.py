@@ -1785,6 +1785,149 @@ class SupRegFn(Function):
         return dmu, None, None, None, None, None
 
 
+# ------------------------------------------------------------------ importance-weighted bound (csrc/iwae.hip)
+IWAE_ESTIMATORS = {"iwae": 0, "stl": 1, "dreg": 2}
+IWAE_MAX_D = 512
+IWAE_MAX_K = 1024
+IWAE_MAX_ROWS = 1 << 24
+
+
+class IwaeSample:
+    """What ``IwaeSampleFn`` returns and ``IwaeCombineFn`` completes: ``z`` [K B, D] fp32 and ``lat`` [K B] fp64 (both
+    differentiable in ``mu`` and ``logvar``), the buffer ``weights`` [K B] fp64 that the combine fills with the normalised
+    importance weights, and the code of the gradient estimator that the sample's backward applies (set by the combine;
+    0 = "iwae" until then).  The backward reads the two when it runs."""
+    __slots__ = ("z", "lat", "weights", "estimator", "B", "K")
+
+    def __init__(self, B, K, device):
+        self.B, self.K = B, K
+        self.weights = torch.empty((K * B,), dtype=torch.float64, device=device)
+        self.estimator = 0
+        self.z = self.lat = None
+
+
+class IwaeSampleFn(Function):
+    """K reparameterised samples of each of B posteriors (include/itcv_hip.h: itcv_iwae_sample_fwd): one launch forward,
+    one backward.  ``mu`` / ``logvar`` [B, D]: fp32 views with unit column stride are read in place; ``eps`` [K B, D]."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, sample):
+        (mu, ldm), (logvar, ldl), (eps, lde) = _rows_f32(mu, "mu"), _rows_f32(logvar, "logvar"), _rows_f32(eps, "eps")
+        (B, D), K = mu.shape, sample.K
+        z = torch.empty((K * B, D), dtype=F32, device=mu.device)
+        lat = torch.empty((K * B,), dtype=torch.float64, device=mu.device)
+        call("itcv_iwae_sample_fwd", mu.data_ptr(), ldm, logvar.data_ptr(), ldl, eps.data_ptr(), lde, ptr(z), ptr(lat), B, K,
+             D, stream())
+        ctx.save_for_backward(mu, logvar, eps)
+        ctx.cfg = (sample, ldm, ldl, lde)
+        ctx.set_materialize_grads(False)
+        return z, lat
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dz, h):
+        mu, logvar, eps = ctx.saved_tensors
+        sample, ldm, ldl, lde = ctx.cfg
+        (B, D), K = mu.shape, sample.K
+        if dz is None and h is None:
+            return None, None, None, None
+        if dz is None:
+            dz = torch.zeros((K * B, D), dtype=F32, device=mu.device)
+        if h is None:
+            h = torch.zeros((K * B,), dtype=torch.float64, device=mu.device)
+        dz, ldz = _rows_f32(dz, "dz")
+        dmu, dlv = torch.empty((B, D), dtype=F32, device=mu.device), torch.empty((B, D), dtype=F32, device=mu.device)
+        call("itcv_iwae_sample_bwd", dz.data_ptr(), ldz, ptr(h.contiguous()), ptr(sample.weights), mu.data_ptr(), ldm,
+             logvar.data_ptr(), ldl, eps.data_ptr(), lde, ptr(dmu), ptr(dlv), B, K, D, int(sample.estimator), stream())
+        return dmu, dlv, None, None
+
+
+class IwaeRowsFn(Function):
+    """rows[k B + b] = sum_p err(recon[k B + b][p], x[b][p]) (include/itcv_hip.h: itcv_iwae_rows_fwd): the bits of
+    ``ReconRowsFn`` on ``x.repeat(K, 1)`` without the K copies; x is treated as a constant."""
+
+    @staticmethod
+    def forward(ctx, x, recon, loss_type):
+        x, recon = _f32c(x), _f32c(recon)
+        B, R = x.shape[0], recon.shape[0]
+        P = x.numel() // B
+        K = R // B
+        rows = torch.empty((R,), dtype=F32, device=recon.device)
+        nws = lib.itcv_iwae_rows_workspace(B, K, P)
+        ws = _ws(nws, recon.device)
+        call("itcv_iwae_rows_fwd", ptr(x), ptr(recon), ptr(rows), B, K, P, loss_type, ptr(ws), nws, stream())
+        ctx.save_for_backward(x, recon)
+        ctx.cfg = (B, K, P, loss_type)
+        return rows
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, recon = ctx.saved_tensors
+        B, K, P, lt = ctx.cfg
+        d = torch.empty_like(recon)
+        call("itcv_iwae_rows_bwd", ptr(x), ptr(recon), ptr(_f32c(g)), ptr(d), B, K, P, lt, stream())
+        return None, d, None
+
+
+class IwaeCombineFn(Function):
+    """The K-sample bound from the per-row terms (include/itcv_hip.h: itcv_iwae_combine_fwd): two launches forward, one
+    backward.  ``rows`` [K B] fp32, ``lat`` [K B] fp64.  Outputs: the scalar -mean_b bound_b, differentiable in both, and,
+    without a gradient, terms [4] = (rec, kl, bound, ess) and img [4, B] fp64 = per image (bound, ess, sum_k w rows,
+    sum_k w lat).  The normalised weights go into ``sample.weights`` and ``estimator`` into ``sample.estimator``."""
+
+    @staticmethod
+    def forward(ctx, rows, lat, sample, beta_rec, beta_kl, estimator):
+        B, K = sample.B, sample.K
+        rows, lat = _f32c(rows), lat.contiguous()
+        if lat.dtype != torch.float64 or rows.numel() != K * B or lat.numel() != K * B:
+            raise ValueError(f"rows (fp32) and lat (fp64) must hold K B = {K * B} values")
+        dev = rows.device
+        out = torch.empty((), dtype=F32, device=dev)
+        terms = torch.empty((4,), dtype=F32, device=dev)
+        img = torch.empty((4, B), dtype=torch.float64, device=dev)
+        call("itcv_iwae_combine_fwd", ptr(rows), ptr(lat), float(beta_rec), float(beta_kl), ptr(sample.weights), ptr(img),
+             ptr(out), ptr(terms), B, K, stream())
+        sample.estimator = int(estimator)
+        ctx.cfg = (sample, float(beta_rec), float(beta_kl))
+        ctx.mark_non_differentiable(terms, img)
+        ctx.set_materialize_grads(False)
+        return out, terms, img
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_terms, _g_img):
+        sample, beta_rec, beta_kl = ctx.cfg
+        if g is None:
+            return (None,) * 6
+        B, K = sample.B, sample.K
+        g_rows = torch.empty((K * B,), dtype=F32, device=g.device)
+        g_lat = torch.empty((K * B,), dtype=torch.float64, device=g.device)
+        call("itcv_iwae_combine_bwd", ptr(_f32c(g)), ptr(sample.weights), beta_rec, beta_kl, ptr(g_rows), ptr(g_lat), B, K,
+             stream())
+        return g_rows, g_lat, None, None, None, None
+
+
+def iwae_accumulate(rows, lat, state, beta_rec, beta_kl):
+    """Merge one chunk's ``rows`` [Kc B] fp32 and ``lat`` [Kc B] fp64 into ``state`` [5, B] fp64 (a zero-filled state is
+    empty): include/itcv_hip.h, itcv_iwae_accumulate.  One launch, no gradient."""
+    B = state.shape[1]
+    if state.dtype != torch.float64 or state.dim() != 2 or state.shape[0] != 5 or lat.dtype != torch.float64 \
+            or rows.numel() != lat.numel() or rows.numel() % B:
+        raise ValueError("state must be [5, B] fp64, lat fp64, and rows and lat hold Kc B values each")
+    call("itcv_iwae_accumulate", ptr(_f32c(rows)), ptr(lat.contiguous()), float(beta_rec), float(beta_kl), ptr(state), B,
+         rows.numel() // B, stream())
+    return state
+
+
+def iwae_finalize(state):
+    """(log_px, elbo, ess), each [B] fp64, of an accumulated ``state`` (itcv_iwae_finalize).  One launch."""
+    B = state.shape[1]
+    out = torch.empty((3, B), dtype=torch.float64, device=state.device)
+    call("itcv_iwae_finalize", ptr(state), ptr(out[0]), ptr(out[1]), ptr(out[2]), B, stream())
+    return out[0], out[1], out[2]
+
+
 class DiscPass:
     """One forward of the discriminator MLP over R stacked rows, the first R0 labelled 0 ("from q(z)") and the rest 1
     ("from the product of the marginals"): the input ``x`` [R, zdim], the hidden activations, the logits [R, 2], the

@@ -440,6 +440,73 @@ def supervised_regularizer(mu, labels, kind="xent", factor_sizes=None, gamma=1.0
     return (out, terms) if with_terms else out
 
 
+IWAE_ESTIMATORS = tuple(HF.IWAE_ESTIMATORS)
+
+
+def iwae_sample(mu, logvar, K, eps=None):
+    """K reparameterised samples of each of the B posteriors ``(mu, logvar)`` [B, D] for the importance-weighted bound
+    (Burda, Grosse and Salakhutdinov 2016; not in the reference).  Row ``r = k B + b`` is sample k of image b, so slab
+    ``k = 0`` has the layout of a plain batch:
+
+        z_r = mu_b + exp(logvar_b / 2) eps_r,      lat_r = 1/2 sum_d (z_rd^2 - eps_rd^2 - logvar_bd) = log q(z_r | x_b) - log p(z_r)
+
+    with no clamp and no variance floor.  Returns an ``HF.IwaeSample``: ``z`` [K B, D] fp32 for the decoder, ``lat`` [K B]
+    fp64, both differentiable in ``mu`` and ``logvar`` (row-strided views are read in place), and the buffer ``weights``
+    that ``iwae_bound`` fills.  ``eps`` None: ONE draw ``noise((K B, D))``, so recorded draws and graph capture work as for
+    ``reparameterize``.  One launch forward, one backward, fp64 inside, bitwise reproducible; 1 <= D <= 512,
+    1 <= K <= 1024, K B <= 2^24."""
+    if mu.dim() != 2 or mu.shape != logvar.shape or mu.shape[0] < 1:
+        raise ValueError(f"mu and logvar must share one [B, D] shape (got {tuple(mu.shape)}, {tuple(logvar.shape)})")
+    B, D = mu.shape
+    if isinstance(K, bool) or int(K) != K or not 1 <= K <= HF.IWAE_MAX_K or K * B > HF.IWAE_MAX_ROWS:
+        raise ValueError(f"iwae_sample takes an integer 1 <= K <= {HF.IWAE_MAX_K} with K B <= 2^24 (got K = {K!r}, B = {B})")
+    if not 1 <= D <= HF.IWAE_MAX_D:
+        raise ValueError(f"iwae_sample takes 1 <= D <= {HF.IWAE_MAX_D} (got {D})")
+    K = int(K)
+    if eps is not None and tuple(eps.shape) != (K * B, D):
+        raise ValueError(f"eps must be [K B, D] = {(K * B, D)} (got {tuple(eps.shape)})")
+    abi.need_device(mu, logvar)
+    if eps is None:
+        eps = noise((K * B, D), mu.device)
+    sample = HF.IwaeSample(B, K, mu.device)
+    sample.z, sample.lat = HF.IwaeSampleFn.apply(mu, logvar, eps.detach(), sample)
+    return sample
+
+
+def iwae_bound(x, recon, sample, beta_rec, beta_kl, loss_type="mse", estimator="iwae", with_terms=False):
+    """The K-sample importance-weighted bound of ``x`` [B, ...] from the reconstructions ``recon`` [K B, ...] of
+    ``sample.z`` (``sample``: what ``iwae_sample`` returned).  With err that of ``reconstruction_loss``:
+
+        rows_r = sum_p err(recon_rp, x_bp),   logw_r = -(beta_rec rows_r + beta_kl lat_r),   w_r = softmax_k(logw)_r
+        bound_b = logsumexp_k logw_r - log K,   loss = -mean_b bound_b
+
+    ``x`` is read in place by every one of its K rows, never copied.  Returns ``loss``, differentiable in ``recon`` and,
+    through ``sample``, in ``mu`` and ``logvar``; with ``with_terms`` also the device vector (beta_rec mean_b sum_k w rows,
+    beta_kl mean_b sum_k w lat, mean_b bound_b, mean_b ess_b), ess_b = 1 / sum_k w_r^2, no gradient.  ``estimator`` selects
+    the gradient that reaches ``mu`` and ``logvar``: "iwae" the plain reparameterised one; "stl" (Roeder et al. 2017) drops
+    the direct dependence of log q on them and keeps the path through z; "dreg" (Tucker et al. 2019) weights that path by
+    w once more.  The decoder's gradient is the same under all three, and so is every forward value.  Unknown
+    ``estimator``: ValueError; unknown ``loss_type``: NotImplementedError.  Four launches forward, two backward (plus the
+    sample's one), fp64 inside, bitwise reproducible."""
+    if estimator not in HF.IWAE_ESTIMATORS:
+        raise ValueError(f"estimator must be one of {IWAE_ESTIMATORS} (got {estimator!r})")
+    if loss_type not in abi.LOSS_TYPES:
+        raise NotImplementedError
+    if not isinstance(sample, HF.IwaeSample):
+        raise ValueError("sample must be what iwae_sample returned")
+    B, K = sample.B, sample.K
+    if x.size(0) != B or recon.size(0) != K * B or x.numel() * K != recon.numel():
+        raise ValueError(f"x must hold B = {B} images and recon K B = {K * B} of the same size "
+                         f"(got {tuple(x.shape)}, {tuple(recon.shape)})")
+    beta_rec, beta_kl = float(beta_rec), float(beta_kl)
+    if not (math.isfinite(beta_rec) and math.isfinite(beta_kl)):
+        raise ValueError(f"beta_rec and beta_kl must be finite (got {beta_rec}, {beta_kl})")
+    abi.need_device(x, recon)
+    rows = HF.IwaeRowsFn.apply(x.detach().reshape(B, -1), recon.reshape(K * B, -1), abi.LOSS_TYPES[loss_type])
+    loss, terms, _ = HF.IwaeCombineFn.apply(rows, sample.lat, sample, beta_rec, beta_kl, HF.IWAE_ESTIMATORS[estimator])
+    return (loss, terms) if with_terms else loss
+
+
 def tc_components(z, mu, logvar, dataset_size, *, var_from_row=True, eps_density=True, weighted=False):
     """Fused ops.py:80-84 + :92-115: returns (logqz_prodmarginals [B], log_qz [B]) of the stratified
     (default) or weighted sampler, for either density flavour / variance orientation.  No grad."""

@@ -10,6 +10,8 @@ from .joint import JointVAESolver, AnnealedVAESolver
 # the semi-supervised family takes (x, y) batches: imported by name (``from solvers import S2VAESolver``); ``__all__``
 # stays the twelve solvers that train from images alone
 from .semi import S2VAESolver, S2TCSolver, S2DIPSolver, S2FactorSolver
+# the importance-weighted bound: imported by name too (``from solvers import IWAESolver``)
+from .iwae import IWAESolver
 
 __all__ = ["VAESolver", "IntroSolver", "TCSovler", "IntroTCSovler", "DIPSolver", "IntroDIPSolver", "MMDSolver",
            "IntroMMDSolver", "FactorSolver", "AdaGVAESolver", "JointVAESolver", "AnnealedVAESolver"]

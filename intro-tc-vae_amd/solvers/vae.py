@@ -65,6 +65,7 @@ class VAESolver:
         self.elbo_params = None
         self.irs_params = None
         self.unsupervised_params = None
+        self.likelihood_params = None     # keyword arguments of hipvae.likelihood.compute_log_likelihood
         # "udr" ranks this model against ``udr_peers``: models trained from other seeds on the same data (a sequence of
         # networks; required by that score); ``udr_params``: ``params`` of hipvae.disentangle.compute_udr_score
         self.udr_peers = None
@@ -285,11 +286,16 @@ class VAESolver:
     def _side_walk(self, z: Tensor):
         """Between the VAE's backward and the clip: a further loss and walk over a group of its own."""
 
+    def _total_loss(self, loss_rec: Tensor, loss_kl: Tensor) -> Tensor:
+        """The scalar the step differentiates, from what ``_losses`` returned: scale * (loss_rec + loss_kl), vae.py:106.
+        An objective whose loss is not that sum overrides this."""
+        return self._lincomb((self.scale, self.scale), loss_rec, loss_kl)
+
     def _device_step(self, real: Tensor) -> Tensor:
         """Returns the stats vector [loss, loss_kl, loss_rec, *extra, norm]."""
         self._set_trainable(True, True)
         z, loss_rec, loss_kl, extra = self._losses(real)
-        loss = self._lincomb((self.scale, self.scale), loss_rec, loss_kl)      # scale * (loss_rec + loss_kl), vae.py:106
+        loss = self._total_loss(loss_rec, loss_kl)
         self._backward(loss, ("decoder", "encoder"))
         self._side_walk(z)
         norm = self._clip()
@@ -381,21 +387,27 @@ class VAESolver:
         factors either and is read like the decomposition: the record ``unsupervised`` {gaussian_total_correlation,
         gaussian_wasserstein_correlation, gaussian_wasserstein_correlation_norm, mutual_info_score}
         (``unsupervised_params``).  "udr" needs no factors either: the record ``udr`` {model_score, mean_pairwise}, the
-        Unsupervised Disentanglement Ranking of this model among ``[self.model, *self.udr_peers]`` (``udr_params``)."""
+        Unsupervised Disentanglement Ranking of this model among ``[self.model, *self.udr_peers]`` (``udr_params``).
+        "log_likelihood" needs no factors and is read like the decomposition: the record ``log_likelihood`` {log_px,
+        bits_per_dim, elbo, ess}, the importance-weighted estimate of log p(x) (hipvae.likelihood; ``likelihood_params``;
+        the reconstruction loss and ``beta_rec`` are this solver's unless given there)."""
         extras = tuple(self.extra_scores or ())
         with_elbo = "elbo_decomposition" in extras
         with_unsup = "unsupervised" in extras
         with_udr = "udr" in extras
+        with_ll = "log_likelihood" in extras
         factored = isinstance(self.dataset, DisentanglementDataset)
-        if self.writer is None or not (factored or with_elbo or with_unsup or with_udr) or cur_iter % self.test_iter:
+        if self.writer is None or not (factored or with_elbo or with_unsup or with_udr or with_ll) \
+                or cur_iter % self.test_iter:
             return
-        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr")
+        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr", "log_likelihood")
         unknown = [e for e in extras if e not in known]
         if unknown:
             raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, known))})")
         if factored:
             self._write_factor_scores(cur_iter, num_samples,
-                                      tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised", "udr")))
+                                      tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised", "udr",
+                                                                           "log_likelihood")))
         if with_elbo:
             from hipvae import aggregate
             kw = dict(batch_size=self.batch_size)
@@ -424,6 +436,14 @@ class VAESolver:
             mine = [float(v) for v in got["pairwise_disentanglement_scores"][1:, 0] if v == v]
             self.writer.add_scalars("udr", dict(model_score=got["model_scores"][0],
                                                 mean_pairwise=sum(mine) / len(mine) if mine else float("nan")),
+                                    global_step=cur_iter)
+        if with_ll:
+            from hipvae import likelihood
+            kw = dict(batch_size=self.batch_size, loss_type=self.recon_loss_type, beta_rec=self.beta_rec)
+            kw.update(self.likelihood_params or {})
+            got = likelihood.compute_log_likelihood(self.dataset if self._device_table is None else self._device_table,
+                                                    self.model, **kw)
+            self.writer.add_scalars("log_likelihood", {k: got[k] for k in ("log_px", "bits_per_dim", "elbo", "ess")},
                                     global_step=cur_iter)
 
     def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: tuple):
