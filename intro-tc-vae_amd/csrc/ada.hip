@@ -6,16 +6,13 @@
 //                reductions), the threshold, the mask, the averaged posteriors, both samples and the KL sums of the two
 //                adapted rows (two more wave reductions) are fp64 from the fp32 inputs.  The wave writes z, the mask, and
 //                three fp64 numbers per pair: the KL of its two rows and its count of shared dimensions.
-//   ada_finish : ONE block sums the 2B KL partials in row order and the B counts in pair order (a contiguous run per
-//                thread, then the 256 run totals in thread order) into the scalar and the two logged terms.
+//   ada_finish : ONE block sums the 2B KL partials in row order and the B counts in pair order (objective.h's ordered_sum)
+//                into the scalar and the two logged terms.
 //   ada_bwd    : ONE launch with the forward's mapping; with the mask a constant, the gradient is a function of the pair's
 //                dimension alone, so it needs no reduction.
 // Every sum has a fixed order, there is no atomic, and nothing depends on the grid or on timing: the same inputs give the
 // same bits.  Nothing in this file may be contracted into a fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "objective.h"
 
 #pragma clang fp contract(off)
 
@@ -27,15 +24,6 @@ constexpr int kAdaThreads = 256;
 constexpr int kAdaPairs = kAdaThreads / kWave;
 constexpr int kAdaMaxBlocks = 256;        // 1024 pairs a trip; the rest of the batch is walked by the stride
 constexpr int kAdaGvae = 1, kAdaMlvae = 2;
-
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double u = __shfl_xor(v, o, 64);
-    v = u < v ? u : v;
-  }
-  return v;
-}
 
 // the averaged posterior of one shared dimension: mean and variance (logvar = log of it)
 __device__ __forceinline__ void ada_average(int averaging, double m1, double l1, double m2, double l2, double& mb,
@@ -80,7 +68,7 @@ __global__ __launch_bounds__(kAdaThreads) void ada_fwd_kernel(const float* __res
         delta[r] = 0.0;
       }
     }
-    mn = wave_min_f64(mn);
+    mn = wave_min(mn);
     mx = wave_max(mx);
     const double tau = 0.5 * (mn + mx);
     double kl1 = 0.0, kl2 = 0.0, shared = 0.0;
@@ -94,10 +82,10 @@ __global__ __launch_bounds__(kAdaThreads) void ada_fwd_kernel(const float* __res
         const double a1 = m1[r], b1 = l1[r], a2 = m2[r], b2 = l2[r];
         const double n1 = eps[r1 * lde + d], n2 = eps[r2 * lde + d];
         if (mine) {
-          z[r1 * D + d] = (float)(a1 + n1 * exp(0.5 * b1));
-          z[r2 * D + d] = (float)(a2 + n2 * exp(0.5 * b2));
-          kl1 += 1.0 + b1 - a1 * a1 - exp(b1);
-          kl2 += 1.0 + b2 - a2 * a2 - exp(b2);
+          z[r1 * D + d] = (float)posterior_sample(a1, b1, n1);
+          z[r2 * D + d] = (float)posterior_sample(a2, b2, n2);
+          kl1 += posterior_kl_term(a1, b1);
+          kl2 += posterior_kl_term(a2, b2);
         } else {
           double mb, vb;
           ada_average(averaging, a1, b1, a2, b2, mb, vb);
@@ -121,28 +109,12 @@ __global__ __launch_bounds__(kAdaThreads) void ada_fwd_kernel(const float* __res
   }
 }
 
-// a[0] + a[1] + ... + a[n - 1] by one block of kAdaThreads: thread t folds the run [t * per, (t + 1) * per) in order, thread 0
-// the run totals in thread order; the result is valid in thread 0
-__device__ __forceinline__ double ada_ordered_sum(const double* __restrict__ a, size_t n, double* red) {
-  const size_t per = (n + kAdaThreads - 1) / kAdaThreads;
-  const size_t lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-  double s = 0.0;
-  for (size_t i = lo; i < hi; ++i) s += a[i];
-  __syncthreads();
-  red[threadIdx.x] = s;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int k = 0; k < kAdaThreads; ++k) t += red[k];
-  return t;
-}
-
 // out[0] = beta * mean_{2B rows} KL; terms[2] = {mean KL, mean number of shared dimensions per pair}
 __global__ __launch_bounds__(kAdaThreads) void ada_finish_kernel(const double* __restrict__ part, int B, double beta,
                                                                  float* __restrict__ out, float* __restrict__ terms) {
   __shared__ double red[kAdaThreads];
-  const double kl = ada_ordered_sum(part, 2 * (size_t)B, red);
-  const double sh = ada_ordered_sum(part + 2 * (size_t)B, (size_t)B, red);
+  const double kl = ordered_sum<kAdaThreads>(part, 2 * (size_t)B, red);
+  const double sh = ordered_sum<kAdaThreads>(part + 2 * (size_t)B, (size_t)B, red);
   if (threadIdx.x == 0) {
     const double mean = kl / (2.0 * (double)B);
     out[0] = (float)(beta != 0.0 ? beta * mean : 0.0);
@@ -168,10 +140,10 @@ __global__ __launch_bounds__(kAdaThreads) void ada_bwd_kernel(const float* __res
       const double g1 = dz[r1 * ldz + d], g2 = dz[r2 * ldz + d];
       double dm1, dm2, dl1, dl2;
       if (own[(size_t)b * D + d]) {
-        dm1 = g1 + gk * m1;
-        dm2 = g2 + gk * m2;
-        dl1 = 0.5 * exp(0.5 * l1) * (g1 * n1) + gk * (0.5 * (exp(l1) - 1.0));
-        dl2 = 0.5 * exp(0.5 * l2) * (g2 * n2) + gk * (0.5 * (exp(l2) - 1.0));
+        dm1 = posterior_dmu(g1, m1, gk);
+        dm2 = posterior_dmu(g2, m2, gk);
+        dl1 = posterior_dlv(g1, n1, l1, gk);
+        dl2 = posterior_dlv(g2, n2, l2, gk);
       } else {
         double mb, vb;
         ada_average(averaging, m1, l1, m2, l2, mb, vb);
@@ -199,21 +171,15 @@ __global__ __launch_bounds__(kAdaThreads) void ada_bwd_kernel(const float* __res
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-static inline int ada_grid(int B) {
-  const int blocks = cdiv(B, kAdaPairs);
-  return blocks < kAdaMaxBlocks ? blocks : kAdaMaxBlocks;
-}
-
 // nothing is launched on a failure
 static int ada_check(const char* name, bool ptrs, int B, int D, int averaging, double beta, size_t ld_min) {
-  if (!ptrs) return fail("%s: a required pointer is NULL", name);
-  if (B < 1 || B > kAdaMaxB) return fail("%s: B = %lld pairs is outside 1..2^30", name, B);
-  if (D < 1 || D > kAdaMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
+  if (need_pointers(name, ptrs) || need_dim(name, "B = %lld pairs", B, 1, kAdaMaxB, "1..2^30") ||
+      need_dim(name, "D = %lld", D, 1, kAdaMaxD, "1..512"))
+    return 1;
   if (averaging != kAdaGvae && averaging != kAdaMlvae)
     return fail("%s: averaging %lld is not 1 (gvae) or 2 (mlvae)", name, averaging);
-  if (!(fabs(beta) <= DBL_MAX)) return fail("%s: beta must be a finite number", name);
-  if (ld_min < (size_t)D) return fail("%s: a row stride of %lld is below D = %lld", name, (long long)ld_min, D);
-  return 0;
+  if (!finite(beta)) return fail("%s: beta must be a finite number", name);
+  return need_stride(name, "a", ld_min, "D", D);
 }
 
 }  // namespace itcv
@@ -230,7 +196,7 @@ int itcv_ada_group_fwd(const float* mu, size_t ld_mu, const float* logvar, size_
   if (int e = ada_check(name, mu && logvar && eps && z && own && part && out && terms, B, D, averaging, beta, ld_min))
     return e;
   hipStream_t st = S(stream);
-  const dim3 grid(ada_grid(B)), block(kAdaThreads);
+  const dim3 grid(row_grid(B, kAdaPairs, kAdaMaxBlocks)), block(kAdaThreads);
   pick_of<1, 2, 4, 8>(D <= 64 ? 1 : D <= 128 ? 2 : D <= 256 ? 4 : 8, [&](auto nr) {
     hipLaunchKernelGGL(ada_fwd_kernel<decltype(nr)::value>, grid, block, 0, st, mu, ld_mu, logvar, ld_logvar, eps, ld_eps,
                        own_in, B, D, averaging, z, own, part);
@@ -250,8 +216,9 @@ int itcv_ada_group_bwd(const float* dz, size_t ld_dz, const float* g, const floa
   ld_min = ld_eps < ld_min ? ld_eps : ld_min;
   if (int e = ada_check(name, dz && g && mu && logvar && eps && own && dmu && dlogvar, B, D, averaging, beta, ld_min))
     return e;
-  hipLaunchKernelGGL(ada_bwd_kernel, dim3(ada_grid(B)), dim3(kAdaThreads), 0, S(stream), dz, ld_dz, g, mu, ld_mu, logvar,
-                     ld_logvar, eps, ld_eps, own, B, D, averaging, beta, dmu, dlogvar);
+  const dim3 grid(row_grid(B, kAdaPairs, kAdaMaxBlocks));
+  hipLaunchKernelGGL(ada_bwd_kernel, grid, dim3(kAdaThreads), 0, S(stream), dz, ld_dz, g, mu, ld_mu, logvar, ld_logvar, eps,
+                     ld_eps, own, B, D, averaging, beta, dmu, dlogvar);
   ITCV_CHECK_LAUNCH(name);
   return 0;
 }

@@ -61,6 +61,15 @@ __device__ __forceinline__ T wave_max(T v) {
   }
   return v;
 }
+template <typename T>
+__device__ __forceinline__ T wave_min(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    T u = __shfl_xor(v, o, 64);
+    v = u < v ? u : v;
+  }
+  return v;
+}
 // block-wide sum; result valid in every thread.  `scratch` holds >= blockDim/64 elements.
 template <typename T>
 __device__ __forceinline__ T block_sum(T v, T* scratch) {

@@ -8,17 +8,14 @@
 //                diagonal (the spare half of the means pass of a diagonal tile computes it).  The block writes its patch of
 //                W = 2 lambda_od offdiag(C) + diag(2 lambda_d (C_ii - 1)) in fp32, the means of its strip (diagonal tiles)
 //                and its two fp64 loss partials {sum C_ij^2 (i != j), sum (C_ii - 1)^2} into the workspace.
-//   dip_finish : ONE block folds the tile partials (one per thread, fixed tree) and the KL of the local rows (the arithmetic
-//                of kl_loss_fwd_kernel: fp32 per row, fp64 across rows) into the scalar and the three logged terms.
+//   dip_finish : ONE block folds the tile partials (one per thread, fixed tree) and the KL of the local rows (objective.h's
+//                mean_kl_rows) into the scalar and the three logged terms.
 //   dip_bwd    : ONE launch, a kDipBwdRows x kDipBwdCols tile of [Bt, D] per block: (2 / Bt) X W in fp64 over LDS-staged
 //                chunks of kDipBwdK, plus the diagonal term of logvar (kind II) and the KL gradient on the local rows.
 // D up to 512 is covered by the grid, never by one block's LDS.  Every sum has a fixed order, there is no atomic, and
 // nothing depends on the grid or on timing: the same inputs give the same bits.  Nothing in this file may be contracted into
 // a fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "objective.h"
 
 #pragma clang fp contract(off)
 
@@ -147,26 +144,14 @@ __global__ __launch_bounds__(1024) void dip_finish_kernel(const float* __restric
                                                           float* __restrict__ out, float* __restrict__ terms) {
   __shared__ double red[16];
   __shared__ double klw[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   double od = 0.0, dg = 0.0;
   if (tid < nt * nt && (tid % nt) >= (tid / nt)) od = part[2 * tid], dg = part[2 * tid + 1];
   od = block_sum(od, red);
   dg = block_sum(dg, red);
-  double acc = 0.0;
-  for (int j = w; j < Bl; j += 16) {
-    float a = 0.f;
-    for (int l = lane; l < D; l += 64) {
-      const float v = lv[(size_t)j * ld + l], mm = mu[(size_t)j * ld + l];
-      a += 1.f + v - expf(v) - mm * mm;
-    }
-    acc += (double)(-0.5f * wave_sum(a));
-  }
-  if (lane == 0) klw[w] = acc;
-  __syncthreads();
+  const double kl = mean_kl_rows(mu, lv, (size_t)ld, Bl, D, klw);
   if (tid == 0) {
-    double t = 0.0;
-    for (int k = 0; k < 16; ++k) t += klw[k];
-    const double kl = t / (double)Bl, t_od = lam_od * od, t_dg = lam_d * dg;
+    const double t_od = lam_od * od, t_dg = lam_d * dg;
     out[0] = (float)((coef_kl != 0.0 ? coef_kl * kl : 0.0) + (t_od + t_dg));
     terms[0] = (float)kl, terms[1] = (float)t_od, terms[2] = (float)t_dg;
   }
@@ -235,15 +220,15 @@ static inline size_t dip_ws(int D) { return (size_t)dip_tiles(D) * dip_tiles(D) 
 // nothing is launched on a failure
 static int dip_check(const char* name, bool ptrs, int ld, int Bl, int Bt, int row_offset, int D, int kind, double lam_od,
                      double lam_d, double coef_kl) {
-  if (!ptrs) return fail("%s: a required pointer is NULL", name);
-  if (Bt < 2 || Bt > kDipMaxBt) return fail("%s: Bt = %lld rows is outside 2..2^24", name, Bt);
-  if (D < 1 || D > kDipMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
+  if (need_pointers(name, ptrs) || need_dim(name, "Bt = %lld rows", Bt, 2, kDipMaxBt, "2..2^24") ||
+      need_dim(name, "D = %lld", D, 1, kDipMaxD, "1..512"))
+    return 1;
   if (Bl < 1 || row_offset < 0 || (long long)row_offset + Bl > Bt)
     return fail("%s: rows must lie inside the global batch (row_offset = %lld, Bt = %lld)", name, row_offset, Bt);
   if (kind != 1 && kind != 2) return fail("%s: kind %lld is not 1 (DIP-VAE-I) or 2 (DIP-VAE-II)", name, kind);
-  if (!(lam_od >= 0.0) || !(lam_od <= DBL_MAX) || !(lam_d >= 0.0) || !(lam_d <= DBL_MAX))
+  if (!(lam_od >= 0.0 && finite(lam_od) && lam_d >= 0.0 && finite(lam_d)))
     return fail("%s: lambda_od and lambda_d must be finite numbers >= 0", name);
-  if (!(fabs(coef_kl) <= DBL_MAX)) return fail("%s: coef_kl must be a finite number", name);
+  if (!finite(coef_kl)) return fail("%s: coef_kl must be a finite number", name);
   if (ld != D && ld != 2 * D)
     return fail("%s: row stride %lld of mu_all / logvar_all is neither D nor 2 D (D = %lld)", name, ld, D);
   return 0;

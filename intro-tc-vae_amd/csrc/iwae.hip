@@ -12,16 +12,14 @@
 //                      the interleaved fp32 terms differently.)
 //   iwae_rows_bwd    : the same blocking, drecon = g[r] err'.
 //   iwae_combine     : ONE wave per image, lanes striding over k: max, sum of e^(logw - max), normalised weights, the
-//                      weighted means of the two terms.  iwae_finish: ONE block adds the per-image values in image order.
+//                      weighted means of the two terms.  iwae_finish: ONE block adds the per-image values in image order
+//                      (objective.h's ordered_sum).
 //   iwae_accumulate / iwae_finalize: the same wave per image over one chunk, merged into a per-image fp64 state.
 // Every sum has a fixed order, there is no atomic, and nothing depends on the grid or on timing: the same inputs give the
 // same bits.  Nothing in this file's fp64 arithmetic may be contracted into a fused multiply-add: the pragma stands inside
 // every fp64 body and not at file scope, because the fp32 error terms of recon_rows.h have to be compiled here exactly as
 // loss_optim.hip compiles them.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "objective.h"
 #include "recon_rows.h"
 
 namespace itcv {
@@ -33,11 +31,6 @@ constexpr int kIwaeThreads = 256;
 constexpr int kIwaeRowsPerBlock = kIwaeThreads / kWave;
 constexpr int kIwaeMaxBlocks = 2048;
 constexpr int kIwaeEstIwae = 0, kIwaeEstDreg = 2;     // 1: stl
-
-static inline int iwae_wave_grid(int rows) {
-  const int blocks = cdiv(rows, kIwaeRowsPerBlock);
-  return blocks < kIwaeMaxBlocks ? blocks : kIwaeMaxBlocks;
-}
 
 __global__ __launch_bounds__(kIwaeThreads) void iwae_sample_kernel(const float* __restrict__ mu, size_t ldm,
                                                                    const float* __restrict__ logvar, size_t ldl,
@@ -209,30 +202,15 @@ __global__ __launch_bounds__(kIwaeThreads) void iwae_combine_kernel(const float*
   }
 }
 
-// a[0] + a[1] + ... + a[n - 1] by one block: thread t folds the run [t * per, (t + 1) * per) in order, thread 0 the run
-// totals in thread order; the result is valid in thread 0
-__device__ __forceinline__ double iwae_ordered_sum(const double* __restrict__ a, size_t n, double* red) {
-  const size_t per = (n + kIwaeThreads - 1) / kIwaeThreads;
-  const size_t lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-  double s = 0.0;
-  for (size_t i = lo; i < hi; ++i) s += a[i];
-  __syncthreads();
-  red[threadIdx.x] = s;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int k = 0; k < kIwaeThreads; ++k) t += red[k];
-  return t;
-}
 __global__ __launch_bounds__(kIwaeThreads) void iwae_finish_kernel(const double* __restrict__ img, int B, double beta_rec,
                                                                    double beta_kl, float* __restrict__ out,
                                                                    float* __restrict__ terms) {
 #pragma clang fp contract(off)
   __shared__ double red[kIwaeThreads];
-  const double bound = iwae_ordered_sum(img, B, red);
-  const double ess = iwae_ordered_sum(img + B, B, red);
-  const double rec = iwae_ordered_sum(img + 2 * (size_t)B, B, red);
-  const double kl = iwae_ordered_sum(img + 3 * (size_t)B, B, red);
+  const double bound = ordered_sum<kIwaeThreads>(img, B, red);
+  const double ess = ordered_sum<kIwaeThreads>(img + B, B, red);
+  const double rec = ordered_sum<kIwaeThreads>(img + 2 * (size_t)B, B, red);
+  const double kl = ordered_sum<kIwaeThreads>(img + 3 * (size_t)B, B, red);
   if (threadIdx.x == 0) {
     const double inv = 1.0 / (double)B;
     out[0] = (float)(-(bound * inv));
@@ -302,21 +280,18 @@ static inline bool iwae_shape_ok(int B, int K) {
 }
 // nothing is launched on a failure
 static int iwae_check(const char* name, bool ptrs, int B, int K) {
-  if (!ptrs) return fail("%s: a required pointer is NULL", name);
+  if (need_pointers(name, ptrs)) return 1;
   if (B < 1) return fail("%s: B = %lld images is below 1", name, B);
-  if (K < 1 || K > kIwaeMaxK) return fail("%s: K = %lld samples is outside 1..1024", name, K);
+  if (need_dim(name, "K = %lld samples", K, 1, kIwaeMaxK, "1..1024")) return 1;
   if ((long long)B * K > kIwaeMaxRows) return fail("%s: B K = %lld rows exceed 2^24", name, (long long)B * K);
   return 0;
 }
 static int iwae_check_d(const char* name, int D, size_t ld_mu, size_t ld_logvar, size_t ld_eps) {
-  if (D < 1 || D > kIwaeMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
-  if (ld_mu < (size_t)D) return fail("%s: mu's row stride of %lld is below D = %lld", name, (long long)ld_mu, D);
-  if (ld_logvar < (size_t)D) return fail("%s: logvar's row stride of %lld is below D = %lld", name, (long long)ld_logvar, D);
-  if (ld_eps < (size_t)D) return fail("%s: eps's row stride of %lld is below D = %lld", name, (long long)ld_eps, D);
-  return 0;
+  return need_dim(name, "D = %lld", D, 1, kIwaeMaxD, "1..512") || need_stride(name, "mu's", ld_mu, "D", D) ||
+         need_stride(name, "logvar's", ld_logvar, "D", D) || need_stride(name, "eps's", ld_eps, "D", D);
 }
 static inline bool iwae_betas_ok(double beta_rec, double beta_kl) {
-  return fabs(beta_rec) <= DBL_MAX && fabs(beta_kl) <= DBL_MAX;
+  return finite(beta_rec) && finite(beta_kl);
 }
 // k-groups of the broadcast kernels' grid: enough blocks to fill the device, never more than K
 static inline int iwae_kgroups(int B, int K, int splits) {
@@ -342,8 +317,9 @@ int itcv_iwae_sample_fwd(const float* mu, size_t ld_mu, const float* logvar, siz
   if (int e = iwae_check(name, mu && logvar && eps && z && lat, B, K)) return e;
   if (int e = iwae_check_d(name, D, ld_mu, ld_logvar, ld_eps)) return e;
   const int R = B * K;
-  hipLaunchKernelGGL(iwae_sample_kernel, dim3(iwae_wave_grid(R)), dim3(kIwaeThreads), 0, S(stream), mu, ld_mu, logvar,
-                     ld_logvar, eps, ld_eps, z, lat, B, R, D);
+  const dim3 grid(row_grid(R, kIwaeRowsPerBlock, kIwaeMaxBlocks));
+  hipLaunchKernelGGL(iwae_sample_kernel, grid, dim3(kIwaeThreads), 0, S(stream), mu, ld_mu, logvar, ld_logvar, eps, ld_eps,
+                     z, lat, B, R, D);
   ITCV_CHECK_LAUNCH(name);
   return 0;
 }
@@ -355,7 +331,7 @@ int itcv_iwae_sample_bwd(const float* dz, size_t ld_dz, const double* h, const d
   const bool ptrs = dz && h && mu && logvar && eps && dmu && dlogvar && (estimator != kIwaeEstDreg || wt);
   if (int e = iwae_check(name, ptrs, B, K)) return e;
   if (int e = iwae_check_d(name, D, ld_mu, ld_logvar, ld_eps)) return e;
-  if (ld_dz < (size_t)D) return fail("%s: dz's row stride of %lld is below D = %lld", name, (long long)ld_dz, D);
+  if (need_stride(name, "dz's", ld_dz, "D", D)) return 1;
   if (estimator < kIwaeEstIwae || estimator > kIwaeEstDreg)
     return fail("%s: estimator %lld is not 0 (iwae), 1 (stl) or 2 (dreg)", name, estimator);
   hipLaunchKernelGGL(iwae_sample_bwd_kernel, dim3((unsigned)cdivz((size_t)B * D, kIwaeThreads)), dim3(kIwaeThreads), 0,
@@ -421,8 +397,8 @@ int itcv_iwae_combine_fwd(const float* rows, const double* lat, double beta_rec,
   if (int e = iwae_check(name, rows && lat && wt && img && out && terms, B, K)) return e;
   if (!iwae_betas_ok(beta_rec, beta_kl)) return fail("%s: beta_rec and beta_kl must be finite numbers", name);
   hipStream_t st = S(stream);
-  hipLaunchKernelGGL(iwae_combine_kernel, dim3(iwae_wave_grid(B)), dim3(kIwaeThreads), 0, st, rows, lat, beta_rec, beta_kl,
-                     wt, img, B, K);
+  const dim3 grid(row_grid(B, kIwaeRowsPerBlock, kIwaeMaxBlocks));
+  hipLaunchKernelGGL(iwae_combine_kernel, grid, dim3(kIwaeThreads), 0, st, rows, lat, beta_rec, beta_kl, wt, img, B, K);
   ITCV_CHECK_LAUNCH(name);
   hipLaunchKernelGGL(iwae_finish_kernel, dim3(1), dim3(kIwaeThreads), 0, st, (const double*)img, B, beta_rec, beta_kl, out,
                      terms);
@@ -447,8 +423,9 @@ int itcv_iwae_accumulate(const float* rows, const double* lat, double beta_rec, 
   const char* name = "itcv_iwae_accumulate";
   if (int e = iwae_check(name, rows && lat && state, B, K)) return e;
   if (!iwae_betas_ok(beta_rec, beta_kl)) return fail("%s: beta_rec and beta_kl must be finite numbers", name);
-  hipLaunchKernelGGL(iwae_accumulate_kernel, dim3(iwae_wave_grid(B)), dim3(kIwaeThreads), 0, S(stream), rows, lat, beta_rec,
-                     beta_kl, state, B, K);
+  const dim3 grid(row_grid(B, kIwaeRowsPerBlock, kIwaeMaxBlocks));
+  hipLaunchKernelGGL(iwae_accumulate_kernel, grid, dim3(kIwaeThreads), 0, S(stream), rows, lat, beta_rec, beta_kl, state, B,
+                     K);
   ITCV_CHECK_LAUNCH(name);
   return 0;
 }

@@ -7,16 +7,12 @@
 //                  its own discrete columns, the columns of that column's group IN ORDER (max, sums, sum alpha log alpha),
 //                  so every lane of a group gets the same fixed-order numbers with no cross-lane traffic and a group may
 //                  lie anywhere across the 64-lane edges.  The wave writes z and two fp64 numbers per row.
-//   joint_finish : ONE block sums the 2B partials in row order (a contiguous run per thread, then the 256 run totals in
-//                  thread order), READS THE TWO CAPACITIES FROM DEVICE MEMORY and writes the loss, the two signs and the
-//                  four logged terms.
+//   joint_finish : ONE block sums the 2B partials in row order (objective.h's ordered_sum), READS THE TWO CAPACITIES FROM
+//                  DEVICE MEMORY and writes the loss, the two signs and the four logged terms.
 //   joint_bwd    : ONE launch with the forward's mapping and the stored signs.
 // Every sum has a fixed order, there is no atomic, and nothing depends on the grid or on timing: the same inputs give the
 // same bits.  Nothing in this file may be contracted into a fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "objective.h"
 
 #pragma clang fp contract(off)
 
@@ -85,8 +81,8 @@ __global__ __launch_bounds__(kJointThreads) void joint_fwd_kernel(const float* _
           z[r * D + d] = mf;
         } else {
           const double m = mf, l = lv[r * ldl + d], n = eps[r * lde + d];
-          z[r * D + d] = (float)(m + n * exp(0.5 * l));
-          klz += 1.0 + l - m * m - exp(l);
+          z[r * D + d] = (float)posterior_sample(m, l, n);
+          klz += posterior_kl_term(m, l);
         }
       }
       for (int j = lane; j < nd; j += 64) {
@@ -128,22 +124,6 @@ __global__ __launch_bounds__(kJointThreads) void joint_fwd_kernel(const float* _
   }
 }
 
-// a[0] + a[1] + ... + a[n - 1] by one block of kJointThreads: thread t folds the run [t * per, (t + 1) * per) in order,
-// thread 0 the run totals in thread order; the result is valid in thread 0
-__device__ __forceinline__ double joint_ordered_sum(const double* __restrict__ a, size_t n, double* red) {
-  const size_t per = (n + kJointThreads - 1) / kJointThreads;
-  const size_t lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-  double s = 0.0;
-  for (size_t i = lo; i < hi; ++i) s += a[i];
-  __syncthreads();
-  red[threadIdx.x] = s;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int k = 0; k < kJointThreads; ++k) t += red[k];
-  return t;
-}
-
 __device__ __forceinline__ double joint_sign(double v) { return (double)(v > 0.0) - (double)(v < 0.0); }
 
 // out[0] = beta (gz |KL_z - C_z| + gc |KL_c - C_c|) with (C_z, C_c) = cap[0], cap[1] READ HERE; sgn[2] the signs of the two
@@ -153,8 +133,8 @@ __global__ __launch_bounds__(kJointThreads) void joint_finish_kernel(const doubl
                                                                      double gz, double gc, float* __restrict__ out,
                                                                      float* __restrict__ sgn, float* __restrict__ terms) {
   __shared__ double red[kJointThreads];
-  const double sz = joint_ordered_sum(part, (size_t)B, red);
-  const double sc = joint_ordered_sum(part + (size_t)B, (size_t)B, red);
+  const double sz = ordered_sum<kJointThreads>(part, (size_t)B, red);
+  const double sc = ordered_sum<kJointThreads>(part + (size_t)B, (size_t)B, red);
   if (threadIdx.x == 0) {
     const double klz = sz / (double)B, klc = sc / (double)B, cz = cap[0], cc = cap[1];
     const double dz = klz - cz, dc = klc - cc;
@@ -184,8 +164,8 @@ __global__ __launch_bounds__(kJointThreads) void joint_bwd_kernel(const float* _
     if (live) {
       for (int d = lane; d < nc; d += 64) {
         const double m = mu[r * ldm + d], l = lv[r * ldl + d], n = eps[r * lde + d], gd = dz[r * ldz + d];
-        dmu[r * D + d] = (float)(gd + kz * m);
-        dlv[r * D + d] = (float)(0.5 * exp(0.5 * l) * (gd * n) + kz * (0.5 * (exp(l) - 1.0)));
+        dmu[r * D + d] = (float)posterior_dmu(gd, m, kz);
+        dlv[r * D + d] = (float)posterior_dlv(gd, n, l, kz);
       }
       for (int j = lane; j < nd; j += 64) {
         const double a = mu[r * ldm + nc + j];
@@ -217,40 +197,29 @@ __global__ __launch_bounds__(kJointThreads) void joint_bwd_kernel(const float* _
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-static inline int joint_grid(int B) {
-  const int blocks = cdiv(B, kJointRows);
-  return blocks < kJointMaxBlocks ? blocks : kJointMaxBlocks;
-}
-
-static inline bool joint_weight_ok(double v) { return v >= 0.0 && v <= DBL_MAX; }
+static inline bool joint_weight_ok(double v) { return v >= 0.0 && finite(v); }
 
 // nothing is launched on a failure
 static int joint_check(const char* name, bool ptrs, int B, int nc, int nd, bool soft, double tau, double gz, double gc,
                        double beta) {
-  if (!ptrs) return fail("%s: a required pointer is NULL", name);
-  if (B < 1 || B > kJointMaxB) return fail("%s: B = %lld rows is outside 1..2^30", name, B);
+  if (need_pointers(name, ptrs) || need_dim(name, "B = %lld rows", B, 1, kJointMaxB, "1..2^30")) return 1;
   if (nc < 0 || nd < 0) return fail("%s: n_cont = %lld and n_disc = %lld must not be negative", name, nc, nd);
-  if (nc + (long long)nd < 1 || nc + (long long)nd > kJointMaxD)
-    return fail("%s: D = n_cont + n_disc = %lld is outside 1..512", name, nc + (long long)nd);
+  if (need_dim(name, "D = n_cont + n_disc = %lld", nc + (long long)nd, 1, kJointMaxD, "1..512")) return 1;
   if (!soft) return 0;
-  if (!(tau > 0.0 && tau <= DBL_MAX)) return fail("%s: the temperature must be a finite number above 0", name);
+  if (!(tau > 0.0 && finite(tau))) return fail("%s: the temperature must be a finite number above 0", name);
   if (!joint_weight_ok(gz) || !joint_weight_ok(gc))
     return fail("%s: gamma_cont and gamma_disc must be finite and not negative", name);
-  if (!(fabs(beta) <= DBL_MAX)) return fail("%s: beta must be a finite number", name);
+  if (!finite(beta)) return fail("%s: beta must be a finite number", name);
   return 0;
 }
 
 static int joint_strides(const char* name, size_t ld_mu, size_t ld_logvar, size_t ld_eps, size_t ld_u, int nc, int nd,
                          bool soft) {
-  const size_t D = (size_t)nc + nd;
-  if (ld_mu < D) return fail("%s: a row stride of %lld is below D = %lld", name, (long long)ld_mu, (long long)D);
+  const long long D = (long long)nc + nd;
+  if (need_stride(name, "a", ld_mu, "D", D)) return 1;
   if (!soft) return 0;
-  if (nc && ld_logvar < D)
-    return fail("%s: a row stride of %lld is below D = %lld", name, (long long)ld_logvar, (long long)D);
-  if (nc && ld_eps < (size_t)nc)
-    return fail("%s: a row stride of %lld is below n_cont = %lld", name, (long long)ld_eps, nc);
-  if (nd && ld_u < (size_t)nd) return fail("%s: a row stride of %lld is below n_disc = %lld", name, (long long)ld_u, nd);
-  return 0;
+  if (nc && (need_stride(name, "a", ld_logvar, "D", D) || need_stride(name, "a", ld_eps, "n_cont", nc))) return 1;
+  return nd ? need_stride(name, "a", ld_u, "n_disc", nd) : 0;
 }
 
 }  // namespace itcv
@@ -271,8 +240,9 @@ int itcv_joint_latent_fwd(const float* mu, size_t ld_mu, const float* logvar, si
   if (int e = joint_strides(name, ld_mu, ld_logvar, ld_eps, ld_u, n_cont, n_disc, soft)) return e;
   hipStream_t st = S(stream);
   const dim3 block(kJointThreads);
-  hipLaunchKernelGGL(joint_fwd_kernel, dim3(joint_grid(B)), block, 0, st, mu, ld_mu, logvar, ld_logvar, eps, ld_eps, u,
-                     ld_u, seg, B, n_cont, n_disc, soft ? tau : 1.0, soft ? 0 : 1, z, part);
+  const dim3 grid(row_grid(B, kJointRows, kJointMaxBlocks));
+  hipLaunchKernelGGL(joint_fwd_kernel, grid, block, 0, st, mu, ld_mu, logvar, ld_logvar, eps, ld_eps, u, ld_u, seg, B,
+                     n_cont, n_disc, soft ? tau : 1.0, soft ? 0 : 1, z, part);
   ITCV_CHECK_LAUNCH("itcv_joint_latent_fwd(rows)");
   if (!soft) return 0;
   hipLaunchKernelGGL(joint_finish_kernel, dim3(1), block, 0, st, (const double*)part, B, cap, beta, gamma_cont, gamma_disc,
@@ -289,9 +259,10 @@ int itcv_joint_latent_bwd(const float* dz, size_t ld_dz, const float* g, const f
   const bool ptrs = dz && g && sgn && mu && dmu && dlogvar && (n_cont <= 0 || (logvar && eps)) && (n_disc <= 0 || (u && seg));
   if (int e = joint_check(name, ptrs, B, n_cont, n_disc, true, tau, gamma_cont, gamma_disc, beta)) return e;
   if (int e = joint_strides(name, ld_mu < ld_dz ? ld_mu : ld_dz, ld_logvar, ld_eps, ld_u, n_cont, n_disc, true)) return e;
-  hipLaunchKernelGGL(joint_bwd_kernel, dim3(joint_grid(B)), dim3(kJointThreads), 0, S(stream), dz, ld_dz, g, sgn, mu,
-                     ld_mu, logvar, ld_logvar, eps, ld_eps, u, ld_u, seg, B, n_cont, n_disc, tau, beta, gamma_cont,
-                     gamma_disc, dmu, dlogvar);
+  const dim3 grid(row_grid(B, kJointRows, kJointMaxBlocks));
+  hipLaunchKernelGGL(joint_bwd_kernel, grid, dim3(kJointThreads), 0, S(stream), dz, ld_dz, g, sgn, mu, ld_mu, logvar,
+                     ld_logvar, eps, ld_eps, u, ld_u, seg, B, n_cont, n_disc, tau, beta, gamma_cont, gamma_disc, dmu,
+                     dlogvar);
   ITCV_CHECK_LAUNCH(name);
   return 0;
 }

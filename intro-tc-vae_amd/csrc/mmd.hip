@@ -10,19 +10,16 @@
 //                patch of Wt = (A | C) in fp32, ONE fp64 partial of its kernel sum, and the fp64 sums of its weights along
 //                its rows (and, mirrored, along its columns) into the workspace: they are taken from the fp64 values in a
 //                fixed order, never from the rounded fp32 ones.
-//   mmd_finish : block 0 folds the tile partials (fixed per-thread order, fixed tree) and the KL of the local rows (the
-//                arithmetic of kl_loss_fwd_kernel: fp32 per row, fp64 across rows) into the scalar and the five logged
-//                terms; the blocks behind it fold the per-strip row sums into rs [Bt], one row a thread, strips ascending.
+//   mmd_finish : block 0 folds the tile partials (fixed per-thread order, fixed tree) and the KL of the local rows
+//                (objective.h's mean_kl_rows) into the scalar and the five logged terms; the blocks behind it fold the
+//                per-strip row sums into rs [Bt], one row a thread, strips ascending.
 //   mmd_bwd    : ONE launch, a kMmdBwdRows x kMmdBwdCols tile of [Bt, D] per block: rs o z - Wt [z ; p] in fp64 over
 //                LDS-staged chunks of kMmdBwdK points; the blocks behind those write the KL gradient of the local rows.
 // Limits: Bt, P in 2..4096 and D in 1..512, covered by the grid, never by one block's LDS; they bound Wt at
 // 4096 x 8192 x 4 bytes = 128 MiB and the workspace at 8.5 MiB.  Nothing of size Bt x Bt x D exists anywhere.  Every sum
 // has a fixed order, there is no atomic, and nothing depends on the grid or on timing: the same inputs give the same bits.
 // Nothing in this file may be contracted into a fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "objective.h"
 
 #pragma clang fp contract(off)
 
@@ -162,7 +159,6 @@ __global__ __launch_bounds__(1024) void mmd_finish_kernel(const float* __restric
   }
   __shared__ double red[16];
   __shared__ double klw[16];
-  const int lane = tid & 63, w = tid >> 6;
   const int nz = cdiv(Bt, kMmdTile);
   double zz = 0.0, pp = 0.0, zp = 0.0;
   for (int e = tid; e < nt * nt; e += 1024) {
@@ -176,21 +172,8 @@ __global__ __launch_bounds__(1024) void mmd_finish_kernel(const float* __restric
   zz = block_sum(zz, red);
   pp = block_sum(pp, red);
   zp = block_sum(zp, red);
-  double acc = 0.0;
-  for (int j = w; j < Bl; j += 16) {
-    float a = 0.f;
-    for (int l = lane; l < D; l += 64) {
-      const float v = lv[(size_t)j * D + l], mm = mu[(size_t)j * D + l];
-      a += 1.f + v - expf(v) - mm * mm;
-    }
-    acc += (double)(-0.5f * wave_sum(a));
-  }
-  if (lane == 0) klw[w] = acc;
-  __syncthreads();
+  const double kl = mean_kl_rows(mu, lv, (size_t)D, Bl, D, klw);
   if (tid == 0) {
-    double t = 0.0;
-    for (int k = 0; k < 16; ++k) t += klw[k];
-    const double kl = t / (double)Bl;
     const double s_zz = zz / ((double)Bt * (double)(Bt - 1)), s_pp = pp / ((double)P * (double)(P - 1));
     const double s_zp = zp / ((double)Bt * (double)P);
     const double mmd2 = (s_zz + s_pp) - 2.0 * s_zp;
@@ -278,15 +261,15 @@ static inline size_t mmd_ws(int Bt, int P) {
 // nothing is launched on a failure
 static int mmd_check(const char* name, bool ptrs, int Bl, int Bt, int P, int D, int kind, double h, double lambda,
                      double coef_kl) {
-  if (!ptrs) return fail("%s: a required pointer is NULL", name);
-  if (Bt < 2 || Bt > kMmdMaxN) return fail("%s: Bt = %lld rows is outside 2..4096", name, Bt);
-  if (P < 2 || P > kMmdMaxN) return fail("%s: P = %lld prior rows is outside 2..4096", name, P);
-  if (Bl < 1 || Bl > kMmdMaxBl) return fail("%s: Bl = %lld local rows is outside 1..2^24", name, Bl);
-  if (D < 1 || D > kMmdMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
+  if (need_pointers(name, ptrs) || need_dim(name, "Bt = %lld rows", Bt, 2, kMmdMaxN, "2..4096") ||
+      need_dim(name, "P = %lld prior rows", P, 2, kMmdMaxN, "2..4096") ||
+      need_dim(name, "Bl = %lld local rows", Bl, 1, kMmdMaxBl, "1..2^24") ||
+      need_dim(name, "D = %lld", D, 1, kMmdMaxD, "1..512"))
+    return 1;
   if (kind != 1 && kind != 2) return fail("%s: kernel %lld is not 1 (rbf) or 2 (imq)", name, kind);
-  if (!(h > 0.0) || !(h <= DBL_MAX)) return fail("%s: the bandwidth h must be a finite number > 0", name);
-  if (!(lambda >= 0.0) || !(lambda <= DBL_MAX)) return fail("%s: lambda_mmd must be a finite number >= 0", name);
-  if (!(fabs(coef_kl) <= DBL_MAX)) return fail("%s: coef_kl must be a finite number", name);
+  if (!(h > 0.0 && finite(h))) return fail("%s: the bandwidth h must be a finite number > 0", name);
+  if (!(lambda >= 0.0 && finite(lambda))) return fail("%s: lambda_mmd must be a finite number >= 0", name);
+  if (!finite(coef_kl)) return fail("%s: coef_kl must be a finite number", name);
   return 0;
 }
 

@@ -11,18 +11,15 @@
 //                  registers.  The block writes its patch of W (C with W_ii = 0) TRANSPOSED, [F][D] fp64, so that the
 //                  backward is a row-major product, the means of its y strip (the blocks of the first mu strip) and one
 //                  fp64 partial, sum W_ij^2.
-//   sup_finish   : ONE block adds the partials in index order (a contiguous run per thread, then the 256 run totals in thread
-//                  order), reads gamma -- from the device when a pointer is given -- and writes the scalar, the two logged
-//                  terms and the gamma it used (the backward reads that copy, not the pointer again).
+//   sup_finish   : ONE block adds the partials in index order (objective.h's ordered_sum), reads gamma -- from the device
+//                  when a pointer is given -- and writes the scalar, the two logged terms and the gamma it used (the
+//                  backward reads that copy, not the pointer again).
 //   sup_rows_bwd / sup_cov_bwd : ONE launch.  xent and l2 need no reduction; cov is (2 / B) Y_c W^T in fp64 over LDS-staged
 //                  chunks of kSupBwdK factors, a kSupBwdRows x kSupBwdCols tile of [B, D] per block.
 // D up to 512 and F up to 64 are covered by the grid, never by one block's LDS.  Every sum has a fixed order, there is no
 // atomic, and nothing depends on the grid or on timing: the same inputs give the same bits.  Nothing in this file may be
 // contracted into a fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "objective.h"
 
 #pragma clang fp contract(off)
 
@@ -63,28 +60,13 @@ __global__ __launch_bounds__(kSupThreads) void sup_rows_kernel(const float* __re
   }
 }
 
-// a[0] + a[1] + ... + a[n - 1] by one block of kSupThreads: thread t folds the run [t * per, (t + 1) * per) in order, thread 0
-// the run totals in thread order; the result is valid in thread 0
-__device__ __forceinline__ double sup_ordered_sum(const double* __restrict__ a, size_t n, double* red) {
-  const size_t per = (n + kSupThreads - 1) / kSupThreads;
-  const size_t lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-  double s = 0.0;
-  for (size_t i = lo; i < hi; ++i) s += a[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int k = 0; k < kSupThreads; ++k) t += red[k];
-  return t;
-}
-
 // out[0] = gamma * sup; terms[2] = {sup, gamma}; keep[0] = gamma, as read here
 __global__ __launch_bounds__(kSupThreads) void sup_finish_kernel(const double* __restrict__ part, size_t n,
                                                                  const double* __restrict__ gamma_dev, double gamma,
                                                                  float* __restrict__ out, float* __restrict__ terms,
                                                                  double* __restrict__ keep) {
   __shared__ double red[kSupThreads];
-  const double sup = sup_ordered_sum(part, n, red);
+  const double sup = ordered_sum<kSupThreads>(part, n, red);
   if (threadIdx.x == 0) {
     const double g = gamma_dev ? gamma_dev[0] : gamma;
     out[0] = (float)(g != 0.0 ? g * sup : 0.0);
@@ -241,10 +223,6 @@ __global__ __launch_bounds__(kSupThreads) void sup_cov_bwd_kernel(const float* _
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------
-static inline int sup_grid(int B) {
-  const int blocks = cdiv(B, kSupRowsPerBlock);
-  return blocks < kSupMaxBlocks ? blocks : kSupMaxBlocks;
-}
 static inline size_t sup_parts(int B, int D, int F, int form) {
   return form == kSupCov ? (size_t)cdiv(D, kSupTile) * cdiv(F, kSupTile) : (size_t)B;
 }
@@ -256,18 +234,15 @@ static inline bool sup_shape_ok(int B, int D, int F, int form) {
 // nothing is launched on a failure
 static int sup_check(const char* name, bool ptrs, int B, int D, int F, int form, int min_size, bool gamma_ok, double scale,
                      size_t ld_mu, size_t ld_y) {
-  if (!ptrs) return fail("%s: a required pointer is NULL", name);
-  if (B < 1 || B > kSupMaxB) return fail("%s: B_l = %lld labelled rows is outside 1..2^24", name, B);
-  if (D < 1 || D > kSupMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
-  if (F < 1 || F > kSupMaxF) return fail("%s: F = %lld factors is outside 1..64", name, F);
+  if (need_pointers(name, ptrs) || need_dim(name, "B_l = %lld labelled rows", B, 1, kSupMaxB, "1..2^24") ||
+      need_dim(name, "D = %lld", D, 1, kSupMaxD, "1..512") || need_dim(name, "F = %lld factors", F, 1, kSupMaxF, "1..64"))
+    return 1;
   if (F > D) return fail("%s: F = %lld factors exceed the D = %lld latent dimensions", name, F, D);
   if (form != kSupXent && form != kSupL2 && form != kSupCov) return fail("%s: form %lld is not 1 (xent), 2 (l2) or 3 (cov)", name, form);
   if (form == kSupXent && min_size < 1) return fail("%s: xent needs every factor size >= 1 (got %lld)", name, min_size);
   if (!gamma_ok) return fail("%s: gamma must be a finite number", name);
-  if (!(fabs(scale) <= DBL_MAX)) return fail("%s: scale must be a finite number", name);
-  if (ld_mu < (size_t)D) return fail("%s: mu's row stride of %lld is below D = %lld", name, (long long)ld_mu, D);
-  if (ld_y < (size_t)F) return fail("%s: y's row stride of %lld is below F = %lld", name, (long long)ld_y, F);
-  return 0;
+  if (!finite(scale)) return fail("%s: scale must be a finite number", name);
+  return need_stride(name, "mu's", ld_mu, "D", D) || need_stride(name, "y's", ld_y, "F", F);
 }
 
 }  // namespace itcv
@@ -285,7 +260,7 @@ int itcv_sup_fwd(const float* mu, size_t ld_mu, const float* y, size_t ld_y, con
                  void* ws, size_t ws_bytes, int B, int D, int F, int form, void* stream) {
   const char* name = "itcv_sup_fwd";
   const bool ptrs = mu && y && out && terms && keep && (form != kSupXent || sizes) && (form != kSupCov || Wt);
-  if (int e = sup_check(name, ptrs, B, D, F, form, min_size, gamma_dev || fabs(gamma) <= DBL_MAX, scale, ld_mu, ld_y))
+  if (int e = sup_check(name, ptrs, B, D, F, form, min_size, gamma_dev || itcv::finite(gamma), scale, ld_mu, ld_y))
     return e;
   const size_t n = sup_parts(B, D, F, form);
   ITCV_REQUIRE(ws && ws_bytes >= n * sizeof(double), "itcv_sup_fwd(workspace)");
@@ -296,8 +271,8 @@ int itcv_sup_fwd(const float* mu, size_t ld_mu, const float* y, size_t ld_y, con
                        y, ld_y, B, D, F, Wt, keep, part);
     ITCV_CHECK_LAUNCH("itcv_sup_fwd(tiles)");
   } else {
-    hipLaunchKernelGGL(sup_rows_kernel, dim3(sup_grid(B)), dim3(kSupThreads), 0, st, mu, ld_mu, y, ld_y, sizes, B, F, form,
-                       scale, part);
+    const dim3 grid(row_grid(B, kSupRowsPerBlock, kSupMaxBlocks));
+    hipLaunchKernelGGL(sup_rows_kernel, grid, dim3(kSupThreads), 0, st, mu, ld_mu, y, ld_y, sizes, B, F, form, scale, part);
     ITCV_CHECK_LAUNCH("itcv_sup_fwd(rows)");
   }
   hipLaunchKernelGGL(sup_finish_kernel, dim3(1), dim3(kSupThreads), 0, st, (const double*)part, n, gamma_dev, gamma, out,
@@ -317,8 +292,8 @@ int itcv_sup_bwd(const float* g, const float* mu, size_t ld_mu, const float* y, 
     hipLaunchKernelGGL(sup_cov_bwd_kernel, dim3(cdiv(B, kSupBwdRows), cdiv(D, kSupBwdCols)), dim3(kSupThreads), 0, st, g, y,
                        ld_y, Wt, keep, B, D, F, dmu);
   else
-    hipLaunchKernelGGL(sup_rows_bwd_kernel, dim3(sup_grid(B)), dim3(kSupThreads), 0, st, g, mu, ld_mu, y, ld_y, sizes, keep,
-                       B, D, F, form, scale, dmu);
+    hipLaunchKernelGGL(sup_rows_bwd_kernel, dim3(row_grid(B, kSupRowsPerBlock, kSupMaxBlocks)), dim3(kSupThreads), 0, st, g,
+                       mu, ld_mu, y, ld_y, sizes, keep, B, D, F, form, scale, dmu);
   ITCV_CHECK_LAUNCH(name);
   return 0;
 }

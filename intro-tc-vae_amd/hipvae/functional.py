@@ -1418,6 +1418,11 @@ class TcFullFn(Function):
         return dz, dmu, dlv, None, None, None, None, None, None
 
 
+def _loss_terms(n, device):
+    """(out, terms): the fp32 scalar that an objective's finish kernel writes and its ``n`` logged terms."""
+    return torch.empty((), dtype=F32, device=device), torch.empty((n,), dtype=F32, device=device)
+
+
 def dip_kl_forward(mu_all, logvar_all, Bl, row_offset, kind, lambda_od, lambda_d, coef_kl):
     """itcv_dip_kl_fwd on a [Bt, D] pair in either layout (two dense tensors, or the halves of one packed [Bt, 2D] tensor,
     read in place; anything else is copied dense).  Returns (mu_all, logvar_all, ld) as read and (out, terms [3], W [D, D],
@@ -1429,8 +1434,7 @@ def dip_kl_forward(mu_all, logvar_all, Bl, row_offset, kind, lambda_od, lambda_d
     mu_all, logvar_all, ld = _pair_in(mu_all, logvar_all)
     Bt, D = mu_all.shape
     dev = mu_all.device
-    out = torch.empty((), dtype=F32, device=dev)
-    terms = torch.empty((3,), dtype=F32, device=dev)
+    out, terms = _loss_terms(3, dev)
     W = torch.empty((D, D), dtype=F32, device=dev)
     mean = torch.empty((D,), dtype=torch.float64, device=dev)
     nws = lib.itcv_dip_kl_workspace(Bt, D)
@@ -1490,8 +1494,7 @@ def _mmd_kl_forward(z_all, prior, mu, logvar, kernel, h, lambda_mmd, coef_kl):
     z_all, prior, mu, logvar = _f32c(z_all), _f32c(prior), _f32c(mu), _f32c(logvar)
     (Bt, D), P, Bl = z_all.shape, prior.shape[0], mu.shape[0]
     dev = z_all.device
-    out = torch.empty((), dtype=F32, device=dev)
-    terms = torch.empty((5,), dtype=F32, device=dev)
+    out, terms = _loss_terms(5, dev)
     Wt = torch.empty((Bt, Bt + P), dtype=F32, device=dev)
     rs = torch.empty((Bt,), dtype=torch.float64, device=dev)
     nws = lib.itcv_mmd_kl_workspace(Bt, P)
@@ -1588,21 +1591,14 @@ class AdaGroupFn(Function):
     ``eps`` [2B, D]: fp32 views with unit column stride are read in place (the halves of one packed [2B, 2D] tensor too).
     ``own_in``: None (the adaptive threshold) or a [B, D] mask (non-zero: the dimension keeps its own posterior).  Outputs:
     z [2B, D] and the scalar beta * mean KL, both differentiable in ``mu`` and ``logvar``; the mask as used [B, D] uint8
-    and (mean KL, mean shared dimensions per pair) [2], no gradient.  The mask is a constant of the backward pass."""
+    and (mean KL, mean shared dimensions per pair) [2], no gradient.  The mask is a constant of the backward pass.
+    The arguments are those ``ops.ada_group`` has validated (shapes, the even row count, the range of D, the mask's shape):
+    nothing of that is checked again here, only the layout is handled and the mask normalised."""
 
     @staticmethod
     def forward(ctx, mu, logvar, eps, own_in, averaging, beta):
-        if mu.dim() != 2 or mu.shape != logvar.shape or mu.shape != eps.shape:
-            raise ValueError(f"mu, logvar and eps must share one [2B, D] shape (got {tuple(mu.shape)}, "
-                             f"{tuple(logvar.shape)}, {tuple(eps.shape)})")
-        R, D = mu.shape
-        if R < 2 or R % 2:
-            raise ValueError(f"the rows are pairs (b, B + b): an even, positive number of them (got {R})")
-        if not 1 <= D <= ADA_MAX_D:
-            raise ValueError(f"the pair op takes 1 <= D <= {ADA_MAX_D} (got {D})")
-        B, dev = R // 2, mu.device
-        if own_in is not None and tuple(own_in.shape) != (B, D):
-            raise ValueError(f"own must be a [B, D] = {(B, D)} mask (got {tuple(own_in.shape)})")
+        (R, D), dev = mu.shape, mu.device
+        B = R // 2
         (mu, ldm), (logvar, ldl), (eps, lde) = _rows_f32(mu, "mu"), _rows_f32(logvar, "logvar"), _rows_f32(eps, "eps")
         if own_in is not None:
             abi.need_device(own_in)
@@ -1610,8 +1606,7 @@ class AdaGroupFn(Function):
         z = torch.empty((R, D), dtype=F32, device=dev)
         own = torch.empty((B, D), dtype=torch.uint8, device=dev)
         part = torch.empty((3 * B,), dtype=torch.float64, device=dev)
-        out = torch.empty((), dtype=F32, device=dev)
-        terms = torch.empty((2,), dtype=F32, device=dev)
+        out, terms = _loss_terms(2, dev)
         call("itcv_ada_group_fwd", mu.data_ptr(), ldm, logvar.data_ptr(), ldl, eps.data_ptr(), lde, ptr(own_in), ptr(z),
              ptr(own), ptr(part), ptr(out), ptr(terms), B, D, int(averaging), float(beta), stream())
         ctx.save_for_backward(mu, logvar, eps, own)
@@ -1648,25 +1643,13 @@ class JointLatentFn(Function):
     [n_disc, 2] int32: the group of every discrete column; ``capacity`` [2] fp64 on the device, read when the kernel runs.
     Outputs: z [B, D] and the scalar beta (gamma_cont |KL_z - C_z| + gamma_disc |KL_c - C_c|), both differentiable in
     ``mu`` and ``logvar``, and (KL_z, KL_c, C_z, C_c) [4], no gradient.  The signs of the two differences are kept for the
-    backward pass, so it does not read ``capacity`` again."""
+    backward pass, so it does not read ``capacity`` again.  The arguments are those ``ops.joint_latent`` has validated
+    (shapes, the latent spec against D, the device ``capacity``) with the table of ``ops.joint_segments``: nothing of that is
+    checked again here, only the layout is handled."""
 
     @staticmethod
     def forward(ctx, mu, logvar, eps, u, seg, capacity, n_cont, n_disc, tau, gamma_cont, gamma_disc, beta):
-        if mu.dim() != 2 or mu.shape != logvar.shape:
-            raise ValueError(f"mu and logvar must share one [B, D] shape (got {tuple(mu.shape)}, {tuple(logvar.shape)})")
         B, D = mu.shape
-        if n_cont < 0 or n_disc < 0 or n_cont + n_disc != D:
-            raise ValueError(f"n_cont + n_disc = {n_cont} + {n_disc} is not D = {D}")
-        if B < 1 or not 1 <= D <= JOINT_MAX_D:
-            raise ValueError(f"the joint op takes B >= 1 and 1 <= D <= {JOINT_MAX_D} (got {(B, D)})")
-        if n_cont and (eps is None or tuple(eps.shape) != (B, n_cont)):
-            raise ValueError(f"eps must be [B, n_cont] = {(B, n_cont)}")
-        if n_disc and (u is None or tuple(u.shape) != (B, n_disc) or seg is None or tuple(seg.shape) != (n_disc, 2)
-                       or seg.dtype != torch.int32):
-            raise ValueError(f"u must be [B, n_disc] = {(B, n_disc)} and seg an int32 [n_disc, 2] table")
-        if tuple(capacity.shape) != (2,) or capacity.dtype != torch.float64:
-            raise ValueError(f"capacity must be a [2] float64 tensor (got {tuple(capacity.shape)}, {capacity.dtype})")
-        abi.need_device(capacity, seg)
         (mu, ldm), (logvar, ldl) = _rows_f32(mu, "mu"), _rows_f32(logvar, "logvar")
         (eps, lde) = _rows_f32(eps, "eps") if n_cont else (None, 0)
         (u, ldu) = _rows_f32(u, "u") if n_disc else (None, 0)
@@ -1674,9 +1657,8 @@ class JointLatentFn(Function):
         dev = mu.device
         z = torch.empty((B, D), dtype=F32, device=dev)
         part = torch.empty((2 * B,), dtype=torch.float64, device=dev)
-        out = torch.empty((), dtype=F32, device=dev)
         sgn = torch.empty((2,), dtype=F32, device=dev)
-        terms = torch.empty((4,), dtype=F32, device=dev)
+        out, terms = _loss_terms(4, dev)
         call("itcv_joint_latent_fwd", mu.data_ptr(), ldm, logvar.data_ptr(), ldl, _row_ptr(eps), lde, _row_ptr(u), ldu,
              ptr(seg), ptr(capacity.contiguous()), ptr(z), ptr(part), ptr(out), ptr(sgn), ptr(terms), B, int(n_cont),
              int(n_disc), 0, float(tau), float(gamma_cont), float(gamma_disc), float(beta), stream())
@@ -1707,15 +1689,9 @@ class JointLatentFn(Function):
 
 def joint_latent_hard(mu, seg, n_cont, n_disc):
     """The deterministic code of ``JointLatentFn``'s model, one launch, no gradient: the continuous columns of ``mu`` bit
-    for bit, and per group the one-hot of the first maximum of the fp32 logits."""
-    if mu.dim() != 2 or n_cont < 0 or n_disc < 0 or n_cont + n_disc != mu.size(1):
-        raise ValueError(f"mu must be [B, n_cont + n_disc] (got {tuple(mu.shape)} for {n_cont} + {n_disc})")
+    for bit, and per group the one-hot of the first maximum of the fp32 logits.  ``mu``, the spec and ``seg`` are those
+    ``ops.joint_latent`` has validated; nothing of that is checked again here."""
     B, D = mu.shape
-    if B < 1 or not 1 <= D <= JOINT_MAX_D:
-        raise ValueError(f"the joint op takes B >= 1 and 1 <= D <= {JOINT_MAX_D} (got {(B, D)})")
-    if n_disc and (seg is None or tuple(seg.shape) != (n_disc, 2) or seg.dtype != torch.int32):
-        raise ValueError("seg must be an int32 [n_disc, 2] table")
-    abi.need_device(seg)
     mu, ldm = _rows_f32(mu.detach(), "mu")
     z = torch.empty((B, D), dtype=F32, device=mu.device)
     call("itcv_joint_latent_fwd", mu.data_ptr(), ldm, None, 0, None, 0, None, 0, ptr(seg.contiguous() if n_disc else None),
@@ -1756,8 +1732,7 @@ class SupRegFn(Function):
         on_device = isinstance(gamma, torch.Tensor)
         if on_device:
             abi.need_device(gamma)
-        out = torch.empty((), dtype=F32, device=dev)
-        terms = torch.empty((2,), dtype=F32, device=dev)
+        out, terms = _loss_terms(2, dev)
         keep = torch.empty((1 + F,), dtype=torch.float64, device=dev)
         Wt = torch.empty((F, D), dtype=torch.float64, device=dev) if kind == SUP_KINDS["cov"] else None
         nws = lib.itcv_sup_workspace(B, D, F, int(kind))
@@ -1883,8 +1858,7 @@ class IwaeCombineFn(Function):
         if lat.dtype != torch.float64 or rows.numel() != K * B or lat.numel() != K * B:
             raise ValueError(f"rows (fp32) and lat (fp64) must hold K B = {K * B} values")
         dev = rows.device
-        out = torch.empty((), dtype=F32, device=dev)
-        terms = torch.empty((4,), dtype=F32, device=dev)
+        out, terms = _loss_terms(4, dev)
         img = torch.empty((4, B), dtype=torch.float64, device=dev)
         call("itcv_iwae_combine_fwd", ptr(rows), ptr(lat), float(beta_rec), float(beta_kl), ptr(sample.weights), ptr(img),
              ptr(out), ptr(terms), B, K, stream())
