@@ -1007,6 +1007,64 @@ size_t itcv_udr_lasso_workspace(int Da, int Db);
 int itcv_udr_lasso(const double* cov, int Da, int Db, double alpha, double gtol, int max_sweeps, double* W, int* info,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* ---- sample quality: neighbour radii, PRDC counts, polynomial MMD, Frechet distance (not in the reference) ------- */
+/* Scores of generated samples against real ones over feature rows x[N][D] (fp32, row stride ld elements, read in place;
+ * nothing left of a strided view is read): Kynkaanniemi et al. 2019 and Naeem et al. 2020 (the `prdc` package), Binkowski
+ * et al. 2018 (KID), Heusel et al. 2017 (the Frechet distance).  Fixed rules; all arithmetic is fp64, every operation
+ * rounded on its own (no fused multiply-add outside the matrix cores), every floating-point sum in a fixed order that
+ * depends on the shapes alone, counts and minima through integer atomics (order-free), no floating-point atomic: same
+ * inputs, same bits.  flags[0] is set by a non-finite element, as for itcv_unsup_cov; the outputs are then unspecified.
+ *
+ * Distance.  d2(a, b) = sum_d (a_d - b_d)^2: the difference of the widened values, its square, added in ascending d (the
+ *   difference form of csrc/mmd.hip; never |a|^2 + |b|^2 - 2 a.b).  Integer-valued features give exact integers.
+ * Radii.  r2[i] = the (k + 1)-th smallest of {d2(x_i, x_j) : j = 0 .. N - 1}, row i's own 0 included: prdc's
+ *   get_kth_value(dist, k + 1), squared.  A block owns 32 rows and streams the candidates through LDS, 64 rows by 32
+ *   columns a step, keeping the k + 1 smallest values of every row; nothing of size N x N is written.  A selection does not
+ *   depend on the visiting order, so the candidates are cut into `splits` slices (grid = row tiles x slices) whose lists a
+ *   second kernel merges: r2 is the same for every `splits`, bit for bit.  splits = 0 lets the library choose: slices until
+ *   the grid has 1024 blocks, ceil(1024 / ceil(N / 32)); any value is lowered to min(ceil(N / 64), 256), and slices that
+ *   would be empty are not made.  With s the slice count used, itcv_knn_radius_workspace = s * N * (k + 1) * sizeof(double).
+ *   Supported: 2 <= N <= 2^20, 1 <= D <= 2048, 1 <= k <= 16, k < N, splits >= 0.
+ * Counts.  real[N][D], fake[M][D], r2_real[N], r2_fake[M] (radii of each set among itself):
+ *     fake_hits[j]    = #{i : d2(real_i, fake_j) < r2_real[i]}          (int32)
+ *     real_covered[i] = 1 if some j has d2(real_i, fake_j) < r2_fake[j], else 0      (int32)
+ *     real_min[i]     = min_j d2(real_i, fake_j)                         (fp64)
+ *   every comparison strict, as in prdc.  The scores are rationals of these integers: precision = #{j : fake_hits[j] > 0}
+ *   / M, recall = sum real_covered / N, density = sum fake_hits / (k M), coverage = #{i : real_min[i] < r2_real[i]} / N.
+ *   The same streamed pass, the fakes as the candidates, `splits` as above (of M, for N rows); the outputs are cleared by
+ *   the call and need no workspace.  Supported: 2 <= N, M <= 2^20, 1 <= D <= 2048.
+ * Polynomial MMD.  kappa(a, b) = (gamma a.b + coef0)^degree, gamma = 1 / D when passed as 0, degree 1..4 by repeated
+ *   multiplication (t, t t, (t t) t, (t t)(t t)).  a.b runs on v_mfma_f64_16x16x4_f64 from the widened values (D padded to
+ *   a multiple of 4 with zeros, ascending).  res[4] = {Sxx, Syy, Sxy, mmd2}: Sxx = sum_{i != j} kappa(x_i, x_j), Syy
+ *   likewise, Sxy = sum_{i, j} kappa(x_i, y_j), mmd2 = (Sxx / (N (N - 1)) + Syy / (M (M - 1))) - 2 Sxy / (N M), the unbiased
+ *   estimate.  The kernel matrix is cut into 64 x 64 tiles, t = (row tile) * (column tiles) + (column tile); G = min(tiles,
+ *   1024) blocks take the tiles b, b + G, ... and add their sums in that order; the G partials are added in ascending b.
+ *   itcv_poly_mmd_workspace = 3 * 1024 * sizeof(double).  Supported: 2 <= N, M <= 2^20, 1 <= D <= 2048, gamma >= 0.
+ * Frechet distance.  m1, m2 [D] and c1, c2 [D][D] fp64 as itcv_unsup_cov writes them, eps >= 0; with A = c1 + eps I and
+ *   B = c2 + eps I:  L = the Cholesky factor of A (the rules of itcv_unsup_gauss; a failed pivot sets info[0] and info[1],
+ *   the results are then nan);  T = B L, T[i][j] = sum_{k = j}^{D-1} B[i][k] L[k][j];  M[i][j] = sum_{k = i}^{D-1} L[k][i]
+ *   T[k][j] for i <= j, mirrored (both sums ascending);  lambda = the eigenvalues of M by the cyclic Jacobi rules of
+ *   itcv_unsup_gauss, on M itself (stop at off(M)_F <= 1e-14 |M|_F, 60 sweeps at most).  M is similar to A B, so
+ *   tr sqrt(A B) = sum_i sqrt(max(lambda_i, 0)) in index order.  Only A has to be positive definite.
+ *   res[5] = {fd, |m1 - m2|^2, tr A, tr B, tr sqrt}, fd = ((|m1 - m2|^2 + tr A) + tr B) - 2 tr sqrt (the traces include
+ *   eps, so equal inputs give 0 up to rounding); eig[D] = lambda in index order; info[5] = {pivot failed, its dimension
+ *   (-1), Jacobi did not converge, sweeps taken, number of lambda < 0 clipped}.  One block; the matrix sits in LDS up to
+ *   D = itcv_unsup_gauss_lds_dim(), above that in the workspace (itcv_frechet_workspace).  Supported: 1 <= D <= 512.
+ * Anything unsupported, a null operand or a short workspace returns non-zero before a launch; the workspace queries
+ * return 0 for it. */
+size_t itcv_knn_radius_workspace(int N, int D, int k, int splits);
+int itcv_knn_radius(const float* x, size_t ld, int N, int D, int k, int splits, double* r2, int* flags, void* ws,
+                    size_t ws_bytes, void* stream);
+int itcv_prdc_counts(const float* real, size_t ldr, const float* fake, size_t ldf, int N, int M, int D,
+                     const double* r2_real, const double* r2_fake, int splits, int* fake_hits, int* real_covered,
+                     double* real_min, int* flags, void* stream);
+size_t itcv_poly_mmd_workspace(int N, int M, int D);
+int itcv_poly_mmd(const float* x, size_t ldx, const float* y, size_t ldy, int N, int M, int D, int degree, double gamma,
+                  double coef0, double* res, int* flags, void* ws, size_t ws_bytes, void* stream);
+size_t itcv_frechet_workspace(int D);
+int itcv_frechet(const double* m1, const double* c1, const double* m2, const double* c2, int D, double eps, double* res,
+                 double* eig, int* info, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- reconstruction loss (ops.py:188-236) --------------------------------------------- */
 #define ITCV_LOSS_MSE 0
 #define ITCV_LOSS_L1 1

@@ -1,5 +1,5 @@
-// What the objective kernels share: dip.hip, mmd.hip, ada.hip, joint.hip, sup.hip and iwae.hip include this header, and
-// nothing else does.  Device side: the ordered block sum of their finish kernels, the mean KL of the local rows (dip, mmd)
+// What the objective kernels share: dip.hip, mmd.hip, ada.hip, joint.hip, sup.hip and iwae.hip include this header;
+// quality.hip includes it for the host-side refusals alone.  Device side: the ordered block sum of their finish kernels, the mean KL of the local rows (dip, mmd)
 // and the fp64 reparameterised sample, its KL term and their gradient (ada, joint).  Host side: the capped row grid, the
 // finite test and the refusals that every entry point words alike.
 //

@@ -2751,3 +2751,73 @@ def udr_lasso(cov, Da, Db, alpha=0.1, gtol=1e-12, max_sweeps=1000):
     call("itcv_udr_lasso", ptr(cov), Da, Db, float(alpha), float(gtol), int(max_sweeps), ptr(W), ptr(info), ptr(ws), nws,
          stream())
     return W, info
+
+
+# ------------------------------------------------------------------ sample quality (csrc/quality.hip)
+def knn_radius(x, k, flags, splits=0):
+    """fp64 ``r2 [N]``: the (k + 1)-th smallest squared distance from every row of x[N, D] to the rows of x, itself
+    included (itcv_knn_radius).  ``splits``: slices of the candidate rows (0: the library's choice); the result does not
+    depend on it.  Sets flags[0] on a non-finite element."""
+    x = _disent_mu(x)
+    N, D = x.shape
+    r2 = torch.empty((N,), dtype=F64, device=x.device)
+    nws = lib.itcv_knn_radius_workspace(N, D, int(k), int(splits))      # 0 for what the call below refuses
+    ws = _ws(nws, x.device)
+    call("itcv_knn_radius", x.data_ptr(), x.stride(0), N, D, int(k), int(splits), ptr(r2), ptr(flags), ptr(ws), nws,
+         stream())
+    return r2
+
+
+def prdc_counts(real, fake, r2_real, r2_fake, flags, splits=0):
+    """``(fake_hits [M] int32, real_covered [N] int32, real_min [N] fp64)`` of real[N, D] against fake[M, D] under the
+    squared radii ``r2_real [N]``, ``r2_fake [M]`` (itcv_prdc_counts; every comparison strict)."""
+    real, fake = _disent_mu(real), _disent_mu(fake)
+    (N, D), M = real.shape, fake.shape[0]
+    r2_real, r2_fake = _gbt_dense(r2_real, F64, "r2_real"), _gbt_dense(r2_fake, F64, "r2_fake")
+    if fake.shape[1] != D or tuple(r2_real.shape) != (N,) or tuple(r2_fake.shape) != (M,):
+        raise abi.HipExtensionError(f"prdc: real [N, D], fake [M, D], r2_real [N] and r2_fake [M] are expected (got "
+                                    f"{tuple(real.shape)}, {tuple(fake.shape)}, {tuple(r2_real.shape)}, "
+                                    f"{tuple(r2_fake.shape)})")
+    dev = real.device
+    hits = torch.empty((M,), dtype=torch.int32, device=dev)
+    covered = torch.empty((N,), dtype=torch.int32, device=dev)
+    rmin = torch.empty((N,), dtype=F64, device=dev)
+    call("itcv_prdc_counts", real.data_ptr(), real.stride(0), fake.data_ptr(), fake.stride(0), N, M, D, ptr(r2_real),
+         ptr(r2_fake), int(splits), ptr(hits), ptr(covered), ptr(rmin), ptr(flags), stream())
+    return hits, covered, rmin
+
+
+def poly_mmd(x, y, flags, degree=3, gamma=0.0, coef0=1.0):
+    """fp64 ``res [4] = (Sxx, Syy, Sxy, mmd2)`` of the polynomial kernel (gamma a.b + coef0)^degree on x[N, D], y[M, D]
+    (itcv_poly_mmd; gamma 0: 1 / D).  Nothing is read back."""
+    x, y = _disent_mu(x), _disent_mu(y)
+    (N, D), M = x.shape, y.shape[0]
+    if y.shape[1] != D:
+        raise abi.HipExtensionError(f"poly_mmd: x [N, D] and y [M, D] are expected (got {tuple(x.shape)}, {tuple(y.shape)})")
+    res = torch.empty((4,), dtype=F64, device=x.device)
+    nws = lib.itcv_poly_mmd_workspace(N, M, D)                          # 0 for what the call below refuses
+    ws = _ws(nws, x.device)
+    call("itcv_poly_mmd", x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), N, M, D, int(degree), float(gamma),
+         float(coef0), ptr(res), ptr(flags), ptr(ws), nws, stream())
+    return res
+
+
+def frechet(mean1, cov1, mean2, cov2, eps=0.0):
+    """``(res [5] fp64 = fd, |m1 - m2|^2, tr(C1 + eps I), tr(C2 + eps I), tr sqrt; eig [D] fp64; info [5] int32 = pivot of
+    C1 + eps I failed, its dimension, Jacobi did not converge, sweeps, eigenvalues clipped at 0)`` of two fp64 means [D]
+    and symmetric covariances [D, D] (itcv_frechet): one launch, nothing is read back."""
+    mean1, mean2 = _gbt_dense(mean1, F64, "mean1"), _gbt_dense(mean2, F64, "mean2")
+    cov1, cov2 = _gbt_dense(cov1, F64, "cov1"), _gbt_dense(cov2, F64, "cov2")
+    D = mean1.numel()
+    if cov1.dim() != 2 or D < 1 or tuple(cov1.shape) != (D, D) or tuple(cov2.shape) != (D, D) or mean2.numel() != D:
+        raise abi.HipExtensionError(f"frechet: means [D] and covariances [D, D] are expected (got {tuple(mean1.shape)}, "
+                                    f"{tuple(cov1.shape)}, {tuple(mean2.shape)}, {tuple(cov2.shape)})")
+    dev = cov1.device
+    res = torch.empty((5,), dtype=F64, device=dev)
+    eig = torch.empty((D,), dtype=F64, device=dev)
+    info = torch.empty((5,), dtype=torch.int32, device=dev)
+    nws = lib.itcv_frechet_workspace(D)                                 # 0 for what the call below refuses
+    ws = _ws(nws, dev)
+    call("itcv_frechet", ptr(mean1), ptr(cov1), ptr(mean2), ptr(cov2), D, float(eps), ptr(res), ptr(eig), ptr(info),
+         ptr(ws), nws, stream())
+    return res, eig, info

@@ -1,0 +1,219 @@
+"""Sample quality on the device: how good, and how varied, are the images a model generates?  Four families of scores of
+generated ("fake") against real feature rows, all from the kernels of csrc/quality.hip (rules: include/itcv_hip.h):
+
+* ``frechet_distance``: the Frechet distance of the two Gaussians fitted to the features (Heusel et al. 2017);
+* ``kernel_distance``: the unbiased MMD^2 under the cubic polynomial kernel (KID, Binkowski et al. 2018);
+* ``prdc``: precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020), the `prdc`
+  package's definitions over k-th-neighbour radii.
+
+The features are pluggable.  The default is the model's own encoder mean, so the records are ``frechet`` and ``kid`` over
+THAT feature map: they rank models that share an encoder architecture and are NOT comparable with a published FID, which
+is defined over Inception features.  A callable ``feature(images) -> [B, D]`` replaces the encoder."""
+import numpy as np
+import torch
+
+from . import functional as HF
+from .aggregate import _device_of, _images
+
+FRECHET_MAX_DIM = 512
+SCORES = ("frechet", "kid", "prdc")
+
+
+def _raise_on(flag):
+    if flag:
+        raise ValueError("quality: the features contain non-finite values")
+
+
+def knn_radius(x, k, splits=0):
+    """fp64 ``[N]`` on the device: the squared distance from every row of ``x [N, D]`` to its k-th nearest neighbour among
+    the other rows (the (k + 1)-th smallest of the row's distances, its own 0 included: ``prdc``'s
+    ``get_kth_value(dist, k + 1)``, squared).  One read-back (the non-finite flag)."""
+    flags = HF.disent_flags(x.device)
+    r2 = HF.knn_radius(x, k, flags, splits)
+    _raise_on(flags.tolist()[0])
+    return r2
+
+
+def prdc_counts(real, fake, nearest_k=5, splits=0):
+    """The integers the four scores are made of, as device tensors: ``dict(r2_real [N], r2_fake [M], fake_hits [M],
+    real_covered [N], real_min [N])`` and the ``counts`` [5] int64 = (fakes with a hit, reals covered, hits, reals whose
+    nearest fake is inside their radius, the non-finite flag).  Nothing is read back."""
+    flags = HF.disent_flags(real.device)
+    r2r, r2f = HF.knn_radius(real, nearest_k, flags, splits), HF.knn_radius(fake, nearest_k, flags, splits)
+    hits, covered, rmin = HF.prdc_counts(real, fake, r2r, r2f, flags, splits)
+    i64 = torch.int64
+    counts = torch.stack([(hits > 0).sum(), covered.sum(dtype=i64), hits.sum(dtype=i64), (rmin < r2r).sum(),
+                          flags[0].to(i64)])
+    return dict(r2_real=r2r, r2_fake=r2f, fake_hits=hits, real_covered=covered, real_min=rmin, counts=counts)
+
+
+def prdc(real, fake, nearest_k=5):
+    """``dict(precision, recall, density, coverage)`` of ``fake [M, D]`` against ``real [N, D]``: exact fractions of
+    integer counts (every comparison strict, as in ``prdc``).  One read-back."""
+    nearest_k = int(nearest_k)
+    c = prdc_counts(real, fake, nearest_k)["counts"].tolist()           # the one read-back
+    _raise_on(c[4])
+    N, M = real.shape[0], fake.shape[0]
+    return dict(precision=c[0] / M, recall=c[1] / N, density=c[2] / (nearest_k * M), coverage=c[3] / N)
+
+
+_FRECHET_KEYS = ("frechet", "mean_term", "trace_real", "trace_fake", "trace_sqrt")
+
+
+def _frechet_once(m1, c1, m2, c2, eps):
+    res, eig, info = HF.frechet(m1, c1, m2, c2, eps)
+    return torch.cat([res, info.to(torch.float64)]).tolist(), eig
+
+
+def frechet_distance(real, fake, eps=0.0):
+    """``dict(frechet, mean_term, trace_real, trace_fake, trace_sqrt, eigenvalues)`` of the Gaussians fitted to ``real
+    [N, D]`` and ``fake [M, D]``: |m1 - m2|^2 + tr C1 + tr C2 - 2 tr sqrt(C1 C2), with C + eps I for both covariances.
+    The Cholesky factor of the first covariance is needed; when its pivot fails the roles are exchanged (the trace is
+    symmetric, and a singular second covariance is fine).  Both failing raises ``ValueError``."""
+    D = real.shape[1] if real.dim() == 2 else 0
+    if D > FRECHET_MAX_DIM:
+        raise ValueError(f"frechet_distance: D = {D} features are above the limit of {FRECHET_MAX_DIM}")
+    if not eps >= 0.0:
+        raise ValueError(f"frechet_distance: eps must be >= 0 (got {eps!r})")
+    flags = HF.disent_flags(real.device)
+    (m1, c1), (m2, c2) = HF.unsup_cov(real, flags), HF.unsup_cov(fake, flags)
+    out, eig = _frechet_once(m1, c1, m2, c2, eps)
+    _raise_on(flags.tolist()[0])
+    swapped = False
+    if out[5]:
+        first = int(out[6])
+        out, eig = _frechet_once(m2, c2, m1, c1, eps)
+        swapped = True
+        if out[5]:
+            raise ValueError(f"frechet_distance: neither covariance is positive definite (the Cholesky pivot of dimension "
+                             f"{first} of the real features and of dimension {int(out[6])} of the fake ones is not "
+                             "positive: constant or linearly dependent columns); eps > 0 regularises both")
+    if out[7]:
+        raise RuntimeError("frechet_distance: the Jacobi iteration did not converge in 60 sweeps")
+    if swapped:
+        out[2], out[3] = out[3], out[2]
+    got = dict(zip(_FRECHET_KEYS, out[:5]))
+    got["eigenvalues"] = eig
+    return got
+
+
+def kernel_distance(real, fake, degree=3, gamma=None, coef0=1.0, subset_size=None, num_subsets=100, seed=0):
+    """``dict(kid, kid_std)``: the unbiased MMD^2 of ``real [N, D]`` and ``fake [M, D]`` under (gamma a.b + coef0)^degree
+    (gamma None: 1 / D).  ``subset_size`` None: the estimator over the full samples, ``kid_std`` 0.0.  Otherwise the mean and
+    the (ddof = 0) standard deviation over ``num_subsets`` pairs of subsets of that size, drawn without replacement by a
+    private ``np.random.RandomState(seed)`` (reals first, then fakes, per subset) and gathered by ``index_select``."""
+    g = 0.0 if gamma is None else float(gamma)
+    flags = HF.disent_flags(real.device)
+    if subset_size is None:
+        res = [HF.poly_mmd(real, fake, flags, degree, g, coef0)[3]]
+    else:
+        m = int(subset_size)
+        if not 2 <= m <= min(real.shape[0], fake.shape[0]) or int(num_subsets) < 1:
+            raise ValueError(f"kernel_distance: subset_size must lie in 2..min(N, M) and num_subsets be positive (got "
+                             f"{subset_size!r}, {num_subsets!r})")
+        rs = np.random.RandomState(seed)
+        res = []
+        for _ in range(int(num_subsets)):
+            ir = torch.from_numpy(rs.choice(real.shape[0], m, replace=False).astype(np.int64)).to(real.device)
+            jf = torch.from_numpy(rs.choice(fake.shape[0], m, replace=False).astype(np.int64)).to(real.device)
+            res.append(HF.poly_mmd(real.index_select(0, ir), fake.index_select(0, jf), flags, degree, g, coef0)[3])
+    vals = torch.stack(res)
+    out = torch.cat([vals.mean().reshape(1), vals.std(unbiased=False).reshape(1) if len(res) > 1 else vals.new_zeros(1),
+                     flags[:1].to(torch.float64)]).tolist()
+    _raise_on(out[2])
+    return dict(kid=out[0], kid_std=out[1])
+
+
+# ---- features ------------------------------------------------------------------------------------------------------------
+def _feature_fn(model, feature):
+    if callable(feature):
+        return feature
+    if feature != "encoder":
+        raise ValueError(f'feature must be "encoder" or a callable images -> [B, D] (got {feature!r})')
+    return lambda images: model.encode(images)[0]
+
+
+def _collect(model, batches, feature):
+    """The rows ``feature(images)`` of every batch in one fp32 [N, D] device tensor; eval mode, no gradients, the training
+    flag put back."""
+    fn = _feature_fn(model, feature)
+    rows = []
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for images in batches():
+                f = fn(images)
+                if not isinstance(f, torch.Tensor) or f.dim() != 2 or not f.is_floating_point():
+                    raise ValueError("feature(images) must return a floating-point [B, D] tensor")
+                rows.append(f.detach().to(torch.float32))
+    finally:
+        model.train(was_training)
+    return torch.cat(rows, 0).contiguous()
+
+
+def real_features(source, model, indices, batch_size=64, feature="encoder"):
+    """fp32 ``[N, D]`` on the device: the features of the images of ``source`` (a ``DeviceImageTable`` or a dataset) at
+    ``indices``, batch by batch.  The model runs in eval mode under ``no_grad``; its training flag is put back and its
+    BatchNorm buffers are not written."""
+    indices = np.asarray(indices, dtype=np.int64)
+    if indices.ndim != 1 or not len(indices):
+        raise ValueError("real_features: indices must be a non-empty 1-D integer array")
+    device, bs = _device_of(model), int(batch_size)
+    if bs < 1:
+        raise ValueError(f"batch_size must be positive (got {batch_size})")
+    return _collect(model, lambda: (_images(source, indices[a:a + bs], device) for a in range(0, len(indices), bs)), feature)
+
+
+def generated_features(model, num, batch_size=64, seed=0, feature="encoder"):
+    """fp32 ``[num, D]`` on the device: the features of ``model.decode(z)``, z ~ N(0, I) from a private CPU
+    ``torch.Generator`` seeded by ``seed``, one draw per batch in a fixed order: torch's global generators are untouched
+    and two calls with one seed give the same bits.  Same contract for the model as ``real_features``."""
+    num, bs = int(num), int(batch_size)
+    if num < 1 or bs < 1:
+        raise ValueError(f"num and batch_size must be positive (got {num}, {batch_size})")
+    device = _device_of(model)
+    zdim = model.zdim
+    gen = torch.Generator().manual_seed(int(seed))
+
+    def batches():
+        for a in range(0, num, bs):
+            z = torch.randn((min(bs, num - a), zdim), generator=gen).to(device)
+            yield model.decode(z)
+
+    return _collect(model, batches, feature)
+
+
+def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature="encoder", nearest_k=5, batch_size=64,
+                           seed=0, scores=SCORES, eps=0.0, indices=None, kid_subset_size=None):
+    """The sample-quality scores of ``model`` on ``source`` (a ``DeviceImageTable`` or a dataset; no factors are needed): a
+    flat dict with ``frechet`` ("frechet" in ``scores``), ``kid`` and ``kid_std`` ("kid") and ``precision``, ``recall``,
+    ``density``, ``coverage`` ("prdc"), plus ``features = dict(real, fake)`` (fp32 device tensors) and the ``indices`` used.
+
+    Real images: ``indices``, or ``np.sort(RandomState(seed).choice(len(source), num_real, replace=False))``, or all of them
+    when ``num_real >= len(source)``.  Fakes: ``num_fake`` (None: as many as real images) decoded prior samples,
+    ``generated_features(model, num_fake, batch_size, seed, feature)``.  The default feature is the model's own encoder
+    mean, so the numbers compare models of one architecture and are not a published FID / KID.  The Frechet distance
+    needs D <= 512; ``eps`` regularises its covariances."""
+    unknown = [s for s in scores if s not in SCORES]
+    if unknown:
+        raise ValueError(f"compute_sample_quality: unknown score(s) {unknown} (known: {', '.join(map(repr, SCORES))})")
+    if indices is None:
+        n = len(source)
+        if int(num_real) >= n:
+            indices = np.arange(n, dtype=np.int64)
+        else:
+            indices = np.sort(np.random.RandomState(seed).choice(n, int(num_real), replace=False)).astype(np.int64)
+    indices = np.asarray(indices, dtype=np.int64)
+    real = real_features(source, model, indices, batch_size, feature)
+    fake = generated_features(model, len(indices) if num_fake is None else num_fake, batch_size, seed, feature)
+    out = {}
+    if "frechet" in scores:
+        out["frechet"] = frechet_distance(real, fake, eps)["frechet"]
+    if "kid" in scores:
+        out.update(kernel_distance(real, fake, subset_size=kid_subset_size, seed=seed))
+    if "prdc" in scores:
+        out.update(prdc(real, fake, nearest_k))
+    out["features"] = dict(real=real, fake=fake)
+    out["indices"] = indices
+    return out

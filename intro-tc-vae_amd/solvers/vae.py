@@ -66,6 +66,7 @@ class VAESolver:
         self.irs_params = None
         self.unsupervised_params = None
         self.likelihood_params = None     # keyword arguments of hipvae.likelihood.compute_log_likelihood
+        self.quality_params = None        # keyword arguments of hipvae.quality.compute_sample_quality
         # "udr" ranks this model against ``udr_peers``: models trained from other seeds on the same data (a sequence of
         # networks; required by that score); ``udr_params``: ``params`` of hipvae.disentangle.compute_udr_score
         self.udr_peers = None
@@ -390,24 +391,30 @@ class VAESolver:
         Unsupervised Disentanglement Ranking of this model among ``[self.model, *self.udr_peers]`` (``udr_params``).
         "log_likelihood" needs no factors and is read like the decomposition: the record ``log_likelihood`` {log_px,
         bits_per_dim, elbo, ess}, the importance-weighted estimate of log p(x) (hipvae.likelihood; ``likelihood_params``;
-        the reconstruction loss and ``beta_rec`` are this solver's unless given there)."""
+        the reconstruction loss and ``beta_rec`` are this solver's unless given there).
+        "sample_quality" needs no factors either: the record ``sample_quality`` {frechet, kid, precision, recall, density,
+        coverage} of decoded prior samples against the dataset's images (hipvae.quality; ``quality_params``).  The features
+        are the model's own encoder means unless ``quality_params`` names a callable, so ``frechet`` and ``kid`` compare
+        models of one architecture and are not a published FID / KID."""
         extras = tuple(self.extra_scores or ())
         with_elbo = "elbo_decomposition" in extras
         with_unsup = "unsupervised" in extras
         with_udr = "udr" in extras
         with_ll = "log_likelihood" in extras
+        with_quality = "sample_quality" in extras
         factored = isinstance(self.dataset, DisentanglementDataset)
-        if self.writer is None or not (factored or with_elbo or with_unsup or with_udr or with_ll) \
+        if self.writer is None or not (factored or with_elbo or with_unsup or with_udr or with_ll or with_quality) \
                 or cur_iter % self.test_iter:
             return
-        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr", "log_likelihood")
+        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr", "log_likelihood",
+                 "sample_quality")
         unknown = [e for e in extras if e not in known]
         if unknown:
             raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, known))})")
         if factored:
             self._write_factor_scores(cur_iter, num_samples,
                                       tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised", "udr",
-                                                                           "log_likelihood")))
+                                                                           "log_likelihood", "sample_quality")))
         if with_elbo:
             from hipvae import aggregate
             kw = dict(batch_size=self.batch_size)
@@ -445,6 +452,14 @@ class VAESolver:
                                                     self.model, **kw)
             self.writer.add_scalars("log_likelihood", {k: got[k] for k in ("log_px", "bits_per_dim", "elbo", "ess")},
                                     global_step=cur_iter)
+        if with_quality:
+            from hipvae import quality
+            kw = dict(batch_size=self.batch_size)
+            kw.update(self.quality_params or {})
+            got = quality.compute_sample_quality(self.dataset if self._device_table is None else self._device_table,
+                                                 self.model, **kw)
+            self.writer.add_scalars("sample_quality", {k: got[k] for k in (
+                "frechet", "kid", "precision", "recall", "density", "coverage")}, global_step=cur_iter)
 
     def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: tuple):
         """The factor-based scores of ``write_disentanglemnt_scores`` (a ``DisentanglementDataset``, at a test iteration)."""
