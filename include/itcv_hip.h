@@ -1084,6 +1084,40 @@ int itcv_recon_loss_fwd(const float* x, const float* recon, float* out, int B, s
                         float scale, void* ws, size_t ws_bytes, void* stream);
 int itcv_recon_loss_bwd(const float* x, const float* recon, const float* g, float* drecon, int B, size_t P,
                         int loss_type, int reduction, float scale, void* stream);
+/* ---- structural similarity: a reconstruction loss and the PSNR / SSIM / MS-SSIM scores (not in the reference) ---- */
+/* SSIM (Wang et al. 2004) of y (reconstruction) against x (target, a constant), both dense fp32 [B][C][H][W].  `window`
+ * is K doubles in device memory, the 1-D taps g (made on the host in fp64, sum 1); the 2-D window is g (x) g, applied per
+ * channel with valid filtering: H' x W' = (H - K + 1) x (W - K + 1) positions.  C1 = 0.01^2, C2 = 0.03^2 (L = 1).  With
+ * w* the windowed sum, at every position
+ *     mx = w*x, my = w*y, ex2 = w*x^2, ey2 = w*y^2, exy = w*xy;   sx = ex2 - mx^2, sy = ey2 - my^2, sxy = exy - mx my;
+ *     A1 = 2 mx my + C1, A2 = 2 sxy + C2, B1 = (mx^2 + my^2) + C1, B2 = (sx + sy) + C2;
+ *     S = (A1 A2) / (B1 B2),  cs = A2 / B2            (no clamp anywhere)
+ * and SSIM_b is the mean of S over the n = C H' W' positions of image b.  With P = C H W:
+ *     rows[b] = (P alpha) (1 - SSIM_b) + (1 - alpha) sum_p |y_bp - x_bp|,     0 <= alpha <= 1,
+ * the units of the other reconstruction losses (a sum over P elements).  reduction 0 (none): out[B] = scale * rows;
+ * 1 (sum) / 2 (mean): out[1] = scale * sum_b rows [/ B]; the arithmetic is fp64 up to ONE rounding to fp32 at the end.
+ * _bwd: for the gradient g of out ([B] for none, [1] else), gb = g scale [/ B],
+ *     dy = -gb (P alpha / n) [ Wt(dS/dmy) + 2 y Wt(dS/dey2) + x Wt(dS/dexy) ] + gb (1 - alpha) sign(y - x),
+ *     dS/dmy = 2 mx (A2 - A1) / (B1 B2) + 2 my S (1 / B2 - 1 / B1),  dS/dey2 = -S / B2,  dS/dexy = 2 A1 / (B1 B2),
+ * Wt the full correlation of a map on H' x W' back onto H x W (the adjoint of valid filtering), sign(0) = 0.
+ * _stats: stats[B][C][2] fp64 = the mean of S and the mean of cs over the H' W' positions of every plane.
+ * Everything is fp64 from the widened inputs (x^2 and xy are exact there), every operation rounded on its own, every sum
+ * in a fixed order that depends on the shapes alone (taps ascending, rows of the window outside columns), no atomic: same
+ * inputs, same bits, and a plane's numbers do not depend on B or on where the plane sits in the batch.  The forward and
+ * the statistics are two launches (16 x 16 tiles of positions with their halo in LDS, one fp64 partial per tile and sum;
+ * a finish) and write nothing of image size; the backward is one launch that recomputes the moments.
+ * itcv_ssim_workspace = 3 * B * C * ceil(H' / 16) * ceil(W' / 16) * sizeof(double).
+ * Supported: K odd, 3 <= K <= 15; K <= H, W <= 4096; B * C <= 2^20; B * C * ceil(H / 16) * ceil(W / 16) <= 2^30;
+ * 0 <= alpha <= 1.  Anything else, a null operand or a short workspace returns non-zero before a launch; the workspace
+ * query returns 0 for it. */
+size_t itcv_ssim_workspace(int B, int C, int H, int W, int K);
+int itcv_ssim_loss_fwd(const float* x, const float* y, const double* window, float* out, int B, int C, int H, int W, int K,
+                       double alpha, int reduction, float scale, void* ws, size_t ws_bytes, void* stream);
+int itcv_ssim_loss_bwd(const float* x, const float* y, const double* window, const float* g, float* dy, int B, int C, int H,
+                       int W, int K, double alpha, int reduction, float scale, void* stream);
+int itcv_ssim_stats(const float* x, const float* y, const double* window, double* stats, int B, int C, int H, int W, int K,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* solvers/intro.py:102-103: out[0] = mean_j exp(c * (a[j] + b[j])) (c = -2 * scale); w[B] is kept for _bwd, which
  * writes da[j] = db[j] = g[0] * d out / d a[j] (db may be NULL). */
 int itcv_exp_elbo_fwd(const float* a, const float* b, float* out, float* w, int B, float c, void* stream);

@@ -14,6 +14,7 @@ import os
 import weakref
 from typing import NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 from torch.autograd import Function
@@ -2046,6 +2047,81 @@ class ReconLossFn(Function):
         d = torch.empty_like(recon)
         call("itcv_recon_loss_bwd", ptr(x), ptr(recon), ptr(_f32c(g)), ptr(d), B, P, lt, reduction, scale, stream())
         return None, d, None, None, None
+
+
+def ssim_window_host(K, sigma):
+    """The K taps of the SSIM window as Python floats: exp(-(i - (K - 1) / 2)^2 / (2 sigma^2)), normalised to sum 1, in
+    fp64 on the host -- the device never evaluates exp for it."""
+    K, sigma = int(K), float(sigma)
+    if K < 1 or not sigma > 0.0:
+        raise ValueError(f"ssim window: K >= 1 taps and sigma > 0 are needed (got {K}, {sigma})")
+    i = np.arange(K, dtype=np.float64) - (K - 1) / 2.0
+    g = np.exp(-(i * i) / (2.0 * sigma * sigma))
+    return (g / g.sum()).tolist()
+
+
+_SSIM_WINDOWS = {}
+
+
+def ssim_window(K, sigma, device):
+    """fp64 ``[K]`` on the device: ``ssim_window_host``, cached per (K, sigma, device)."""
+    device = torch.device(device)
+    key = (int(K), float(sigma), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    w = _SSIM_WINDOWS.get(key)
+    if w is None:
+        w = _SSIM_WINDOWS[key] = torch.tensor(ssim_window_host(K, sigma), dtype=torch.float64).to(device)
+    return w
+
+
+def _ssim_images(x, y):
+    x, y = _f32c(x), _f32c(y)
+    if x.dim() != 4 or x.shape != y.shape:
+        raise abi.HipExtensionError(f"ssim: two [B, C, H, W] images of one shape are expected (got {tuple(x.shape)}, "
+                                    f"{tuple(y.shape)})")
+    abi.need_device(x, y)
+    return x, y
+
+
+class SsimLossFn(Function):
+    """scale * reduction_b [P alpha (1 - SSIM_b) + (1 - alpha) sum |y - x|] (itcv_ssim_loss_fwd): two launches forward,
+    one backward; x is a constant; nothing of image size is kept but the two operands themselves."""
+
+    @staticmethod
+    def forward(ctx, x, recon, reduction, scale, alpha, K, sigma):
+        x, recon = _ssim_images(x, recon)
+        B, C, H, W = recon.shape
+        win = ssim_window(K, sigma, recon.device)
+        out = torch.empty((B,) if reduction == 0 else (), dtype=F32, device=recon.device)
+        nws = lib.itcv_ssim_workspace(B, C, H, W, int(K))                # 0 for what the call below refuses
+        ws = _ws(nws, recon.device)
+        call("itcv_ssim_loss_fwd", ptr(x), ptr(recon), ptr(win), ptr(out), B, C, H, W, int(K), float(alpha), reduction,
+             float(scale), ptr(ws), nws, stream())
+        ctx.save_for_backward(x, recon, win)
+        ctx.cfg = (B, C, H, W, int(K), float(alpha), reduction, float(scale))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, recon, win = ctx.saved_tensors
+        B, C, H, W, K, alpha, reduction, scale = ctx.cfg
+        d = torch.empty_like(recon)
+        call("itcv_ssim_loss_bwd", ptr(x), ptr(recon), ptr(win), ptr(_f32c(g)), ptr(d), B, C, H, W, K, alpha, reduction,
+             scale, stream())
+        return None, d, None, None, None, None, None
+
+
+def ssim_stats(x, y, K=11, sigma=1.5):
+    """fp64 ``[B, C, 2]`` on the device: the mean of S (SSIM) and the mean of cs (its contrast-structure factor) over the
+    positions of every plane of y against x (itcv_ssim_stats): two launches, nothing is read back."""
+    x, y = _ssim_images(x.detach(), y.detach())
+    B, C, H, W = y.shape
+    win = ssim_window(K, sigma, y.device)
+    stats = torch.empty((B, C, 2), dtype=torch.float64, device=y.device)
+    nws = lib.itcv_ssim_workspace(B, C, H, W, int(K))                    # 0 for what the call below refuses
+    ws = _ws(nws, y.device)
+    call("itcv_ssim_stats", ptr(x), ptr(y), ptr(win), ptr(stats), B, C, H, W, int(K), ptr(ws), nws, stream())
+    return stats
 
 
 class ExpElboFn(Function):

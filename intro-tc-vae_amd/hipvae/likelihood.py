@@ -26,7 +26,9 @@ def compute_log_likelihood(source, model, num_samples=1000, chunk=None, batch_si
     ``ops.reconstruction_loss``.  ONLY ``loss_type="bce"`` with ``beta_rec=1`` is a normalised likelihood (Bernoulli
     pixels); "mse" / "l1" estimate log p(x) up to the additive constant of the fixed-scale Gaussian / Laplace observation
     model that the reconstruction loss stands for (mse with beta_rec: N(recon, 1 / (2 beta_rec)) per value), so their
-    ``bits_per_dim`` compares models trained alike and is not an absolute code length.
+    ``bits_per_dim`` compares models trained alike and is not an absolute code length.  The structural types "ssim" and
+    "ssim_l1" of ``ops.reconstruction_loss`` stand for no observation model of independent values and raise
+    NotImplementedError here, like every unknown name.
 
     ``indices``: which images (default: all, or the first ``num_images``).  The images go through in batches of
     ``batch_size``; per batch of B the K samples are decoded ``chunk`` per image at a time (default: as many as keep

@@ -8,9 +8,14 @@ generated ("fake") against real feature rows, all from the kernels of csrc/quali
 
 The features are pluggable.  The default is the model's own encoder mean, so the records are ``frechet`` and ``kid`` over
 THAT feature map: they rank models that share an encoder architecture and are NOT comparable with a published FID, which
-is defined over Inception features.  A callable ``feature(images) -> [B, D]`` replaces the encoder."""
+is defined over Inception features.  A callable ``feature(images) -> [B, D]`` replaces the encoder.
+
+Pixel space, for reconstructions rather than samples: ``reconstruction_quality`` gives PSNR, SSIM (Wang et al. 2004) and
+MS-SSIM (Wang et al. 2003) per image from the kernels of csrc/ssim.hip, ``compute_reconstruction_quality`` their means
+over a dataset."""
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import functional as HF
 from .aggregate import _device_of, _images
@@ -215,5 +220,97 @@ def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature
     if "prdc" in scores:
         out.update(prdc(real, fake, nearest_k))
     out["features"] = dict(real=real, fake=fake)
+    out["indices"] = indices
+    return out
+
+
+# ---- reconstructions: PSNR, SSIM, MS-SSIM --------------------------------------------------------------------------------
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)       # Wang et al. 2003, finest level first
+RECONSTRUCTION_SCORES = ("psnr", "ssim", "ms_ssim", "mse", "l1")
+
+
+def ms_ssim_levels(H, W, window=11):
+    """The largest L <= 5 such that the coarsest of L levels, ``min(H, W) >> (L - 1)``, still holds one window."""
+    if min(H, W) < window:
+        raise ValueError(f"reconstruction_quality: H, W = {H}, {W} are below window = {window}")
+    L = 1
+    while L < len(MS_SSIM_WEIGHTS) and (min(H, W) >> L) >= window:
+        L += 1
+    return L
+
+
+def reconstruction_quality(x, y, window=11, sigma=1.5, levels=None):
+    """Per-image scores of the reconstructions ``y`` of ``x`` (fp32 [B, C, H, W] on the device, values in [0, 1]): a dict of
+    fp64 device vectors [B], nothing is read back.
+
+    ``mse`` and ``l1`` are the means over the image of (y - x)^2 and |y - x|; ``psnr`` = 10 log10(1 / mse), inf for an exact
+    reconstruction; ``ssim`` the mean over channels and positions of the SSIM map (``ops.ssim_loss``'s definition).
+    ``ms_ssim``: with (ssim_l, cs_l) the per-channel means of ``HF.ssim_stats`` at level l, level l + 1 being both images
+    halved by a 2 x 2 mean (``F.avg_pool2d``, an odd last row or column dropped),
+        prod_{l < L - 1} max(cs_l, 0)^{w_l} * max(ssim_{L-1}, 0)^{w_{L-1}},   averaged over channels,
+    w the first L = ``levels`` of ``MS_SSIM_WEIGHTS`` renormalised to sum 1.  ``levels`` None: ``ms_ssim_levels``, the most
+    that the image size allows, 5 from 176 pixels on."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError(f"reconstruction_quality: x and y must be [B, C, H, W] images of one shape (got {tuple(x.shape)}, "
+                         f"{tuple(y.shape)})")
+    x, y = x.detach(), y.detach()
+    H, W = x.shape[2:]
+    most = ms_ssim_levels(H, W, int(window))
+    L = most if levels is None else int(levels)
+    if L < 1 or L > most:
+        raise ValueError(f"reconstruction_quality: levels must lie in 1..{most} for {H} x {W} images and window = {window} "
+                         f"(got {levels})")
+    d = y.to(torch.float64) - x.to(torch.float64)
+    mse, l1 = (d * d).flatten(1).mean(1), d.abs().flatten(1).mean(1)
+    w = torch.tensor(MS_SSIM_WEIGHTS[:L], dtype=torch.float64)
+    w = (w / w.sum()).tolist()
+    ms = ssim = None
+    xl, yl = x, y
+    for lev in range(L):
+        if lev:
+            xl, yl = F.avg_pool2d(xl, 2), F.avg_pool2d(yl, 2)
+        st = HF.ssim_stats(xl, yl, window, sigma)                       # [B, C, 2]
+        if lev == 0:
+            ssim = st[:, :, 0].mean(1)
+        term = st[:, :, 0 if lev == L - 1 else 1].clamp_min(0.0) ** w[lev]
+        ms = term if ms is None else ms * term
+    return dict(psnr=10.0 * torch.log10(1.0 / mse), ssim=ssim, ms_ssim=ms.mean(1), mse=mse, l1=l1)
+
+
+def compute_reconstruction_quality(source, model, num=10000, batch_size=64, seed=0, indices=None, **kw):
+    """The means of ``reconstruction_quality`` over images of ``source`` (a ``DeviceImageTable`` or a dataset; no factors are
+    needed) and their deterministic reconstructions ``model.decode(model.encode(x)[0])``: a dict with ``psnr``, ``ssim``,
+    ``ms_ssim``, ``mse``, ``l1`` (Python floats), ``per_image`` (the five fp64 device vectors) and the ``indices`` used --
+    ``indices``, or ``np.sort(RandomState(seed).choice(len(source), num, replace=False))``, or all images when ``num >=
+    len(source)``, as ``compute_sample_quality`` draws them.  ``kw`` goes to ``reconstruction_quality``.  The model runs in
+    eval mode under ``no_grad``; its training flag is put back and its BatchNorm buffers are not written.  ``psnr`` is the
+    mean of the per-image values (inf as soon as one image is reconstructed exactly)."""
+    if indices is None:
+        n = len(source)
+        if int(num) >= n:
+            indices = np.arange(n, dtype=np.int64)
+        else:
+            indices = np.sort(np.random.RandomState(seed).choice(n, int(num), replace=False)).astype(np.int64)
+    indices = np.asarray(indices, dtype=np.int64)
+    if indices.ndim != 1 or not len(indices):
+        raise ValueError("compute_reconstruction_quality: indices must be a non-empty 1-D integer array")
+    device, bs = _device_of(model), int(batch_size)
+    if bs < 1:
+        raise ValueError(f"batch_size must be positive (got {batch_size})")
+    parts = {k: [] for k in RECONSTRUCTION_SCORES}
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for a in range(0, len(indices), bs):
+                images = _images(source, indices[a:a + bs], device)
+                got = reconstruction_quality(images, model.decode(model.encode(images)[0]), **kw)
+                for k in RECONSTRUCTION_SCORES:
+                    parts[k].append(got[k])
+    finally:
+        model.train(was_training)
+    per_image = {k: torch.cat(v, 0) for k, v in parts.items()}
+    out = {k: float(v.mean()) for k, v in per_image.items()}
+    out["per_image"] = per_image
     out["indices"] = indices
     return out

@@ -91,15 +91,48 @@ def kl_divergence(logvar, mu, reduce="sum", scale=1.0):
 def reconstruction_loss(x, recon_x, loss_type="mse", reduction="sum", scale=1.0):
     """ops.py:188-236; NotImplementedError for unknown loss_type / reduction, AssertionError on
     an empty batch, x is detached.  The reduction runs inside the kernels (two launches in all); ``scale`` (extension)
-    multiplies the result there -- the solver hooks pass their beta."""
+    multiplies the result there -- the solver hooks pass their beta.  Two structural types (extension, not in the
+    reference) go to ``ssim_loss`` and need the 4-D images: "ssim" (alpha = 1) and "ssim_l1" (alpha = 0.84, the mix of
+    Zhao et al. 2017)."""
     batch_size = x.size(0)
     assert batch_size != 0
     if reduction not in ("sum", "mean", "none"):
         raise NotImplementedError
+    if loss_type in SSIM_LOSS_ALPHA:
+        if x.dim() != 4 or recon_x.dim() != 4:
+            raise ValueError(f'loss_type "{loss_type}" needs [B, C, H, W] images (got {tuple(x.shape)}, '
+                             f"{tuple(recon_x.shape)})")
+        return ssim_loss(x, recon_x, reduction, scale, alpha=SSIM_LOSS_ALPHA[loss_type])
     if loss_type not in abi.LOSS_TYPES:
         raise NotImplementedError
     return HF.ReconLossFn.apply(x.detach().reshape(x.size(0), -1), recon_x.reshape(recon_x.size(0), -1),
                                 abi.LOSS_TYPES[loss_type], HF._REDUCTION[reduction], float(scale))
+
+
+SSIM_LOSS_ALPHA = {"ssim": 1.0, "ssim_l1": 0.84}      # reconstruction_loss's structural types -> alpha of ssim_loss
+
+
+def ssim_loss(x, recon, reduction="sum", scale=1.0, alpha=1.0, window=11, sigma=1.5):
+    """Structural-similarity reconstruction loss (Wang et al. 2004; as a training loss Snell et al. 2017, mixed with L1
+    Zhao et al. 2017), in the units of the other reconstruction losses.  With SSIM_b the mean over channels and positions
+    of the SSIM map of image b (a ``window``-tap Gaussian of width ``sigma``, valid filtering, C1 = 0.01^2, C2 = 0.03^2)
+    and P = C H W:  rows[b] = P alpha (1 - SSIM_b) + (1 - alpha) sum_p |recon - x|;  ``reduction`` and ``scale`` as in
+    ``reconstruction_loss``.  fp32 out, fp64 inside; x is detached.  Two launches forward, one backward
+    (itcv_ssim_loss_fwd / _bwd).  ValueError: alpha outside [0, 1], a window that is not an odd number in 3..15, images that
+    are not 4-D or smaller than the window; NotImplementedError: an unknown reduction."""
+    if reduction not in ("sum", "mean", "none"):
+        raise NotImplementedError
+    alpha, window = float(alpha), int(window)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"ssim_loss: alpha must lie in [0, 1] (got {alpha})")
+    if window < 3 or window > 15 or window % 2 == 0:
+        raise ValueError(f"ssim_loss: window must be an odd number of taps in 3..15 (got {window})")
+    if x.dim() != 4 or recon.shape != x.shape:
+        raise ValueError(f"ssim_loss: x and recon must be [B, C, H, W] images of one shape (got {tuple(x.shape)}, "
+                         f"{tuple(recon.shape)})")
+    if min(x.shape[2], x.shape[3]) < window:
+        raise ValueError(f"ssim_loss: H, W = {x.shape[2]}, {x.shape[3]} are below window = {window}")
+    return HF.SsimLossFn.apply(x.detach(), recon, HF._REDUCTION[reduction], float(scale), alpha, window, float(sigma))
 
 
 def gaussian_log_density_torch(x, mu, logvar):
@@ -486,8 +519,9 @@ def iwae_bound(x, recon, sample, beta_rec, beta_kl, loss_type="mse", estimator="
     the gradient that reaches ``mu`` and ``logvar``: "iwae" the plain reparameterised one; "stl" (Roeder et al. 2017) drops
     the direct dependence of log q on them and keeps the path through z; "dreg" (Tucker et al. 2019) weights that path by
     w once more.  The decoder's gradient is the same under all three, and so is every forward value.  Unknown
-    ``estimator``: ValueError; unknown ``loss_type``: NotImplementedError.  Four launches forward, two backward (plus the
-    sample's one), fp64 inside, bitwise reproducible."""
+    ``estimator``: ValueError; unknown ``loss_type``: NotImplementedError -- "ssim" and "ssim_l1" among them: they are
+    not likelihoods of independent elements and have no broadcast-row kernel.  Four launches forward, two backward (plus
+    the sample's one), fp64 inside, bitwise reproducible."""
     if estimator not in HF.IWAE_ESTIMATORS:
         raise ValueError(f"estimator must be one of {IWAE_ESTIMATORS} (got {estimator!r})")
     if loss_type not in abi.LOSS_TYPES:

@@ -67,6 +67,7 @@ class VAESolver:
         self.unsupervised_params = None
         self.likelihood_params = None     # keyword arguments of hipvae.likelihood.compute_log_likelihood
         self.quality_params = None        # keyword arguments of hipvae.quality.compute_sample_quality
+        self.reconstruction_params = None  # keyword arguments of hipvae.quality.compute_reconstruction_quality
         # "udr" ranks this model against ``udr_peers``: models trained from other seeds on the same data (a sequence of
         # networks; required by that score); ``udr_params``: ``params`` of hipvae.disentangle.compute_udr_score
         self.udr_peers = None
@@ -395,26 +396,32 @@ class VAESolver:
         "sample_quality" needs no factors either: the record ``sample_quality`` {frechet, kid, precision, recall, density,
         coverage} of decoded prior samples against the dataset's images (hipvae.quality; ``quality_params``).  The features
         are the model's own encoder means unless ``quality_params`` names a callable, so ``frechet`` and ``kid`` compare
-        models of one architecture and are not a published FID / KID."""
+        models of one architecture and are not a published FID / KID.
+        "reconstruction_quality" needs no factors either: the record ``reconstruction_quality`` {psnr, ssim, ms_ssim, mse,
+        l1}, the means over the dataset's images of the pixel-space scores of their deterministic reconstructions
+        (hipvae.quality; ``reconstruction_params``)."""
         extras = tuple(self.extra_scores or ())
         with_elbo = "elbo_decomposition" in extras
         with_unsup = "unsupervised" in extras
         with_udr = "udr" in extras
         with_ll = "log_likelihood" in extras
         with_quality = "sample_quality" in extras
+        with_recq = "reconstruction_quality" in extras
         factored = isinstance(self.dataset, DisentanglementDataset)
-        if self.writer is None or not (factored or with_elbo or with_unsup or with_udr or with_ll or with_quality) \
+        if self.writer is None or not (factored or with_elbo or with_unsup or with_udr or with_ll or with_quality
+                                      or with_recq) \
                 or cur_iter % self.test_iter:
             return
-        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr", "log_likelihood",
-                 "sample_quality")
+        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr", "reconstruction_quality",
+                 "log_likelihood", "sample_quality")
         unknown = [e for e in extras if e not in known]
         if unknown:
             raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, known))})")
         if factored:
             self._write_factor_scores(cur_iter, num_samples,
                                       tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised", "udr",
-                                                                           "log_likelihood", "sample_quality")))
+                                                                           "log_likelihood", "sample_quality",
+                                                                           "reconstruction_quality")))
         if with_elbo:
             from hipvae import aggregate
             kw = dict(batch_size=self.batch_size)
@@ -460,6 +467,14 @@ class VAESolver:
                                                  self.model, **kw)
             self.writer.add_scalars("sample_quality", {k: got[k] for k in (
                 "frechet", "kid", "precision", "recall", "density", "coverage")}, global_step=cur_iter)
+        if with_recq:
+            from hipvae import quality
+            kw = dict(batch_size=self.batch_size)
+            kw.update(self.reconstruction_params or {})
+            got = quality.compute_reconstruction_quality(self.dataset if self._device_table is None else self._device_table,
+                                                         self.model, **kw)
+            self.writer.add_scalars("reconstruction_quality", {k: got[k] for k in quality.RECONSTRUCTION_SCORES},
+                                    global_step=cur_iter)
 
     def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: tuple):
         """The factor-based scores of ``write_disentanglemnt_scores`` (a ``DisentanglementDataset``, at a test iteration)."""
