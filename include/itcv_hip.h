@@ -1065,6 +1065,45 @@ size_t itcv_frechet_workspace(int D);
 int itcv_frechet(const double* m1, const double* c1, const double* m2, const double* c2, int D, double eps, double* res,
                  double* eig, int* info, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- ex-post latent density: full-covariance Gaussian mixture (not in the reference; Ghosh et al. 2020) ----------- */
+/* The EM rules of sklearn.mixture.GaussianMixture(covariance_type="full") over rows x[N][D] (fp32, row stride ld elements,
+ * read in place; nothing left of a strided view is read).  Fixed rules; all arithmetic is fp64, every operation rounded on
+ * its own (no fused multiply-add outside the matrix cores), every floating-point sum in a fixed order that depends on the
+ * shapes alone, no floating-point atomic: same inputs, same bits.  flags[2] as for itcv_disent_*: [0] a non-finite x (the
+ * outputs are then unspecified), [1] a component number outside [0, K) (the sampler).  w[K], mean[K][D], cov / chol / linv
+ * [K][D][D], logdet[K], nk[K] are fp64 and dense.
+ * Factor.  chol holds C_k on entry and L_k on return, C_k = L_k L_k^T by the right-looking loop of itcv_unsup_gauss, the
+ *   upper triangle zero; linv = L_k^-1 by forward substitution (X = I; for k ascending: row k / L[k][k], then X[i][j] -=
+ *   L[i][k] X[k][j] for i > k, j <= k); logdet[k] = 2 sum_i log L[i][i], ascending.  info[k] = 0, or 1 + the dimension of the
+ *   first pivot that is <= 0 or non-finite (chol, linv and logdet of that component are then nan).  One block per
+ *   component; the matrix sits in LDS up to D = itcv_unsup_gauss_lds_dim(), above that the block works in chol itself.
+ * E-step.  y = linv_k (x_n - mean_k) on v_mfma_f64_16x16x4_f64 from the widened, centred values (the 16 x 16 tiles of linv_k
+ *   above its diagonal are skipped, elements above the diagonal enter as zeros); q = sum_i y_i^2 in ascending i;
+ *     lp[n][k] = log w[k] - ((D log 2 pi + logdet[k]) + q) / 2.
+ *   Then per row, with m = max_k lp[n][k]: lse = m + log sum_k exp(lp[n][k] - m) (ascending k), resp[n][k] = exp(lp[n][k] -
+ *   lse), loglik[n] = lse.  hard != 0: resp[n] is the one-hot of the largest lp[n][k] (ties to the lowest k) and loglik[n]
+ *   that value.  sum_loglik[0] = the sums of loglik over blocks of 256 rows, added in block order.  w need not sum to one.
+ * M-step.  nk[k] = sum_n resp[n][k] + 10 DBL_EPSILON;  w[k] = nk[k] / sum_k nk[k];  mean[k][d] = (sum_n resp[n][k] x[n][d]) /
+ *   nk[k];  cov[k][i][j] = (sum_n resp[n][k] (x[n][i] - mean[k][i]) (x[n][j] - mean[k][j])) / nk[k], + reg on the diagonal:
+ *   two passes over centred values, the products on the f64 matrix cores.  The sums over n follow itcv_unsup_cov: slices
+ *   whose length is a function of N alone, folded in ascending order; one triangle is computed and mirrored.  with_cov == 0
+ *   stops after the means (cov may be null): the centre update of Lloyd's iteration.
+ * Sampler.  z[r][i] = (float)(mean[c][i] + sum_{j <= i} chol[c][i][j] eps[r][j]), c = comp[r] (int32), eps[R][D] and
+ *   z[R][D] fp32 dense, the sum in ascending j; a row whose c is outside [0, K) is not written and sets flags[1].
+ * Supported: 1 <= K <= 64, 1 <= D <= 512, K <= N <= 2^24, 1 <= R <= 2^24, reg >= 0.  Anything unsupported, a null operand
+ * or a short workspace returns non-zero before a launch; the workspace queries return 0 for it. */
+int itcv_gmm_factor(double* chol, int K, int D, double* linv, double* logdet, int* info, void* stream);
+size_t itcv_gmm_estep_workspace(int N, int D, int K);
+int itcv_gmm_estep(const float* x, size_t ld, int N, int D, int K, const double* w, const double* mean, const double* linv,
+                   const double* logdet, int hard, double* lp, double* resp, double* loglik, double* sum_loglik,
+                   int* flags, void* ws, size_t ws_bytes, void* stream);
+size_t itcv_gmm_mstep_workspace(int N, int D, int K, int with_cov);
+int itcv_gmm_mstep(const float* x, size_t ld, const double* resp, int N, int D, int K, double reg, int with_cov,
+                   double* nk, double* w, double* mean, double* cov, int* flags, void* ws, size_t ws_bytes,
+                   void* stream);
+int itcv_gmm_sample(const double* mean, const double* chol, const int* comp, const float* eps, int R, int D, int K,
+                    float* z, int* flags, void* stream);
+
 /* ---- reconstruction loss (ops.py:188-236) --------------------------------------------- */
 #define ITCV_LOSS_MSE 0
 #define ITCV_LOSS_L1 1

@@ -2897,3 +2897,87 @@ def frechet(mean1, cov1, mean2, cov2, eps=0.0):
     call("itcv_frechet", ptr(mean1), ptr(cov1), ptr(mean2), ptr(cov2), D, float(eps), ptr(res), ptr(eig), ptr(info),
          ptr(ws), nws, stream())
     return res, eig, info
+
+
+# ------------------------------------------------------------------ Gaussian mixture (csrc/gmm.hip)
+def _gmm_params(weights, means, third, what):
+    """(K, D) of dense fp64 ``weights [K]``, ``means [K, D]`` and a third operand ``[K, D, D]`` named ``what``."""
+    for t, n in ((weights, "weights"), (means, "means"), (third, what)):
+        _gbt_dense(t, F64, n)
+    if means.dim() != 2 or tuple(weights.shape) != means.shape[:1] or tuple(third.shape) != (*means.shape, means.shape[1]):
+        raise abi.HipExtensionError(f"gmm: weights [K], means [K, D] and {what} [K, D, D] are expected (got "
+                                    f"{tuple(weights.shape)}, {tuple(means.shape)}, {tuple(third.shape)})")
+    return means.shape
+
+
+def gmm_factor(cov):
+    """``(chol, prec_chol, log_det [K], info [K] int32)`` of fp64 covariances ``cov [K, D, D]`` (itcv_gmm_factor; ``cov`` is
+    not written): the lower Cholesky factors, their inverses, the log-determinants, and per component 0 or 1 + the dimension
+    of the first failed pivot.  One launch, nothing is read back."""
+    cov = _gbt_dense(cov, F64, "cov")
+    if cov.dim() != 3 or cov.shape[1] != cov.shape[2] or cov.shape[0] < 1 or cov.shape[1] < 1:
+        raise abi.HipExtensionError(f"gmm: the covariances must be a [K, D, D] tensor (got {tuple(cov.shape)})")
+    K, D = cov.shape[:2]
+    chol = cov.clone()
+    linv = torch.empty_like(cov)
+    logdet = torch.empty((K,), dtype=F64, device=cov.device)
+    info = torch.empty((K,), dtype=torch.int32, device=cov.device)
+    call("itcv_gmm_factor", ptr(chol), K, D, ptr(linv), ptr(logdet), ptr(info), stream())
+    return chol, linv, logdet, info
+
+
+def gmm_estep(x, weights, means, prec_chol, log_det, flags, hard=False):
+    """``(lp [N, K], resp [N, K], loglik [N], sum_loglik [1])`` (fp64) of x[N, D] under the mixture (itcv_gmm_estep);
+    ``hard``: one-hot responsibilities of the largest ``lp``.  Sets flags[0] on a non-finite element."""
+    x = _disent_mu(x)
+    N, D = x.shape
+    K, Dm = _gmm_params(weights, means, prec_chol, "prec_chol")
+    if Dm != D or tuple(_gbt_dense(log_det, F64, "log_det").shape) != (K,):
+        raise abi.HipExtensionError(f"gmm: x [N, {Dm}] and log_det [{K}] are expected (got {tuple(x.shape)}, "
+                                    f"{tuple(log_det.shape)})")
+    dev = x.device
+    lp, resp = torch.empty((N, K), dtype=F64, device=dev), torch.empty((N, K), dtype=F64, device=dev)
+    loglik, total = torch.empty((N,), dtype=F64, device=dev), torch.empty((1,), dtype=F64, device=dev)
+    nws = lib.itcv_gmm_estep_workspace(N, D, K)                         # 0 for what the call below refuses
+    ws = _ws(nws, dev)
+    call("itcv_gmm_estep", x.data_ptr(), x.stride(0), N, D, K, ptr(weights), ptr(means), ptr(prec_chol), ptr(log_det),
+         int(bool(hard)), ptr(lp), ptr(resp), ptr(loglik), ptr(total), ptr(flags), ptr(ws), nws, stream())
+    return lp, resp, loglik, total
+
+
+def gmm_mstep(x, resp, flags, reg=0.0, with_cov=True):
+    """``(nk [K], weights [K], means [K, D], covariances [K, D, D] or None)`` (fp64) of x[N, D] under the responsibilities
+    ``resp [N, K]`` (itcv_gmm_mstep); ``with_cov`` false stops after the means."""
+    x = _disent_mu(x)
+    N, D = x.shape
+    resp = _gbt_dense(resp, F64, "resp")
+    if resp.dim() != 2 or resp.shape[0] != N or resp.shape[1] < 1:
+        raise abi.HipExtensionError(f"gmm: resp [{N}, K] is expected (got {tuple(resp.shape)})")
+    K, dev = resp.shape[1], x.device
+    nk, w = torch.empty((K,), dtype=F64, device=dev), torch.empty((K,), dtype=F64, device=dev)
+    mean = torch.empty((K, D), dtype=F64, device=dev)
+    cov = torch.empty((K, D, D), dtype=F64, device=dev) if with_cov else None
+    nws = lib.itcv_gmm_mstep_workspace(N, D, K, int(bool(with_cov)))    # 0 for what the call below refuses
+    ws = _ws(nws, dev)
+    call("itcv_gmm_mstep", x.data_ptr(), x.stride(0), ptr(resp), N, D, K, float(reg), int(bool(with_cov)), ptr(nk), ptr(w),
+         ptr(mean), ptr(cov), ptr(flags), ptr(ws), nws, stream())
+    return nk, w, mean, cov
+
+
+def gmm_sample(means, chol, comp, eps, flags):
+    """fp32 ``z [R, D]``, ``z[r] = (float)(means[c] + chol[c] eps[r])`` with ``c = comp[r]`` (int32 [R]) and fp32 ``eps
+    [R, D]`` (itcv_gmm_sample); sets flags[1] on a component number outside [0, K)."""
+    means, chol = _gbt_dense(means, F64, "means"), _gbt_dense(chol, F64, "chol")
+    if means.dim() != 2 or tuple(chol.shape) != (*means.shape, means.shape[1]):
+        raise abi.HipExtensionError(f"gmm: means [K, D] and chol [K, D, D] are expected (got {tuple(means.shape)}, "
+                                    f"{tuple(chol.shape)})")
+    K, D = means.shape
+    eps = _gbt_dense(eps, F32, "eps")
+    comp = _gbt_dense(comp, torch.int32, "comp")
+    if eps.dim() != 2 or eps.shape[1] != D or tuple(comp.shape) != eps.shape[:1]:
+        raise abi.HipExtensionError(f"gmm: eps [R, {D}] and comp [R] are expected (got {tuple(eps.shape)}, "
+                                    f"{tuple(comp.shape)})")
+    R = eps.shape[0]
+    z = torch.empty((R, D), dtype=F32, device=eps.device)
+    call("itcv_gmm_sample", ptr(means), ptr(chol), ptr(comp), ptr(eps), R, D, K, ptr(z), ptr(flags), stream())
+    return z

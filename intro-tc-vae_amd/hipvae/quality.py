@@ -170,27 +170,40 @@ def real_features(source, model, indices, batch_size=64, feature="encoder"):
     return _collect(model, lambda: (_images(source, indices[a:a + bs], device) for a in range(0, len(indices), bs)), feature)
 
 
-def generated_features(model, num, batch_size=64, seed=0, feature="encoder"):
+def generated_features(model, num, batch_size=64, seed=0, feature="encoder", prior=None):
     """fp32 ``[num, D]`` on the device: the features of ``model.decode(z)``, z ~ N(0, I) from a private CPU
     ``torch.Generator`` seeded by ``seed``, one draw per batch in a fixed order: torch's global generators are untouched
-    and two calls with one seed give the same bits.  Same contract for the model as ``real_features``."""
+    and two calls with one seed give the same bits.  Same contract for the model as ``real_features``.  ``prior``: a
+    ``hipvae.density.GaussianMixture`` whose ``gmm_sample(prior, num, seed)`` replaces the normal draws."""
     num, bs = int(num), int(batch_size)
     if num < 1 or bs < 1:
         raise ValueError(f"num and batch_size must be positive (got {num}, {batch_size})")
     device = _device_of(model)
     zdim = model.zdim
-    gen = torch.Generator().manual_seed(int(seed))
+    if prior is None:
+        gen = torch.Generator().manual_seed(int(seed))
 
-    def batches():
-        for a in range(0, num, bs):
-            z = torch.randn((min(bs, num - a), zdim), generator=gen).to(device)
-            yield model.decode(z)
+        def batches():
+            for a in range(0, num, bs):
+                z = torch.randn((min(bs, num - a), zdim), generator=gen).to(device)
+                yield model.decode(z)
+    else:
+        from . import density
+        if not isinstance(prior, density.GaussianMixture) or prior.dim != zdim:
+            raise ValueError(f"generated_features: prior must be None or a GaussianMixture over the model's {zdim} latent "
+                             "dimensions")
+        zs = density.gmm_sample(prior, num, seed)
+
+        def batches():
+            for a in range(0, num, bs):
+                yield model.decode(zs[a:a + bs])
 
     return _collect(model, batches, feature)
 
 
 def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature="encoder", nearest_k=5, batch_size=64,
-                           seed=0, scores=SCORES, eps=0.0, indices=None, kid_subset_size=None):
+                           seed=0, scores=SCORES, eps=0.0, indices=None, kid_subset_size=None, prior="normal",
+                           gmm_params=None):
     """The sample-quality scores of ``model`` on ``source`` (a ``DeviceImageTable`` or a dataset; no factors are needed): a
     flat dict with ``frechet`` ("frechet" in ``scores``), ``kid`` and ``kid_std`` ("kid") and ``precision``, ``recall``,
     ``density``, ``coverage`` ("prdc"), plus ``features = dict(real, fake)`` (fp32 device tensors) and the ``indices`` used.
@@ -199,10 +212,21 @@ def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature
     when ``num_real >= len(source)``.  Fakes: ``num_fake`` (None: as many as real images) decoded prior samples,
     ``generated_features(model, num_fake, batch_size, seed, feature)``.  The default feature is the model's own encoder
     mean, so the numbers compare models of one architecture and are not a published FID / KID.  The Frechet distance
-    needs D <= 512; ``eps`` regularises its covariances."""
+    needs D <= 512; ``eps`` regularises its covariances.
+
+    ``prior``: ``"normal"``, or ``"gmm"``: the fakes are decoded from an ex-post density instead (hipvae.density), a Gaussian
+    mixture fitted to the real images' latents ``model.encode(x)[0]`` (whatever ``feature`` is) by ``fit_gmm(latents,
+    **gmm_params)`` (``seed`` unless given there) and sampled by ``gmm_sample(gmm, num_fake, seed)``; a ``GaussianMixture``
+    instance is used as given.  The result then carries ``gmm`` too.  The scores of the two priors differ by what the
+    drift of the aggregate posterior from N(0, I) costs."""
     unknown = [s for s in scores if s not in SCORES]
     if unknown:
         raise ValueError(f"compute_sample_quality: unknown score(s) {unknown} (known: {', '.join(map(repr, SCORES))})")
+    gmm = None
+    if not isinstance(prior, str):
+        gmm = prior
+    elif prior not in ("normal", "gmm"):
+        raise ValueError(f'compute_sample_quality: prior must be "normal", "gmm" or a GaussianMixture (got {prior!r})')
     if indices is None:
         n = len(source)
         if int(num_real) >= n:
@@ -211,8 +235,14 @@ def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature
             indices = np.sort(np.random.RandomState(seed).choice(n, int(num_real), replace=False)).astype(np.int64)
     indices = np.asarray(indices, dtype=np.int64)
     real = real_features(source, model, indices, batch_size, feature)
-    fake = generated_features(model, len(indices) if num_fake is None else num_fake, batch_size, seed, feature)
+    if isinstance(prior, str) and prior == "gmm":
+        from . import density
+        latents = real if feature == "encoder" else real_features(source, model, indices, batch_size)
+        gmm = density.fit_gmm(latents, **{"seed": seed, **(gmm_params or {})})
+    fake = generated_features(model, len(indices) if num_fake is None else num_fake, batch_size, seed, feature, gmm)
     out = {}
+    if gmm is not None:
+        out["gmm"] = gmm
     if "frechet" in scores:
         out["frechet"] = frechet_distance(real, fake, eps)["frechet"]
     if "kid" in scores:

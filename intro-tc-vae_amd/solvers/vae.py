@@ -68,6 +68,7 @@ class VAESolver:
         self.likelihood_params = None     # keyword arguments of hipvae.likelihood.compute_log_likelihood
         self.quality_params = None        # keyword arguments of hipvae.quality.compute_sample_quality
         self.reconstruction_params = None  # keyword arguments of hipvae.quality.compute_reconstruction_quality
+        self.density_params = None        # keyword arguments of hipvae.density.compute_latent_density
         # "udr" ranks this model against ``udr_peers``: models trained from other seeds on the same data (a sequence of
         # networks; required by that score); ``udr_params``: ``params`` of hipvae.disentangle.compute_udr_score
         self.udr_peers = None
@@ -399,7 +400,11 @@ class VAESolver:
         models of one architecture and are not a published FID / KID.
         "reconstruction_quality" needs no factors either: the record ``reconstruction_quality`` {psnr, ssim, ms_ssim, mse,
         l1}, the means over the dataset's images of the pixel-space scores of their deterministic reconstructions
-        (hipvae.quality; ``reconstruction_params``)."""
+        (hipvae.quality; ``reconstruction_params``).
+        "latent_density" needs no factors either: the record ``latent_density`` {loglik_heldout, loglik_prior, gap, n_iter}
+        of a Gaussian mixture fitted to the encoder's latents of one part of the dataset's images and scored on another
+        (hipvae.density; ``density_params``); ``gap`` is what N(0, I) loses against that ex-post density, in nats per image.
+        ``quality_params = dict(prior="gmm")`` makes "sample_quality" decode samples of such a mixture, not of the prior."""
         extras = tuple(self.extra_scores or ())
         with_elbo = "elbo_decomposition" in extras
         with_unsup = "unsupervised" in extras
@@ -407,13 +412,14 @@ class VAESolver:
         with_ll = "log_likelihood" in extras
         with_quality = "sample_quality" in extras
         with_recq = "reconstruction_quality" in extras
+        with_density = "latent_density" in extras
         factored = isinstance(self.dataset, DisentanglementDataset)
         if self.writer is None or not (factored or with_elbo or with_unsup or with_udr or with_ll or with_quality
-                                      or with_recq) \
+                                      or with_recq or with_density) \
                 or cur_iter % self.test_iter:
             return
         known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr", "reconstruction_quality",
-                 "log_likelihood", "sample_quality")
+                 "latent_density", "log_likelihood", "sample_quality")
         unknown = [e for e in extras if e not in known]
         if unknown:
             raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, known))})")
@@ -421,7 +427,8 @@ class VAESolver:
             self._write_factor_scores(cur_iter, num_samples,
                                       tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised", "udr",
                                                                            "log_likelihood", "sample_quality",
-                                                                           "reconstruction_quality")))
+                                                                           "reconstruction_quality",
+                                                                           "latent_density")))
         if with_elbo:
             from hipvae import aggregate
             kw = dict(batch_size=self.batch_size)
@@ -475,6 +482,14 @@ class VAESolver:
                                                          self.model, **kw)
             self.writer.add_scalars("reconstruction_quality", {k: got[k] for k in quality.RECONSTRUCTION_SCORES},
                                     global_step=cur_iter)
+        if with_density:
+            from hipvae import density
+            kw = dict(batch_size=self.batch_size)
+            kw.update(self.density_params or {})
+            got = density.compute_latent_density(self.dataset if self._device_table is None else self._device_table,
+                                                 self.model, **kw)
+            self.writer.add_scalars("latent_density", {k: got[k] for k in (
+                "loglik_heldout", "loglik_prior", "gap", "n_iter")}, global_step=cur_iter)
 
     def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: tuple):
         """The factor-based scores of ``write_disentanglemnt_scores`` (a ``DisentanglementDataset``, at a test iteration)."""
