@@ -2607,6 +2607,37 @@ def gbt_split(tab, nbins, cvalid, level, trees, nsum, lam=1.0, eta=0.3, c0=0):
          ptr(_gbt_dense(tgain, F64, "tgain")), stream())
 
 
+def gbt_advance(bins, cvalid, tfeat, tbin, level, node):
+    """Move the rows that sit in a split node of ``level`` to its children, in place: node[csum, N] uint8 heap indices,
+    tfeat / tbin [csum, GBT_NODES] of ONE round.  Rows in a leaf and rows of an invalid class stay."""
+    bins, node = _gbt_dense(bins, U8, "bins"), _gbt_dense(node, U8, "node")
+    csum, N = node.shape
+    if bins.shape[1] != N or tuple(tfeat.shape) != (csum, GBT_NODES) or tuple(tbin.shape) != (csum, GBT_NODES):
+        raise abi.HipExtensionError(f"gbt: node ids [{csum}, {N}] need bins [D, {N}] and trees [{csum}, {GBT_NODES}]")
+    call("itcv_gbt_advance", ptr(bins), N, csum, ptr(_gbt_dense(cvalid, torch.int32, "cvalid")),
+         ptr(_gbt_dense(tfeat, torch.int32, "tfeat")), ptr(_gbt_dense(tbin, torch.int32, "tbin")), int(level), ptr(node),
+         stream())
+    return node
+
+
+def gbt_margins(bins, cvalid, node, trees, max_depth, F):
+    """F[csum, N] += the value of every row's leaf in ONE round's ``trees`` = (tfeat, tbin, tvalue, tgain), each
+    [csum, GBT_NODES], in place: the leaf is node[csum, N] where the node ids are given, else (``node`` None) the row
+    walks the tree from the root for at most ``max_depth`` levels.  Invalid classes are left alone."""
+    bins, F = _gbt_dense(bins, U8, "bins"), _gbt_dense(F, F64, "the margins")
+    csum, N = F.shape
+    tfeat, tbin, tvalue = trees[0], trees[1], trees[2]
+    if bins.shape[1] != N or any(tuple(t.shape) != (csum, GBT_NODES) for t in (tfeat, tbin, tvalue)) \
+            or (node is not None and tuple(node.shape) != (csum, N)):
+        raise abi.HipExtensionError(f"gbt: margins [{csum}, {N}] need bins [D, {N}], node ids [{csum}, {N}] and trees "
+                                    f"[{csum}, {GBT_NODES}]")
+    call("itcv_gbt_margins", ptr(bins), N, csum, ptr(_gbt_dense(cvalid, torch.int32, "cvalid")),
+         ptr(None if node is None else _gbt_dense(node, U8, "node")), ptr(_gbt_dense(tfeat, torch.int32, "tfeat")),
+         ptr(_gbt_dense(tbin, torch.int32, "tbin")), ptr(_gbt_dense(tvalue, F64, "tvalue")), int(max_depth), ptr(F),
+         stream())
+    return F
+
+
 def gbt_predict(F, y, class_sizes, cvalid, flags):
     """(pred[N, K] int32, correct[K] int64): first argmax of F[csum, N] over the valid classes and the number of rows whose
     label equals it; sets flags[1] on a label outside its range."""

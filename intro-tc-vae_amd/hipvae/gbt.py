@@ -30,9 +30,11 @@ def _present(y, sizes):
 
 
 def fit_device(x_train, y_train, x_test, y_test, class_sizes, rounds=100, max_depth=6, max_bin=256, eta=0.3, lam=1.0,
-               cvalid=None, flags=None):
+               cvalid=None, flags=None, table_bytes=None):
     """The fit without any read-back: a dict of device tensors (``importance [K, D]`` fp64, ``correct`` /
-    ``correct_test [K]`` int64, ``nvalid [K]``, ``flags [2]``, the tree arrays, margins and predictions)."""
+    ``correct_test [K]`` int64, ``nvalid [K]``, ``flags [2]``, the tree arrays, margins and predictions).
+    ``table_bytes`` bounds the histogram table (default: what ``itcv_gbt_workspace`` asks for); it is rounded down to
+    whole class slots, the classes are taken in chunks of that many, and less than one slot is refused."""
     sizes, csizes = HF._lr_sizes(class_sizes)
     K, csum = len(sizes), sum(sizes)
     rounds, max_depth, max_bin = int(rounds), int(max_depth), int(max_bin)
@@ -51,6 +53,11 @@ def fit_device(x_train, y_train, x_test, y_test, class_sizes, rounds=100, max_de
         call("itcv_gbt_round", None, N, D, max_bin, None, None, K, csizes, None, None, None, Nt, None, max_depth,
              float(lam), float(eta), None, None, None, None, None, 0, None, None, None, None, None, None)
         raise abi.HipExtensionError("gbt: the problem lies outside the supported range")
+    if table_bytes is not None:
+        per = (1 << (max_depth - 1)) * D * max_bin * 16   # one class slot: deepest level's nodes x D x max_bin x (G, H)
+        if int(table_bytes) < per:
+            raise abi.HipExtensionError(f"gbt: table_bytes = {int(table_bytes)} is below one class slot ({per} bytes)")
+        nws = min(nws, int(table_bytes) // per * per)
     cvalid = _present(y, sizes) if cvalid is None else cvalid.to(device=dev, dtype=torch.int32).contiguous()
     if cvalid.numel() != csum:
         raise abi.HipExtensionError(f"gbt: the class mask needs {csum} entries (got {cvalid.numel()})")
@@ -99,13 +106,14 @@ def read_back(fit, extra=()):
 
 
 def fit_boosted_trees(x_train, y_train, x_test, y_test, class_sizes, rounds=100, max_depth=6, max_bin=256, eta=0.3,
-                      lam=1.0, cvalid=None):
+                      lam=1.0, cvalid=None, table_bytes=None):
     """Fit the K boosted-tree classifiers of (x_train[N, D], y_train[N, K]) jointly and evaluate them on both sets.
     Returns a ``BoostedTrees``: ``importance [K, D]`` (fp64, on the device), per-problem train / test accuracy (integer
     counts divided by the number of rows), the counts, and the tree arrays / cuts / margins / predictions as device
     tensors.  Non-finite representations, labels outside their range and a problem with fewer than two valid classes
-    raise ``ValueError``."""
-    fit = fit_device(x_train, y_train, x_test, y_test, class_sizes, rounds, max_depth, max_bin, eta, lam, cvalid)
+    raise ``ValueError``.  ``table_bytes``: see ``fit_device``."""
+    fit = fit_device(x_train, y_train, x_test, y_test, class_sizes, rounds, max_depth, max_bin, eta, lam, cvalid,
+                     table_bytes=table_bytes)
     tr, te, _ = read_back(fit)
     return BoostedTrees(fit["importance"], [c / fit["N"] for c in tr], [c / fit["Nt"] for c in te], tr, te, fit["trees"],
                         fit["cuts"], fit["nbins"], fit["margins"], fit["test_margins"], fit["pred"], fit["test_pred"],
