@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <float.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -29,6 +31,26 @@ inline int fail(const char* fmt, const char* a = "", long long b = 0, long long 
   do {                                                                        \
     if (!(cond)) return itcv::fail("%s: requirement failed: " #cond, name);   \
   } while (0)
+
+inline bool finite(double x) { return fabs(x) <= DBL_MAX; }   // false for NaN too
+
+// The refusals: each returns 0 when the call may go on; otherwise it leaves the message and returns fail()'s 1, so a chain
+// of them joined with || stops at the first failure.
+inline int need_pointers(const char* name, bool all) { return all ? 0 : fail("%s: a required pointer is NULL", name); }
+// `what` names the dimension with a %lld for its value ("B = %lld pairs"), `range` words lo..hi ("1..2^30")
+inline int need_dim(const char* name, const char* what, long long v, long long lo, long long hi, const char* range) {
+  if (v >= lo && v <= hi) return 0;
+  char fmt[128];
+  snprintf(fmt, sizeof(fmt), "%%s: %s is outside %s", what, range);
+  return fail(fmt, name, v);
+}
+// `whose` is "a" or the operand's name ("mu's"), `dim` the name of the width the stride has to cover
+inline int need_stride(const char* name, const char* whose, size_t ld, const char* dim, long long width) {
+  if (ld >= (size_t)width) return 0;
+  char fmt[128];
+  snprintf(fmt, sizeof(fmt), "%%s: %s row stride of %%lld is below %s = %%lld", whose, dim);
+  return fail(fmt, name, (long long)ld, width);
+}
 
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -8,15 +8,11 @@
 // (hipvae/disentangle.py).  The histogram is the only stage with real work: N * D * K integer adds.  They go to an LDS
 // table with ds_add_u32 and are flushed with integer global atomics: integer sums do not depend on arrival order, so
 // the tables -- and everything computed from them in a fixed order -- are bitwise reproducible.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "dense.h"
 
 namespace itcv {
 
 constexpr int kDisMaxBins = 32;
-constexpr int kDisMaxK = 16;
 constexpr int kDisMaxFsize = 256;
 constexpr int kDisMaxN = 1 << 30;       // row arithmetic is 32-bit: slices are rounded up to whole blocks of rows
 constexpr int kMmRows = 256;            // rows of mu per block of the minmax kernel
@@ -71,13 +67,13 @@ __global__ __launch_bounds__(256) void disent_minmax_part_kernel(const float* __
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         mn = fminf(mn, x[u]), mx = fmaxf(mx, x[u]);
-        bad |= !(fabsf(x[u]) <= FLT_MAX);
+        bad |= !finite_f(x[u]);
       }
     }
     for (; r < r1; r += 4) {
       const float x = mu[(size_t)r * ld + d];
       mn = fminf(mn, x), mx = fmaxf(mx, x);
-      bad |= !(fabsf(x) <= FLT_MAX);
+      bad |= !finite_f(x);
     }
   }
   smn[wid][lane] = mn, smx[wid][lane] = mx;
@@ -114,10 +110,9 @@ __global__ __launch_bounds__(256) void disent_bins_kernel(const float* __restric
 // Factors are cut into groups of consecutive factors whose tables fit the LDS budget; a block owns (TC columns) x (a
 // slice of kHistRows rows) x (one group).  The table of column d is counts[d][bins * off[k] + b * fsize[k] + f]: the
 // group's part of it is one contiguous range, in LDS and in global memory alike.
-struct HistPlan {
-  int K, ng;
-  int off[kDisMaxK + 1];    // prefix sums of fsize
-  int gk[kDisMaxK + 1];     // group g covers factors [gk[g], gk[g + 1])
+struct HistPlan : SegPlan {  // K and off[]: the prefix sums of fsize
+  int ng;
+  int gk[kSegMaxK + 1];     // group g covers factors [gk[g], gk[g + 1])
 };
 
 __global__ __launch_bounds__(256) void disent_hist_kernel(const float* __restrict__ mu, size_t ld,
@@ -148,14 +143,14 @@ __global__ __launch_bounds__(256) void disent_hist_kernel(const float* __restric
   for (int r0 = sl * kHistRows + rl; r0 < r_end; r0 += rp * kHistU) {
     // every load of these kHistU rows is issued before the first LDS add
     float x[kHistU];
-    int vv[kHistU][kDisMaxK];
+    int vv[kHistU][kSegMaxK];
 #pragma unroll
     for (int u = 0; u < kHistU; ++u) {
       const int r = r0 + u * rp;
       const bool have = act && r < r_end;
       x[u] = have ? mu[(size_t)r * ld + d] : 0.f;
 #pragma unroll
-      for (int kk = 0; kk < kDisMaxK; ++kk) vv[u][kk] = (have && kk < nk) ? v[(size_t)r * pl.K + k0 + kk] : 0;
+      for (int kk = 0; kk < kSegMaxK; ++kk) vv[u][kk] = (have && kk < nk) ? v[(size_t)r * pl.K + k0 + kk] : 0;
     }
 #pragma unroll
     for (int u = 0; u < kHistU; ++u) {
@@ -164,7 +159,7 @@ __global__ __launch_bounds__(256) void disent_hist_kernel(const float* __restric
       int b = bin_of(x[u], br, bins) - 1;
       b = b < 0 ? 0 : b;                                   // only a non-finite x gets here: flagged by the minmax pass
 #pragma unroll
-      for (int kk = 0; kk < kDisMaxK; ++kk) {
+      for (int kk = 0; kk < kSegMaxK; ++kk) {
         if (kk >= nk) continue;
         const int fo = pl.off[k0 + kk] - f0, fs = pl.off[k0 + kk + 1] - pl.off[k0 + kk];
         const int f = vv[u][kk];
@@ -257,13 +252,8 @@ __global__ __launch_bounds__(256) void disent_mi_kernel(const unsigned* __restri
 // of two) and *lds, or fails.
 static int hist_plan(const char* name, int D, int K, const int* fsize, int bins, HistPlan* pl, int* tc, size_t* lds) {
   if (bins < 1 || bins > kDisMaxBins) return fail("%s: bins = %lld is outside 1..32", name, bins);
-  if (K < 1 || K > kDisMaxK) return fail("%s: K = %lld factors is outside 1..16", name, K);
-  pl->K = K, pl->off[0] = 0;
-  for (int k = 0; k < K; ++k) {
-    if (fsize[k] < 1 || fsize[k] > kDisMaxFsize)
-      return fail("%s: factor %lld has size %lld, outside 1..256", name, k, fsize[k]);
-    pl->off[k + 1] = pl->off[k] + fsize[k];
-  }
+  const SegWords words = {"K = %lld factors", nullptr, "factor %lld has size %lld"};   // the callers require fsize
+  if (seg_plan(name, K, fsize, kDisMaxFsize, words, pl)) return 1;
   // greedy groups of consecutive factors: (bins + 1) * gsum words for one column must fit the budget
   const size_t cap = kHistLds / sizeof(unsigned) / (size_t)(bins + 1);
   int ng = 0, gmax = 0;
@@ -283,13 +273,6 @@ static int hist_plan(const char* name, int D, int K, const int* fsize, int bins,
   return 0;
 }
 
-static inline int mm_slices(int N, int* rows) {
-  int r = kMmRows;
-  while (cdiv(N, r) > kMmMaxSlices) r *= 2;
-  *rows = r;
-  return cdiv(N, r);
-}
-
 }  // namespace itcv
 
 using namespace itcv;
@@ -299,7 +282,7 @@ extern "C" {
 size_t itcv_disent_minmax_workspace(int N, int D) {
   if (N < 1 || N > kDisMaxN || D < 1) return 0;
   int rows;
-  return (size_t)2 * mm_slices(N, &rows) * D * sizeof(float);
+  return (size_t)2 * doubling_slices(N, kMmRows, kMmMaxSlices, &rows) * D * sizeof(float);
 }
 
 int itcv_disent_minmax(const float* mu, size_t ld, int N, int D, float* mn, float* mx, int* flags, void* ws,
@@ -307,7 +290,7 @@ int itcv_disent_minmax(const float* mu, size_t ld, int N, int D, float* mn, floa
   ITCV_REQUIRE(mu && mn && mx && flags && N >= 1 && N <= kDisMaxN && D >= 1 && ld >= (size_t)D, "itcv_disent_minmax");
   ITCV_REQUIRE(ws && ws_bytes >= itcv_disent_minmax_workspace(N, D), "itcv_disent_minmax(workspace)");
   int rows;
-  const int ns = mm_slices(N, &rows), nct = cdiv(D, 64);
+  const int ns = doubling_slices(N, kMmRows, kMmMaxSlices, &rows), nct = cdiv(D, 64);
   float* pmn = static_cast<float*>(ws);
   float* pmx = pmn + (size_t)ns * D;
   hipLaunchKernelGGL(disent_minmax_part_kernel, dim3(nct, ns), dim3(256), 0, S(stream), mu, ld, N, D, rows,

@@ -10,16 +10,12 @@
 // Every floating-point reduction has a fixed order (per-lane partials over ascending rows, then the xor butterfly of the
 // wave, whose sums are the same bits in every lane because an fp64 add commutes); there is no floating-point atomic.  The
 // order of operations is part of the rule: nothing in this file may be contracted into a fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "dense.h"
 
 #pragma clang fp contract(off)
 
 namespace itcv {
 
-constexpr int kXsMaxK = 16;
 constexpr int kXsMaxCsize = 256;
 constexpr int kXsMaxD = 512;
 constexpr int kXsMaxN = 1 << 24;          // rows of any one call
@@ -28,13 +24,6 @@ constexpr int kSvcThreads = 512;          // 8 waves: 8 problems of one (latent,
 constexpr int kSvcLdsRows = 12800;        // 5 bytes a row (fp32 x, uint8 y): 62.5 KiB, two blocks per CU
 constexpr int kSvcMaxHalvings = 50;       // step lengths tried per Newton step: 1, 1/2, ..., 2^-50
 constexpr double kSvcArmijo = 1e-4;
-
-struct XsPlan {
-  int K;
-  int coff[kXsMaxK + 1];   // prefix sums of the class counts; csum = coff[K]
-};
-
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
 
 // ---- FactorVAE: global variances -----------------------------------------------------------------------------------
 // One block of 16 waves per tile of 32 columns; a wave covers 2 rows x 32 columns per step (128-byte segments), so lane
@@ -155,7 +144,7 @@ __global__ __launch_bounds__(256) void fvae_classify_kernel(const unsigned long 
 // grid (64-row tile, 64-column tile): xt[D][N] = x^T through an LDS tile; the blocks of column tile 0 also write the labels
 // as yt[K][N] uint8 (255 for a label outside its range, which sets flags[1]) and count the classes with integer atomics.
 __global__ __launch_bounds__(256) void svc_prep_kernel(const float* __restrict__ x, size_t ld, const int* __restrict__ y,
-                                                       int N, int D, XsPlan pl, float* __restrict__ xt,
+                                                       int N, int D, SegPlan pl, float* __restrict__ xt,
                                                        unsigned char* __restrict__ yt, int* __restrict__ counts,
                                                        int* __restrict__ flags) {
   __shared__ float tile[64][65];
@@ -178,12 +167,12 @@ __global__ __launch_bounds__(256) void svc_prep_kernel(const float* __restrict__
   const int K = pl.K, n = r0 + lane;
   if (n >= N) return;
   for (int k = wid; k < K; k += 4) {
-    const int S = pl.coff[k + 1] - pl.coff[k];
+    const int S = pl.off[k + 1] - pl.off[k];
     const int yv = y[(size_t)n * K + k];
     const bool ok = (unsigned)yv < (unsigned)S;
     yt[(size_t)k * N + n] = ok ? (unsigned char)yv : (unsigned char)255;
     if (ok)
-      atomicAdd(&counts[pl.coff[k] + yv], 1);
+      atomicAdd(&counts[pl.off[k] + yv], 1);
     else
       atomicOr(&flags[1], 1);
   }
@@ -267,7 +256,7 @@ __device__ __forceinline__ int svc_solve(XP xs, YP ys, int N, int c, double cp, 
 // class value alone when there are 2, none when there is 1.
 template <bool IN_LDS>
 __global__ __launch_bounds__(kSvcThreads) void svc_fit_kernel(const float* __restrict__ xt, const unsigned char* __restrict__ yt,
-                                                              const int* __restrict__ counts, int N, int D, XsPlan pl,
+                                                              const int* __restrict__ counts, int N, int D, SegPlan pl,
                                                               double C, double gtol, int max_iter,
                                                               double* __restrict__ theta, double* __restrict__ gnorm,
                                                               int* __restrict__ iters, int* __restrict__ cvalid,
@@ -275,7 +264,7 @@ __global__ __launch_bounds__(kSvcThreads) void svc_fit_kernel(const float* __res
   extern __shared__ __attribute__((aligned(16))) unsigned char svc_lds[];
   const int i = blockIdx.x, j = blockIdx.y;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int K = pl.K, csum = pl.coff[K], c0 = pl.coff[j], S = pl.coff[j + 1] - c0;
+  const int K = pl.K, csum = pl.off[K], c0 = pl.off[j], S = pl.off[j + 1] - c0;
   const float* xg = xt + (size_t)i * N;
   const unsigned char* yg = yt + (size_t)j * N;
   float* xs = reinterpret_cast<float*>(svc_lds);
@@ -322,15 +311,15 @@ __global__ __launch_bounds__(kSvcThreads) void svc_fit_kernel(const float* __res
 
 // grid (256-row tile, latent i): a thread per test row.  correct[i][j] counts the rows whose prediction equals the label.
 __global__ __launch_bounds__(256) void svc_score_kernel(const float* __restrict__ x, size_t ld, const int* __restrict__ y,
-                                                        int Nt, int D, XsPlan pl, const int* __restrict__ cvalid,
+                                                        int Nt, int D, SegPlan pl, const int* __restrict__ cvalid,
                                                         const double* __restrict__ theta,
                                                         unsigned long long* __restrict__ correct, int* __restrict__ pred,
                                                         int* __restrict__ flags) {
-  __shared__ int nv_s[kXsMaxK], first_s[kXsMaxK], last_s[kXsMaxK], cnt_s[kXsMaxK];
+  __shared__ int nv_s[kSegMaxK], first_s[kSegMaxK], last_s[kSegMaxK], cnt_s[kSegMaxK];
   const int i = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
-  const int K = pl.K, csum = pl.coff[K];
+  const int K = pl.K, csum = pl.off[K];
   if ((int)threadIdx.x < K) {
-    const int c0 = pl.coff[threadIdx.x], S = pl.coff[threadIdx.x + 1] - c0;
+    const int c0 = pl.off[threadIdx.x], S = pl.off[threadIdx.x + 1] - c0;
     int nv = 0, first = -1, last = -1;
     for (int c = 0; c < S; ++c)
       if (cvalid[c0 + c]) {
@@ -346,7 +335,7 @@ __global__ __launch_bounds__(256) void svc_score_kernel(const float* __restrict_
   const double xd = (double)xv;
   const double* th = theta + (size_t)i * csum * 2;
   for (int j = 0; j < K; ++j) {
-    const int c0 = pl.coff[j], S = pl.coff[j + 1] - c0, nv = nv_s[j];
+    const int c0 = pl.off[j], S = pl.off[j + 1] - c0, nv = nv_s[j];
     int p = -1;
     if (nv == 1) {
       p = first_s[j];
@@ -378,18 +367,10 @@ __global__ __launch_bounds__(256) void svc_score_kernel(const float* __restrict_
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-static int xs_plan(const char* name, int N, int D, int K, const int* csize, XsPlan* pl) {
-  if (N < 1 || N > kXsMaxN) return fail("%s: N = %lld is outside 1..2^24", name, N);
-  if (D < 1 || D > kXsMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
-  if (K < 1 || K > kXsMaxK) return fail("%s: K = %lld problems is outside 1..16", name, K);
-  if (!csize) return fail("%s: no class counts", name);
-  pl->K = K, pl->coff[0] = 0;
-  for (int k = 0; k < K; ++k) {
-    if (csize[k] < 1 || csize[k] > kXsMaxCsize)
-      return fail("%s: problem %lld has %lld classes, outside 1..256", name, k, csize[k]);
-    pl->coff[k + 1] = pl->coff[k] + csize[k];
-  }
-  return 0;
+constexpr SegWords kXsWords = {"K = %lld problems", "no class counts", "problem %lld has %lld classes"};
+static int xs_plan(const char* name, int N, int D, int K, const int* csize, SegPlan* pl) {
+  return need_dim(name, "N = %lld", N, 1, kXsMaxN, "1..2^24") || need_dim(name, "D = %lld", D, 1, kXsMaxD, "1..512") ||
+         seg_plan(name, K, csize, kXsMaxCsize, kXsWords, pl);
 }
 struct SvcWs {
   size_t xt, yt, counts, total;
@@ -410,8 +391,9 @@ using namespace itcv;
 extern "C" {
 
 int itcv_fvae_gvar(const float* mu, size_t ld, int N, int D, double* gvar, int* flags, void* stream) {
-  if (N < 2 || N > kXsMaxN) return fail("%s: N = %lld rows is outside 2..2^24", "itcv_fvae_gvar", N);
-  if (D < 1 || D > kXsMaxD) return fail("%s: D = %lld is outside 1..512", "itcv_fvae_gvar", D);
+  if (need_dim("itcv_fvae_gvar", "N = %lld rows", N, 2, kXsMaxN, "2..2^24") ||
+      need_dim("itcv_fvae_gvar", "D = %lld", D, 1, kXsMaxD, "1..512"))
+    return 1;
   ITCV_REQUIRE(mu && gvar && flags && ld >= (size_t)D, "itcv_fvae_gvar");
   hipLaunchKernelGGL(fvae_gvar_kernel, dim3(cdiv(D, 32)), dim3(1024), 0, S(stream), mu, ld, N, D, gvar, flags);
   ITCV_CHECK_LAUNCH("itcv_fvae_gvar");
@@ -421,10 +403,10 @@ int itcv_fvae_gvar(const float* mu, size_t ld, int N, int D, double* gvar, int* 
 int itcv_fvae_votes(const float* mu, size_t ld, int M, int L, int D, const double* gvar, double threshold, const int* fidx,
                     int K, long long* votes, int* flags, void* stream) {
   const char* name = "itcv_fvae_votes";
-  if (L < 2 || L > kXsMaxL) return fail("%s: L = %lld rows a group is outside 2..2^16", name, L);
+  if (need_dim(name, "L = %lld rows a group", L, 2, kXsMaxL, "2..2^16")) return 1;
   if (M < 1 || (long long)M * L > kXsMaxN) return fail("%s: M = %lld groups (M * L rows) is outside 1..2^24 rows", name, M);
-  if (D < 1 || D > kXsMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
-  if (K < 1 || K > kXsMaxCsize) return fail("%s: K = %lld factors is outside 1..256", name, K);
+  if (need_dim(name, "D = %lld", D, 1, kXsMaxD, "1..512") || need_dim(name, "K = %lld factors", K, 1, kXsMaxCsize, "1..256"))
+    return 1;
   ITCV_REQUIRE(mu && gvar && fidx && votes && flags && ld >= (size_t)D, name);
   hipStream_t st = S(stream);
   if (hipMemsetAsync(votes, 0, (size_t)D * K * sizeof(long long), st) != hipSuccess)
@@ -438,8 +420,8 @@ int itcv_fvae_votes(const float* mu, size_t ld, int M, int L, int D, const doubl
 int itcv_fvae_classify(const long long* votes_train, const long long* votes_eval, int D, int K, int Mt, int Me,
                        const double* gvar, double threshold, int* classifier, double* res, void* stream) {
   const char* name = "itcv_fvae_classify";
-  if (D < 1 || D > kXsMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
-  if (K < 1 || K > kXsMaxCsize) return fail("%s: K = %lld factors is outside 1..256", name, K);
+  if (need_dim(name, "D = %lld", D, 1, kXsMaxD, "1..512") || need_dim(name, "K = %lld factors", K, 1, kXsMaxCsize, "1..256"))
+    return 1;
   ITCV_REQUIRE(votes_train && votes_eval && gvar && classifier && res && Mt >= 1 && Me >= 1, name);
   hipLaunchKernelGGL(fvae_classify_kernel, dim3(1), dim3(256), 0, S(stream),
                      reinterpret_cast<const unsigned long long*>(votes_train),
@@ -451,7 +433,7 @@ int itcv_fvae_classify(const long long* votes_train, const long long* votes_eval
 int itcv_sap_svc_lds_rows(void) { return kSvcLdsRows; }
 
 size_t itcv_sap_svc_workspace(int N, int D, int K, int csum) {
-  if (N < 1 || N > kXsMaxN || D < 1 || D > kXsMaxD || K < 1 || K > kXsMaxK || csum < K || csum > K * kXsMaxCsize) return 0;
+  if (N < 1 || N > kXsMaxN || D < 1 || D > kXsMaxD || K < 1 || K > kSegMaxK || csum < K || csum > K * kXsMaxCsize) return 0;
   return svc_ws(N, D, K, csum).total;
 }
 
@@ -459,12 +441,12 @@ int itcv_sap_svc_fit(const float* x, size_t ld, const int* y, int N, int D, int 
                      int max_iter, double* theta, double* gnorm, int* iters, int* cvalid, int* flags, void* ws,
                      size_t ws_bytes, void* stream) {
   const char* name = "itcv_sap_svc_fit";
-  XsPlan pl;
+  SegPlan pl;
   if (int e = xs_plan(name, N, D, K, csize, &pl)) return e;
   ITCV_REQUIRE(x && y && theta && gnorm && iters && cvalid && flags && ld >= (size_t)D && C > 0.0 && gtol > 0.0 &&
                    max_iter >= 1,
                name);
-  const int csum = pl.coff[K];
+  const int csum = pl.off[K];
   const SvcWs w = svc_ws(N, D, K, csum);
   ITCV_REQUIRE(ws && ws_bytes >= w.total, "itcv_sap_svc_fit(workspace)");
   char* base = static_cast<char*>(ws);
@@ -492,7 +474,7 @@ int itcv_sap_svc_fit(const float* x, size_t ld, const int* y, int N, int D, int 
 int itcv_sap_svc_score(const float* x, size_t ld, const int* y, int Nt, int D, int K, const int* csize, const int* cvalid,
                        const double* theta, long long* correct, int* pred, int* flags, void* stream) {
   const char* name = "itcv_sap_svc_score";
-  XsPlan pl;
+  SegPlan pl;
   if (int e = xs_plan(name, Nt, D, K, csize, &pl)) return e;
   ITCV_REQUIRE(x && y && cvalid && theta && correct && flags && ld >= (size_t)D, name);
   hipStream_t st = S(stream);

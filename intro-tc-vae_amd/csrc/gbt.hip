@@ -11,14 +11,11 @@
 // Every sum of gradients is an integer sum, so it does not depend on arrival order: LDS atomics and global atomics may
 // be used freely and the trees are bitwise reproducible.  The histogram uses the node-id-per-row form: rows
 // are never moved, each carries the heap index of the node it sits in (root 0, children of i at 2 i + 1 and 2 i + 2).
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "dense.h"
 
 namespace itcv {
 
-constexpr int kGbtMaxK = 16;
+constexpr int kGbtMaxK = kSegMaxK;                      // the name is part of the wording of the requirements below
 constexpr int kGbtMaxCsize = 256;
 constexpr int kGbtMaxD = 512;
 constexpr int kGbtMaxN = 1 << 30;
@@ -33,11 +30,6 @@ constexpr int kGbtHistMaxTf = 32;                       // features per block at
 constexpr double kGbtQ = 16777216.0;                    // 2^24
 constexpr long long kGbtOneQ = 1LL << 24;               // min_child_weight = 1 in table units
 constexpr double kGbtMinGain = 1e-6;
-
-struct GbtPlan {
-  int K;
-  int off[kGbtMaxK + 1];    // prefix sums of csize
-};
 
 // ---- (a) cuts and bins -----------------------------------------------------------------------------------------------
 // One thread per feature: candidates s[(j * N) / B], j = 1..B-1, keep the distinct values above s[0].
@@ -75,7 +67,7 @@ __global__ __launch_bounds__(256) void gbt_bin_kernel(const float* __restrict__ 
     const int mid = (lo + hi) >> 1;
     if (sc[mid] <= v) lo = mid + 1; else hi = mid;
   }
-  if (!(fabsf(v) <= FLT_MAX)) {
+  if (!finite_f(v)) {
     atomicOr(&flags[0], 1);
     lo = 0;
   }
@@ -85,7 +77,7 @@ __global__ __launch_bounds__(256) void gbt_bin_kernel(const float* __restrict__ 
 // ---- (b) gradients ---------------------------------------------------------------------------------------------------
 // One thread per (row, problem); the margins are class-major [csum][N], so a wave reads consecutive rows of one class.
 __global__ __launch_bounds__(256) void gbt_grad_kernel(const double* __restrict__ F, const int* __restrict__ y, int N,
-                                                       GbtPlan pl, const int* __restrict__ cvalid,
+                                                       SegPlan pl, const int* __restrict__ cvalid,
                                                        long long* __restrict__ gq, long long* __restrict__ hq,
                                                        double* __restrict__ gout, double* __restrict__ hout,
                                                        int* __restrict__ flags) {
@@ -323,7 +315,7 @@ __global__ __launch_bounds__(256) void gbt_margins_kernel(const uint8_t* __restr
 
 // ---- (f) predictions -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gbt_predict_kernel(const double* __restrict__ F, const int* __restrict__ y, int N,
-                                                          GbtPlan pl, const int* __restrict__ cvalid,
+                                                          SegPlan pl, const int* __restrict__ cvalid,
                                                           int* __restrict__ pred, unsigned long long* __restrict__ correct,
                                                           int* __restrict__ flags) {
   const int n = blockIdx.x * 256 + threadIdx.x, k = blockIdx.y;
@@ -350,7 +342,7 @@ __global__ __launch_bounds__(256) void gbt_predict_kernel(const double* __restri
 // One block per problem; a thread owns a feature and reads every node of the problem's trees in the order round, class,
 // node (all threads read the same word: one broadcast load per wave), so each total is an fp64 sum in that fixed order.
 __global__ __launch_bounds__(256) void gbt_importance_kernel(const int* __restrict__ tfeat,
-                                                             const double* __restrict__ tgain, int rounds, GbtPlan pl,
+                                                             const double* __restrict__ tgain, int rounds, SegPlan pl,
                                                              int D, double* __restrict__ imp) {
   __shared__ double raw[kGbtMaxD];
   __shared__ double total;
@@ -386,16 +378,9 @@ static int gbt_depth(const char* name, long long max_depth) {
   if (max_depth < 1 || max_depth > kGbtMaxDepth) return fail("%s: max_depth = %lld is outside 1..6", name, max_depth);
   return 0;
 }
-static int gbt_plan(const char* name, int K, const int* csize, GbtPlan* pl) {
-  if (K < 1 || K > kGbtMaxK) return fail("%s: K = %lld problems is outside 1..16", name, K);
-  if (!csize) return fail("%s: csize is NULL", name);
-  pl->K = K, pl->off[0] = 0;
-  for (int k = 0; k < K; ++k) {
-    if (csize[k] < 1 || csize[k] > kGbtMaxCsize)
-      return fail("%s: problem %lld has csize %lld, outside 1..256", name, k, csize[k]);
-    pl->off[k + 1] = pl->off[k] + csize[k];
-  }
-  return 0;
+static int gbt_plan(const char* name, int K, const int* csize, SegPlan* pl) {
+  const SegWords words = {"K = %lld problems", "csize is NULL", "problem %lld has csize %lld"};
+  return seg_plan(name, K, csize, kGbtMaxCsize, words, pl);
 }
 static inline size_t gbt_class_bytes(int D, int max_depth, int max_bin) {
   return ((size_t)1 << (max_depth - 1)) * D * max_bin * 2 * sizeof(long long);
@@ -436,7 +421,7 @@ int itcv_gbt_bin(const float* x, size_t ld, int N, int D, int max_bin, const flo
 
 int itcv_gbt_grad(const double* F, const int* y, int N, int K, const int* csize, const int* cvalid, long long* gq,
                   long long* hq, double* g, double* h, int* flags, void* stream) {
-  GbtPlan pl;
+  SegPlan pl;
   if (int e = gbt_plan("itcv_gbt_grad", K, csize, &pl)) return e;
   ITCV_REQUIRE(F && y && cvalid && gq && hq && flags && N >= 1 && N <= kGbtMaxN && (!g) == (!h), "itcv_gbt_grad");
   hipLaunchKernelGGL(gbt_grad_kernel, dim3(cdiv(N, 256), K), dim3(256), 0, S(stream), F, y, N, pl, cvalid, gq, hq, g, h,
@@ -507,7 +492,7 @@ int itcv_gbt_margins(const unsigned char* bins, int N, int csum, const int* cval
 
 int itcv_gbt_predict(const double* F, const int* y, int N, int K, const int* csize, const int* cvalid, int* pred,
                      unsigned long long* correct, int* flags, void* stream) {
-  GbtPlan pl;
+  SegPlan pl;
   if (int e = gbt_plan("itcv_gbt_predict", K, csize, &pl)) return e;
   ITCV_REQUIRE(F && y && cvalid && pred && correct && flags && N >= 1 && N <= kGbtMaxN, "itcv_gbt_predict");
   hipStream_t st = S(stream);
@@ -521,7 +506,7 @@ int itcv_gbt_predict(const double* F, const int* y, int N, int K, const int* csi
 
 int itcv_gbt_importance(const int* tfeat, const double* tgain, int rounds, int K, const int* csize, int D, double* imp,
                         void* stream) {
-  GbtPlan pl;
+  SegPlan pl;
   if (int e = gbt_plan("itcv_gbt_importance", K, csize, &pl)) return e;
   if (D < 1 || D > kGbtMaxD) return fail("%s: D = %lld features is outside 1..512", "itcv_gbt_importance", D);
   if (rounds < 1) return fail("%s: rounds = %lld is below 1", "itcv_gbt_importance", rounds);
@@ -541,7 +526,7 @@ int itcv_gbt_round(const unsigned char* bins, int N, int D, int max_bin, const i
   const char* name = "itcv_gbt_round";
   if (int e = gbt_shape(name, N, D, max_bin, 2)) return e;
   if (int e = gbt_depth(name, max_depth)) return e;
-  GbtPlan pl;
+  SegPlan pl;
   if (int e = gbt_plan(name, K, csize, &pl)) return e;
   const int csum = pl.off[K];
   ITCV_REQUIRE(bins && nbins && y && cvalid && F && gq && hq && node && nsum && tab && tfeat && tbin && tvalue && tgain &&

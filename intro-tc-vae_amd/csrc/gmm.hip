@@ -1,55 +1,41 @@
 // Ex-post latent density: a full-covariance Gaussian mixture on the device (Ghosh et al. 2020, section 4; the EM rules of
 // sklearn.mixture.GaussianMixture(covariance_type="full")).  The rules are in include/itcv_hip.h; all arithmetic is fp64
 // on fp32 rows x[N][D] (row stride ld):
-//   gmm_factor : one block per component: the Cholesky factor L_k of C_k in place (the loop of itcv_unsup_gauss), its
+//   gmm_factor : one block per component: the Cholesky factor L_k of C_k in place (block_cholesky of csrc/dense.h), its
 //                inverse by a right-looking forward substitution, the log-determinant; the matrix sits in LDS up to
-//                itcv_unsup_gauss_lds_dim(), above that the block works in the caller's buffer itself;
+//                kLdsMatrixDim, above that the block works in the caller's buffer itself;
 //   gmm_estep  : y = Linv_k (x - m_k) on v_mfma_f64_16x16x4_f64, one wave per 16 rows and one component, the tiles above
 //                the diagonal of Linv_k skipped, |y|^2 folded in ascending column order; then one thread per row takes
 //                the max-shifted log-sum-exp over ascending k and the last block folds the block sums in block order;
-//   gmm_mstep  : the weighted column sums (the slices and the wave order of itcv_unsup_cov), the means, then the weighted
-//                covariance of the centred values on the f64 matrix cores, one tile pair, row slice and component per wave;
+//   gmm_mstep  : the weighted column sums, the means, then the weighted covariance of the centred values on the f64 matrix
+//                cores, one tile pair, row slice and component per wave: the covariance pass of csrc/dense.h, which
+//                itcv_unsup_cov runs unweighted, so with K = 1 and unit responsibilities the M-step adds what that call
+//                adds, in its order (tests/test_hip_score_bits.py holds it to that);
 //   gmm_sample : z = (float)(m_k + L_k eps), one wave per row.
 // Every floating-point reduction has a fixed order that depends on the shapes alone, never on the grid; the only atomics
 // are integer ones (the flags, the counter that finds the last block).  Nothing in this file may be contracted into a
 // fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "dense.h"
 
 #pragma clang fp contract(off)
 
 namespace itcv {
 
-constexpr int kGmmMaxD = 512;
+constexpr int kGmmMaxD = kMatrixMaxDim;
 constexpr int kGmmMaxN = 1 << 24;
 constexpr int kGmmMaxK = 64;
-constexpr int kGmmSliceRows = 512;        // the slice rule of itcv_unsup_cov (csrc/unsup_scores.hip): with K = 1 and unit
-constexpr int kGmmMaxSlices = 64;         // responsibilities the M-step adds what that call adds, in its order
-constexpr int kFactorThreads = 1024;
 constexpr double kLog2Pi = 1.8378770664093453;
-
-typedef double gm_f64x4 __attribute__((ext_vector_type(4)));
-
-static inline int gmm_slice_rows(int N) {
-  int ns = cdiv(N, kGmmSliceRows);
-  if (ns > kGmmMaxSlices) ns = kGmmMaxSlices;
-  return cdiv(cdiv(N, ns), 4) * 4;
-}
-
-__device__ __forceinline__ bool gm_finite(float v) { return fabsf(v) <= FLT_MAX; }
 
 // ---- factor ------------------------------------------------------------------------------------------------------------
 // grid (component), 1024 threads.  A[D][lda] is the working matrix: LDS, or the component's own [D][D] of `chol` (a
 // __syncthreads orders the block's own global writes).  X = Linv is built in its output: X = I, then for k ascending row k
 // is divided by L[k][k] and L[i][k] X[k][j] is taken off X[i][j] for every i > k, j <= k.
 template <bool IN_LDS>
-__global__ __launch_bounds__(kFactorThreads) void gmm_factor_kernel(double* __restrict__ chol, int D,
+__global__ __launch_bounds__(kMatrixThreads) void gmm_factor_kernel(double* __restrict__ chol, int D,
                                                                     double* __restrict__ linv,
                                                                     double* __restrict__ logdet, int* __restrict__ info) {
   extern __shared__ double gm_lds[];
-  const int tid = threadIdx.x, T = kFactorThreads;
+  const int tid = threadIdx.x, T = kMatrixThreads;
   const int comp = blockIdx.x;
   double* G = chol + (size_t)comp * D * D;
   double* X = linv + (size_t)comp * D * D;
@@ -64,26 +50,7 @@ __global__ __launch_bounds__(kFactorThreads) void gmm_factor_kernel(double* __re
     }
   }
   __syncthreads();
-  // Cholesky, right-looking, lower triangle in place
-  int fail_dim = -1;
-  const int tx = tid & 31, ty = tid >> 5;
-  for (int j = 0; j < D; ++j) {
-    const double piv = A[(size_t)j * lda + j];
-    if (!(piv > 0.0) || !(piv <= DBL_MAX)) {          // block-uniform: every thread reads the same value
-      fail_dim = j;
-      break;
-    }
-    const double l = sqrt(piv);
-    __syncthreads();
-    if (tid == 0) A[(size_t)j * lda + j] = l;
-    for (int i = j + 1 + tid; i < D; i += T) A[(size_t)i * lda + j] = A[(size_t)i * lda + j] / l;
-    __syncthreads();
-    for (int i = j + 1 + ty; i < D; i += 32) {
-      const double lij = A[(size_t)i * lda + j];
-      for (int k = j + 1 + tx; k <= i; k += 32) A[(size_t)i * lda + k] = A[(size_t)i * lda + k] - lij * A[(size_t)k * lda + j];
-    }
-    __syncthreads();
-  }
+  const int fail_dim = block_cholesky<kMatrixThreads>(A, lda, D);
   if (fail_dim >= 0) {
     __syncthreads();
     for (int e = tid; e < D * D; e += T) G[e] = nan, X[e] = nan;
@@ -120,8 +87,7 @@ __global__ __launch_bounds__(kFactorThreads) void gmm_factor_kernel(double* __re
 }
 
 // ---- E-step ------------------------------------------------------------------------------------------------------------
-// grid (64-row tile, component), four waves of 16 rows.  f64 MFMA operand maps (csrc/unsup_scores.hip): lane l holds
-// A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; result register i of lane l is C[row (l >> 4) + 4 i][col l & 15].
+// grid (64-row tile, component), four waves of 16 rows.  The f64 MFMA operand maps are at f64x4 in csrc/dense.h.
 // Here A is the tile of centred rows (k runs over four columns j of x), B[j][i] = Linv[i][j] for the 16 outputs i of tile
 // ti, zero for j > i; the products run over j < min(D, 16 ti + 16) only.  The 16 x 16 results go through LDS so that one
 // lane per row adds y^2 in ascending column order.
@@ -146,13 +112,13 @@ __global__ __launch_bounds__(256) void gmm_logp_kernel(const float* __restrict__
     const int ci = ti * 16 + lr;
     const bool iok = ci < D;
     const int jend = min(D, ti * 16 + 16);
-    gm_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
     for (int j0 = 0; j0 < jend; j0 += 4) {
       const int j = j0 + lk;
       double a = 0.0, b = 0.0;
       if (rok && j < D) {
         const float v = x[(size_t)n * ld + j];
-        bad |= !gm_finite(v);
+        bad |= !finite_f(v);
         a = (double)v - mu[j];
       }
       if (iok && j <= ci) b = Li[(size_t)ci * D + j];
@@ -218,31 +184,18 @@ __global__ __launch_bounds__(256) void gmm_resp_kernel(const double* __restrict_
 }
 
 // ---- M-step ------------------------------------------------------------------------------------------------------------
-// grid (64-column tile of D + 1, row slice, component): column d < D adds resp x, column D adds resp.  Wave w takes rows
-// r0 + w, r0 + w + 4, ... in ascending order; the four are added in wave order (us_colsum_kernel).
+// grid (64-column tile of D + 1, row slice, component): the weighted block_colsum of the slice's rows; column d < D adds
+// resp x, column D adds resp.
 __global__ __launch_bounds__(256) void gmm_colsum_kernel(const float* __restrict__ x, size_t ld,
                                                          const double* __restrict__ resp, int N, int D, int K, int rows,
                                                          double* __restrict__ part, int* __restrict__ flags) {
   __shared__ double sm[4][64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int d = blockIdx.x * 64 + lane, comp = blockIdx.z;
+  const int d = blockIdx.x * 64 + (threadIdx.x & 63), comp = blockIdx.z;
   const int r0 = blockIdx.y * rows, r1 = min(N, r0 + rows);
-  double s = 0.0;
   bool bad = false;
-  if (d < D) {
-    for (int r = r0 + wid; r < r1; r += 4) {
-      const float v = x[(size_t)r * ld + d];
-      bad |= !gm_finite(v);
-      s += resp[(size_t)r * K + comp] * (double)v;
-    }
-  } else if (d == D) {
-    for (int r = r0 + wid; r < r1; r += 4) s += resp[(size_t)r * K + comp];
-  }
-  sm[wid][lane] = s;
+  const double s = block_colsum<true>(x, ld, d, D, r0, r1, resp + comp, (size_t)K, sm, &bad);
   if (bad) atomicOr(&flags[0], 1);
-  __syncthreads();
-  if (wid == 0 && d <= D)
-    part[((size_t)comp * gridDim.y + blockIdx.y) * (D + 1) + d] = ((sm[0][lane] + sm[1][lane]) + sm[2][lane]) + sm[3][lane];
+  if (threadIdx.x < 64 && d <= D) part[((size_t)comp * gridDim.y + blockIdx.y) * (D + 1) + d] = s;
 }
 // grid (256-column tile of D + 1, component): Nk = the slices in ascending order + 10 DBL_EPSILON, m = the slices / Nk; the
 // thread of column D writes Nk and w = Nk / (sum of every Nk, ascending).
@@ -262,32 +215,17 @@ __global__ __launch_bounds__(256) void gmm_mean_kernel(const double* __restrict_
     w[comp] = tot / all;
   }
 }
-// grid (tile pair ti <= tj, row slice, component), one wave: us_cov_tile_kernel with A = resp (x_i - m_i).
+// grid (tile pair ti <= tj, row slice, component), one wave: the weighted cov_tile_rows, A = resp (x_i - m_i).
 __global__ __launch_bounds__(64) void gmm_cov_tile_kernel(const float* __restrict__ x, size_t ld,
                                                           const double* __restrict__ resp, int N, int D, int K, int rows,
                                                           int nt, const double* __restrict__ mean,
                                                           double* __restrict__ part) {
-  const int lane = threadIdx.x, lr = lane & 15, lk = lane >> 4;
   const int comp = blockIdx.z;
-  int p = blockIdx.x, ti = 0;
-  while (p >= nt - ti) p -= nt - ti, ++ti;
-  const int tj = ti + p;
-  const int ci = ti * 16 + lr, cj = tj * 16 + lr;
-  const bool iok = ci < D, jok = cj < D;
-  const double* mu = mean + (size_t)comp * D;
-  const double mi = iok ? mu[ci] : 0.0, mj = jok ? mu[cj] : 0.0;
+  int ti, tj;
+  tile_pair(blockIdx.x, nt, &ti, &tj);
   const int r0 = blockIdx.y * rows, r1 = min(N, r0 + rows);
-  gm_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-  for (int r = r0; r < r1; r += 4) {
-    const int n = r + lk;
-    const bool rok = n < r1;
-    const double a = (rok && iok) ? resp[(size_t)n * K + comp] * ((double)x[(size_t)n * ld + ci] - mi) : 0.0;
-    const double b = (rok && jok) ? (double)x[(size_t)n * ld + cj] - mj : 0.0;
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-  }
-  double* out = part + (((size_t)comp * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 256;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) out[(lk + 4 * i) * 16 + lr] = acc[i];
+  const f64x4 acc = cov_tile_rows<true>(x, ld, D, ti, tj, r0, r1, mean + (size_t)comp * D, resp + comp, (size_t)K);
+  cov_tile_store(part + (((size_t)comp * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 256, acc);
 }
 // grid (tile pair, component): the slices in ascending order, divided by Nk, reg added on the diagonal; the upper triangle
 // is written and mirrored.
@@ -295,12 +233,8 @@ __global__ __launch_bounds__(256) void gmm_cov_fold_kernel(const double* __restr
                                                            int D, double reg, const double* __restrict__ nk,
                                                            double* __restrict__ cov) {
   const int comp = blockIdx.y;
-  int p = blockIdx.x, ti = 0;
-  while (p >= nt - ti) p -= nt - ti, ++ti;
-  const int tj = ti + p;
-  const int a = threadIdx.x >> 4, b = threadIdx.x & 15;
-  const int i = ti * 16 + a, j = tj * 16 + b;
-  if (i >= D || j >= D || (ti == tj && a > b)) return;
+  int i, j;
+  if (!cov_fold_element(blockIdx.x, nt, D, &i, &j)) return;
   const double s = fold_strided(0.0, part + ((size_t)comp * ns * npairs + blockIdx.x) * 256 + threadIdx.x,
                                 (size_t)npairs * 256, ns);
   double c = s / nk[comp];
@@ -335,9 +269,11 @@ __global__ __launch_bounds__(256) void gmm_sample_kernel(const double* __restric
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
+static int gmm_kd(const char* name, int D, int K) {
+  return need_dim(name, "K = %lld components", K, 1, kGmmMaxK, "1..64") || need_dim(name, "D = %lld", D, 1, kGmmMaxD, "1..512");
+}
 static int gmm_shape(const char* name, int N, int D, int K) {
-  if (K < 1 || K > kGmmMaxK) return fail("%s: K = %lld components is outside 1..64", name, K);
-  if (D < 1 || D > kGmmMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
+  if (gmm_kd(name, D, K)) return 1;
   if (N < K || N > kGmmMaxN) return fail("%s: N = %lld rows is outside K = %lld..2^24", name, N, K);
   return 0;
 }
@@ -350,7 +286,7 @@ struct MstepWs {
 };
 static inline MstepWs mstep_ws(int N, int D, int K, bool with_cov) {
   MstepWs w;
-  w.rows = gmm_slice_rows(N), w.ns = cdiv(N, w.rows);
+  w.rows = cov_slice_rows(N), w.ns = cdiv(N, w.rows);
   w.nt = cdiv(D, 16), w.npairs = w.nt * (w.nt + 1) / 2;
   w.sums = 0;
   w.part = w.sums + (size_t)K * w.ns * (D + 1) * sizeof(double);
@@ -367,15 +303,14 @@ extern "C" {
 
 int itcv_gmm_factor(double* chol, int K, int D, double* linv, double* logdet, int* info, void* stream) {
   const char* name = "itcv_gmm_factor";
-  if (K < 1 || K > kGmmMaxK) return fail("%s: K = %lld components is outside 1..64", name, K);
-  if (D < 1 || D > kGmmMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
+  if (gmm_kd(name, D, K)) return 1;
   ITCV_REQUIRE(chol && linv && logdet && info, name);
   hipStream_t st = S(stream);
-  if (D <= itcv_unsup_gauss_lds_dim())
-    launch_lds<gmm_factor_kernel<true>>(dim3(K), dim3(kFactorThreads), (size_t)D * (D | 1) * sizeof(double), st, chol, D,
+  if (D <= kLdsMatrixDim)
+    launch_lds<gmm_factor_kernel<true>>(dim3(K), dim3(kMatrixThreads), (size_t)D * (D | 1) * sizeof(double), st, chol, D,
                                         linv, logdet, info);
   else
-    hipLaunchKernelGGL(gmm_factor_kernel<false>, dim3(K), dim3(kFactorThreads), 0, st, chol, D, linv, logdet, info);
+    hipLaunchKernelGGL(gmm_factor_kernel<false>, dim3(K), dim3(kMatrixThreads), 0, st, chol, D, linv, logdet, info);
   ITCV_CHECK_LAUNCH(name);
   return 0;
 }
@@ -437,9 +372,7 @@ int itcv_gmm_mstep(const float* x, size_t ld, const double* resp, int N, int D, 
 int itcv_gmm_sample(const double* mean, const double* chol, const int* comp, const float* eps, int R, int D, int K,
                     float* z, int* flags, void* stream) {
   const char* name = "itcv_gmm_sample";
-  if (K < 1 || K > kGmmMaxK) return fail("%s: K = %lld components is outside 1..64", name, K);
-  if (D < 1 || D > kGmmMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
-  if (R < 1 || R > kGmmMaxN) return fail("%s: R = %lld rows is outside 1..2^24", name, R);
+  if (gmm_kd(name, D, K) || need_dim(name, "R = %lld rows", R, 1, kGmmMaxN, "1..2^24")) return 1;
   ITCV_REQUIRE(mean && chol && comp && eps && z && flags, name);
   hipLaunchKernelGGL(gmm_sample_kernel, dim3(cdiv(R, 4)), dim3(256), 0, S(stream), mean, chol, comp, eps, R, D, K, z,
                      flags);

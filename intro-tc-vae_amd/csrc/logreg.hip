@@ -9,14 +9,10 @@
 // The two GEMMs of valgrad (logits X.W and gradient X^T (P - Y)) run on v_mfma_f64_16x16x4_f64.  Every floating-point
 // reduction has a fixed order (per-block partials folded in ascending block order, no floating-point atomics); the pair
 // counts are integers.  Two calls with the same inputs return the same bits.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "dense.h"
 
 namespace itcv {
 
-constexpr int kLrMaxK = 16;
 constexpr int kLrMaxCsize = 256;
 constexpr int kLrMaxD = 512;
 constexpr int kLrMaxN = 1 << 30;
@@ -27,13 +23,6 @@ constexpr size_t kLrPartBudget = (size_t)256 << 20;   // bytes of partial gradie
 constexpr size_t kLrLdsTwoTiles = 96 * 1024;          // 32 rows per tile while the block's LDS stays below this
 constexpr int kAucRows = 256;           // rows i per block of the pair count (one per thread)
 constexpr int kAucTj = 16;              // rows j per LDS tile
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-struct LrPlan {
-  int K;
-  int coff[kLrMaxK + 1];   // prefix sums of the class counts; csum = coff[K]
-};
 
 // ---- column statistics ---------------------------------------------------------------------------------------------
 // grid (64-column tile, row slice).  center == nullptr: partial sums of x; else partial sums of (x - center)^2.
@@ -50,7 +39,7 @@ __global__ __launch_bounds__(256) void lr_colsum_part_kernel(const float* __rest
     const double c = center ? center[d] : 0.0;
     for (int r = r0 + wid; r < r1; r += 4) {
       const float v = x[(size_t)r * ld + d];
-      bad |= !(fabsf(v) <= FLT_MAX);
+      bad |= !finite_f(v);
       const double t = (double)v - c;
       s += center ? t * t : t;
     }
@@ -75,12 +64,11 @@ __global__ __launch_bounds__(256) void lr_colsum_fold_kernel(const double* __res
 //   logits   Z[rows][S_p] = Xs . W[:, seg_p] + b      (MFMA, A from LDS, B = theta from global / L2)      -> LDS
 //   softmax  over the valid classes of every row; R = P - Y (0 for rows whose label is not a valid class)   in place
 //   gradient G[D + 1][S_p] = [Xs 1]^T . R             (MFMA, both operands from LDS)   -> this block's partial gradient
-// f64 MFMA operand maps: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; result register i of lane l
-// is C[row (l >> 4) + 4 i][col l & 15].
+// The f64 MFMA operand maps are at f64x4 in csrc/dense.h.
 template <int MT, bool GRAD>
 __global__ __launch_bounds__(256) void lr_softmax_kernel(const float* __restrict__ x, size_t ld,
                                                          const double* __restrict__ mean, const double* __restrict__ scale,
-                                                         const int* __restrict__ y, int N, int D, LrPlan pl, int segmax,
+                                                         const int* __restrict__ y, int N, int D, SegPlan pl, int segmax,
                                                          const int* __restrict__ cvalid, const double* __restrict__ theta,
                                                          double* __restrict__ part, double* __restrict__ fpart,
                                                          int* __restrict__ cnt, double* __restrict__ P,
@@ -90,15 +78,15 @@ __global__ __launch_bounds__(256) void lr_softmax_kernel(const float* __restrict
   const int ldx = D | 1, ldz = segmax | 1;
   double* xs = lds;                                  // [RT][ldx]
   double* zs = xs + (size_t)RT * ldx;                // [RT][ldz]
-  double* fs = zs + (size_t)RT * ldz;                // [4][kLrMaxK]
-  int* cs = reinterpret_cast<int*>(fs + 4 * kLrMaxK);   // [4][kLrMaxK]
+  double* fs = zs + (size_t)RT * ldz;                // [4][kSegMaxK]
+  int* cs = reinterpret_cast<int*>(fs + 4 * kSegMaxK);   // [4][kSegMaxK]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int lr = lane & 15, lk = lane >> 4;
-  const int K = pl.K, csum = pl.coff[K];
+  const int K = pl.K, csum = pl.off[K];
   const int ntiles = cdiv(N, RT);
   const size_t gsz = (size_t)(D + 1) * csum;
   double* mypart = GRAD ? part + (size_t)blockIdx.x * gsz : nullptr;
-  if (tid < 4 * kLrMaxK) fs[tid] = 0.0, cs[tid] = 0;
+  if (tid < 4 * kSegMaxK) fs[tid] = 0.0, cs[tid] = 0;
   bool bad_x = false, bad_y = false;
 
   for (int t = blockIdx.x, it = 0; t < ntiles; t += gridDim.x, ++it) {
@@ -109,14 +97,14 @@ __global__ __launch_bounds__(256) void lr_softmax_kernel(const float* __restrict
       double v = 0.0;
       if (r0 + r < N) {
         const float xv = x[(size_t)(r0 + r) * ld + d];
-        bad_x |= !(fabsf(xv) <= FLT_MAX);
+        bad_x |= !finite_f(xv);
         v = (double)xv;
         if (mean) v = (v - mean[d]) / scale[d];
       }
       xs[(size_t)r * ldx + d] = v;
     }
     for (int p = 0; p < K; ++p) {
-      const int c0 = pl.coff[p], S = pl.coff[p + 1] - c0, nct = cdiv(S, 16);
+      const int c0 = pl.off[p], S = pl.off[p + 1] - c0, nct = cdiv(S, 16);
       __syncthreads();                               // xs is complete; zs of the previous problem is no longer read
       for (int u = wid; u < nct * MT; u += 4) {
         const int m = u % MT, ct = u / MT;
@@ -175,8 +163,8 @@ __global__ __launch_bounds__(256) void lr_softmax_kernel(const float* __restrict
             P[(size_t)row * csum + c0 + c] = (rok && cvalid[c0 + c]) ? exp(z[c] - mx) / se : 0.0;
         } else {
           if (rok && lane == 0) {
-            fs[wid * kLrMaxK + p] += (mx + log(se)) - z[yv];
-            cs[wid * kLrMaxK + p] += 1;
+            fs[wid * kSegMaxK + p] += (mx + log(se)) - z[yv];
+            cs[wid * kSegMaxK + p] += 1;
           }
           for (int c = lane; c < S; c += 64) {
             double g = 0.0;
@@ -218,8 +206,8 @@ __global__ __launch_bounds__(256) void lr_softmax_kernel(const float* __restrict
   if (GRAD) {
     __syncthreads();
     if (tid < K) {
-      fpart[(size_t)blockIdx.x * K + tid] = ((fs[tid] + fs[kLrMaxK + tid]) + fs[2 * kLrMaxK + tid]) + fs[3 * kLrMaxK + tid];
-      cnt[(size_t)blockIdx.x * K + tid] = cs[tid] + cs[kLrMaxK + tid] + cs[2 * kLrMaxK + tid] + cs[3 * kLrMaxK + tid];
+      fpart[(size_t)blockIdx.x * K + tid] = ((fs[tid] + fs[kSegMaxK + tid]) + fs[2 * kSegMaxK + tid]) + fs[3 * kSegMaxK + tid];
+      cnt[(size_t)blockIdx.x * K + tid] = cs[tid] + cs[kSegMaxK + tid] + cs[2 * kSegMaxK + tid] + cs[3 * kSegMaxK + tid];
     }
   }
 }
@@ -227,12 +215,12 @@ __global__ __launch_bounds__(256) void lr_softmax_kernel(const float* __restrict
 // One block per problem: n = its valid rows, lambda = m / (C n), f = data / n + (lambda / 2) sum_{valid c} |W_c|^2.
 // sc[p] = 1 / n (0 for a problem without rows), sc[K + p] = lambda.
 __global__ __launch_bounds__(256) void lr_fold_value_kernel(const double* __restrict__ fpart, const int* __restrict__ cnt,
-                                                            int nb, int D, LrPlan pl, const int* __restrict__ cvalid,
+                                                            int nb, int D, SegPlan pl, const int* __restrict__ cvalid,
                                                             const double* __restrict__ theta, double C,
                                                             double* __restrict__ f, double* __restrict__ sc) {
   __shared__ double scratch[4];
-  const int p = blockIdx.x, K = pl.K, csum = pl.coff[K];
-  const int c0 = pl.coff[p], S = pl.coff[p + 1] - c0;
+  const int p = blockIdx.x, K = pl.K, csum = pl.off[K];
+  const int c0 = pl.off[p], S = pl.off[p + 1] - c0;
   double w2 = 0.0;
   for (int e = threadIdx.x; e < D * S; e += 256) {
     const int d = e / S, c = e - d * S;
@@ -253,10 +241,10 @@ __global__ __launch_bounds__(256) void lr_fold_value_kernel(const double* __rest
   f[p] = data * inv + 0.5 * lam * w2;
   sc[p] = inv, sc[K + p] = lam;
 }
-__global__ __launch_bounds__(256) void lr_fold_grad_kernel(const double* __restrict__ part, int nb, int D, LrPlan pl,
+__global__ __launch_bounds__(256) void lr_fold_grad_kernel(const double* __restrict__ part, int nb, int D, SegPlan pl,
                                                            const int* __restrict__ cvalid, const double* __restrict__ theta,
                                                            const double* __restrict__ sc, double* __restrict__ grad) {
-  const int K = pl.K, csum = pl.coff[K];
+  const int K = pl.K, csum = pl.off[K];
   const size_t gsz = (size_t)(D + 1) * csum;
   const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= gsz) return;
@@ -266,7 +254,7 @@ __global__ __launch_bounds__(256) void lr_fold_grad_kernel(const double* __restr
     return;
   }
   int p = 0;
-  while (p + 1 < K && c >= pl.coff[p + 1]) ++p;
+  while (p + 1 < K && c >= pl.off[p + 1]) ++p;
   double g = fold_strided(0.0, part + e, gsz, nb) * sc[p];
   if (d < D) g += sc[K + p] * theta[e];
   grad[e] = g;
@@ -276,12 +264,12 @@ __global__ __launch_bounds__(256) void lr_fold_grad_kernel(const double* __restr
 // grid (256-row tile of i, problem, slice of j).  Thread i keeps s_i = P[i][y_i] and streams the rows j of its slice through
 // LDS; a pair counts when both labels are valid classes and differ.
 __global__ __launch_bounds__(kAucRows) void lr_auc_kernel(const double* __restrict__ P, const int* __restrict__ y, int N,
-                                                          LrPlan pl, const int* __restrict__ cvalid, int jrows,
+                                                          SegPlan pl, const int* __restrict__ cvalid, int jrows,
                                                           unsigned long long* __restrict__ count2,
                                                           unsigned long long* __restrict__ pos, int* __restrict__ flags) {
   extern __shared__ double tile[];                   // [kAucTj][S], then the labels [kAucTj]
-  const int p = blockIdx.y, K = pl.K, csum = pl.coff[K];
-  const int c0 = pl.coff[p], S = pl.coff[p + 1] - c0;
+  const int p = blockIdx.y, K = pl.K, csum = pl.off[K];
+  const int c0 = pl.off[p], S = pl.off[p + 1] - c0;
   int* yj = reinterpret_cast<int*>(tile + (size_t)kAucTj * S);
   const int tid = threadIdx.x, i = blockIdx.x * kAucRows + tid;
   int ci = -1;
@@ -322,10 +310,10 @@ __global__ __launch_bounds__(kAucRows) void lr_auc_kernel(const double* __restri
   }
 }
 // neg[c] = (valid rows of the problem) - pos[c] for a valid class, 0 otherwise
-__global__ __launch_bounds__(256) void lr_auc_neg_kernel(LrPlan pl, const int* __restrict__ cvalid,
+__global__ __launch_bounds__(256) void lr_auc_neg_kernel(SegPlan pl, const int* __restrict__ cvalid,
                                                          const unsigned long long* __restrict__ pos,
                                                          unsigned long long* __restrict__ neg) {
-  const int p = blockIdx.x, c0 = pl.coff[p], S = pl.coff[p + 1] - c0;
+  const int p = blockIdx.x, c0 = pl.off[p], S = pl.off[p + 1] - c0;
   unsigned long long n = 0;
   for (int c = 0; c < S; ++c) n += pos[c0 + c];
   for (int c = threadIdx.x; c < S; c += 256) neg[c0 + c] = cvalid[c0 + c] ? n - pos[c0 + c] : 0ull;
@@ -346,22 +334,17 @@ __global__ __launch_bounds__(256) void lr_zdiff_kernel(const float* __restrict__
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-static int lr_plan(const char* name, int N, int D, int K, const int* csize, LrPlan* pl, int* segmax) {
-  if (N < 1 || N > kLrMaxN) return fail("%s: N = %lld is outside 1..2^30", name, N);
-  if (D < 1 || D > kLrMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
-  if (K < 1 || K > kLrMaxK) return fail("%s: K = %lld problems is outside 1..16", name, K);
-  if (!csize) return fail("%s: no class counts", name);
-  pl->K = K, pl->coff[0] = 0, *segmax = 0;
-  for (int k = 0; k < K; ++k) {
-    if (csize[k] < 1 || csize[k] > kLrMaxCsize)
-      return fail("%s: problem %lld has %lld classes, outside 1..256", name, k, csize[k]);
-    pl->coff[k + 1] = pl->coff[k] + csize[k];
-    *segmax = csize[k] > *segmax ? csize[k] : *segmax;
-  }
+static int lr_plan(const char* name, int N, int D, int K, const int* csize, SegPlan* pl, int* segmax) {
+  const SegWords words = {"K = %lld problems", "no class counts", "problem %lld has %lld classes"};
+  if (need_dim(name, "N = %lld", N, 1, kLrMaxN, "1..2^30") || need_dim(name, "D = %lld", D, 1, kLrMaxD, "1..512") ||
+      seg_plan(name, K, csize, kLrMaxCsize, words, pl))
+    return 1;
+  *segmax = 0;
+  for (int k = 0; k < K; ++k) *segmax = csize[k] > *segmax ? csize[k] : *segmax;
   return 0;
 }
 static inline size_t lr_lds(int mt, int D, int segmax) {
-  return ((size_t)16 * mt * ((D | 1) + (segmax | 1)) + 4 * kLrMaxK) * sizeof(double) + 4 * kLrMaxK * sizeof(int);
+  return ((size_t)16 * mt * ((D | 1) + (segmax | 1)) + 4 * kSegMaxK) * sizeof(double) + 4 * kSegMaxK * sizeof(int);
 }
 static inline int lr_mt(int D, int segmax) { return lr_lds(2, D, segmax) <= kLrLdsTwoTiles ? 2 : 1; }
 static inline int lr_blocks(int N, int D, int csum, int mt) {
@@ -370,12 +353,6 @@ static inline int lr_blocks(int N, int D, int csum, int mt) {
   nb = nb > (size_t)kLrMaxBlocks ? kLrMaxBlocks : (nb < 1 ? 1 : nb);
   const int nt = cdiv(N, 16 * mt);
   return nt < (int)nb ? nt : (int)nb;
-}
-static inline int stat_slices(int N, int* rows) {
-  int r = kLrStatRows;
-  while (cdiv(N, r) > kLrStatMaxSlices) r *= 2;
-  *rows = r;
-  return cdiv(N, r);
 }
 struct LrWs {
   size_t part, fpart, cnt, sc, total;
@@ -407,7 +384,7 @@ extern "C" {
 size_t itcv_logreg_colstats_workspace(int N, int D) {
   if (N < 1 || N > kLrMaxN || D < 1) return 0;
   int rows;
-  return (size_t)stat_slices(N, &rows) * D * sizeof(double);
+  return (size_t)doubling_slices(N, kLrStatRows, kLrStatMaxSlices, &rows) * D * sizeof(double);
 }
 
 int itcv_logreg_colstats(const float* x, size_t ld, int N, int D, double* mean, double* scale, int* flags, void* ws,
@@ -415,7 +392,7 @@ int itcv_logreg_colstats(const float* x, size_t ld, int N, int D, double* mean, 
   ITCV_REQUIRE(x && mean && scale && flags && N >= 1 && N <= kLrMaxN && D >= 1 && ld >= (size_t)D, "itcv_logreg_colstats");
   ITCV_REQUIRE(ws && ws_bytes >= itcv_logreg_colstats_workspace(N, D), "itcv_logreg_colstats(workspace)");
   int rows;
-  const int ns = stat_slices(N, &rows), nct = cdiv(D, 64);
+  const int ns = doubling_slices(N, kLrStatRows, kLrStatMaxSlices, &rows), nct = cdiv(D, 64);
   double* part = static_cast<double*>(ws);
   hipStream_t st = S(stream);
   for (int mode = 0; mode < 2; ++mode) {
@@ -430,7 +407,7 @@ int itcv_logreg_colstats(const float* x, size_t ld, int N, int D, double* mean, 
 }
 
 size_t itcv_logreg_workspace(int N, int D, int K, int csum) {
-  if (N < 1 || N > kLrMaxN || D < 1 || D > kLrMaxD || K < 1 || K > kLrMaxK || csum < K || csum > K * kLrMaxCsize) return 0;
+  if (N < 1 || N > kLrMaxN || D < 1 || D > kLrMaxD || K < 1 || K > kSegMaxK || csum < K || csum > K * kLrMaxCsize) return 0;
   // the tile height depends on the largest class count: take the larger of the two possible block counts
   const int nb1 = lr_blocks(N, D, csum, 1), nb2 = lr_blocks(N, D, csum, 2);
   return lr_ws(nb1 > nb2 ? nb1 : nb2, D, csum, K).total;
@@ -439,12 +416,12 @@ size_t itcv_logreg_workspace(int N, int D, int K, int csum) {
 int itcv_logreg_valgrad(const float* x, size_t ld, const double* mean, const double* scale, const int* y, int N, int D,
                         int K, const int* csize, const int* cvalid, const double* theta, double C, double* f,
                         double* grad, int* flags, void* ws, size_t ws_bytes, void* stream) {
-  LrPlan pl;
+  SegPlan pl;
   int segmax;
   if (int e = lr_plan("itcv_logreg_valgrad", N, D, K, csize, &pl, &segmax)) return e;
   ITCV_REQUIRE(x && y && cvalid && theta && f && grad && flags && ld >= (size_t)D && (!mean) == (!scale) && C > 0.0,
                "itcv_logreg_valgrad");
-  const int csum = pl.coff[K], mt = lr_mt(D, segmax), nb = lr_blocks(N, D, csum, mt);
+  const int csum = pl.off[K], mt = lr_mt(D, segmax), nb = lr_blocks(N, D, csum, mt);
   const LrWs w = lr_ws(nb, D, csum, K);
   ITCV_REQUIRE(ws && ws_bytes >= w.total, "itcv_logreg_valgrad(workspace)");
   char* base = static_cast<char*>(ws);
@@ -469,7 +446,7 @@ int itcv_logreg_valgrad(const float* x, size_t ld, const double* mean, const dou
 int itcv_logreg_proba(const float* x, size_t ld, const double* mean, const double* scale, const int* y, int N, int D,
                       int K, const int* csize, const int* cvalid, const double* theta, double* P, int* pred, int* flags,
                       void* stream) {
-  LrPlan pl;
+  SegPlan pl;
   int segmax;
   if (int e = lr_plan("itcv_logreg_proba", N, D, K, csize, &pl, &segmax)) return e;
   ITCV_REQUIRE(x && y && cvalid && theta && P && pred && flags && ld >= (size_t)D && (!mean) == (!scale),
@@ -485,11 +462,11 @@ int itcv_logreg_proba(const float* x, size_t ld, const double* mean, const doubl
 int itcv_logreg_auc(const double* P, const int* y, int N, int K, const int* csize, const int* cvalid,
                     unsigned long long* count2, unsigned long long* pos, unsigned long long* neg, int* flags,
                     void* stream) {
-  LrPlan pl;
+  SegPlan pl;
   int segmax;
   if (int e = lr_plan("itcv_logreg_auc", N, 1, K, csize, &pl, &segmax)) return e;
   ITCV_REQUIRE(P && y && cvalid && count2 && pos && neg && flags, "itcv_logreg_auc");
-  const int csum = pl.coff[K];
+  const int csum = pl.off[K];
   hipStream_t st = S(stream);
   if (hipMemsetAsync(count2, 0, (size_t)csum * sizeof(unsigned long long), st) != hipSuccess ||
       hipMemsetAsync(pos, 0, (size_t)csum * sizeof(unsigned long long), st) != hipSuccess)

@@ -1,7 +1,7 @@
-// What the objective kernels share: dip.hip, mmd.hip, ada.hip, joint.hip, sup.hip and iwae.hip include this header;
-// quality.hip includes it for the host-side refusals alone.  Device side: the ordered block sum of their finish kernels, the mean KL of the local rows (dip, mmd)
-// and the fp64 reparameterised sample, its KL term and their gradient (ada, joint).  Host side: the capped row grid, the
-// finite test and the refusals that every entry point words alike.
+// What the objective kernels share: dip.hip, mmd.hip, ada.hip, joint.hip, sup.hip and iwae.hip include this header, and
+// nothing else does.  Device side: the ordered block sum of their finish kernels, the mean KL of the local rows (dip, mmd)
+// and the fp64 reparameterised sample, its KL term and their gradient (ada, joint).  Host side: the capped row grid.  The
+// host's finite test and the refusals that every entry point words alike are in common.h: nothing ties them to objectives.
 //
 // None of these files may contract a multiply and an add into a fused multiply-add -- that is what keeps their bits --
 // but they say so in different places: five at file scope, iwae.hip inside its fp64 bodies only.  So EVERY arithmetic
@@ -91,26 +91,6 @@ __device__ __forceinline__ double posterior_dlv(double g, double n, double l, do
 inline int row_grid(int rows, int rows_per_block, int max_blocks) {
   const int blocks = cdiv(rows, rows_per_block);
   return blocks < max_blocks ? blocks : max_blocks;
-}
-
-inline bool finite(double x) { return fabs(x) <= DBL_MAX; }   // false for NaN too
-
-// The refusals: each returns 0 when the call may go on; otherwise it leaves the message and returns fail()'s 1, so a chain
-// of them joined with || stops at the first failure.
-inline int need_pointers(const char* name, bool all) { return all ? 0 : fail("%s: a required pointer is NULL", name); }
-// `what` names the dimension with a %lld for its value ("B = %lld pairs"), `range` words lo..hi ("1..2^30")
-inline int need_dim(const char* name, const char* what, long long v, long long lo, long long hi, const char* range) {
-  if (v >= lo && v <= hi) return 0;
-  char fmt[128];
-  snprintf(fmt, sizeof(fmt), "%%s: %s is outside %s", what, range);
-  return fail(fmt, name, v);
-}
-// `whose` is "a" or the operand's name ("mu's"), `dim` the name of the width the stride has to cover
-inline int need_stride(const char* name, const char* whose, size_t ld, const char* dim, long long width) {
-  if (ld >= (size_t)width) return 0;
-  char fmt[128];
-  snprintf(fmt, sizeof(fmt), "%%s: %s row stride of %%lld is below %s = %%lld", whose, dim);
-  return fail(fmt, name, (long long)ld, width);
 }
 
 }  // namespace itcv

@@ -10,11 +10,11 @@
 //   poly_mmd  : a 64 x 64 tile of dot products a block on v_mfma_f64_16x16x4_f64 from the widened fp32 values, the kernel
 //               value and the tile's sum in the epilogue; a block walks the tiles b, b + G, ... (G a function of the
 //               shapes) and leaves one partial, one thread folds each sum's partials in ascending order;
-//   frechet   : ONE block: Cholesky of C1 + eps I, M = L^T (C2 + eps I) L, then the cyclic Jacobi iteration of
-//               unsup_scores.hip on M itself.
+//   frechet   : ONE block: Cholesky of C1 + eps I, M = L^T (C2 + eps I) L, then the cyclic Jacobi iteration on M itself
+//               (block_cholesky and block_jacobi of csrc/dense.h, which itcv_unsup_gauss runs too).
 // A selection does not depend on the visiting order and every floating-point sum has a fixed order that depends on the
 // shapes alone; there is no floating-point atomic.  Nothing in this file may be contracted into a fused multiply-add.
-#include "objective.h"
+#include "dense.h"
 
 #pragma clang fp contract(off)
 
@@ -34,15 +34,7 @@ constexpr int kQMaxSplits = 256;
 constexpr int kQFillBlocks = 1024;        // splits = 0: slices until the grid has this many blocks
 constexpr int kPolyTile = 64;
 constexpr int kPolyParts = 1024;          // partial sums of one of the three sums
-constexpr int kFrMaxD = 512;
-constexpr int kFrLdsDim = 128;            // = itcv_unsup_gauss_lds_dim(): 128 x 129 doubles
-constexpr int kFrThreads = 1024;
-constexpr int kFrMaxSweeps = 60;
-constexpr double kFrTol = 1e-14;
-
-typedef double q_f64x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool q_finite(float v) { return fabsf(v) <= FLT_MAX; }
+constexpr int kFrMaxD = kMatrixMaxDim;
 
 // rows [r0, r0 + R) x columns [d0, d0 + kQChunk) of src into s[R][kQLd]; rows from rend on and columns from D on are 0
 template <int R, int THREADS>
@@ -55,7 +47,7 @@ __device__ __forceinline__ bool q_load_rows(float (*s)[kQLd], const float* __res
     float v = 0.f;
     if (row < rend && d < D) {
       v = src[(size_t)row * ld + d];
-      bad |= !q_finite(v);
+      bad |= !finite_f(v);
     }
     s[r][dd] = v;
   }
@@ -204,9 +196,8 @@ __device__ __forceinline__ double q_poly(double dot, double gamma, double c0, in
 }
 
 // Block b takes the 64 x 64 tiles b, b + gridDim.x, ... of the NA x NB kernel matrix (tile t = ti * ntb + tj) and leaves
-// part[b] = the sum of their sums in that order.  Four waves, each a 32 x 32 quarter as 2 x 2 MFMA tiles; operand maps as in
-// us_cov_tile_kernel: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15], result register i of lane l
-// is C[row (l >> 4) + 4 i][col l & 15].  Tile sum: every lane adds its 16 elements in register order, the xor butterfly
+// part[b] = the sum of their sums in that order.  Four waves, each a 32 x 32 quarter as 2 x 2 MFMA tiles; the operand maps
+// are at f64x4 in csrc/dense.h.  Tile sum: every lane adds its 16 elements in register order, the xor butterfly
 // folds a wave, the four waves are added in wave order.  skip_diag leaves out the elements with row == col (a on a).
 __global__ __launch_bounds__(256) void q_poly_kernel(const float* __restrict__ a, size_t lda, int NA,
                                                      const float* __restrict__ b, size_t ldb, int NB, int D, int p,
@@ -221,11 +212,11 @@ __global__ __launch_bounds__(256) void q_poly_kernel(const float* __restrict__ a
   bool bad = false;
   for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int r0 = (int)(t / ntb) * kPolyTile, c0t = (int)(t % ntb) * kPolyTile;
-    q_f64x4 acc[2][2];
+    f64x4 acc[2][2];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-      for (int n = 0; n < 2; ++n) acc[m][n] = q_f64x4{0.0, 0.0, 0.0, 0.0};
+      for (int n = 0; n < 2; ++n) acc[m][n] = f64x4{0.0, 0.0, 0.0, 0.0};
     for (int d0 = 0; d0 < D; d0 += kQChunk) {
       __syncthreads();
       bad |= q_load_rows<kPolyTile, 256>(sa, a, lda, r0, NA, d0, D);
@@ -277,19 +268,17 @@ __global__ __launch_bounds__(64) void q_poly_finish_kernel(const double* __restr
 
 // ---- Frechet distance --------------------------------------------------------------------------------------------------
 // One block of 1024 threads.  A[D][lda] is the working matrix (LDS, or the third D x D block of the workspace); the first
-// two blocks of the workspace hold T = (C2 + eps I) L and M.  The Cholesky factorisation and the Jacobi sweep are those of
-// us_gauss_kernel, statement for statement; the sweep runs on M itself.
+// two blocks of the workspace hold T = (C2 + eps I) L and M.  The Cholesky factorisation and the Jacobi sweep are
+// block_cholesky and block_jacobi (csrc/dense.h); the sweep runs on M itself.
 template <bool IN_LDS>
-__global__ __launch_bounds__(kFrThreads) void q_frechet_kernel(const double* __restrict__ m1, const double* __restrict__ c1,
+__global__ __launch_bounds__(kMatrixThreads) void q_frechet_kernel(const double* __restrict__ m1, const double* __restrict__ c1,
                                                                const double* __restrict__ m2, const double* __restrict__ c2,
                                                                int D, double eps, double* __restrict__ ws,
                                                                double* __restrict__ res, double* __restrict__ eig,
                                                                int* __restrict__ info) {
   extern __shared__ double q_lds[];
-  __shared__ double rc[kFrMaxD / 2], rs[kFrMaxD / 2], npp[kFrMaxD / 2], nqq[kFrMaxD / 2];
-  __shared__ int pp[kFrMaxD / 2], qq[kFrMaxD / 2];
-  __shared__ double red[kFrThreads / 64];
-  const int tid = threadIdx.x, T = kFrThreads;
+  __shared__ JacobiScratch js;
+  const int tid = threadIdx.x, T = kMatrixThreads;
   const int lda = IN_LDS ? (D | 1) : D;
   double* A = IN_LDS ? q_lds : ws + 2 * (size_t)D * D;
   double* Tm = ws;
@@ -301,26 +290,7 @@ __global__ __launch_bounds__(kFrThreads) void q_frechet_kernel(const double* __r
     A[(size_t)i * lda + j] = i == j ? c1[e] + eps : c1[e];
   }
   __syncthreads();
-  // Cholesky, right-looking, lower triangle in place
-  int fail_dim = -1;
-  const int tx = tid & 31, ty = tid >> 5;
-  for (int j = 0; j < D; ++j) {
-    const double piv = A[(size_t)j * lda + j];
-    if (!(piv > 0.0) || !(piv <= DBL_MAX)) {          // block-uniform: every thread reads the same value
-      fail_dim = j;
-      break;
-    }
-    const double l = sqrt(piv);
-    __syncthreads();
-    if (tid == 0) A[(size_t)j * lda + j] = l;
-    for (int i = j + 1 + tid; i < D; i += T) A[(size_t)i * lda + j] = A[(size_t)i * lda + j] / l;
-    __syncthreads();
-    for (int i = j + 1 + ty; i < D; i += 32) {
-      const double lij = A[(size_t)i * lda + j];
-      for (int k = j + 1 + tx; k <= i; k += 32) A[(size_t)i * lda + k] = A[(size_t)i * lda + k] - lij * A[(size_t)k * lda + j];
-    }
-    __syncthreads();
-  }
+  const int fail_dim = block_cholesky<kMatrixThreads>(A, lda, D);
   if (fail_dim >= 0) {
     if (tid == 0) {
       info[0] = 1, info[1] = fail_dim, info[2] = 0, info[3] = 0, info[4] = 0;
@@ -355,75 +325,8 @@ __global__ __launch_bounds__(kFrThreads) void q_frechet_kernel(const double* __r
     A[(size_t)i * lda + j] = Mm[e];
   }
   __syncthreads();
-  // cyclic Jacobi, round-robin order: the rules of itcv_unsup_gauss
-  const int Dp = (D + 1) & ~1, np = Dp / 2, M = Dp - 1;
-  int sweeps = 0;
-  bool conv = false;
-  for (;;) {
-    double off = 0.0, tot = 0.0;
-    for (int e = tid; e < D * D; e += T) {
-      const int i = e / D, j = e - i * D;
-      const double v = A[(size_t)i * lda + j];
-      const double sq = v * v;
-      tot += sq;
-      if (i != j) off += sq;
-    }
-    off = block_sum(off, red);
-    tot = block_sum(tot, red);
-    if (sqrt(off) <= kFrTol * sqrt(tot)) {
-      conv = true;
-      break;
-    }
-    if (sweeps == kFrMaxSweeps) break;
-    for (int r = 0; r < M; ++r) {
-      if (tid < np) {
-        const int k = tid;
-        const int a = k == 0 ? r : (r + k) % M, b = k == 0 ? M : (r + M - k) % M;
-        const int p = min(a, b), q = max(a, b);
-        int po = -1;
-        if (q < D) {
-          const double apq = A[(size_t)p * lda + q];
-          if (apq != 0.0) {
-            const double app = A[(size_t)p * lda + p], aqq = A[(size_t)q * lda + q];
-            const double tau = (aqq - app) / (2.0 * apq);
-            const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            const double c = 1.0 / sqrt(1.0 + t * t);
-            rc[k] = c, rs[k] = t * c;
-            npp[k] = app - t * apq, nqq[k] = aqq + t * apq;
-            po = p;
-          }
-        }
-        pp[k] = po, qq[k] = q;
-      }
-      __syncthreads();
-      for (int e = tid; e < np * D; e += T) {          // rows p, q of J^T A
-        const int k = e / D, j = e - k * D;
-        const int p = pp[k];
-        if (p < 0) continue;
-        const int q = qq[k];
-        const double c = rc[k], s = rs[k];
-        const double ap = A[(size_t)p * lda + j], aq = A[(size_t)q * lda + j];
-        A[(size_t)p * lda + j] = c * ap - s * aq;
-        A[(size_t)q * lda + j] = s * ap + c * aq;
-      }
-      __syncthreads();
-      for (int e = tid; e < np * D; e += T) {          // columns p, q of (J^T A) J; the 2 x 2 block takes its closed form
-        const int i = e / np, k = e - i * np;
-        const int p = pp[k];
-        if (p < 0) continue;
-        const int q = qq[k];
-        const double c = rc[k], s = rs[k];
-        const double ap = A[(size_t)i * lda + p], aq = A[(size_t)i * lda + q];
-        double vp = c * ap - s * aq, vq = s * ap + c * aq;
-        if (i == p) vp = npp[k], vq = 0.0;
-        if (i == q) vp = 0.0, vq = nqq[k];
-        A[(size_t)i * lda + p] = vp;
-        A[(size_t)i * lda + q] = vq;
-      }
-      __syncthreads();
-    }
-    ++sweeps;
-  }
+  int sweeps;
+  const bool conv = block_jacobi<kMatrixThreads>(A, lda, D, &js, &sweeps);
   for (int d = tid; d < D; d += T) eig[d] = A[(size_t)d * lda + d];
   if (tid == 0) {
     double dm = 0.0, tr1 = 0.0, tr2 = 0.0, trs = 0.0;
@@ -561,7 +464,7 @@ int itcv_poly_mmd(const float* x, size_t ldx, const float* y, size_t ldy, int N,
 
 size_t itcv_frechet_workspace(int D) {
   if (D < 1 || D > kFrMaxD) return 0;
-  return (size_t)(D <= kFrLdsDim ? 2 : 3) * D * D * sizeof(double);
+  return (size_t)(D <= kLdsMatrixDim ? 2 : 3) * D * D * sizeof(double);
 }
 
 int itcv_frechet(const double* m1, const double* c1, const double* m2, const double* c2, int D, double eps, double* res,
@@ -572,11 +475,11 @@ int itcv_frechet(const double* m1, const double* c1, const double* m2, const dou
   if (need_pointers(name, m1 && c1 && m2 && c2 && res && eig && info)) return 1;
   ITCV_REQUIRE(ws && ws_bytes >= itcv_frechet_workspace(D), "itcv_frechet(workspace)");
   hipStream_t st = S(stream);
-  if (D <= kFrLdsDim)
-    launch_lds<q_frechet_kernel<true>>(dim3(1), dim3(kFrThreads), (size_t)D * (D | 1) * sizeof(double), st, m1, c1, m2, c2, D,
+  if (D <= kLdsMatrixDim)
+    launch_lds<q_frechet_kernel<true>>(dim3(1), dim3(kMatrixThreads), (size_t)D * (D | 1) * sizeof(double), st, m1, c1, m2, c2, D,
                                        eps, static_cast<double*>(ws), res, eig, info);
   else
-    hipLaunchKernelGGL(q_frechet_kernel<false>, dim3(1), dim3(kFrThreads), 0, st, m1, c1, m2, c2, D, eps,
+    hipLaunchKernelGGL(q_frechet_kernel<false>, dim3(1), dim3(kMatrixThreads), 0, st, m1, c1, m2, c2, D, eps,
                        static_cast<double*>(ws), res, eig, info);
   ITCV_CHECK_LAUNCH(name);
   return 0;

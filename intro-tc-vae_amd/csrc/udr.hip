@@ -16,16 +16,13 @@
 //               info[3].
 // Nothing depends on the grid or on timing: the same inputs give the same bits.  The only atomic is the integer OR that
 // raises the sticky non-finite flag.  Nothing in this file may be contracted into a fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "dense.h"
 
 #pragma clang fp contract(off)
 
 namespace itcv {
 
-constexpr int kUdrMaxD = 512;             // the limits of itcv_unsup_cov
+constexpr int kUdrMaxD = kMatrixMaxDim;   // the limits of itcv_unsup_cov
 constexpr int kUdrMaxN = 1 << 24;
 constexpr int kRankThreads = 1024;
 constexpr int kRankLdsRows = 32768;       // 128 KiB of keys; the in-place sort needs nothing else of the CU's 160 KiB
@@ -51,7 +48,7 @@ __global__ __launch_bounds__(kRankThreads) void udr_rank_kernel(const float* __r
   bool bad = false;
   for (int n = tid; n < N; n += T) {
     const float v = x[(size_t)n * ld + d];
-    bad |= !(fabsf(v) <= FLT_MAX);
+    bad |= !finite_f(v);
     keys[n] = rank_key(v);
   }
   if (bad) atomicOr(&flags[0], 1);
@@ -233,8 +230,8 @@ size_t itcv_udr_ranks_workspace(int N, int D) { return rank_shape_ok(N, D) ? ran
 int itcv_udr_ranks(const float* x, size_t ld, int N, int D, float* r2, int* flags, void* ws, size_t ws_bytes,
                    void* stream) {
   const char* name = "itcv_udr_ranks";
-  if (N < 2 || N > kUdrMaxN) return fail("%s: N = %lld rows is outside 2..2^24", name, N);
-  if (D < 1 || D > kUdrMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
+  if (need_dim(name, "N = %lld rows", N, 2, kUdrMaxN, "2..2^24") || need_dim(name, "D = %lld", D, 1, kUdrMaxD, "1..512"))
+    return 1;
   const size_t need = rank_ws(N, D);
   ITCV_REQUIRE(ws_bytes >= need && (need == 0 || ws), "itcv_udr_ranks(workspace)");
   ITCV_REQUIRE(x && r2 && flags && ld >= (size_t)D, name);

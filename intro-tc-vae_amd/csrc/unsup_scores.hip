@@ -5,7 +5,7 @@
 //                 16 x 16 tile pair and one row slice per wave; the slices are folded in ascending order and the lower
 //                 triangle is the mirror of the upper one;
 //   unsup_gauss : ONE block: Cholesky log-determinant of C, then the eigenvalues of S = D^1/2 C D^1/2 by a cyclic Jacobi
-//                 iteration with a round-robin rotation order; the matrix sits in LDS up to kGaussLdsDim, above that in a
+//                 iteration with a round-robin rotation order; the matrix sits in LDS up to kLdsMatrixDim, above that in a
 //                 global workspace;
 //   irs         : column means and largest deviations, the class counts, then one block per (factor value, 64 dimensions)
 //                 that finds the two order statistics of |x - e| EXACTLY by a radix select on the bit patterns of the
@@ -13,65 +13,29 @@
 // Every floating-point reduction has a fixed order that depends on the shapes alone, never on the grid; counts and maxima
 // go through integer atomics (order-free); there is no floating-point atomic.  Nothing in this file may be contracted
 // into a fused multiply-add.
-#include <float.h>
-#include <math.h>
-
-#include "common.h"
+#include "dense.h"
 
 #pragma clang fp contract(off)
 
 namespace itcv {
 
-constexpr int kUsMaxD = 512;
+constexpr int kUsMaxD = kMatrixMaxDim;
 constexpr int kUsMaxN = 1 << 24;
-constexpr int kUsMaxK = 16;
 constexpr int kUsMaxCsize = 256;
-constexpr int kCovSliceRows = 512;        // rows per slice while that gives at most kCovMaxSlices slices
-constexpr int kCovMaxSlices = 64;
-constexpr int kGaussLdsDim = 128;         // 128 x 129 doubles = 129 KiB of the CU's 160 KiB
-constexpr int kGaussThreads = 1024;
-constexpr int kJacobiMaxSweeps = 60;
-constexpr double kJacobiTol = 1e-14;
 constexpr int kIrsThreads = 1024;         // 16 row lanes x 64 dimensions
 constexpr int kIrsRowLanes = kIrsThreads / 64;
 
-typedef double us_f64x4 __attribute__((ext_vector_type(4)));
-
-struct UsPlan {
-  int K;
-  int coff[kUsMaxK + 1];   // prefix sums of the factor sizes; fsum = coff[K]
-};
-
-// rows per slice and number of slices: a function of N alone
-static inline int cov_slice_rows(int N) {
-  int ns = cdiv(N, kCovSliceRows);
-  if (ns > kCovMaxSlices) ns = kCovMaxSlices;
-  return cdiv(cdiv(N, ns), 4) * 4;
-}
-
-__device__ __forceinline__ bool us_finite(float v) { return fabsf(v) <= FLT_MAX; }
-
 // ---- column means ----------------------------------------------------------------------------------------------------
-// grid (64-column tile, row slice): wave w sums rows r0 + w, r0 + w + 4, ... in ascending order; the four are added in
-// wave order.
+// grid (64-column tile, row slice): block_colsum of the slice's rows
 __global__ __launch_bounds__(256) void us_colsum_kernel(const float* __restrict__ x, size_t ld, int N, int D, int rows,
                                                         double* __restrict__ part, int* __restrict__ flags) {
   __shared__ double sm[4][64];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int d = blockIdx.x * 64 + lane;
+  const int d = blockIdx.x * 64 + (threadIdx.x & 63);
   const int r0 = blockIdx.y * rows, r1 = min(N, r0 + rows);
-  double s = 0.0;
   bool bad = false;
-  if (d < D)
-    for (int r = r0 + wid; r < r1; r += 4) {
-      const float v = x[(size_t)r * ld + d];
-      bad |= !us_finite(v);
-      s += (double)v;
-    }
-  sm[wid][lane] = s;
+  const double s = block_colsum<false>(x, ld, d, D, r0, r1, nullptr, 0, sm, &bad);
   if (bad && flags) atomicOr(&flags[0], 1);
-  __syncthreads();
-  if (wid == 0 && d < D) part[(size_t)blockIdx.y * D + d] = ((sm[0][lane] + sm[1][lane]) + sm[2][lane]) + sm[3][lane];
+  if (threadIdx.x < 64 && d < D) part[(size_t)blockIdx.y * D + d] = s;
 }
 __global__ __launch_bounds__(256) void us_mean_kernel(const double* __restrict__ part, int ns, int D, int N,
                                                       double* __restrict__ mean) {
@@ -80,42 +44,21 @@ __global__ __launch_bounds__(256) void us_mean_kernel(const double* __restrict__
 }
 
 // ---- covariance ------------------------------------------------------------------------------------------------------
-// grid (tile pair ti <= tj, row slice), one wave.  f64 MFMA operand maps (csrc/logreg.hip): lane l holds A[row l & 15]
-// [k = l >> 4] and B[k = l >> 4][col l & 15]; result register i of lane l is C[row (l >> 4) + 4 i][col l & 15].  Here A
-// is the transposed tile of centred columns ti, B the tile of centred columns tj, k runs over four rows of x per product;
-// rows past the slice and columns past D enter as zeros.
+// grid (tile pair ti <= tj, row slice), one wave: cov_tile_rows of the slice's rows (csrc/dense.h)
 __global__ __launch_bounds__(64) void us_cov_tile_kernel(const float* __restrict__ x, size_t ld, int N, int D, int rows,
                                                          int nt, const double* __restrict__ mean,
                                                          double* __restrict__ part) {
-  const int lane = threadIdx.x, lr = lane & 15, lk = lane >> 4;
-  int p = blockIdx.x, ti = 0;
-  while (p >= nt - ti) p -= nt - ti, ++ti;
-  const int tj = ti + p;
-  const int ci = ti * 16 + lr, cj = tj * 16 + lr;
-  const bool iok = ci < D, jok = cj < D;
-  const double mi = iok ? mean[ci] : 0.0, mj = jok ? mean[cj] : 0.0;
+  int ti, tj;
+  tile_pair(blockIdx.x, nt, &ti, &tj);
   const int r0 = blockIdx.y * rows, r1 = min(N, r0 + rows);
-  us_f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-  for (int r = r0; r < r1; r += 4) {
-    const int n = r + lk;
-    const bool rok = n < r1;
-    const double a = (rok && iok) ? (double)x[(size_t)n * ld + ci] - mi : 0.0;
-    const double b = (rok && jok) ? (double)x[(size_t)n * ld + cj] - mj : 0.0;
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-  }
-  double* out = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) out[(lk + 4 * i) * 16 + lr] = acc[i];
+  const f64x4 acc = cov_tile_rows<false>(x, ld, D, ti, tj, r0, r1, mean, nullptr, 0);
+  cov_tile_store(part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256, acc);
 }
 // grid (tile pair): the slices in ascending order, divided by N - 1; the upper triangle is written and mirrored.
 __global__ __launch_bounds__(256) void us_cov_fold_kernel(const double* __restrict__ part, int ns, int npairs, int nt, int N,
                                                           int D, double* __restrict__ cov) {
-  int p = blockIdx.x, ti = 0;
-  while (p >= nt - ti) p -= nt - ti, ++ti;
-  const int tj = ti + p;
-  const int a = threadIdx.x >> 4, b = threadIdx.x & 15;
-  const int i = ti * 16 + a, j = tj * 16 + b;
-  if (i >= D || j >= D || (ti == tj && a > b)) return;
+  int i, j;
+  if (!cov_fold_element(blockIdx.x, nt, D, &i, &j)) return;
   const double s = fold_strided(0.0, part + (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)npairs * 256, ns);
   const double c = s / (double)(N - 1);
   cov[(size_t)i * D + j] = c;
@@ -127,15 +70,13 @@ __global__ __launch_bounds__(256) void us_cov_fold_kernel(const double* __restri
 // block's own global writes).  res[5] = {tc, w, w / tr C, tr C, logdet C}; eig[D] = the diagonal of S after the last
 // sweep; info[4] = {pivot failed, its dimension, Jacobi not converged, sweeps taken}.
 template <bool IN_LDS>
-__global__ __launch_bounds__(kGaussThreads) void us_gauss_kernel(const double* __restrict__ cov, int D,
-                                                                 double* __restrict__ wsA, double* __restrict__ res,
-                                                                 double* __restrict__ eig, int* __restrict__ info) {
+__global__ __launch_bounds__(kMatrixThreads) void us_gauss_kernel(const double* __restrict__ cov, int D,
+                                                                  double* __restrict__ wsA, double* __restrict__ res,
+                                                                  double* __restrict__ eig, int* __restrict__ info) {
   extern __shared__ double us_lds[];
   __shared__ double sd[kUsMaxD];
-  __shared__ double rc[kUsMaxD / 2], rs[kUsMaxD / 2], npp[kUsMaxD / 2], nqq[kUsMaxD / 2];
-  __shared__ int pp[kUsMaxD / 2], qq[kUsMaxD / 2];
-  __shared__ double red[kGaussThreads / 64];
-  const int tid = threadIdx.x, T = kGaussThreads;
+  __shared__ JacobiScratch js;
+  const int tid = threadIdx.x, T = kMatrixThreads;
   const int lda = IN_LDS ? (D | 1) : D;
   double* A = IN_LDS ? us_lds : wsA;
   const double nan = __builtin_nan("");
@@ -145,26 +86,7 @@ __global__ __launch_bounds__(kGaussThreads) void us_gauss_kernel(const double* _
     A[(size_t)i * lda + j] = cov[e];
   }
   __syncthreads();
-  // Cholesky, right-looking, lower triangle in place
-  int fail_dim = -1;
-  const int tx = tid & 31, ty = tid >> 5;
-  for (int j = 0; j < D; ++j) {
-    const double piv = A[(size_t)j * lda + j];
-    if (!(piv > 0.0) || !(piv <= DBL_MAX)) {          // block-uniform: every thread reads the same value
-      fail_dim = j;
-      break;
-    }
-    const double l = sqrt(piv);
-    __syncthreads();
-    if (tid == 0) A[(size_t)j * lda + j] = l;
-    for (int i = j + 1 + tid; i < D; i += T) A[(size_t)i * lda + j] = A[(size_t)i * lda + j] / l;
-    __syncthreads();
-    for (int i = j + 1 + ty; i < D; i += 32) {
-      const double lij = A[(size_t)i * lda + j];
-      for (int k = j + 1 + tx; k <= i; k += 32) A[(size_t)i * lda + k] = A[(size_t)i * lda + k] - lij * A[(size_t)k * lda + j];
-    }
-    __syncthreads();
-  }
+  const int fail_dim = block_cholesky<kMatrixThreads>(A, lda, D);
   if (fail_dim >= 0) {
     if (tid == 0) {
       info[0] = 1, info[1] = fail_dim, info[2] = 0, info[3] = 0;
@@ -195,77 +117,8 @@ __global__ __launch_bounds__(kGaussThreads) void us_gauss_kernel(const double* _
     }
   }
   __syncthreads();
-  // cyclic Jacobi; round r of a sweep rotates the disjoint pairs of the round-robin schedule on Dp = D rounded up to even:
-  // (r, Dp - 1) and ((r + k) mod (Dp - 1), (r - k) mod (Dp - 1)), k = 1 .. Dp / 2 - 1; a pair that touches index D (odd D)
-  // or whose off-diagonal element is exactly 0 is skipped
-  const int Dp = (D + 1) & ~1, np = Dp / 2, M = Dp - 1;
-  int sweeps = 0;
-  bool conv = false;
-  for (;;) {
-    double off = 0.0, tot = 0.0;
-    for (int e = tid; e < D * D; e += T) {
-      const int i = e / D, j = e - i * D;
-      const double v = A[(size_t)i * lda + j];
-      const double sq = v * v;
-      tot += sq;
-      if (i != j) off += sq;
-    }
-    off = block_sum(off, red);
-    tot = block_sum(tot, red);
-    if (sqrt(off) <= kJacobiTol * sqrt(tot)) {
-      conv = true;
-      break;
-    }
-    if (sweeps == kJacobiMaxSweeps) break;
-    for (int r = 0; r < M; ++r) {
-      if (tid < np) {
-        const int k = tid;
-        const int a = k == 0 ? r : (r + k) % M, b = k == 0 ? M : (r + M - k) % M;
-        const int p = min(a, b), q = max(a, b);
-        int po = -1;
-        if (q < D) {
-          const double apq = A[(size_t)p * lda + q];
-          if (apq != 0.0) {
-            const double app = A[(size_t)p * lda + p], aqq = A[(size_t)q * lda + q];
-            const double tau = (aqq - app) / (2.0 * apq);
-            const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            const double c = 1.0 / sqrt(1.0 + t * t);
-            rc[k] = c, rs[k] = t * c;
-            npp[k] = app - t * apq, nqq[k] = aqq + t * apq;
-            po = p;
-          }
-        }
-        pp[k] = po, qq[k] = q;
-      }
-      __syncthreads();
-      for (int e = tid; e < np * D; e += T) {          // rows p, q of J^T A
-        const int k = e / D, j = e - k * D;
-        const int p = pp[k];
-        if (p < 0) continue;
-        const int q = qq[k];
-        const double c = rc[k], s = rs[k];
-        const double ap = A[(size_t)p * lda + j], aq = A[(size_t)q * lda + j];
-        A[(size_t)p * lda + j] = c * ap - s * aq;
-        A[(size_t)q * lda + j] = s * ap + c * aq;
-      }
-      __syncthreads();
-      for (int e = tid; e < np * D; e += T) {          // columns p, q of (J^T A) J; the 2 x 2 block takes its closed form
-        const int i = e / np, k = e - i * np;
-        const int p = pp[k];
-        if (p < 0) continue;
-        const int q = qq[k];
-        const double c = rc[k], s = rs[k];
-        const double ap = A[(size_t)i * lda + p], aq = A[(size_t)i * lda + q];
-        double vp = c * ap - s * aq, vq = s * ap + c * aq;
-        if (i == p) vp = npp[k], vq = 0.0;
-        if (i == q) vp = 0.0, vq = nqq[k];
-        A[(size_t)i * lda + p] = vp;
-        A[(size_t)i * lda + q] = vq;
-      }
-      __syncthreads();
-    }
-    ++sweeps;
-  }
+  int sweeps;
+  const bool conv = block_jacobi<kMatrixThreads>(A, lda, D, &js, &sweeps);
   for (int d = tid; d < D; d += T) eig[d] = A[(size_t)d * lda + d];
   if (tid == 0) {
     double ws = 0.0;
@@ -282,15 +135,15 @@ __global__ __launch_bounds__(kGaussThreads) void us_gauss_kernel(const double* _
 
 // ---- IRS -------------------------------------------------------------------------------------------------------------
 // class counts of every factor (integer atomics; cleared by the host) and the range check of the factor values
-__global__ __launch_bounds__(256) void irs_count_kernel(const int* __restrict__ v, int N, UsPlan pl, int* __restrict__ cnt,
+__global__ __launch_bounds__(256) void irs_count_kernel(const int* __restrict__ v, int N, SegPlan pl, int* __restrict__ cnt,
                                                         int* __restrict__ flags) {
   const int K = pl.K;
   const size_t total = (size_t)N * K;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
     const int k = (int)(e % K);
     const int val = v[e];
-    if ((unsigned)val < (unsigned)(pl.coff[k + 1] - pl.coff[k]))
-      atomicAdd(&cnt[pl.coff[k] + val], 1);
+    if ((unsigned)val < (unsigned)(pl.off[k + 1] - pl.off[k]))
+      atomicAdd(&cnt[pl.off[k] + val], 1);
     else
       atomicOr(&flags[1], 1);
   }
@@ -326,7 +179,7 @@ __global__ __launch_bounds__(256) void irs_maxdev_kernel(const float* __restrict
 // largest P with #{a < P} <= lo, which is a[lo] itself; one more pass gives a[hi].
 __global__ __launch_bounds__(kIrsThreads) void irs_group_kernel(const float* __restrict__ x, size_t ld,
                                                                 const int* __restrict__ order,
-                                                                const int* __restrict__ cnt, int N, int D, UsPlan pl,
+                                                                const int* __restrict__ cnt, int N, int D, SegPlan pl,
                                                                 double q, double* __restrict__ Qs,
                                                                 int* __restrict__ flags) {
   __shared__ double part[kIrsRowLanes][64];
@@ -336,7 +189,7 @@ __global__ __launch_bounds__(kIrsThreads) void irs_group_kernel(const float* __r
   const int tid = threadIdx.x, dl = tid & 63, rl = tid >> 6;
   const int slot = blockIdx.x;
   int k = 0;
-  while (pl.coff[k + 1] <= slot) ++k;
+  while (pl.off[k + 1] <= slot) ++k;
   const int d = blockIdx.y * 64 + dl;
   const bool live = d < D;
   const int n = cnt[slot];
@@ -345,7 +198,7 @@ __global__ __launch_bounds__(kIrsThreads) void irs_group_kernel(const float* __r
     return;
   }
   int start = 0;
-  for (int u = pl.coff[k]; u < slot; ++u) start += cnt[u];
+  for (int u = pl.off[k]; u < slot; ++u) start += cnt[u];
   if (start + n > N) {                                // cannot happen with counts of this call; keeps every read inside
     if (tid == 0) atomicOr(&flags[1], 1);
     return;
@@ -420,7 +273,7 @@ __global__ __launch_bounds__(kIrsThreads) void irs_group_kernel(const float* __r
 // One block, a thread per dimension: cum, M = 1 - cum / maxdev, the row maxima and their first arg-max; thread 0 then adds
 // the weighted scores of the active dimensions in ascending d.  res = {IRS, number of active dimensions}.
 __global__ __launch_bounds__(kUsMaxD) void irs_final_kernel(const double* __restrict__ Qs, const int* __restrict__ cnt,
-                                                            UsPlan pl, int D, const float* __restrict__ mn,
+                                                            SegPlan pl, int D, const float* __restrict__ mn,
                                                             const float* __restrict__ mx,
                                                             const double* __restrict__ maxdev, double* __restrict__ cum,
                                                             double* __restrict__ Mo, double* __restrict__ score,
@@ -437,7 +290,7 @@ __global__ __launch_bounds__(kUsMaxD) void irs_final_kernel(const double* __rest
     for (int k = 0; k < K; ++k) {
       double sq = 0.0;
       int present = 0;
-      for (int u = pl.coff[k]; u < pl.coff[k + 1]; ++u)
+      for (int u = pl.off[k]; u < pl.off[k + 1]; ++u)
         if (cnt[u] > 0) sq += Qs[(size_t)u * D + d], ++present;
       const double c = sq / (double)present;
       const double m = on ? 1.0 - c / md : 0.0;
@@ -461,9 +314,8 @@ __global__ __launch_bounds__(kUsMaxD) void irs_final_kernel(const double* __rest
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 static int us_shape(const char* name, int N, int D, int minN) {
-  if (N < minN || N > kUsMaxN) return fail(minN == 2 ? "%s: N = %lld rows is outside 2..2^24" : "%s: N = %lld rows is outside 1..2^24", name, N);
-  if (D < 1 || D > kUsMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
-  return 0;
+  return need_dim(name, "N = %lld rows", N, minN, kUsMaxN, minN == 2 ? "2..2^24" : "1..2^24") ||
+         need_dim(name, "D = %lld", D, 1, kUsMaxD, "1..512");
 }
 struct CovWs {
   int rows, ns, nt, npairs;
@@ -500,17 +352,7 @@ static inline IrsWs irs_ws(int N, int D, int fsum) {
   w.total = w.cnt + (size_t)fsum * sizeof(int);
   return w;
 }
-static int us_plan(const char* name, int K, const int* fsize, UsPlan* pl) {
-  if (K < 1 || K > kUsMaxK) return fail("%s: K = %lld factors is outside 1..16", name, K);
-  if (!fsize) return fail("%s: no factor sizes", name);
-  pl->K = K, pl->coff[0] = 0;
-  for (int k = 0; k < K; ++k) {
-    if (fsize[k] < 1 || fsize[k] > kUsMaxCsize)
-      return fail("%s: factor %lld has %lld values, outside 1..256", name, k, fsize[k]);
-    pl->coff[k + 1] = pl->coff[k] + fsize[k];
-  }
-  return 0;
-}
+constexpr SegWords kUsWords = {"K = %lld factors", "no factor sizes", "factor %lld has %lld values"};
 
 }  // namespace itcv
 
@@ -544,7 +386,7 @@ int itcv_unsup_cov(const float* x, size_t ld, int N, int D, double* mean, double
   return 0;
 }
 
-int itcv_unsup_gauss_lds_dim(void) { return kGaussLdsDim; }
+int itcv_unsup_gauss_lds_dim(void) { return kLdsMatrixDim; }
 
 size_t itcv_unsup_gauss_workspace(int D) {
   if (D < 1 || D > kUsMaxD) return 0;
@@ -554,15 +396,15 @@ size_t itcv_unsup_gauss_workspace(int D) {
 int itcv_unsup_gauss(const double* cov, int D, double* res, double* eig, int* info, void* ws, size_t ws_bytes,
                      void* stream) {
   const char* name = "itcv_unsup_gauss";
-  if (D < 1 || D > kUsMaxD) return fail("%s: D = %lld is outside 1..512", name, D);
+  if (need_dim(name, "D = %lld", D, 1, kUsMaxD, "1..512")) return 1;
   ITCV_REQUIRE(cov && res && eig && info, name);
   hipStream_t st = S(stream);
-  if (D <= kGaussLdsDim) {
-    launch_lds<us_gauss_kernel<true>>(dim3(1), dim3(kGaussThreads), (size_t)D * (D | 1) * sizeof(double), st, cov, D,
+  if (D <= kLdsMatrixDim) {
+    launch_lds<us_gauss_kernel<true>>(dim3(1), dim3(kMatrixThreads), (size_t)D * (D | 1) * sizeof(double), st, cov, D,
                                       (double*)nullptr, res, eig, info);
   } else {
     ITCV_REQUIRE(ws && ws_bytes >= (size_t)D * D * sizeof(double), "itcv_unsup_gauss(workspace)");
-    hipLaunchKernelGGL(us_gauss_kernel<false>, dim3(1), dim3(kGaussThreads), 0, st, cov, D, static_cast<double*>(ws), res,
+    hipLaunchKernelGGL(us_gauss_kernel<false>, dim3(1), dim3(kMatrixThreads), 0, st, cov, D, static_cast<double*>(ws), res,
                        eig, info);
   }
   ITCV_CHECK_LAUNCH(name);
@@ -570,7 +412,7 @@ int itcv_unsup_gauss(const double* cov, int D, double* res, double* eig, int* in
 }
 
 size_t itcv_irs_workspace(int N, int D, int K, int fsum) {
-  if (N < 1 || N > kUsMaxN || D < 1 || D > kUsMaxD || K < 1 || K > kUsMaxK || fsum < K || fsum > K * kUsMaxCsize) return 0;
+  if (N < 1 || N > kUsMaxN || D < 1 || D > kUsMaxD || K < 1 || K > kSegMaxK || fsum < K || fsum > K * kUsMaxCsize) return 0;
   return irs_ws(N, D, fsum).total;
 }
 
@@ -579,13 +421,13 @@ int itcv_irs(const float* x, size_t ld, const int* v, const int* order, int N, i
              int* active, double* res, int* flags, void* ws, size_t ws_bytes, void* stream) {
   const char* name = "itcv_irs";
   if (int e = us_shape(name, N, D, 1)) return e;
-  UsPlan pl;
-  if (int e = us_plan(name, K, fsize, &pl)) return e;
+  SegPlan pl;
+  if (int e = seg_plan(name, K, fsize, kUsMaxCsize, kUsWords, &pl)) return e;
   if (!(q >= 0.0 && q <= 1.0)) return fail("%s: the quantile lies outside [0, 1]", name);
   ITCV_REQUIRE(x && v && order && mn && mx && maxdev && cum && M && score && parent && active && res && flags &&
                    ld >= (size_t)D,
                name);
-  const int fsum = pl.coff[K];
+  const int fsum = pl.off[K];
   const IrsWs w = irs_ws(N, D, fsum);
   ITCV_REQUIRE(ws && ws_bytes >= w.total, "itcv_irs(workspace)");
   const CovWs c = cov_ws(N, D);

@@ -138,7 +138,10 @@ def test_entry_points_declared_bound_and_exported():
     assert abi.ABI_VERSION == 4
     assert "unsup_scores.hip" in open(os.path.join(ROOT, "intro-tc-vae_amd", "csrc", "Makefile")).read()
     hip = open(os.path.join(ROOT, "intro-tc-vae_amd", "csrc", "unsup_scores.hip")).read()
-    assert "#pragma clang fp contract(off)" in hip and "mfma_f64_16x16x4f64" in hip
+    dense = open(os.path.join(ROOT, "intro-tc-vae_amd", "csrc", "dense.h")).read()         # the covariance pass lives there
+    assert "#pragma clang fp contract(off)" in hip and '#include "dense.h"' in hip and "cov_tile_rows<false>" in hip
+    tile = dense.split("cov_tile_rows(")[1].split("\n}\n")[0]
+    assert "#pragma clang fp contract(off)" in tile and "mfma_f64_16x16x4f64" in tile
 
 
 def test_library_refuses_before_any_launch():
