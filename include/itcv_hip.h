@@ -660,6 +660,50 @@ int itcv_iwae_combine_bwd(const float* g, const double* wt, double beta_rec, dou
 int itcv_iwae_accumulate(const float* rows, const double* lat, double beta_rec, double beta_kl, double* state, int B, int K,
                          void* stream);
 int itcv_iwae_finalize(const double* state, double* log_px, double* elbo, double* ess, int B, void* stream);
+/* The KL term of a VAE with a VampPrior (Tomczak & Welling 2018, "VAE with a VampPrior") with its gradient, csrc/vamp.hip:
+ * one sample per row against the uniform mixture of K diagonal Gaussians.  mu, logvar, eps [B][D] fp32 (the posterior and
+ * its N(0, 1) draw) and p_mu, p_logvar [K][D] fp32 (the components), all with unit column stride and row strides >= D, read
+ * in place (a pair may be the halves of one [.][2D] tensor).  1 <= B, K <= 4096, B K <= 2^22, 1 <= D <= 512.  In fp64 from
+ * the fp32 inputs, with c = log 2 pi:
+ *   z_bd   = fp32(mu + eps exp(logvar / 2))                  (dense [B][D]; L below is formed from this rounded value)
+ *   logq_b = -1/2 sum_d (c + logvar_bd + eps_bd^2)           (exact in eps: no (z - mu) / sigma round trip)
+ *   L_bk   = -1/2 (D c + sum_d p_logvar_kd + sum_d (z_bd - p_mu_kd)^2 exp(-p_logvar_kd))
+ *   logp_b = logsumexp_k L_bk - log K,   r_bk = exp(L_bk - logsumexp_k L_bk)
+ *   rows_b = beta (logq_b - logp_b)      (fp32 [B]);  out[0] = beta * mean_b (logq_b - logp_b), the sum under reduce 2
+ *   terms[3] = {mean_b (logq_b - logp_b), mean_b logq_b, mean_b logp_b};   logq, logp: fp64 [B]
+ * reduce: 0 "none" and 1 "mean" give the mean in out[0], 2 "sum" the sum; rows is written in every case.  L [B][K] fp64
+ * holds r when the call returns: kept for _bwd.  The logsumexp is taken per tile of 32 components about the tile's own
+ * maximum and the tiles are combined about the row's maximum, tiles ascending: a component astronomically far away gets
+ * r_bk = 0.0 exactly and nothing overflows.  Row b of z, logq, logp and rows depends on row b of the inputs and on the
+ * components alone.  Workspace: itcv_vamp_workspace (the max and sum partials per component tile and row, and the KL per
+ * row: at most 2.2 MiB; 0 for shapes the op refuses).  2 launches: 32 x 32 tiles of L over a grid, D staged through LDS in
+ * chunks of 32 with exp(-p_logvar) taken once per staged element; then a finish whose first block writes logp, rows, the
+ * scalar and the terms and whose other blocks (at most 128) turn 16 rows of L a trip into r.
+ * _bwd, ONE launch: gz [B][D] (row stride ld_gz >= D; NULL: zero) is the gradient of z; g (NULL: zero) that of out[0]
+ * (g_rows == 0: g[1]) or of rows (g_rows != 0: g[B]); G_b = g_scale * g.  The caller passes g_scale = 1 / B for the mean.
+ * z and r are the forward's.  Every element of the dense dmu, dlogvar [B][D] and dp_mu, dp_logvar [K][D] fp32 is written,
+ * with iv = exp(-p_logvar):
+ *   A_bd = sum_k r_bk (z_bd - p_mu_kd) iv_kd,   t_bd = gz_bd + G_b beta A_bd
+ *   dmu = t,   dlogvar = exp(logvar / 2) eps t / 2 - G_b beta / 2
+ *   dp_mu_kd = -beta sum_b G_b r_bk (z_bd - p_mu_kd) iv_kd,   dp_logvar_kd = beta / 2 sum_b G_b r_bk (1 - (z_bd - p_mu_kd)^2 iv_kd)
+ * Blocks x < ceil(B / 16) take a 16 x 64 tile of [B][D] over chunks of 32 components, the blocks behind them a 16 x 64 tile
+ * of [K][D] over chunks of 32 rows.  beta == 0 leaves the term out of out[0], rows and the gradients whatever its value.
+ * itcv_vamp_logprob, 2 launches: logp [N] fp64 of given rows x [N][D] fp32 (row stride ld_x >= D) under the same mixture;
+ * the same pair pass, so x = the z of _fwd gives its logp bit for bit.  N takes B's limits.
+ * Every sum is fp64 in a fixed order, there are no atomics: results are bitwise reproducible and do not depend on the grid.
+ * Refused before any launch: a NULL pointer (gz and g excepted), B (N) or K outside 1..4096, D outside 1..512, B K above
+ * 2^22, a non-finite beta or g_scale, another reduce, a row stride below D, a workspace that is too small. */
+size_t itcv_vamp_workspace(int B, int K, int D);
+int itcv_vamp_fwd(const float* mu, size_t ld_mu, const float* logvar, size_t ld_logvar, const float* eps, size_t ld_eps,
+                  const float* p_mu, size_t ld_pmu, const float* p_logvar, size_t ld_plogvar, float* z, double* L,
+                  double* logq, double* logp, float* rows, float* out, float* terms, int B, int K, int D, double beta,
+                  int reduce, void* ws, size_t ws_bytes, void* stream);
+int itcv_vamp_bwd(const float* gz, size_t ld_gz, const float* g, int g_rows, double g_scale, const float* logvar,
+                  size_t ld_logvar, const float* eps, size_t ld_eps, const float* z, const float* p_mu, size_t ld_pmu,
+                  const float* p_logvar, size_t ld_plogvar, const double* r, float* dmu, float* dlogvar, float* dp_mu,
+                  float* dp_logvar, int B, int K, int D, double beta, void* stream);
+int itcv_vamp_logprob(const float* x, size_t ld_x, const float* p_mu, size_t ld_pmu, const float* p_logvar,
+                      size_t ld_plogvar, double* logp, int N, int K, int D, void* ws, size_t ws_bytes, void* stream);
 /* The FactorVAE objective (Kim & Mnih 2018; disentanglement_lib's `factor_vae`), csrc/factor.hip.
  * itcv_permute_dims, ONE launch (a block per column): out[r][d] = z[i][d] where r is the rank of keys[i][d] in column d
  * of keys[B][D] -- ascending in the monotone uint32 image of the float's bits (the sign-flip map of itcv_udr_ranks, +0 and

@@ -177,7 +177,78 @@ def prior_log_prob(z):
     return -0.5 * (z.shape[1] * log(2.0 * pi) + (z * z).sum(1))
 
 
-def compute_latent_density(source, model, num_fit=10000, num_eval=None, latent="mean", batch_size=64, seed=0, **fit_kw):
+# ---- the learned prior of a VampSolver -------------------------------------------------------------------------------------
+VAMP_CHUNK = 4096       # rows of one vamp_log_prob launch (the limit of csrc/vamp.hip), fewer when K is large
+
+
+@dataclass(eq=False)
+class VampPrior:
+    """A VampPrior frozen for scoring: the encoder's outputs on the K pseudo-inputs, fp32 device tensors ``means`` and
+    ``logvars`` [K, D].  The density is the uniform mixture (1 / K) sum_k N(z; means_k, diag exp(logvars_k))."""
+    means: torch.Tensor
+    logvars: torch.Tensor
+
+    @property
+    def n_components(self):
+        return self.means.shape[0]
+
+    @property
+    def dim(self):
+        return self.means.shape[1]
+
+
+def vamp_prior(model, pseudo_inputs, batch_size=64):
+    """The ``VampPrior`` of ``model`` and ``pseudo_inputs`` (a ``models.PseudoInputs``, or a [K, C, H, W] tensor): the
+    encoder's (mu, logvar) of the pseudo-inputs in chunks of ``batch_size``.  The model runs in eval mode under
+    ``no_grad``; its training flag is put back and its BatchNorm buffers are not written."""
+    bs = int(batch_size)
+    if bs < 1:
+        raise ValueError(f"batch_size must be positive (got {batch_size})")
+    device = _device_of(model)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            u = (pseudo_inputs() if callable(pseudo_inputs) else pseudo_inputs).detach().to(device)
+            if u.dim() != 4 or not u.shape[0]:
+                raise ValueError(f"vamp_prior: the pseudo-inputs must be [K, C, H, W] (got {tuple(u.shape)})")
+            parts = [model.encode(u[a:a + bs])[:2] for a in range(0, u.shape[0], bs)]
+    finally:
+        model.train(was_training)
+    return VampPrior(torch.cat([p[0] for p in parts], 0).to(torch.float32).contiguous(),
+                     torch.cat([p[1] for p in parts], 0).to(torch.float32).contiguous())
+
+
+def vamp_log_prob(prior, x):
+    """fp64 ``[N]`` on the device: ``log p(x_n)`` of the fp32 device rows ``x [N, D]`` under the ``VampPrior``, in chunks
+    of at most 4096 rows (fewer when K is large: a launch takes N K <= 2^22 pairs).  Non-finite values raise
+    ``ValueError``.  One read-back."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[1] != prior.dim:
+        raise ValueError(f"vamp_log_prob: x must be a [N, {prior.dim}] tensor")
+    rows = max(1, min(VAMP_CHUNK, HF.VAMP_MAX_PAIRS // prior.n_components))
+    x = x.detach().to(torch.float32)
+    out = torch.cat([HF.vamp_log_prob(x[a:a + rows], prior.means, prior.logvars) for a in range(0, x.shape[0], rows)])
+    _raise_on(not bool(torch.isfinite(out).all()))
+    return out
+
+
+def vamp_sample(prior, num, seed=0):
+    """fp32 ``[num, D]`` on the device: ``z = means[c] + exp(logvars[c] / 2) eps`` with the components ``c`` from
+    ``torch.randint`` and ``eps`` from ``randn``, both from one private CPU ``torch.Generator`` seeded by ``seed``, the
+    components first: torch's global generators are untouched and two calls with one seed give the same bits."""
+    num = int(num)
+    if num < 1:
+        raise ValueError(f"vamp_sample: num must be positive (got {num})")
+    gen = torch.Generator().manual_seed(int(seed))
+    comp = torch.randint(prior.n_components, (num,), generator=gen)
+    eps = torch.randn((num, prior.dim), generator=gen)
+    dev = prior.means.device
+    comp = comp.to(dev)
+    return prior.means.index_select(0, comp) + torch.exp(0.5 * prior.logvars.index_select(0, comp)) * eps.to(dev)
+
+
+def compute_latent_density(source, model, num_fit=10000, num_eval=None, latent="mean", batch_size=64, seed=0, prior=None,
+                           **fit_kw):
     """Fit a mixture to the latents of ``num_fit`` images of ``source`` (a ``DeviceImageTable`` or a dataset; no factors are
     needed) and score it on ``num_eval`` OTHER images (None: as many again, or what is left): a dict with ``gmm``,
     ``loglik_fit`` and ``loglik_heldout`` (the mean log-density of the fitted and of the held-out latents under the mixture),
@@ -188,7 +259,10 @@ def compute_latent_density(source, model, num_fit=10000, num_eval=None, latent="
     The two index sets are the sorted halves of one ``RandomState(seed).choice(len(source), num_fit + num_eval,
     replace=False)``.  ``latent``: ``"mean"`` (the encoder mean) or ``"sample"`` (mean + std * eps, eps from a private CPU
     generator seeded by ``seed``).  The latents come through ``real_features``: eval mode, no gradients, the BatchNorm
-    buffers are not written.  ``fit_kw`` goes to ``fit_gmm`` (``seed`` too unless given there)."""
+    buffers are not written.  ``fit_kw`` goes to ``fit_gmm`` (``seed`` too unless given there).  ``prior``: a ``VampPrior``
+    replaces N(0, I) in ``loglik_prior`` and ``gap`` (the model's own learned prior); the result then carries ``prior``."""
+    if prior is not None and not isinstance(prior, VampPrior):
+        raise ValueError(f"compute_latent_density: prior must be None or a VampPrior (got {type(prior).__name__})")
     if latent not in ("mean", "sample"):
         raise ValueError(f'compute_latent_density: latent must be "mean" or "sample" (got {latent!r})')
     n = len(source)
@@ -214,6 +288,10 @@ def compute_latent_density(source, model, num_fit=10000, num_eval=None, latent="
     fit_kw.setdefault("seed", seed)
     gmm = fit_gmm(z["fit"], **fit_kw)
     got = torch.stack([gmm_log_prob(gmm, z["fit"]).mean(), gmm_log_prob(gmm, z["heldout"]).mean(),
-                       prior_log_prob(z["heldout"]).mean()]).tolist()
-    return dict(gmm=gmm, loglik_fit=got[0], loglik_heldout=got[1], loglik_prior=got[2], gap=got[1] - got[2],
-                n_iter=gmm.n_iter, converged=gmm.converged, latents=z, indices=idx)
+                       (prior_log_prob(z["heldout"]) if prior is None else vamp_log_prob(prior, z["heldout"])).mean()
+                       ]).tolist()
+    out = dict(gmm=gmm, loglik_fit=got[0], loglik_heldout=got[1], loglik_prior=got[2], gap=got[1] - got[2],
+               n_iter=gmm.n_iter, converged=gmm.converged, latents=z, indices=idx)
+    if prior is not None:
+        out["prior"] = prior
+    return out

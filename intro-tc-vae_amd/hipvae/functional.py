@@ -1628,6 +1628,87 @@ class AdaGroupFn(Function):
         return dmu, dlv, None, None, None, None
 
 
+# ------------------------------------------------------------------ VampPrior: the mixture-prior KL op
+VAMP_MAX_B, VAMP_MAX_K, VAMP_MAX_D, VAMP_MAX_PAIRS = 4096, 4096, 512, 1 << 22
+VAMP_REDUCES = {"none": 0, "mean": 1, "sum": 2}
+
+
+def vamp_check_shapes(B, K, D, what="vamp_latent"):
+    """ValueError unless (B, K, D) is inside the limits of csrc/vamp.hip; host arithmetic only."""
+    if not (1 <= B <= VAMP_MAX_B and 1 <= K <= VAMP_MAX_K):
+        raise ValueError(f"{what} takes 1 <= B <= {VAMP_MAX_B} rows and 1 <= K <= {VAMP_MAX_K} components "
+                         f"(got B = {B}, K = {K})")
+    if not 1 <= D <= VAMP_MAX_D:
+        raise ValueError(f"{what} takes 1 <= D <= {VAMP_MAX_D} (got {D})")
+    if B * K > VAMP_MAX_PAIRS:
+        raise ValueError(f"{what} takes B K <= 2^22 pairs (got B = {B}, K = {K})")
+
+
+def vamp_latent_forward(mu, logvar, eps, p_mu, p_logvar, beta, reduce):
+    """itcv_vamp_fwd on the posterior ``mu`` / ``logvar`` / ``eps`` [B, D] and the components ``p_mu`` / ``p_logvar``
+    [K, D] (fp32 views with unit column stride are read in place).  Returns the five inputs as read with their row strides,
+    then (z [B, D], out, rows [B], terms [3], logq [B] fp64, logp [B] fp64, r [B, K] fp64).  No gradient:
+    ``VampLatentFn`` is the differentiable form."""
+    (B, D), K, dev = mu.shape, p_mu.shape[0], mu.device
+    ins = [_rows_f32(t, n) for t, n in ((mu, "mu"), (logvar, "logvar"), (eps, "eps"), (p_mu, "p_mu"),
+                                        (p_logvar, "p_logvar"))]
+    z = torch.empty((B, D), dtype=F32, device=dev)
+    r = torch.empty((B, K), dtype=torch.float64, device=dev)
+    logq, logp = torch.empty((B,), dtype=torch.float64, device=dev), torch.empty((B,), dtype=torch.float64, device=dev)
+    rows = torch.empty((B,), dtype=F32, device=dev)
+    out, terms = _loss_terms(3, dev)
+    nws = lib.itcv_vamp_workspace(B, K, D)
+    ws = _ws(nws, dev)
+    flat = [a for t, ld in ins for a in (t.data_ptr(), ld)]
+    call("itcv_vamp_fwd", *flat, ptr(z), ptr(r), ptr(logq), ptr(logp), ptr(rows), ptr(out), ptr(terms), B, K, D,
+         float(beta), int(reduce), ptr(ws), nws, stream())
+    return ins, (z, out, rows, terms, logq, logp, r)
+
+
+class VampLatentFn(Function):
+    """The latent op of a VAE with a VampPrior (include/itcv_hip.h: itcv_vamp_fwd; ``reduce`` 0 = none, 1 = mean,
+    2 = sum): two launches forward, one backward.  Outputs: z [B, D] and the loss (a scalar, or rows [B] under "none"),
+    both differentiable in ``mu``, ``logvar``, ``p_mu`` and ``p_logvar``; (mean KL, mean logq, mean logp) [3], logq [B],
+    logp [B] and r [B, K] (fp64), no gradient.  Kept for the backward: logvar, eps, the components, z and r.  The arguments
+    are those ``ops.vamp_latent`` has validated (shapes and limits): only the layout is handled here."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, eps, p_mu, p_logvar, beta, reduce):
+        ins, (z, out, rows, terms, logq, logp, r) = vamp_latent_forward(mu, logvar, eps, p_mu, p_logvar, beta, reduce)
+        (_, _), (lv, ldl), (ep, lde), (pm, ldpm), (pl, ldpl) = ins
+        ctx.save_for_backward(lv, ep, pm, pl, z, r)
+        ctx.cfg = (float(beta), int(reduce), ldl, lde, ldpm, ldpl)
+        ctx.mark_non_differentiable(terms, logq, logp, r)
+        return z, (rows if reduce == 0 else out), terms, logq, logp, r
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gz, g, *_unused):
+        lv, ep, pm, pl, z, r = ctx.saved_tensors
+        beta, reduce, ldl, lde, ldpm, ldpl = ctx.cfg
+        (B, D), K, dev = z.shape, pm.shape[0], z.device
+        gz, ldgz = _rows_f32(gz, "gz")
+        dmu, dlv = torch.empty((B, D), dtype=F32, device=dev), torch.empty((B, D), dtype=F32, device=dev)
+        dpm, dpl = torch.empty((K, D), dtype=F32, device=dev), torch.empty((K, D), dtype=F32, device=dev)
+        call("itcv_vamp_bwd", gz.data_ptr(), ldgz, ptr(_f32c(g)), int(reduce == 0), 1.0 / B if reduce == 1 else 1.0,
+             lv.data_ptr(), ldl, ep.data_ptr(), lde, ptr(z), pm.data_ptr(), ldpm, pl.data_ptr(), ldpl, ptr(r), ptr(dmu),
+             ptr(dlv), ptr(dpm), ptr(dpl), B, K, D, beta, stream())
+        return dmu, dlv, None, dpm, dpl, None, None
+
+
+def vamp_log_prob(x, p_mu, p_logvar):
+    """itcv_vamp_logprob: fp64 [N] log (1 / K) sum_k N(x_n; p_mu_k, diag exp(p_logvar_k)) of the fp32 rows ``x`` [N, D]
+    (row-strided views are read in place).  Shapes and limits are the caller's (``ops.vamp_log_prob``).  No gradient."""
+    (x, ldx), (pm, ldpm), (pl, ldpl) = _rows_f32(x, "x"), _rows_f32(p_mu, "p_mu"), _rows_f32(p_logvar, "p_logvar")
+    (N, D), K = x.shape, pm.shape[0]
+    logp = torch.empty((N,), dtype=torch.float64, device=x.device)
+    nws = lib.itcv_vamp_workspace(N, K, D)
+    ws = _ws(nws, x.device)
+    call("itcv_vamp_logprob", x.data_ptr(), ldx, pm.data_ptr(), ldpm, pl.data_ptr(), ldpl, ptr(logp), N, K, D, ptr(ws),
+         nws, stream())
+    return logp
+
+
 # ------------------------------------------------------------------ JointVAE / AnnealedVAE: the capacity-controlled latent op
 JOINT_MAX_D = 512
 

@@ -174,7 +174,8 @@ def generated_features(model, num, batch_size=64, seed=0, feature="encoder", pri
     """fp32 ``[num, D]`` on the device: the features of ``model.decode(z)``, z ~ N(0, I) from a private CPU
     ``torch.Generator`` seeded by ``seed``, one draw per batch in a fixed order: torch's global generators are untouched
     and two calls with one seed give the same bits.  Same contract for the model as ``real_features``.  ``prior``: a
-    ``hipvae.density.GaussianMixture`` whose ``gmm_sample(prior, num, seed)`` replaces the normal draws."""
+    ``hipvae.density.GaussianMixture`` whose ``gmm_sample(prior, num, seed)`` replaces the normal draws, or a
+    ``hipvae.density.VampPrior`` (``vamp_sample``)."""
     num, bs = int(num), int(batch_size)
     if num < 1 or bs < 1:
         raise ValueError(f"num and batch_size must be positive (got {num}, {batch_size})")
@@ -189,10 +190,13 @@ def generated_features(model, num, batch_size=64, seed=0, feature="encoder", pri
                 yield model.decode(z)
     else:
         from . import density
-        if not isinstance(prior, density.GaussianMixture) or prior.dim != zdim:
+        if isinstance(prior, density.VampPrior) and prior.dim == zdim:
+            zs = density.vamp_sample(prior, num, seed)
+        elif not isinstance(prior, density.GaussianMixture) or prior.dim != zdim:
             raise ValueError(f"generated_features: prior must be None or a GaussianMixture over the model's {zdim} latent "
                              "dimensions")
-        zs = density.gmm_sample(prior, num, seed)
+        else:
+            zs = density.gmm_sample(prior, num, seed)
 
         def batches():
             for a in range(0, num, bs):
@@ -218,13 +222,18 @@ def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature
     mixture fitted to the real images' latents ``model.encode(x)[0]`` (whatever ``feature`` is) by ``fit_gmm(latents,
     **gmm_params)`` (``seed`` unless given there) and sampled by ``gmm_sample(gmm, num_fake, seed)``; a ``GaussianMixture``
     instance is used as given.  The result then carries ``gmm`` too.  The scores of the two priors differ by what the
-    drift of the aggregate posterior from N(0, I) costs."""
+    drift of the aggregate posterior from N(0, I) costs.  A ``hipvae.density.VampPrior`` instance -- the learned prior of a
+    ``VampSolver`` -- is sampled by ``vamp_sample(prior, num_fake, seed)``; the result then carries ``prior``."""
     unknown = [s for s in scores if s not in SCORES]
     if unknown:
         raise ValueError(f"compute_sample_quality: unknown score(s) {unknown} (known: {', '.join(map(repr, SCORES))})")
-    gmm = None
+    gmm = vamp = None
     if not isinstance(prior, str):
-        gmm = prior
+        from . import density
+        if isinstance(prior, density.VampPrior):
+            vamp = prior
+        else:
+            gmm = prior
     elif prior not in ("normal", "gmm"):
         raise ValueError(f'compute_sample_quality: prior must be "normal", "gmm" or a GaussianMixture (got {prior!r})')
     if indices is None:
@@ -239,10 +248,13 @@ def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature
         from . import density
         latents = real if feature == "encoder" else real_features(source, model, indices, batch_size)
         gmm = density.fit_gmm(latents, **{"seed": seed, **(gmm_params or {})})
-    fake = generated_features(model, len(indices) if num_fake is None else num_fake, batch_size, seed, feature, gmm)
+    fake = generated_features(model, len(indices) if num_fake is None else num_fake, batch_size, seed, feature,
+                              gmm if vamp is None else vamp)
     out = {}
     if gmm is not None:
         out["gmm"] = gmm
+    if vamp is not None:
+        out["prior"] = vamp
     if "frechet" in scores:
         out["frechet"] = frechet_distance(real, fake, eps)["frechet"]
     if "kid" in scores:

@@ -503,3 +503,34 @@ class Discriminator(nn.Sequential):
 
     def forward(self, z):
         return self.run(z).logits
+
+
+class PseudoInputs(nn.Module):
+    """The K learned pseudo-inputs of a VampPrior (Tomczak & Welling 2018, "VAE with a VampPrior"; not in the reference):
+    one parameter ``raw`` [K, C, H, W], initialised N(mean, std) as in the paper's code.  ``forward()`` returns
+    ``raw.clamp(0, 1)``, the paper's Hardtanh(0, 1): an image in the encoder's input range, and a pixel outside [0, 1]
+    gets an exactly zero gradient.  ``PseudoInputs.from_images(x)`` starts from data instead."""
+
+    def __init__(self, num=500, cdim=3, image_size=64, mean=0.05, std=0.01):
+        super().__init__()
+        if not (isinstance(num, int) and isinstance(cdim, int) and isinstance(image_size, int)
+                and num >= 1 and cdim >= 1 and image_size >= 1):
+            raise ValueError(f"PseudoInputs(num={num!r}, cdim={cdim!r}, image_size={image_size!r}): positive integers")
+        if not std >= 0:
+            raise ValueError(f"std must be >= 0 (got {std!r})")
+        self.num, self.cdim, self.image_size = num, cdim, image_size
+        self.raw = nn.Parameter(torch.empty(num, cdim, image_size, image_size).normal_(float(mean), float(std)))
+
+    @classmethod
+    def from_images(cls, x):
+        """Pseudo-inputs that start as the images ``x`` [K, C, H, H] (copied; values outside [0, 1] are clamped by
+        ``forward`` and do not move)."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[2] != x.shape[3] or not x.shape[0]:
+            raise ValueError(f"from_images: x must be [K, C, H, H] (got {tuple(getattr(x, 'shape', ()))})")
+        self = cls(int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), std=0.0)
+        with torch.no_grad():
+            self.raw.copy_(x.detach().to(torch.float32))
+        return self
+
+    def forward(self):
+        return self.raw.clamp(0, 1)

@@ -315,6 +315,65 @@ def ada_group(mu, logvar, beta, averaging="gvae", own=None, eps=None, with_terms
     return (z, loss, mask, terms) if with_terms else (z, loss)
 
 
+VAMP_REDUCES = tuple(HF.VAMP_REDUCES)
+
+
+def _vamp_components(p_mu, p_logvar, D):
+    if p_mu.dim() != 2 or p_mu.shape != p_logvar.shape or p_mu.shape[1] != D:
+        raise ValueError(f"p_mu and p_logvar must share one [K, D] shape with D = {D} (got {tuple(p_mu.shape)}, "
+                         f"{tuple(p_logvar.shape)})")
+    return p_mu.shape[0]
+
+
+def vamp_latent(mu, logvar, p_mu, p_logvar, beta=1.0, eps=None, reduce="mean", with_terms=False):
+    """The latent op of a VAE with a VampPrior (Tomczak & Welling 2018, "VAE with a VampPrior"; not in the reference): one
+    sample per row of the posterior ``(mu, logvar)`` [B, D] against the uniform mixture of the K diagonal Gaussians
+    ``(p_mu, p_logvar)`` [K, D] -- the encoder's outputs on the pseudo-inputs.  With c = log 2 pi:
+
+        z      = mu + eps exp(logvar / 2),          logq_b = -1/2 sum_d (c + logvar + eps^2)
+        L_bk   = -1/2 sum_d (c + p_logvar_kd + (z_bd - p_mu_kd)^2 exp(-p_logvar_kd))
+        logp_b = logsumexp_k L_bk - log K,          rows_b = beta (logq_b - logp_b)
+
+    Returns ``(z [B, D], loss)`` with ``loss`` the mean ("mean"), the sum ("sum") or the vector ("none") of ``rows``; both
+    are differentiable in all four inputs.  With ``with_terms`` also the device vector (mean KL unscaled, mean logq, mean
+    logp), no gradient.  ``eps`` None: ONE draw ``noise(mu.shape, mu.device)``, so recorded draws and graph capture work as
+    for ``reparameterize``.  A form that takes a sampled z is deliberately not offered: at small variances the direct mu
+    and z gradients of log q are large and of opposite sign, and they would be rounded to fp32 before autograd cancels
+    them.  Two launches forward, one backward, fp64 inside, bitwise reproducible; 1 <= B, K <= 4096, B K <= 2^22,
+    1 <= D <= 512."""
+    if reduce not in HF.VAMP_REDUCES:
+        raise ValueError(f"reduce must be one of {VAMP_REDUCES} (got {reduce!r})")
+    if mu.dim() != 2 or mu.shape != logvar.shape:
+        raise ValueError(f"mu and logvar must share one [B, D] shape (got {tuple(mu.shape)}, {tuple(logvar.shape)})")
+    B, D = mu.shape
+    K = _vamp_components(p_mu, p_logvar, D)
+    HF.vamp_check_shapes(B, K, D, "vamp_latent")
+    if eps is not None and eps.shape != mu.shape:
+        raise ValueError(f"eps must have mu's shape {tuple(mu.shape)} (got {tuple(eps.shape)})")
+    beta = float(beta)
+    if not math.isfinite(beta):
+        raise ValueError(f"beta must be finite (got {beta})")
+    abi.need_device(mu, logvar, p_mu, p_logvar)
+    if eps is None:
+        eps = noise(mu.shape, mu.device)
+    z, loss, terms, _, _, _ = HF.VampLatentFn.apply(mu, logvar, eps.detach(), p_mu, p_logvar, beta,
+                                                    HF.VAMP_REDUCES[reduce])
+    return (z, loss, terms) if with_terms else (z, loss)
+
+
+def vamp_log_prob(x, p_mu, p_logvar):
+    """fp64 [N]: ``log (1 / K) sum_k N(x_n; p_mu_k, diag exp(p_logvar_k))`` of the rows ``x`` [N, D] under the mixture of
+    ``vamp_latent``, by the same pair pass: on the ``z`` that op returned it gives that op's logp bit for bit.  No
+    gradient.  1 <= N, K <= 4096, N K <= 2^22, 1 <= D <= 512 (``hipvae.density.vamp_log_prob`` chunks longer inputs)."""
+    if x.dim() != 2:
+        raise ValueError(f"x must be [N, D] (got {tuple(x.shape)})")
+    N, D = x.shape
+    K = _vamp_components(p_mu, p_logvar, D)
+    HF.vamp_check_shapes(N, K, D, "vamp_log_prob")
+    abi.need_device(x, p_mu, p_logvar)
+    return HF.vamp_log_prob(x.detach(), p_mu.detach(), p_logvar.detach())
+
+
 _JOINT_SEG = {}
 
 

@@ -12,6 +12,8 @@ from .joint import JointVAESolver, AnnealedVAESolver
 from .semi import S2VAESolver, S2TCSolver, S2DIPSolver, S2FactorSolver
 # the importance-weighted bound: imported by name too (``from solvers import IWAESolver``)
 from .iwae import IWAESolver
+# the learned mixture prior: imported by name too (``from solvers import VampSolver``)
+from .vamp import VampSolver
 
 __all__ = ["VAESolver", "IntroSolver", "TCSovler", "IntroTCSovler", "DIPSolver", "IntroDIPSolver", "MMDSolver",
            "IntroMMDSolver", "FactorSolver", "AdaGVAESolver", "JointVAESolver", "AnnealedVAESolver"]

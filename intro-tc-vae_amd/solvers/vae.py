@@ -277,8 +277,10 @@ class VAESolver:
     # ---- solvers/vae.py:89-136 ---------------------------------------------------------------
     # The one VAE step.  An objective supplies what differs: ``_losses`` (how z and the two loss terms come out of the
     # batch, and its further device scalars), ``_batch`` (the batch check), ``_write_losses`` / ``_extra_results`` (what
-    # it logs and returns for those scalars); FactorVAE also ``_side_walk`` and ``_updates`` for its third group.
+    # it logs and returns for those scalars); FactorVAE also ``_side_walk`` and ``_updates`` for its third group; the
+    # VampPrior solver ``_walk``: its third group takes its gradient from the VAE's own backward.
     _updates = ("encoder", "decoder")
+    _walk = ("decoder", "encoder")
 
     def _losses(self, real: Tensor):
         """(z, loss_rec, loss_kl, extra): ``extra`` a device vector of further scalars for the stats, or None."""
@@ -299,7 +301,7 @@ class VAESolver:
         self._set_trainable(True, True)
         z, loss_rec, loss_kl, extra = self._losses(real)
         loss = self._total_loss(loss_rec, loss_kl)
-        self._backward(loss, ("decoder", "encoder"))
+        self._backward(loss, self._walk)
         self._side_walk(z)
         norm = self._clip()
         for part in self._updates:
@@ -337,6 +339,11 @@ class VAESolver:
                 "L2": v_norm if self.clip else None, **self._extra_results(*extra)}
 
     # ---- TensorBoard side channel (solvers/vae.py:138-254); all no-ops without a writer ------
+    def _eval_prior(self):
+        """The model's own prior for "sample_quality" and "latent_density" when their params name none: None is N(0, I);
+        a solver with a learned prior returns what ``hipvae.quality.compute_sample_quality(prior=...)`` takes."""
+        return None
+
     def _write_images_helper(self, batch, cur_iter):
         if self.writer is not None and cur_iter % self.test_iter == 0:
             noise = torch.randn(size=(batch.size(0), self.model.zdim), device=self.device)
@@ -469,6 +476,9 @@ class VAESolver:
         if with_quality:
             from hipvae import quality
             kw = dict(batch_size=self.batch_size)
+            own = self._eval_prior()
+            if own is not None:
+                kw["prior"] = own
             kw.update(self.quality_params or {})
             got = quality.compute_sample_quality(self.dataset if self._device_table is None else self._device_table,
                                                  self.model, **kw)
@@ -485,6 +495,9 @@ class VAESolver:
         if with_density:
             from hipvae import density
             kw = dict(batch_size=self.batch_size)
+            own = self._eval_prior()
+            if own is not None:
+                kw["prior"] = own
             kw.update(self.density_params or {})
             got = density.compute_latent_density(self.dataset if self._device_table is None else self._device_table,
                                                  self.model, **kw)
