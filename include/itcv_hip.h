@@ -133,6 +133,17 @@ int itcv_conv2d_fwd_bf16p_st(const void* xplanes, const void* wp, const float* b
 int itcv_conv2d_fwd_bf16p_sub(const void* xplanes, const void* wp, const float* bias, float* y, int B, int Ci, int H,
                               int W, int Co, int KS, int up2, int ns, int b0, int nb, void* ws, size_t ws_bytes,
                               void* stream);
+/* Data gradient of a conv that read its input through the nearest x2 upsample, with the upsample's adjoint folded into the
+ * store: dx_lo[B][Co][H/2][W/2] = itcv_upsample2_bwd(itcv_conv2d_fwd_bf16p_sub(xplanes, wp, NULL, ..., up2 = 0, ...)), bit
+ * for bit, without the H x W tensor in between.  xplanes: the planes of dy, [.][B][Ci/8][H][W]; wp: the data-gradient
+ * packing of the weight; H, W: the high resolution; images [b0, b0 + nb) only (whole batch: 0, B), planned for B.
+ * The band kernels' two-plane launches without a K split have this form: _supported answers 1 only where the plan of
+ * the two-call path is a band launch (W 16..64) with splits == 1 whose kernel form exists (16x16x32 products: fp16 planes,
+ * or bf16 planes with "band_m16" = 1) and H, W are even.  Host arithmetic only.  The entry point refuses any other
+ * shape; ws / ws_bytes are not used (no slabs) and may be NULL / 0. */
+int itcv_conv2d_dgrad_up2_supported(int B, int Ci, int H, int W, int Co, int KS, int fmt, int nb);
+int itcv_conv2d_dgrad_up2_bf16p(const void* xplanes, const void* wp, float* dx_lo, int B, int Ci, int H, int W, int Co,
+                                int KS, int fmt, int b0, int nb, void* ws, size_t ws_bytes, void* stream);
 /* Weight gradient from the same planes (x: [2][B][Ci/8][Hs][Ws], dy: [2][B][Co/8][H][W]); the pixel
  * reduction runs through the gfx950 transposing LDS read, so no pixel-major copy is needed.  bf16x3
  * only; KS = 3, W a power of two in 4..64, H a power of two, B*H*W % 64 == 0 (see _supported).  Replaces

@@ -17,9 +17,65 @@ static __device__ u32x4 g_zero_chunk = {0u, 0u, 0u, 0u};
 //   * 8 MFMA waves (two per SIMD, so one fills the other's barrier / LDS-latency bubbles) + 4 loader waves.
 // Ingest per MFMA drops ~2.8x.  Same arithmetic and K order as the other split-bf16 kernels (bit-identical).
 
-template <int LOG2W, int BM, bool UP2, bool M16 = false, bool F16 = false>
+// ---- ADJ: the "adjoint store" form of the direct epilogue (16x16x32 products, 256-pixel tiles of 16..64-wide images) ----
+// The data gradient of a conv that read its input through the fused nearest x2 upsample is only ever consumed as the sum
+// of its 2x2 pixel blocks (upstream<2>, norm_act.hip).  In this form the kernel stores that sum -- a quarter of the
+// values -- and the high-resolution tensor never exists.  Only the pixel a lane's accumulator column stands for changes:
+// the tile's 256 pixels are cut into eight units of two image rows x 16 columns, a wave owns TNx / 2 consecutive units,
+// and its N-tiles 2u, 2u + 1 are the upper and the lower row of unit u.  The vertical neighbour of a pixel is then the
+// same lane and register of the next N-tile, the horizontal one lane ^ 1 of the same 16-lane group (one DPP move), and
+// (upper.x + upper.y) + (lower.x + lower.y) is formed in the adjoint kernel's order from the values the plain epilogue
+// stores: bit-identical.  Every output is still one accumulator with the same K sequence; loaders, rings and counted
+// waits do not know about it.
+template <int LOG2W, int TNx>
+__device__ __forceinline__ int adj_pixel(int wn, int j, int col) {   // pixel (within the tile) of column `col` of N-tile j
+  constexpr int CG = (1 << LOG2W) / 16;                              // 16-column groups per image row
+  const int u = wn * (TNx / 2) + (j >> 1), rp = u / CG, cg = u - rp * CG;
+  return ((2 * rp + (j & 1)) << LOG2W) + cg * 16 + col;
+}
+__device__ __forceinline__ float lane_xor1(float v) {                // the value of lane ^ 1 (quad_perm [1,0,3,2])
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
+}
+// out: [B][Co][H/2][W/2]; mrow: first channel row of this wave; n0: first pixel of the tile.  All 64 lanes arrive here
+// together (the DPP moves read neighbouring lanes).  With two units per wave the even lanes store the first and the odd
+// lanes the second, which lies 8 floats further on (the next column group, or at W = 16 the next row): a 16-lane group
+// writes 64 consecutive bytes per channel row, as the plain epilogue does; with one unit (64-row tiles) the even lanes
+// write 32.
+template <class MM, int LOG2W, int TMx, int TNx, bool F16>
+__device__ __forceinline__ void adj_store(const typename MM::acc_t (&acc)[TMx][TNx], const ConvArgsP2& a, float* out, int mrow,
+                                          int n0, int wn, int lr, int kq, float oscale) {
+  constexpr int W = 1 << LOG2W, U = TNx / 2;
+  static_assert(U == 1 || U == 2, "one or two row-pair units per wave");
+  const int HW = a.H << LOG2W, HWl = HW >> 2;
+  const bool odd = lr & 1;
+  const int us = U == 2 ? (lr & 1) : 0;
+  const int nn = n0 + adj_pixel<LOG2W, TNx>(wn, 2 * us, lr & ~1);    // upper left pixel of this lane's 2x2 block
+  const int b2 = nn / HW, hw2 = nn - b2 * HW;
+  const size_t base = (size_t)b2 * a.Co * HWl + (size_t)((hw2 >> LOG2W) >> 1) * (W / 2) + ((hw2 & (W - 1)) >> 1);
+  const bool live = nn < a.N && (U == 2 || !(lr & 1));
+#pragma unroll
+  for (int i = 0; i < TMx; ++i) {
+#pragma unroll
+    for (int r = 0; r < MM::NR; ++r) {
+      float s[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        float v0 = acc[i][2 * u][r], v1 = acc[i][2 * u + 1][r];
+        if (F16) v0 = __fmul_rn(v0, oscale), v1 = __fmul_rn(v1, oscale);
+        const float p0 = lane_xor1(v0), p1 = lane_xor1(v1);
+        // even column + odd column on every lane (an exchanged order could pick the other payload of two NaNs)
+        s[u] = __fadd_rn(odd ? __fadd_rn(p0, v0) : __fadd_rn(v0, p0), odd ? __fadd_rn(p1, v1) : __fadd_rn(v1, p1));
+      }
+      const int m = mrow + i * MM::TS + MM::row(r, kq);
+      if (live && m < a.Co) out[base + (size_t)m * HWl] = (U == 2 && (lr & 1)) ? s[U - 1] : s[0];
+    }
+  }
+}
+
+template <int LOG2W, int BM, bool UP2, bool M16 = false, bool F16 = false, bool ADJ = false>
 __global__ __launch_bounds__(768) void conv_fwd_bf16p2_kernel(ConvArgsP2 a) {
   static_assert(!F16 || M16, "the fp16 planes form uses the 16x16x32 products");
+  static_assert(!ADJ || (M16 && !UP2 && LOG2W >= 4), "the adjoint store: 16x16x32 products, full-resolution input, W >= 16");
   constexpr int W = 1 << LOG2W, WP = W + 2, BN = 256, KC = 4, NS = 2;
   constexpr int WM = BM / 64, WN = 8 / WM, WTN = BN / WN, TM = 2, TN = WTN / 32;   // 128: 2x4 waves of 64x64; 64: 1x8 of 64x32
   constexpr int ASZ = NS * KC * BM;                // chunks per weight tile
@@ -148,7 +204,9 @@ __global__ __launch_bounds__(768) void conv_fwd_bf16p2_kernel(ConvArgsP2 a) {
   uint32_t hoff[TNx];
 #pragma unroll
   for (int j = 0; j < TNx; ++j) {
-    const int nl = wn * WTN + j * TS + lr, R = nl >> LOG2W, w = nl & (W - 1);
+    int nl = wn * WTN + j * TS + lr;
+    if constexpr (ADJ) nl = adj_pixel<LOG2W, TNx>(wn, j, lr);
+    const int R = nl >> LOG2W, w = nl & (W - 1);
     const int seg = R / a.SR, rr = R - seg * a.SR;
     hoff[j] = (uint32_t)((seg * (a.SR + 2) + rr + 1) * WP + w + 1) * 16u;
   }
@@ -267,6 +325,10 @@ __global__ __launch_bounds__(768) void conv_fwd_bf16p2_kernel(ConvArgsP2 a) {
   }
 
   float* out = a.y + (size_t)sk * a.slab_stride;
+  if constexpr (ADJ) {       // (never launched with a K split: a.y is the low-resolution tensor)
+    adj_store<MM, LOG2W, TMx, TNx, F16>(acc, a, out, m0 + wm * 64, n0, wn, lr, kq, oscale);
+    return;
+  }
   if (M16 || !a.stats) {     // (the 16x16x32 instantiation is never launched with statistics)
     // ---- epilogue, direct form: every lane stores its accumulator elements (one pixel of NR channels per MFMA tile:
     // 128-byte -- 64-byte for 16x16 tiles -- row pieces per lane group)
@@ -351,9 +413,11 @@ __global__ __launch_bounds__(768) void conv_fwd_bf16p2_kernel(ConvArgsP2 a) {
 // barrier / LDS-latency bubbles.  Removed.)
 // ROWS2 (128- and 256-wide images): the 128-pixel tile is 2 rows x 64 columns instead of (half of) one row -- the band is
 // 4 x 66 chunks per plane row instead of 3 x 130, a third less ingest per tile.
-template <int LOG2W, int BM, bool UP2, int BN, bool M16 = false, bool ROWS2 = false, bool F16 = false>
+template <int LOG2W, int BM, bool UP2, int BN, bool M16 = false, bool ROWS2 = false, bool F16 = false, bool ADJ = false>
 __global__ __launch_bounds__(768) void conv_fwd_bf16p3_kernel(ConvArgsP2 a) {
   static_assert(!F16 || M16, "the fp16 planes form uses the 16x16x32 products");
+  static_assert(!ADJ || (M16 && !UP2 && !ROWS2 && BN == 256 && LOG2W >= 4 && LOG2W <= 6),
+                "the adjoint store: 16x16x32 products, full-resolution input, whole-row tiles of 16..64-wide images");
   constexpr int NMW = 8;
   // BN = 256 pixels per tile for W <= 64 (whole rows); BN = 128 for 128- and 256-wide images: one row, or one half of a
   // row whose band then takes its halo columns from the neighbouring half instead of the zero padding
@@ -538,7 +602,9 @@ __global__ __launch_bounds__(768) void conv_fwd_bf16p3_kernel(ConvArgsP2 a) {
   uint32_t hoff[TNx];
 #pragma unroll
   for (int j = 0; j < TNx; ++j) {
-    const int nl = wn * WTN + j * TS + lr, R = nl >> LOG2WB, w = nl & (WB - 1);
+    int nl = wn * WTN + j * TS + lr;
+    if constexpr (ADJ) nl = adj_pixel<LOG2W, TNx>(wn, j, lr);
+    const int R = nl >> LOG2WB, w = nl & (WB - 1);
     const int seg = R / a.SR, rr = R - seg * a.SR;
     hoff[j] = (uint32_t)((seg * (a.SR + 2) + rr + 1) * WP + w + 1) * 16u;
   }
@@ -651,6 +717,11 @@ __global__ __launch_bounds__(768) void conv_fwd_bf16p3_kernel(ConvArgsP2 a) {
     int R0e = 0, col0e = 0;
     if constexpr (ROWS2) tile_origin(tile_n_of(tcur), R0e, col0e);
     float* out = a.y + (size_t)sk * a.slab_stride;
+    if constexpr (ADJ) {     // (never launched with a K split: a.y is the low-resolution tensor)
+      adj_store<MM, LOG2W, TMx, TNx, F16>(acc, a, out, m0 + wm * 32 * TM, n0, wn, lr, kq, oscale);
+      tcur = next_tile(tcur);
+      continue;
+    }
 #pragma unroll
     for (int j = 0; j < TNx; ++j) {
       const int nl = wn * WTN + j * TS + lr;
@@ -754,6 +825,32 @@ void launch_fwd_band(const ConvArgsP2& a, const FwdPlanP& p, int W, int up2, int
             });
           }
         });
+      });
+    });
+  });
+}
+
+// The adjoint-store form (ADJ) exists for the whole-row 256-pixel tiles of 16..64-wide images on the 16x16x32 products,
+// without a K split: split launches store partial sums in slabs and the 2x2 fold would have to come behind their reduction.
+bool band_adj_form(const FwdPlanP& p, int W, int f16) {
+  const int lw = log2_exact(W);
+  return p.bn == 256 && !p.rows2 && lw >= 4 && lw <= 6 && p.splits == 1 && (f16 || band_m16()) &&
+         (p.path == FwdPath::Band || p.path == FwdPath::BandPersistent);
+}
+
+// Launch of the ADJ form: a.y is the low-resolution tensor, a.bias NULL, no split.  Grids as in launch_fwd_band.
+void launch_fwd_band_adj(const ConvArgsP2& a, const FwdPlanP& p, int W, int f16, hipStream_t st) {
+  const int ids = cdiv(a.nt, 8) * 8 * a.mt, lw = log2_exact(W);
+  pick<2>(f16 ? 1 : 0, [&](auto f16_c) {
+    pick_of<64, 128>(p.bm, [&](auto bm_c) {
+      pick_of<4, 5, 6>(lw, [&](auto lw_c) {
+        constexpr bool F16 = f16_c.value != 0;
+        constexpr int BM = bm_c.value, LW = lw_c.value;
+        if (p.path == FwdPath::Band)
+          launch_lds<conv_fwd_bf16p2_kernel<LW, BM, false, true, F16, true>>(dim3(ids, 1), dim3(768), p.lds, st, a);
+        else
+          launch_lds<conv_fwd_bf16p3_kernel<LW, BM, false, 256, true, false, F16, true>>(
+              dim3(g_opt.band_persist_blocks, 1), dim3(768), p.lds, st, a);
       });
     });
   });

@@ -2960,6 +2960,70 @@ int itcv_conv2d_fwd_bf16p_sub(const void* xplanes, const void* wp, const float* 
   return fwd_planes_run(xplanes, wp, bias, y, B, Ci, H, W, Co, KS, up2, fmt, nullptr, ws, ws_bytes, b0, nb, stream);
 }
 
+// Data gradient of a conv that read its input through the nearest x2 upsample, with the upsample's adjoint (the sum of
+// every 2x2 block) folded into the band kernel's store.  The plan is the one itcv_conv2d_fwd_bf16p_sub builds for the same
+// arguments (up2 = 0, no statistics); only the launched kernel form differs (conv_band.hip, ADJ).
+static bool dgrad_up2_plan(FwdPlanP& p, int B, int Ci, int H, int W, int Co, int KS, int fmt, int nb) {
+  if (B <= 0 || Ci <= 0 || H <= 0 || W <= 0 || Co <= 0 || nb < 1 || nb > B || !fmt_ok(fmt)) return false;
+  if (planes_of_fmt(fmt) != 2 || (H & 1) || (W & 1) || !itcv_conv2d_bf16s_supported(Ci, Co, KS)) return false;
+  p = plan_fwd_planes(B, Ci, H, W, Co, KS, 2, false);
+  if (p.path == FwdPath::Planes128) return false;
+  if (nb != B) {     // the sub-range launch: fwd_planes_run's rule
+    p.nt = (int)(((long long)nb * H * W + p.bn - 1) / p.bn);
+    if (p.path == FwdPath::Band || p.path == FwdPath::BandPersistent) {
+      const int ids = cdiv(p.nt, 8) * 8 * p.mt, pb = g_opt.band_persist_blocks;
+      p.path = (pb > 0 && ids > pb) ? FwdPath::BandPersistent : FwdPath::Band;
+    }
+  }
+  return band_adj_form(p, W, fmt == ITCV_PLANES_F16X2);
+}
+
+int itcv_conv2d_dgrad_up2_supported(int B, int Ci, int H, int W, int Co, int KS, int fmt, int nb) {
+  FwdPlanP p;
+  return dgrad_up2_plan(p, B, Ci, H, W, Co, KS, fmt, nb) ? 1 : 0;
+}
+
+int itcv_conv2d_dgrad_up2_bf16p(const void* xplanes, const void* wp, float* dx_lo, int B, int Ci, int H, int W, int Co,
+                                int KS, int fmt, int b0, int nb, void* ws, size_t ws_bytes, void* stream) {
+  if (int e = check_dims("itcv_conv2d_dgrad_up2_bf16p", B, Ci, H, W, Co, KS)) return e;
+  ITCV_REQUIRE(xplanes && wp && dx_lo && fmt_ok(fmt), "itcv_conv2d_dgrad_up2_bf16p");
+  ITCV_REQUIRE(b0 >= 0 && nb >= 1 && b0 + nb <= B, "itcv_conv2d_dgrad_up2_bf16p(image range)");
+  (void)ws, (void)ws_bytes;   // no K split, no slabs: kept in the signature beside the two-call path's
+  FwdPlanP p;
+  if (!dgrad_up2_plan(p, B, Ci, H, W, Co, KS, fmt, nb))
+    return fail("%s: no adjoint-store form for this shape / format (see itcv_conv2d_dgrad_up2_supported)",
+                "itcv_conv2d_dgrad_up2_bf16p");
+  const int f16 = fmt == ITCV_PLANES_F16X2;
+  const size_t in_image = (size_t)(Ci / 8) * H * W, in_plane = (size_t)B * in_image;
+  const u32x4* xp = static_cast<const u32x4*>(xplanes);
+  ConvArgsP2 a;
+  a.xscale = f16 ? reinterpret_cast<const ScaleRec*>(xp + 2 * in_plane) : nullptr;
+  a.xp = xp + (size_t)b0 * in_image;
+  a.wp = static_cast<const u32x4*>(wp);
+  a.bias = nullptr;
+  a.y = dx_lo + (size_t)b0 * Co * (H / 2) * (W / 2);
+  a.B = nb, a.Ci = Ci, a.H = H, a.Co = Co;
+  a.Mp = p.mt * p.bm;
+  a.N = nb * H * W;
+  a.mt = p.mt, a.nt = p.nt, a.cpt = p.cpt, a.cpt_per_split = p.cps;
+  a.SR = p.SR, a.NSEG = p.NSEG, a.NP = p.NP, a.NPC = p.NPC, a.PXB = p.PXB;
+  a.h_shift = log2_exact(H);
+  a.stats = nullptr, a.stat_T = p.nt;
+  a.slab_stride = 0;
+  a.plane_stride = in_plane;
+#ifdef ITCV_DIAG
+  a.debug = 0;
+#endif
+  hipStream_t st = S(stream);
+  {
+    ProfScope prof(st, p.path == FwdPath::Band ? kProfFwdBand : kProfFwdBandPersist, log2_exact(W), p.bm, 0, fmt,
+                   2.0 * nb * H * W * (double)Co * Ci * KS * KS);
+    launch_fwd_band_adj(a, p, W, f16, st);
+  }
+  ITCV_CHECK_LAUNCH("itcv_conv2d_dgrad_up2_bf16p");
+  return 0;
+}
+
 size_t itcv_conv2d_wgrad_workspace(int B, int Ci, int H, int W, int Co, int KS) {
   if (B <= 0 || Ci <= 0 || H <= 0 || W <= 0 || Co <= 0) return 0;
   size_t n = plan_wgrad(B, Ci, H, W, Co, KS).ws_need;

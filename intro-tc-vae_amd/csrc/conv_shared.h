@@ -145,5 +145,7 @@ struct FwdPlanP {
 // conv_band.hip
 bool plan_fwd_band(FwdPlanP& p, int B, int Ci, int H, int W, int Co, int KS, int ns);   // false: the band kernels do not take the shape
 void launch_fwd_band(const ConvArgsP2& a, const FwdPlanP& p, int W, int up2, int f16, hipStream_t st);
+bool band_adj_form(const FwdPlanP& p, int W, int f16);   // does the launch of plan p have an adjoint-store (2x2-summed output) form?
+void launch_fwd_band_adj(const ConvArgsP2& a, const FwdPlanP& p, int W, int f16, hipStream_t st);
 
 }  // namespace itcv

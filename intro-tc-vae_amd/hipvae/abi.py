@@ -150,6 +150,10 @@ class _Lib:
         object.__setattr__(self, name, fn)
         return fn
 
+    def forget(self, name):
+        """Drops the memo of one query (the few whose answer depends on a library option, after itcv_set_option)."""
+        self.__dict__.pop(name, None)
+
 
 lib = _Lib(_load())
 

@@ -31,6 +31,8 @@ def set_option(name, value):
     'band_persist_blocks' (0 = one tile per block, else the persistent kernel's block count), 'wgrad_m16' (0 / 1 =
     32x32x16 / 16x16x32 products in the planes weight gradient), 'planes_mfma_waves' (4 / 8).  Validated by the library."""
     call("itcv_set_option", name.encode(), int(value))
+    _up2_fold_route.cache_clear()      # the one cached host decision that reads an option ('band_m16')
+    lib.forget("itcv_conv2d_dgrad_up2_supported")
 
 
 def get_option(name):
@@ -483,6 +485,30 @@ def conv_route_of(conv, B, H, W, up2=False, needs_input_grad=True):
                       bool(needs_input_grad))
 
 
+# Data gradient of a conv that reads its input through the fused x2 upsample: the high-resolution gradient is consumed only
+# as the sum of its 2x2 blocks, and itcv_conv2d_dgrad_up2_bf16p folds that sum into the conv's store.  Taken where the
+# high-resolution tensor (nb * C * H * W fp32) is at least this many bytes: below the 32 MiB of aggregate L2 the round trip
+# through itcv_upsample2_bwd is served on-die and the fold buys nothing, so smaller steps keep issuing the two calls (on
+# purpose: the call sequence of the small configurations is pinned).  Bitwise the same result either way.
+UP2_FOLD_MIN_BYTES = [32 << 20]
+
+
+def set_up2_fold_min_bytes(nbytes):
+    """Threshold of the fused data-gradient + upsample-adjoint route (1: wherever the library has the form)."""
+    UP2_FOLD_MIN_BYTES[0] = int(nbytes)
+
+
+@functools.lru_cache(maxsize=None)
+def _up2_fold_route(B, Cd, H, W, Cx, KS, fmt, nb, min_bytes):
+    return bool(nb * Cx * H * W * 4 >= min_bytes and lib.itcv_conv2d_dgrad_up2_supported(B, Cd, H, W, Cx, KS, fmt, nb))
+
+
+def up2_fold_route(B, Cd, H, W, Cx, KS, fmt, nb):
+    """Does the data gradient dy [B, Cd, H, W] -> dx [B, Cx, H/2, W/2] of an upsampled conv, over ``nb`` live images, take
+    the fused route?  Decided once per shape (memoised like conv_route; kept beside the route record, not in it)."""
+    return _up2_fold_route(B, Cd, H, W, Cx, KS, fmt, nb, UP2_FOLD_MIN_BYTES[0])
+
+
 def missing_operand(fwd, bwd):
     """(fp32 x, sub-range form): what a backward on route ``bwd`` needs that a forward on route ``fwd`` did not leave --
     the conv math mode changed in between."""
@@ -863,7 +889,14 @@ class Conv2dFn(Function):
             dy = full
         dyp = planes_of(dy, ns_d if ns_d else fmt2, gradient=True) if (ns_d or wgrad == "planes") else None
         if need_x:
-            if ns_d:
+            b0, nb = live if live is not None else (0, B)
+            fold = bool(up2 and ns_d) and up2_fold_route(B, Co, H, W, Ci, KS, ns_d, nb)
+            if fold:
+                # the upsample's adjoint folded into the conv's store: the H x W gradient is never written
+                dx = _new_grad((B, Ci, H // 2, W // 2), dy.device, live)
+                call("itcv_conv2d_dgrad_up2_bf16p", ptr(dyp), ptr(packed_weight(weight, weight, 1, ns_d)), ptr(dx), B, Co, H, W,
+                     Ci, KS, ns_d, b0, nb, None, 0, stream())
+            elif ns_d:
                 dx = conv_apply_planes(dyp, weight, weight, 1, None, B, Co, H, W, Ci, KS, False, ns_d, live=live)
             elif live is not None:
                 # the per-image 5x5 kernels on the live images (a contiguous slice; the fp16 scale comes from their maximum,
@@ -874,9 +907,8 @@ class Conv2dFn(Function):
                            out=dx[sl])
             else:
                 dx = conv_apply(_require_fp32(dy, "Conv2dFn.backward"), weight, weight, 1, None, B, Co, H, W, Ci, KS, False)
-            if up2:
+            if up2 and not fold:
                 lo = _new_grad((B, Ci, H // 2, W // 2), dy.device, live)
-                b0, nb = live if live is not None else (0, B)
                 call("itcv_upsample2_bwd", ptr(dx[b0:b0 + nb]), ptr(lo[b0:b0 + nb]), nb * Ci, H // 2, W // 2, stream())
                 dx = lo
         if wgrad is not None:

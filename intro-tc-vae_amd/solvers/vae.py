@@ -225,9 +225,11 @@ class VAESolver:
         # the optimiser hyper-parameters are scalar kernel arguments frozen into a captured graph: the update specs are
         # part of its key, so a scheduler or manual decay of param_groups[0]["lr"] re-captures instead of being ignored
         # the TC solvers' KL hook ("simple" | "full") selects different kernels: a switch re-captures too
-        key = (tuple(real.shape), real.dtype, self.conv_math) + specs + self._graph_key_extra() + self._schedule_key() \
-            + (getattr(self, "kl_loss", None),)
-        from hipvae.functional import bump_weight_epoch
+        # the conv entry: the arithmetic, and the module-level routing threshold of the upsampled convs' data gradient
+        # (both select kernels; one element, so that the specs and everything behind them keep their places)
+        from hipvae.functional import UP2_FOLD_MIN_BYTES, bump_weight_epoch
+        key = (tuple(real.shape), real.dtype, (self.conv_math, UP2_FOLD_MIN_BYTES[0])) + specs + self._graph_key_extra() \
+            + self._schedule_key() + (getattr(self, "kl_loss", None),)
         graphs = self.__dict__.setdefault("_graphs", {})
         ent = graphs.get(key)
         if ent is None:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-layer timing of the implicit-GEMM conv kernels at the 64x64 (c2) shapes: forward,
-data-gradient, weight-gradient, with achieved TFLOP/s against the 157.3 TF fp32-MFMA peak."""
+data-gradient, weight-gradient, with achieved TFLOP/s against the 157.3 TF fp32-MFMA peak.
+`bench_layers.py up2fold`: A/B of the upsampled convs' data gradient, conv + upsample adjoint against the fused call."""
 import os
 import sys
 
@@ -65,5 +66,56 @@ def main():
           f"{tot[0]/tot[2]*1e-3:6.1f} | {tot[3]*1e3:8.3f} {tot[0]/tot[3]*1e-3:6.1f}")
 
 
+def up2_fold_ab():
+    """`bench_layers.py up2fold`: data gradient of the c2 decoder's upsampled convs (f16x3 planes) at 64 and 128 images,
+    the two calls (band conv into the H x W tensor + itcv_upsample2_bwd) against the fused entry point.  Per form 4 calls
+    are captured into a graph; median (and min) of 50 replays, us per call."""
+    from hipvae.abi import call, ptr, stream
+    d, fmt, calls, reps = torch.device("cuda:0"), HF.F16X2, 4, 50
+
+    def timed(once):
+        for _ in range(3):
+            once()
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            for _ in range(calls):
+                once()
+        for _ in range(3):
+            graph.replay()
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            graph.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1) * 1e3 / calls)
+        ts.sort()
+        return ts[len(ts) // 2], ts[0]
+
+    print(f"{'dy -> dx @ size':>20} {'B':>4} {'hi MB':>7} | {'conv+adjoint us':>16} {'min':>7} | {'fused us':>9} {'min':>7} | saved")
+    for D, X, S in ((64, 64, 64), (64, 128, 32), (128, 256, 16)):
+        for B in (64, 128):
+            dy = torch.randn(B, D, S, S, device=d) * 1e-3
+            w = torch.randn(D, X, 3, 3, device=d) * 0.05
+            dyp, wp = HF.split_planes(dy, fmt, gradient=True), HF.pack_weight_bf16s(w, 1, fmt)
+            hi, lo = torch.empty(B, X, S, S, device=d), torch.empty(B, X, S // 2, S // 2, device=d)
+            lo2 = torch.empty_like(lo)
+            assert HF.lib.itcv_conv2d_dgrad_up2_supported(B, D, S, S, X, 3, fmt, B)
+
+            def two():
+                call("itcv_conv2d_fwd_bf16p_st", ptr(dyp), ptr(wp), None, ptr(hi), B, D, S, S, X, 3, 0, fmt, None, None, 0, stream())
+                call("itcv_upsample2_bwd", ptr(hi), ptr(lo), B * X, S // 2, S // 2, stream())
+
+            def one():
+                call("itcv_conv2d_dgrad_up2_bf16p", ptr(dyp), ptr(wp), ptr(lo2), B, D, S, S, X, 3, fmt, 0, B, None, 0, stream())
+
+            (t2, m2), (t1, m1) = timed(two), timed(one)
+            assert torch.equal(lo, lo2)
+            print(f"{D:4d} ->{X:4d} @ {S:3d}x{S:<3d} {B:4d} {hi.numel() * 4 / 1e6:7.1f} | {t2:16.1f} {m2:7.1f} | {t1:9.1f} {m1:7.1f} | "
+                  f"{t2 - t1:6.1f} us", flush=True)
+
+
 if __name__ == "__main__":
-    main()
+    up2_fold_ab() if sys.argv[1:2] == ["up2fold"] else main()
