@@ -985,7 +985,9 @@ int itcv_sap_svc_score(const float* x, size_t ld, const int* y, int Nt, int D, i
  *   square root disentanglement_lib takes); w_norm = w / tr C.  lambda: cyclic Jacobi in fp64 inside one launch.  A sweep is
  *   Dp - 1 rounds (Dp = D rounded up to even) of the round-robin schedule: round r rotates the disjoint pairs (r, Dp - 1) and
  *   ((r + k) mod (Dp - 1), (r - k) mod (Dp - 1)), k = 1 .. Dp / 2 - 1, each ordered p < q; a pair with q >= D or with
- *   S[p][q] == 0 is skipped.  Rotation of (p, q): tau = (S[q][q] - S[p][p]) / (2 S[p][q]), t = sign(tau) / (|tau| +
+ *   S[p][q] == 0 is skipped; an element with |S[p][p]| + |S[p][q]| == |S[p][p]| and |S[q][q]| + |S[p][q]| == |S[q][q]| (fp64)
+ *   is negligible and takes the identity rotation c = 1, s = 0: it is set to 0 and nothing else moves (inside a cluster of
+ *   equal eigenvalues tau would be a quotient of rounding errors).  Rotation of (p, q): tau = (S[q][q] - S[p][p]) / (2 S[p][q]), t = sign(tau) / (|tau| +
  *   sqrt(1 + tau^2)) (sign(0) = +1), c = 1 / sqrt(1 + t^2), s = t c; all rotations of a round are computed from the matrix
  *   as the round finds it, then rows p, q become (c row_p - s row_q, s row_p + c row_q), then the columns likewise, and the
  *   2 x 2 block takes its closed form S[p][p] - t S[p][q], S[q][q] + t S[p][q], 0.  Before every sweep: stop when

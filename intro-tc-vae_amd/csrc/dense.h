@@ -65,7 +65,8 @@ struct JacobiScratch {                    // __shared__ in the calling kernel
 // done (false); the eigenvalues are left on the diagonal, *sweeps is the number taken.  Round r of a sweep rotates the
 // disjoint pairs of the round-robin schedule on Dp = D rounded up to even: (r, Dp - 1) and ((r + k) mod (Dp - 1),
 // (r - k) mod (Dp - 1)), k = 1 .. Dp / 2 - 1; a pair that touches index D (odd D) or whose off-diagonal element is exactly 0
-// is skipped.
+// is skipped, and an element a with |A_pp| + |a| == |A_pp| and |A_qq| + |a| == |A_qq| is set to 0 without a rotation
+// (without that rule a matrix with two eigenvalues of multiplicity 64 each is still unconverged after 60 sweeps).
 template <int THREADS>
 __device__ __forceinline__ bool block_jacobi(double* A, int lda, int D, JacobiScratch* s, int* sweeps) {
 #pragma clang fp contract(off)
@@ -99,11 +100,19 @@ __device__ __forceinline__ bool block_jacobi(double* A, int lda, int D, JacobiSc
           const double apq = A[(size_t)p * lda + q];
           if (apq != 0.0) {
             const double app = A[(size_t)p * lda + p], aqq = A[(size_t)q * lda + q];
-            const double tau = (aqq - app) / (2.0 * apq);
-            const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-            const double c = 1.0 / sqrt(1.0 + t * t);
-            s->rc[k] = c, s->rs[k] = t * c;
-            s->npp[k] = app - t * apq, s->nqq[k] = aqq + t * apq;
+            const double g = fabs(apq);
+            if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) {
+              // negligible against both diagonal elements: dropped by the identity rotation.  Inside a cluster of equal
+              // eigenvalues tau is a quotient of two rounding errors; rotating by it refills what the sweep has cleared.
+              s->rc[k] = 1.0, s->rs[k] = 0.0;
+              s->npp[k] = app, s->nqq[k] = aqq;
+            } else {
+              const double tau = (aqq - app) / (2.0 * apq);
+              const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
+              const double c = 1.0 / sqrt(1.0 + t * t);
+              s->rc[k] = c, s->rs[k] = t * c;
+              s->npp[k] = app - t * apq, s->nqq[k] = aqq + t * apq;
+            }
             po = p;
           }
         }

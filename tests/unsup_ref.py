@@ -64,6 +64,10 @@ def ref_jacobi(S):
                 if q >= D or A[p, q] == 0.0:
                     continue
                 app, aqq, apq = A[p, p], A[q, q], A[p, q]
+                g = abs(apq)
+                if abs(app) + g == abs(app) and abs(aqq) + g == abs(aqq):   # negligible: the identity rotation
+                    rot.append((p, q, 1.0, 0.0, app, aqq))
+                    continue
                 tau = (aqq - app) / (2.0 * apq)
                 t = (1.0 if tau >= 0.0 else -1.0) / (abs(tau) + np.sqrt(1.0 + tau * tau))
                 c = 1.0 / np.sqrt(1.0 + t * t)
