@@ -16,6 +16,7 @@ import torch
 
 from . import functional as HF
 from .abi import call, ptr, stream
+from .inference import device_of, eval_mode, images
 
 KEYS = ("mi", "tc", "dwkl", "kl", "kl_analytic", "joint_entropy", "marginal_entropies", "dimwise_kl")
 _HALF_LOG_2PI = 0.9189385332046727
@@ -55,17 +56,6 @@ def elbo_decomposition(z, rows, mu, logvar, logw=None):
                 marginal_entropies=out[6:6 + D].copy(), dimwise_kl=out[6 + D:6 + 2 * D].copy())
 
 
-def _device_of(model):
-    return next(model.parameters()).device
-
-
-def _images(source, idx, device):
-    if hasattr(source, "gather"):                      # a DeviceImageTable: one launch per batch
-        return source.gather(idx)
-    items = [source[int(i)] for i in idx]
-    return torch.stack([it[0] if isinstance(it, (tuple, list)) else it for it in items], 0).to(device)
-
-
 def dataset_posteriors(source, model, indices, batch_size=64):
     """``(mu, logvar)`` [N, D] fp32 on the device: ``model.encode`` of the images at ``indices``, batch by batch, in eval
     mode and without gradients, written into two preallocated buffers.  ``source``: a ``DeviceImageTable`` (one
@@ -73,22 +63,17 @@ def dataset_posteriors(source, model, indices, batch_size=64):
     indices = np.asarray(indices, dtype=np.int64)
     if indices.ndim != 1 or not len(indices):
         raise ValueError("dataset_posteriors: indices must be a non-empty 1-D integer array")
-    device = _device_of(model)
-    was_training = model.training
-    model.eval()
+    device = device_of(model)
     mu = logvar = None
-    try:
-        with torch.no_grad():
-            for a in range(0, len(indices), int(batch_size)):
-                idx = indices[a:a + int(batch_size)]
-                m, lv = model.encode(_images(source, idx, device))
-                if mu is None:
-                    mu = torch.empty((len(indices), m.shape[1]), dtype=torch.float32, device=m.device)
-                    logvar = torch.empty_like(mu)
-                mu[a:a + len(idx)].copy_(m)
-                logvar[a:a + len(idx)].copy_(lv)
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        for a in range(0, len(indices), int(batch_size)):
+            idx = indices[a:a + int(batch_size)]
+            m, lv = model.encode(images(source, idx, device))
+            if mu is None:
+                mu = torch.empty((len(indices), m.shape[1]), dtype=torch.float32, device=m.device)
+                logvar = torch.empty_like(mu)
+            mu[a:a + len(idx)].copy_(m)
+            logvar[a:a + len(idx)].copy_(lv)
     return mu, logvar
 
 

@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 from . import functional as HF
-from .aggregate import _device_of
-from .quality import _raise_on, real_features
+from .inference import device_of, eval_mode
+from .quality import raise_on_nonfinite, real_features
 
 MAX_COMPONENTS, MAX_DIM = 64, 512
 
@@ -120,7 +120,7 @@ def fit_gmm(x, n_components=10, max_iter=100, tol=1e-3, reg_covar=1e-6, init="km
         flags = HF.disent_flags(x.device)
     chol, linv, logdet, info = HF.gmm_factor(cov)
     got = torch.cat([flags[:1].to(torch.float64), info.to(torch.float64)]).tolist()
-    _raise_on(got[0])
+    raise_on_nonfinite(got[0])
     _raise_on_pivot(got[1:])
     history, prev, converged = [], float("-inf"), False
     for _ in range(int(max_iter)):
@@ -128,7 +128,7 @@ def fit_gmm(x, n_components=10, max_iter=100, tol=1e-3, reg_covar=1e-6, init="km
         _, w, mean, cov = HF.gmm_mstep(x, resp, flags, reg=reg_covar)
         chol, linv, logdet, info = HF.gmm_factor(cov)
         got = torch.cat([total, flags[:1].to(torch.float64), info.to(torch.float64)]).tolist()    # the one read-back
-        _raise_on(got[1])
+        raise_on_nonfinite(got[1])
         _raise_on_pivot(got[2:])
         bound = got[0] / N
         history.append(bound)
@@ -142,7 +142,7 @@ def fit_gmm(x, n_components=10, max_iter=100, tol=1e-3, reg_covar=1e-6, init="km
 def _estep(gmm, x):
     flags = HF.disent_flags(x.device)
     out = HF.gmm_estep(x, gmm.weights, gmm.means, gmm.prec_chol, gmm.log_det, flags)
-    _raise_on(flags.tolist()[0])
+    raise_on_nonfinite(flags.tolist()[0])
     return out
 
 
@@ -204,17 +204,12 @@ def vamp_prior(model, pseudo_inputs, batch_size=64):
     bs = int(batch_size)
     if bs < 1:
         raise ValueError(f"batch_size must be positive (got {batch_size})")
-    device = _device_of(model)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            u = (pseudo_inputs() if callable(pseudo_inputs) else pseudo_inputs).detach().to(device)
-            if u.dim() != 4 or not u.shape[0]:
-                raise ValueError(f"vamp_prior: the pseudo-inputs must be [K, C, H, W] (got {tuple(u.shape)})")
-            parts = [model.encode(u[a:a + bs])[:2] for a in range(0, u.shape[0], bs)]
-    finally:
-        model.train(was_training)
+    device = device_of(model)
+    with eval_mode(model):
+        u = (pseudo_inputs() if callable(pseudo_inputs) else pseudo_inputs).detach().to(device)
+        if u.dim() != 4 or not u.shape[0]:
+            raise ValueError(f"vamp_prior: the pseudo-inputs must be [K, C, H, W] (got {tuple(u.shape)})")
+        parts = [model.encode(u[a:a + bs])[:2] for a in range(0, u.shape[0], bs)]
     return VampPrior(torch.cat([p[0] for p in parts], 0).to(torch.float32).contiguous(),
                      torch.cat([p[1] for p in parts], 0).to(torch.float32).contiguous())
 
@@ -228,7 +223,7 @@ def vamp_log_prob(prior, x):
     rows = max(1, min(VAMP_CHUNK, HF.VAMP_MAX_PAIRS // prior.n_components))
     x = x.detach().to(torch.float32)
     out = torch.cat([HF.vamp_log_prob(x[a:a + rows], prior.means, prior.logvars) for a in range(0, x.shape[0], rows)])
-    _raise_on(not bool(torch.isfinite(out).all()))
+    raise_on_nonfinite(not bool(torch.isfinite(out).all()))
     return out
 
 
@@ -278,7 +273,7 @@ def compute_latent_density(source, model, num_fit=10000, num_eval=None, latent="
         feature = "encoder"
     else:
         gen = torch.Generator().manual_seed(int(seed))
-        device = _device_of(model)
+        device = device_of(model)
 
         def feature(images):
             mu, logvar = model.encode(images)[:2]

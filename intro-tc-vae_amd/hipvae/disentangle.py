@@ -86,6 +86,7 @@ import torch
 from . import functional as HF
 from . import gbt
 from . import logreg
+from .inference import draw_indices, eval_mode
 
 __all__ = ["discretize", "factor_counts", "mutual_info", "mig_score", "modularity_score", "scores", "FactorSampler",
            "factor_representations", "compute_mig_score", "compute_modularity_score", "compute_scores",
@@ -265,20 +266,15 @@ def factor_representations(sampler, model, num_samples, batch_size):
     """``(mu [N, D] fp32, factors [N, K] int32)`` on the device: ``model.encode`` of ``num_samples`` sampled images, batch
     by batch, in eval mode and without gradients (evaluation/utils.py:14-56).  Every batch's means are written into one
     preallocated buffer; nothing is read back.  ``sampler``: a ``FactorSampler`` or the reference's generator."""
-    was_training = model.training
-    model.eval()
     mu, factors, row = None, [], 0
-    try:
-        with torch.no_grad():
-            for f, obs in sampler.generate(num_samples, batch_size, drop_last=False):
-                m, _ = model.encode(obs)
-                if mu is None:
-                    mu = torch.empty((num_samples, m.shape[1]), dtype=m.dtype, device=m.device)
-                mu[row:row + m.shape[0]].copy_(m)
-                row += m.shape[0]
-                factors.append(np.asarray(f))
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        for f, obs in sampler.generate(num_samples, batch_size, drop_last=False):
+            m, _ = model.encode(obs)
+            if mu is None:
+                mu = torch.empty((num_samples, m.shape[1]), dtype=m.dtype, device=m.device)
+            mu[row:row + m.shape[0]].copy_(m)
+            row += m.shape[0]
+            factors.append(np.asarray(f))
     if mu is None or row != num_samples:
         raise ValueError(f"factor_representations: the sampler produced {row} of {num_samples} samples")
     v = torch.from_numpy(np.concatenate(factors, 0).astype(np.int32)).to(mu.device)
@@ -391,26 +387,21 @@ def factor_change_rows(latent_generator, model, num_samples, batch_size, index_s
     images (eval BatchNorm makes stacking exact).  The fixed factor's index is drawn, as the reference writes it, from a
     fresh ``RandomState(latent_generator.seed)`` per batch, or from ``index_state`` if given."""
     nb = int(np.ceil(num_samples / batch_size))
-    was_training = model.training
-    model.eval()
     rows, y = None, np.empty((nb,), dtype=np.int64)
-    try:
-        with torch.no_grad():
-            for r in range(nb):
-                rs = index_state if index_state is not None else np.random.RandomState(latent_generator.seed)
-                y[r] = k = rs.randint(latent_generator.num_latents)
-                v_li = latent_generator.sample_factors_of_variation(batch_size)
-                v_lj = latent_generator.sample_factors_of_variation(batch_size)
-                v_li[:, k] = v_lj[:, k]
-                x_li = latent_generator.sample_observations_from_factors(v_li)
-                x_lj = latent_generator.sample_observations_from_factors(v_lj)
-                mu, _ = model.encode(torch.cat([x_li, x_lj], 0))
-                mu = mu.reshape(2 * batch_size, -1)
-                if rows is None:
-                    rows = torch.empty((nb, mu.shape[1]), dtype=torch.float32, device=mu.device)
-                HF.zdiff_row(mu[:batch_size], mu[batch_size:], rows[r])
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        for r in range(nb):
+            rs = index_state if index_state is not None else np.random.RandomState(latent_generator.seed)
+            y[r] = k = rs.randint(latent_generator.num_latents)
+            v_li = latent_generator.sample_factors_of_variation(batch_size)
+            v_lj = latent_generator.sample_factors_of_variation(batch_size)
+            v_li[:, k] = v_lj[:, k]
+            x_li = latent_generator.sample_observations_from_factors(v_li)
+            x_lj = latent_generator.sample_observations_from_factors(v_lj)
+            mu, _ = model.encode(torch.cat([x_li, x_lj], 0))
+            mu = mu.reshape(2 * batch_size, -1)
+            if rows is None:
+                rows = torch.empty((nb, mu.shape[1]), dtype=torch.float32, device=mu.device)
+            HF.zdiff_row(mu[:batch_size], mu[batch_size:], rows[r])
     return rows, y
 
 
@@ -587,14 +578,9 @@ def compute_factor_vae_score(latent_generator, model, batch_size=64, num_train=1
     nv = int(params.get("num_variance_estimate", num_variance_estimate))
     mu_var, _ = factor_representations(latent_generator, model, nv, L)
     stack = max(1, 1024 // L)
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            mu_t, f_t = _fixed_factor_representations(latent_generator, model, nt, L, stack)
-            mu_e, f_e = _fixed_factor_representations(latent_generator, model, ne, L, stack)
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        mu_t, f_t = _fixed_factor_representations(latent_generator, model, nt, L, stack)
+        mu_e, f_e = _fixed_factor_representations(latent_generator, model, ne, L, stack)
     return factor_vae_score(mu_var, mu_t, f_t, mu_e, f_e, L, int(latent_generator.num_latents),
                             params.get("threshold", 0.05))
 
@@ -753,17 +739,11 @@ def gaussian_scores(cov):
 
 def compute_unsupervised_scores(source, model, num_train=10000, batch_size=64, seed=0):
     """``unsupervised_scores`` of the mean representations of ``num_train`` images of ``source`` (a ``DeviceImageTable``
-    or a dataset; no factors are needed): the images ``np.sort(RandomState(seed).choice(len(source), num_train,
-    replace=False))``, or all of them when ``num_train >= len(source)``, encoded by ``hipvae.aggregate.
-    dataset_posteriors`` in eval mode without gradients.  torch's generators, the BatchNorm buffers and the training flag
-    are left as found."""
+    or a dataset; no factors are needed): the images ``inference.draw_indices(len(source), num_train, seed)``, encoded by
+    ``hipvae.aggregate.dataset_posteriors`` in eval mode without gradients.  torch's generators, the BatchNorm buffers and
+    the training flag are left as found."""
     from . import aggregate
-    n = len(source)
-    if int(num_train) >= n:
-        idx = np.arange(n, dtype=np.int64)
-    else:
-        idx = np.sort(np.random.RandomState(seed).choice(n, int(num_train), replace=False)).astype(np.int64)
-    mu, _ = aggregate.dataset_posteriors(source, model, idx, batch_size)
+    mu, _ = aggregate.dataset_posteriors(source, model, draw_indices(len(source), num_train, seed), batch_size)
     return unsupervised_scores(mu)
 
 
@@ -976,19 +956,14 @@ def udr_scores(mus, logvars=None, correlation="lasso", kl_filter_threshold=0.01,
 
 def compute_udr_score(source, models, num_train=10000, batch_size=64, seed=0, params=None):
     """``udr_scores`` of ``models`` (M >= 2 networks with the same input) on ``num_train`` images of ``source`` (a
-    ``DeviceImageTable`` or a dataset; no factors are needed): the images of ``compute_unsupervised_scores`` (``np.sort(
-    RandomState(seed).choice(len(source), num_train, replace=False))``, or all of them), encoded once per model by
+    ``DeviceImageTable`` or a dataset; no factors are needed): the images ``inference.draw_indices(len(source), num_train,
+    seed)``, the ones ``compute_unsupervised_scores`` sees, encoded once per model by
     ``hipvae.aggregate.dataset_posteriors`` in eval mode without gradients.  torch's generators, the BatchNorm buffers
     and the training flags are left as found.  ``params`` may carry ``correlation``, ``kl_filter_threshold``, ``alpha``
     and ``num_train``."""
     from . import aggregate
     params = params or {}
-    num_train = int(params.get("num_train", num_train))
-    n = len(source)
-    if num_train >= n:
-        idx = np.arange(n, dtype=np.int64)
-    else:
-        idx = np.sort(np.random.RandomState(seed).choice(n, num_train, replace=False)).astype(np.int64)
+    idx = draw_indices(len(source), params.get("num_train", num_train), seed)
     post = [aggregate.dataset_posteriors(source, model, idx, batch_size) for model in models]
     return udr_scores([p[0] for p in post], [p[1] for p in post], params.get("correlation", "lasso"),
                       params.get("kl_filter_threshold", 0.01), params.get("alpha", 0.1))

@@ -9,7 +9,7 @@ import torch
 
 import ops
 from . import functional as HF
-from .aggregate import _device_of, _images
+from .inference import device_of, eval_mode, images
 
 MAX_ROWS = 4096          # rows of one decoder pass under the default ``chunk``
 
@@ -51,30 +51,25 @@ def compute_log_likelihood(source, model, num_samples=1000, chunk=None, batch_si
         raise ValueError("compute_log_likelihood: indices must be a non-empty 1-D integer array")
     if chunk is not None and (int(chunk) != chunk or not 1 <= chunk <= HF.IWAE_MAX_K):
         raise ValueError(f"chunk must be an integer in 1..{HF.IWAE_MAX_K} (got {chunk!r})")
-    device = _device_of(model)
+    device = device_of(model)
     gen = torch.Generator().manual_seed(int(seed))
     lt = HF.abi.LOSS_TYPES[loss_type]
     outs, P = [], None
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for a in range(0, len(indices), batch_size):
-                x = _images(source, indices[a:a + batch_size], device)
-                B = x.shape[0]
-                P = x.numel() // B
-                kc = int(chunk) if chunk is not None else max(1, min(HF.IWAE_MAX_K, MAX_ROWS // B))
-                mu, logvar = model.encode(x)
-                state = torch.zeros((5, B), dtype=torch.float64, device=device)
-                for k0 in range(0, K, kc):
-                    k = min(kc, K - k0)
-                    eps = torch.randn((k * B, mu.shape[1]), generator=gen).to(device)
-                    sample = ops.iwae_sample(mu, logvar, k, eps=eps)
-                    rows = HF.IwaeRowsFn.apply(x.reshape(B, -1), model.decode(sample.z).reshape(k * B, -1), lt)
-                    HF.iwae_accumulate(rows, sample.lat, state, beta_rec, 1.0)
-                outs.append(torch.stack(HF.iwae_finalize(state)))
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        for a in range(0, len(indices), batch_size):
+            x = images(source, indices[a:a + batch_size], device)
+            B = x.shape[0]
+            P = x.numel() // B
+            kc = int(chunk) if chunk is not None else max(1, min(HF.IWAE_MAX_K, MAX_ROWS // B))
+            mu, logvar = model.encode(x)
+            state = torch.zeros((5, B), dtype=torch.float64, device=device)
+            for k0 in range(0, K, kc):
+                k = min(kc, K - k0)
+                eps = torch.randn((k * B, mu.shape[1]), generator=gen).to(device)
+                sample = ops.iwae_sample(mu, logvar, k, eps=eps)
+                rows = HF.IwaeRowsFn.apply(x.reshape(B, -1), model.decode(sample.z).reshape(k * B, -1), lt)
+                HF.iwae_accumulate(rows, sample.lat, state, beta_rec, 1.0)
+            outs.append(torch.stack(HF.iwae_finalize(state)))
     got = torch.cat(outs, dim=1).cpu().numpy()                      # the one read-back
     log_px, elbo, ess = got[0], got[1], got[2]
     return dict(log_px=float(log_px.mean()), bits_per_dim=float(-log_px.mean() / (P * math.log(2.0))),

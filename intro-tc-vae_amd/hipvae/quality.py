@@ -18,13 +18,13 @@ import torch
 import torch.nn.functional as F
 
 from . import functional as HF
-from .aggregate import _device_of, _images
+from .inference import device_of, draw_indices, eval_mode, images
 
 FRECHET_MAX_DIM = 512
 SCORES = ("frechet", "kid", "prdc")
 
 
-def _raise_on(flag):
+def raise_on_nonfinite(flag):
     if flag:
         raise ValueError("quality: the features contain non-finite values")
 
@@ -35,7 +35,7 @@ def knn_radius(x, k, splits=0):
     ``get_kth_value(dist, k + 1)``, squared).  One read-back (the non-finite flag)."""
     flags = HF.disent_flags(x.device)
     r2 = HF.knn_radius(x, k, flags, splits)
-    _raise_on(flags.tolist()[0])
+    raise_on_nonfinite(flags.tolist()[0])
     return r2
 
 
@@ -57,7 +57,7 @@ def prdc(real, fake, nearest_k=5):
     integer counts (every comparison strict, as in ``prdc``).  One read-back."""
     nearest_k = int(nearest_k)
     c = prdc_counts(real, fake, nearest_k)["counts"].tolist()           # the one read-back
-    _raise_on(c[4])
+    raise_on_nonfinite(c[4])
     N, M = real.shape[0], fake.shape[0]
     return dict(precision=c[0] / M, recall=c[1] / N, density=c[2] / (nearest_k * M), coverage=c[3] / N)
 
@@ -83,7 +83,7 @@ def frechet_distance(real, fake, eps=0.0):
     flags = HF.disent_flags(real.device)
     (m1, c1), (m2, c2) = HF.unsup_cov(real, flags), HF.unsup_cov(fake, flags)
     out, eig = _frechet_once(m1, c1, m2, c2, eps)
-    _raise_on(flags.tolist()[0])
+    raise_on_nonfinite(flags.tolist()[0])
     swapped = False
     if out[5]:
         first = int(out[6])
@@ -125,7 +125,7 @@ def kernel_distance(real, fake, degree=3, gamma=None, coef0=1.0, subset_size=Non
     vals = torch.stack(res)
     out = torch.cat([vals.mean().reshape(1), vals.std(unbiased=False).reshape(1) if len(res) > 1 else vals.new_zeros(1),
                      flags[:1].to(torch.float64)]).tolist()
-    _raise_on(out[2])
+    raise_on_nonfinite(out[2])
     return dict(kid=out[0], kid_std=out[1])
 
 
@@ -139,21 +139,15 @@ def _feature_fn(model, feature):
 
 
 def _collect(model, batches, feature):
-    """The rows ``feature(images)`` of every batch in one fp32 [N, D] device tensor; eval mode, no gradients, the training
-    flag put back."""
+    """The rows ``feature(images)`` of every batch in one fp32 [N, D] device tensor, under ``inference.eval_mode``."""
     fn = _feature_fn(model, feature)
     rows = []
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for images in batches():
-                f = fn(images)
-                if not isinstance(f, torch.Tensor) or f.dim() != 2 or not f.is_floating_point():
-                    raise ValueError("feature(images) must return a floating-point [B, D] tensor")
-                rows.append(f.detach().to(torch.float32))
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        for batch in batches():
+            f = fn(batch)
+            if not isinstance(f, torch.Tensor) or f.dim() != 2 or not f.is_floating_point():
+                raise ValueError("feature(images) must return a floating-point [B, D] tensor")
+            rows.append(f.detach().to(torch.float32))
     return torch.cat(rows, 0).contiguous()
 
 
@@ -164,10 +158,10 @@ def real_features(source, model, indices, batch_size=64, feature="encoder"):
     indices = np.asarray(indices, dtype=np.int64)
     if indices.ndim != 1 or not len(indices):
         raise ValueError("real_features: indices must be a non-empty 1-D integer array")
-    device, bs = _device_of(model), int(batch_size)
+    device, bs = device_of(model), int(batch_size)
     if bs < 1:
         raise ValueError(f"batch_size must be positive (got {batch_size})")
-    return _collect(model, lambda: (_images(source, indices[a:a + bs], device) for a in range(0, len(indices), bs)), feature)
+    return _collect(model, lambda: (images(source, indices[a:a + bs], device) for a in range(0, len(indices), bs)), feature)
 
 
 def generated_features(model, num, batch_size=64, seed=0, feature="encoder", prior=None):
@@ -179,7 +173,7 @@ def generated_features(model, num, batch_size=64, seed=0, feature="encoder", pri
     num, bs = int(num), int(batch_size)
     if num < 1 or bs < 1:
         raise ValueError(f"num and batch_size must be positive (got {num}, {batch_size})")
-    device = _device_of(model)
+    device = device_of(model)
     zdim = model.zdim
     if prior is None:
         gen = torch.Generator().manual_seed(int(seed))
@@ -212,9 +206,9 @@ def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature
     flat dict with ``frechet`` ("frechet" in ``scores``), ``kid`` and ``kid_std`` ("kid") and ``precision``, ``recall``,
     ``density``, ``coverage`` ("prdc"), plus ``features = dict(real, fake)`` (fp32 device tensors) and the ``indices`` used.
 
-    Real images: ``indices``, or ``np.sort(RandomState(seed).choice(len(source), num_real, replace=False))``, or all of them
-    when ``num_real >= len(source)``.  Fakes: ``num_fake`` (None: as many as real images) decoded prior samples,
-    ``generated_features(model, num_fake, batch_size, seed, feature)``.  The default feature is the model's own encoder
+    Real images: ``indices``, or ``inference.draw_indices(len(source), num_real, seed)``: a sorted draw without replacement,
+    or all of them when ``num_real >= len(source)``.  Fakes: ``num_fake`` (None: as many as real images) decoded prior
+    samples, ``generated_features(model, num_fake, batch_size, seed, feature)``.  The default feature is the model's own encoder
     mean, so the numbers compare models of one architecture and are not a published FID / KID.  The Frechet distance
     needs D <= 512; ``eps`` regularises its covariances.
 
@@ -237,11 +231,7 @@ def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature
     elif prior not in ("normal", "gmm"):
         raise ValueError(f'compute_sample_quality: prior must be "normal", "gmm" or a GaussianMixture (got {prior!r})')
     if indices is None:
-        n = len(source)
-        if int(num_real) >= n:
-            indices = np.arange(n, dtype=np.int64)
-        else:
-            indices = np.sort(np.random.RandomState(seed).choice(n, int(num_real), replace=False)).astype(np.int64)
+        indices = draw_indices(len(source), num_real, seed)
     indices = np.asarray(indices, dtype=np.int64)
     real = real_features(source, model, indices, batch_size, feature)
     if isinstance(prior, str) and prior == "gmm":
@@ -323,34 +313,24 @@ def compute_reconstruction_quality(source, model, num=10000, batch_size=64, seed
     """The means of ``reconstruction_quality`` over images of ``source`` (a ``DeviceImageTable`` or a dataset; no factors are
     needed) and their deterministic reconstructions ``model.decode(model.encode(x)[0])``: a dict with ``psnr``, ``ssim``,
     ``ms_ssim``, ``mse``, ``l1`` (Python floats), ``per_image`` (the five fp64 device vectors) and the ``indices`` used --
-    ``indices``, or ``np.sort(RandomState(seed).choice(len(source), num, replace=False))``, or all images when ``num >=
-    len(source)``, as ``compute_sample_quality`` draws them.  ``kw`` goes to ``reconstruction_quality``.  The model runs in
-    eval mode under ``no_grad``; its training flag is put back and its BatchNorm buffers are not written.  ``psnr`` is the
-    mean of the per-image values (inf as soon as one image is reconstructed exactly)."""
+    ``indices``, or ``inference.draw_indices(len(source), num, seed)``.  ``kw`` goes to ``reconstruction_quality``.  The
+    model runs in eval mode under ``no_grad``; its training flag is put back and its BatchNorm buffers are not written.  ``psnr``
+    is the mean of the per-image values (inf as soon as one image is reconstructed exactly)."""
     if indices is None:
-        n = len(source)
-        if int(num) >= n:
-            indices = np.arange(n, dtype=np.int64)
-        else:
-            indices = np.sort(np.random.RandomState(seed).choice(n, int(num), replace=False)).astype(np.int64)
+        indices = draw_indices(len(source), num, seed)
     indices = np.asarray(indices, dtype=np.int64)
     if indices.ndim != 1 or not len(indices):
         raise ValueError("compute_reconstruction_quality: indices must be a non-empty 1-D integer array")
-    device, bs = _device_of(model), int(batch_size)
+    device, bs = device_of(model), int(batch_size)
     if bs < 1:
         raise ValueError(f"batch_size must be positive (got {batch_size})")
     parts = {k: [] for k in RECONSTRUCTION_SCORES}
-    was_training = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for a in range(0, len(indices), bs):
-                images = _images(source, indices[a:a + bs], device)
-                got = reconstruction_quality(images, model.decode(model.encode(images)[0]), **kw)
-                for k in RECONSTRUCTION_SCORES:
-                    parts[k].append(got[k])
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        for a in range(0, len(indices), bs):
+            x = images(source, indices[a:a + bs], device)
+            got = reconstruction_quality(x, model.decode(model.encode(x)[0]), **kw)
+            for k in RECONSTRUCTION_SCORES:
+                parts[k].append(got[k])
     per_image = {k: torch.cat(v, 0) for k, v in parts.items()}
     out = {k: float(v.mean()) for k, v in per_image.items()}
     out["per_image"] = per_image

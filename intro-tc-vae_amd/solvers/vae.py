@@ -12,6 +12,7 @@ from torch import Tensor
 from hipvae import ddp
 from hipvae.functional import LinCombFn, conv_math_scope, deferred_wgrad_reduces, direct_grad_accumulation
 from hipvae.flat import FlatGroup, clip_grad_norm, fused_update
+from hipvae.inference import eval_mode
 from models import grad_free_parameters
 from ops import kl_divergence, reconstruction_loss
 from utils import SingletonWriter
@@ -54,9 +55,9 @@ class VAESolver:
         # "all" -> the beta-VAE score and explicitness too; "all+dci" -> DCI as well, nothing delegated
         self.device_scores = None
         self.dci_params = None       # ``params`` of hipvae.disentangle.compute_dci_score (None: 100 rounds, depth 6)
-        # scores the reference does not have, written from the device on top of the above: a tuple drawn from
-        # {"factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr"}; ``params`` of
-        # hipvae.disentangle.compute_factor_vae_score / compute_sap_score / compute_irs_score; keyword arguments of
+        # scores the reference does not have, written from the device on top of the above: a tuple of names of
+        # solvers.scores.TABLE, whose records say what each writes and which of the attributes below feeds it: ``params``
+        # of hipvae.disentangle.compute_factor_vae_score / compute_sap_score / compute_irs_score; keyword arguments of
         # hipvae.aggregate.compute_elbo_decomposition / hipvae.disentangle.compute_unsupervised_scores (None: their
         # defaults, with this solver's batch size)
         self.extra_scores = ()
@@ -381,133 +382,41 @@ class VAESolver:
             self.writer.add_scalars("losses", losses, global_step=cur_iter)
 
     def write_disentanglemnt_scores(self, cur_iter: int, num_samples: int = 10000):
-        """solvers/vae.py:188-213.  The reference's ``evaluation`` package writes all four scores when it imports (it needs
-        sklearn and xgboost).  MIG and modularity do not need it: they are computed on the device (``device_scores``,
+        """solvers/vae.py:188-213, at a test iteration and with a writer.  For a ``DisentanglementDataset`` the factor scores
+        come first.  The reference's ``evaluation`` package writes all four of its scores when it imports (it needs sklearn
+        and xgboost).  MIG and modularity do not need it: they are computed on the device (``device_scores``,
         hipvae.disentangle) from one encode of the sampled images, in eval mode, with a private numpy generator (torch's
         RNG streams and the BatchNorm running buffers are untouched).  The classifier-based scores stay delegated unless
         ``device_scores == "all"``: then ``bvae_score`` {score, scaled} and ``mod_expl`` {modularity_score,
         explicitness_score} are written from the device too (metrics.py:11-17, 222-234) and only DCI is delegated.
         ``device_scores == "all+dci"`` writes those three records and then ``dci`` {dci_informativeness_score,
-        dci_completeness_score, dci_disentanglement_score} from the device (metrics.py:82-103) and delegates nothing:
-        ``evaluation`` is not imported.
-        ``extra_scores`` adds, after all of the above and whatever ``device_scores`` says, ``factor_vae`` {train_accuracy,
-        eval_accuracy} and / or ``sap_score`` from the device (hipvae.disentangle; neither is in the reference), and
-        with "elbo_decomposition" the record ``aggregate_decomp`` {mi, tc, dwkl, kl, kl_analytic}: the decomposition of
-        the aggregate KL over the dataset's aggregate posterior (hipvae.aggregate; ``elbo_params``).  That one needs no
-        factors, so it is written for any dataset, from the device table when ``use_device_dataset`` was called.
-        "irs" is a factor score: the record ``irs`` {IRS, num_active_dims} (``irs_params``).  "unsupervised" needs no
-        factors either and is read like the decomposition: the record ``unsupervised`` {gaussian_total_correlation,
-        gaussian_wasserstein_correlation, gaussian_wasserstein_correlation_norm, mutual_info_score}
-        (``unsupervised_params``).  "udr" needs no factors either: the record ``udr`` {model_score, mean_pairwise}, the
-        Unsupervised Disentanglement Ranking of this model among ``[self.model, *self.udr_peers]`` (``udr_params``).
-        "log_likelihood" needs no factors and is read like the decomposition: the record ``log_likelihood`` {log_px,
-        bits_per_dim, elbo, ess}, the importance-weighted estimate of log p(x) (hipvae.likelihood; ``likelihood_params``;
-        the reconstruction loss and ``beta_rec`` are this solver's unless given there).
-        "sample_quality" needs no factors either: the record ``sample_quality`` {frechet, kid, precision, recall, density,
-        coverage} of decoded prior samples against the dataset's images (hipvae.quality; ``quality_params``).  The features
-        are the model's own encoder means unless ``quality_params`` names a callable, so ``frechet`` and ``kid`` compare
-        models of one architecture and are not a published FID / KID.
-        "reconstruction_quality" needs no factors either: the record ``reconstruction_quality`` {psnr, ssim, ms_ssim, mse,
-        l1}, the means over the dataset's images of the pixel-space scores of their deterministic reconstructions
-        (hipvae.quality; ``reconstruction_params``).
-        "latent_density" needs no factors either: the record ``latent_density`` {loglik_heldout, loglik_prior, gap, n_iter}
-        of a Gaussian mixture fitted to the encoder's latents of one part of the dataset's images and scored on another
-        (hipvae.density; ``density_params``); ``gap`` is what N(0, I) loses against that ex-post density, in nats per image.
-        ``quality_params = dict(prior="gmm")`` makes "sample_quality" decode samples of such a mixture, not of the prior."""
+        dci_completeness_score, dci_disentanglement_score} from the device (metrics.py:82-103; ``dci_params``) and
+        delegates nothing: ``evaluation`` is not imported.
+        ``extra_scores`` adds, after all of the above and whatever ``device_scores`` says, the records of
+        ``solvers.scores.TABLE`` that it names, in the table's order: the factor scores among them for a
+        ``DisentanglementDataset`` only, the others for any dataset, from the device table when ``use_device_dataset``
+        was called."""
+        from solvers import scores              # with the evaluation modules behind it: not needed to train
         extras = tuple(self.extra_scores or ())
-        with_elbo = "elbo_decomposition" in extras
-        with_unsup = "unsupervised" in extras
-        with_udr = "udr" in extras
-        with_ll = "log_likelihood" in extras
-        with_quality = "sample_quality" in extras
-        with_recq = "reconstruction_quality" in extras
-        with_density = "latent_density" in extras
         factored = isinstance(self.dataset, DisentanglementDataset)
-        if self.writer is None or not (factored or with_elbo or with_unsup or with_udr or with_ll or with_quality
-                                      or with_recq or with_density) \
+        if self.writer is None or not (factored or any(e in scores.TABLE and not scores.TABLE[e].factors for e in extras)) \
                 or cur_iter % self.test_iter:
             return
-        known = ("factor_vae", "sap", "elbo_decomposition", "irs", "unsupervised", "udr", "reconstruction_quality",
-                 "latent_density", "log_likelihood", "sample_quality")
-        unknown = [e for e in extras if e not in known]
+        unknown = [e for e in extras if e not in scores.TABLE]
         if unknown:
-            raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, known))})")
+            raise ValueError(f"extra_scores: unknown score(s) {unknown} (known: {', '.join(map(repr, scores.KNOWN))})")
+        wanted = [score for score in scores.TABLE.values() if score.name in extras]
         if factored:
-            self._write_factor_scores(cur_iter, num_samples,
-                                      tuple(e for e in extras if e not in ("elbo_decomposition", "unsupervised", "udr",
-                                                                           "log_likelihood", "sample_quality",
-                                                                           "reconstruction_quality",
-                                                                           "latent_density")))
-        if with_elbo:
-            from hipvae import aggregate
-            kw = dict(batch_size=self.batch_size)
-            kw.update(self.elbo_params or {})
-            got = aggregate.compute_elbo_decomposition(self.dataset if self._device_table is None else self._device_table,
-                                                       self.model, **kw)
-            self.writer.add_scalars("aggregate_decomp", {k: got[k] for k in ("mi", "tc", "dwkl", "kl", "kl_analytic")},
-                                    global_step=cur_iter)
-        if with_unsup:
-            from hipvae import disentangle
-            kw = dict(batch_size=self.batch_size)
-            kw.update(self.unsupervised_params or {})
-            got = disentangle.compute_unsupervised_scores(self.dataset if self._device_table is None else self._device_table,
-                                                          self.model, **kw)
-            self.writer.add_scalars("unsupervised", {k: got[k] for k in (
-                "gaussian_total_correlation", "gaussian_wasserstein_correlation", "gaussian_wasserstein_correlation_norm",
-                "mutual_info_score")}, global_step=cur_iter)
-        if with_udr:
-            from hipvae import disentangle
-            if not self.udr_peers:
-                raise ValueError('extra_scores: "udr" compares this model with models trained from other seeds: set '
-                                 "udr_peers to a sequence of them")
-            got = disentangle.compute_udr_score(self.dataset if self._device_table is None else self._device_table,
-                                                [self.model, *self.udr_peers], batch_size=self.batch_size,
-                                                params=self.udr_params)
-            mine = [float(v) for v in got["pairwise_disentanglement_scores"][1:, 0] if v == v]
-            self.writer.add_scalars("udr", dict(model_score=got["model_scores"][0],
-                                                mean_pairwise=sum(mine) / len(mine) if mine else float("nan")),
-                                    global_step=cur_iter)
-        if with_ll:
-            from hipvae import likelihood
-            kw = dict(batch_size=self.batch_size, loss_type=self.recon_loss_type, beta_rec=self.beta_rec)
-            kw.update(self.likelihood_params or {})
-            got = likelihood.compute_log_likelihood(self.dataset if self._device_table is None else self._device_table,
-                                                    self.model, **kw)
-            self.writer.add_scalars("log_likelihood", {k: got[k] for k in ("log_px", "bits_per_dim", "elbo", "ess")},
-                                    global_step=cur_iter)
-        if with_quality:
-            from hipvae import quality
-            kw = dict(batch_size=self.batch_size)
-            own = self._eval_prior()
-            if own is not None:
-                kw["prior"] = own
-            kw.update(self.quality_params or {})
-            got = quality.compute_sample_quality(self.dataset if self._device_table is None else self._device_table,
-                                                 self.model, **kw)
-            self.writer.add_scalars("sample_quality", {k: got[k] for k in (
-                "frechet", "kid", "precision", "recall", "density", "coverage")}, global_step=cur_iter)
-        if with_recq:
-            from hipvae import quality
-            kw = dict(batch_size=self.batch_size)
-            kw.update(self.reconstruction_params or {})
-            got = quality.compute_reconstruction_quality(self.dataset if self._device_table is None else self._device_table,
-                                                         self.model, **kw)
-            self.writer.add_scalars("reconstruction_quality", {k: got[k] for k in quality.RECONSTRUCTION_SCORES},
-                                    global_step=cur_iter)
-        if with_density:
-            from hipvae import density
-            kw = dict(batch_size=self.batch_size)
-            own = self._eval_prior()
-            if own is not None:
-                kw["prior"] = own
-            kw.update(self.density_params or {})
-            got = density.compute_latent_density(self.dataset if self._device_table is None else self._device_table,
-                                                 self.model, **kw)
-            self.writer.add_scalars("latent_density", {k: got[k] for k in (
-                "loglik_heldout", "loglik_prior", "gap", "n_iter")}, global_step=cur_iter)
+            self._write_factor_scores(cur_iter, num_samples, [score for score in wanted if score.factors])
+        source = self.dataset if self._device_table is None else self._device_table
+        for score in wanted:
+            if not score.factors:
+                scores.write(score, self, source, cur_iter)
 
-    def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: tuple):
-        """The factor-based scores of ``write_disentanglemnt_scores`` (a ``DisentanglementDataset``, at a test iteration)."""
+    def _write_factor_scores(self, cur_iter: int, num_samples: int, extras: list):
+        """The factor-based scores of ``write_disentanglemnt_scores`` (a ``DisentanglementDataset``, at a test iteration):
+        the ``device_scores`` ladder, then the factor records of ``extra_scores``, all with the model in eval mode."""
+        from solvers import scores
         with_dci = isinstance(self.device_scores, str) and self.device_scores == "all+dci"
         M = None
         if not with_dci:
@@ -522,47 +431,26 @@ class VAESolver:
             from hipvae import disentangle
             if getattr(self, "latent_generator", None) is None:
                 self.latent_generator = disentangle.FactorSampler(self.dataset, self.device)
-        was_training = self.model.training
-        self.model.eval()
         n = num_samples if len(self.dataset) >= num_samples else len(self.dataset) // 2
         everything = with_dci or (isinstance(self.device_scores, str) and self.device_scores == "all")
-        if M is not None:
-            kw = dict(latent_generator=self.latent_generator, model=self.model, num_samples=n, batch_size=self.batch_size)
-            writers = (() if everything else (M.write_bvae_score,)) + (M.write_dci_score,) + \
-                (() if native else (M.write_mig_score, M.write_mod_expl_score))
-            for fn in writers:
-                fn(self.writer, cur_iter, **kw)
-        if everything:
-            kw = dict(num_samples=n, batch_size=self.batch_size)
-            score, scaled = disentangle.compute_bvae_score(self.latent_generator, self.model, **kw)
-            self.writer.add_scalars("bvae_score", dict(score=score, scaled=scaled), global_step=cur_iter)
-            self.writer.add_scalar("mig_score", disentangle.compute_mig_score(self.latent_generator, self.model, **kw),
-                                   global_step=cur_iter)
-            mod, expl = disentangle.compute_mod_expl_score(self.latent_generator, self.model, **kw)
-            self.writer.add_scalars("mod_expl", dict(modularity_score=mod, explicitness_score=expl), global_step=cur_iter)
-            if with_dci:
-                info, comp, dis = disentangle.compute_dci_score(self.latent_generator, self.model, params=self.dci_params,
-                                                                **kw)
-                self.writer.add_scalars("dci", dict(dci_informativeness_score=info, dci_completeness_score=comp,
-                                                    dci_disentanglement_score=dis), global_step=cur_iter)
-        elif native:
-            got = disentangle.compute_scores(self.latent_generator, self.model, num_samples=n, batch_size=self.batch_size)
-            self.writer.add_scalar("mig_score", got["mig"], global_step=cur_iter)
-            self.writer.add_scalars("mod_expl", dict(modularity_score=got["modularity"]), global_step=cur_iter)
-        if "factor_vae" in extras:
-            train, ev = disentangle.compute_factor_vae_score(self.latent_generator, self.model, batch_size=self.batch_size,
-                                                             params=self.factor_vae_params)
-            self.writer.add_scalars("factor_vae", dict(train_accuracy=train, eval_accuracy=ev), global_step=cur_iter)
-        if "sap" in extras:
-            self.writer.add_scalar("sap_score", disentangle.compute_sap_score(
-                self.latent_generator, self.model, batch_size=self.batch_size, params=self.sap_params), global_step=cur_iter)
-        if "irs" in extras:
-            got = disentangle.compute_irs_score(self.latent_generator, self.model, batch_size=self.batch_size,
-                                                params=self.irs_params)
-            self.writer.add_scalars("irs", dict(IRS=got["avg_score"], num_active_dims=got["num_active_dims"]),
-                                    global_step=cur_iter)
-        if was_training:
-            self.model.train()
+        with eval_mode(self.model):
+            if M is not None:
+                kw = dict(latent_generator=self.latent_generator, model=self.model, num_samples=n,
+                          batch_size=self.batch_size)
+                writers = (() if everything else (M.write_bvae_score,)) + (M.write_dci_score,) + \
+                    (() if native else (M.write_mig_score, M.write_mod_expl_score))
+                for fn in writers:
+                    fn(self.writer, cur_iter, **kw)
+            if everything:
+                for tag in ("bvae_score", "mig_score", "mod_expl") + (("dci",) if with_dci else ()):
+                    scores.write(scores.DEVICE[tag], self, self.latent_generator, cur_iter, n)
+            elif native:        # MIG and modularity from ONE encode
+                got = disentangle.compute_scores(self.latent_generator, self.model, num_samples=n,
+                                                 batch_size=self.batch_size)
+                self.writer.add_scalar("mig_score", got["mig"], global_step=cur_iter)
+                self.writer.add_scalars("mod_expl", dict(modularity_score=got["modularity"]), global_step=cur_iter)
+            for score in extras:
+                scores.write(score, self, self.latent_generator, cur_iter)
 
     def write_gradient_flow(self, cur_iter, named_parameters):
         """Matplotlib figure of per-layer gradient magnitudes in the reference; not reproduced."""

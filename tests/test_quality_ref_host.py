@@ -118,7 +118,9 @@ def test_sources_state_the_rules():
         assert fn + "(" in hdr
     assert "#define ITCV_ABI_VERSION 4" in hdr
     src = open(os.path.join(ROOT, "intro-tc-vae_amd", "solvers", "vae.py")).read()
-    assert "self.quality_params = None" in src and '"sample_quality")' in src
+    assert "self.quality_params = None" in src
+    from solvers import scores
+    assert scores.TABLE["sample_quality"].params == "quality_params" and not scores.TABLE["sample_quality"].factors
 
 
 def test_restatement_accumulates_in_ascending_order():

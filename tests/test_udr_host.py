@@ -217,8 +217,22 @@ def test_solver_attributes_default_to_nothing():
     from solvers import VAESolver
     src = inspect.getsource(VAESolver.__init__)
     assert "self.extra_scores = ()" in src and "self.udr_peers = None" in src and "self.udr_params = None" in src
-    body = inspect.getsource(VAESolver.write_disentanglemnt_scores)
-    assert '"udr"' in body and "udr_peers" in body
+    from solvers import scores
+    udr = scores.TABLE["udr"]                                  # a record of the score table, which reads the peers
+    assert not udr.factors and udr.params == "udr_params" and udr.tag == "udr"
+    assert "udr_peers" in inspect.getsource(udr.compute)
+
+
+def test_udr_without_peers_is_refused_on_the_cpu():
+    """The writer itself, with a stub writer: the refusal comes before any device call."""
+    import score_writer_cases as C
+    for attrs in ({}, dict(udr_peers=[]), dict(udr_peers=())):
+        log = C.run_case(C.case("udr without peers", extras=("udr",), attrs=attrs))
+        assert log[:-1] == [["raised", "ValueError", 'extra_scores: "udr" compares this model with models trained from '
+                             "other seeds: set udr_peers to a sequence of them"]]
+    log = C.run_case(C.case("udr with a peer", extras=("udr",), peers=1))
+    assert [e[:2] for e in log[:-1]] == [["compute", "disentangle.compute_udr_score"], ["add_scalars", "udr"]]
+    assert log[0][2] == ["Plain", "list"] and log[1][2] == [["model_score", 0.625], ["mean_pairwise", 0.25]]
 
 
 def test_scipy_values_still_agree(golden, pairs):

@@ -202,8 +202,21 @@ def test_solver_attributes_default_to_nothing():
     from solvers import VAESolver
     src = inspect.getsource(VAESolver.__init__)
     assert "self.extra_scores = ()" in src and "self.irs_params = None" in src and "self.unsupervised_params = None" in src
-    body = inspect.getsource(VAESolver.write_disentanglemnt_scores)
-    assert '"irs"' in body and '"unsupervised"' in body and '"mig"' not in body
+    from solvers import scores
+    assert "irs" in scores.TABLE and "unsupervised" in scores.TABLE and "mig" not in scores.TABLE
+    assert scores.TABLE["irs"].factors and scores.TABLE["irs"].params == "irs_params"
+    assert not scores.TABLE["unsupervised"].factors and scores.TABLE["unsupervised"].params == "unsupervised_params"
+
+
+def test_mig_is_not_an_extra_score():
+    """The writer itself on the CPU, with a stub writer: "mig" next to "irs" on a factored dataset is an unknown name,
+    refused before anything is computed; the two names of this file are computed and written."""
+    import score_writer_cases as C
+    log = C.run_case(C.case("irs and mig", factored=True, extras=("irs", "mig")))
+    assert log[:-1] == [["raised", "ValueError", "extra_scores: unknown score(s) ['mig'] (known: "]]
+    log = C.run_case(C.case("irs and unsupervised", factored=True, extras=("unsupervised", "irs"), device_scores=False))
+    assert [e[1] for e in log[:-1]] == ["disentangle.compute_irs_score", "irs", "disentangle.compute_unsupervised_scores",
+                                        "unsupervised"]
 
 
 def test_scipy_formula_still_agrees(golden):
