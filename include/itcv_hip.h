@@ -37,6 +37,9 @@ const char* itcv_last_error(void);
  *                          0: one tile per block; range 0..1024
  *   "wgrad_m16"            1 (default): v_mfma_f32_16x16x32 in itcv_conv2d_wgrad_bf16p; 0: 32x32x16 (equal to rounding)
  *   "planes_mfma_waves"    8 (default) or 4: MFMA waves of the 128 x 128 tile of the 128-pixel planes kernel (bit-identical)
+ *   "sw_lds_rows"          0 (default: 4096): rows of itcv_sw_kl_fwd whose sort keys sit in LDS, above that in the workspace;
+ *                          range 0..4096 (bit-identical: a test option that forces the workspace path at any Bt)
+ *   "sw_max_blocks"        0 (default: 256): the grid cap of itcv_sw_kl_fwd's first launch; range 0..1024 (bit-identical)
  * itcv_set_option returns non-zero for an unknown name or a value out of range; itcv_get_option returns -1 for an unknown name. */
 int itcv_set_option(const char* name, int value);
 int itcv_get_option(const char* name);
@@ -512,6 +515,46 @@ int itcv_mmd_kl_fwd(const float* z_all, const float* prior, const float* mu, con
 int itcv_mmd_kl_bwd(const float* g, const float* z_all, const float* prior, const float* mu, const float* logvar,
                     const float* Wt, const double* rs, float* dz_all, float* dmu, float* dlogvar, int Bl, int Bt, int P,
                     int D, double lambda_mmd, double coef_kl, void* stream);
+/* The KL hook of the sliced-Wasserstein autoencoder (Kolouri et al. 2018) with its gradient, and the sliced-Wasserstein
+ * distance as a score (Deshpande et al. 2018) (csrc/sw.hip).  z_all [Bt][D] fp32 with row stride ldz >= D, read in place:
+ * the reparameterised samples of the whole global batch (the gradient flows to it); prior [Bt][D] fp32 with row stride
+ * ldp >= D: as many draws from N(0, I), a constant; t [L][D] fp32, dense: N(0, I) draws, a constant; mu / logvar [Bl][D]
+ * fp32, dense: this rank's rows, read for the KL only.
+ *   theta_l = t_l / |t_l|, the norm in fp64; a row of norm 0 gives theta_l = 0;
+ *   u_l[i] = sum_d theta_ld z_id, v_l[i] = sum_d theta_ld p_id in fp64 from the fp32 inputs, in an order that depends on
+ *   D alone (equal rows get equal bits wherever they stand);
+ *   pi_l = the ascending order of u_l, ties broken by the smaller row index (the stable sort; the order is total for any
+ *   keys, +0 and -0 are one key); v_l is sorted ascending;
+ *   SW_l^2 = (1 / Bt) sum_i (u_l[pi_l(i)] - v_l(i))^2, SW^2 = (1 / L) sum_l SW_l^2, both sums in index order;
+ *   out[0]   = coef_kl * mean_{b < Bl} kl_b (ops.py:161-163) + lambda_sw * SW^2
+ *   terms[3] = {mean kl_b, SW^2, max_l SW_l^2};  per[L] (fp64) = the SW_l^2
+ *   Theta[L][D] (fp64) = the theta_l;  G[L][Bt] (fp64), G[l][pi_l(i)] = u_l[pi_l(i)] - v_l(i): the difference of every row,
+ *   written to the row it came from, so that _bwd needs no permutation.  Both are kept for _bwd.  G == NULL is the
+ *   forward-only form of the score: nothing of size L x Bt is written.  mu and logvar may both be NULL when coef_kl == 0:
+ *   no KL is read and terms[0] = 0.
+ * coef_kl == 0 leaves the KL out of out[0] and of the gradients whatever its value.  2 launches: one block per projection
+ * (the grid is capped at 256 blocks; a block walks further projections by the grid stride) normalises, projects, sorts
+ * (key, row) pairs with a bitonic network and folds; then a one-block finish.  The sort keys sit in LDS up to
+ * Bt = itcv_sw_lds_rows() (4096 rows of 20 bytes), above that in the workspace: itcv_sw_workspace bytes, one slice of
+ * Bt rows per resident block (0 when the keys sit in LDS; ws may then be NULL).  There the steps of the network that stay
+ * inside an aligned chunk of 4096 rows run on the chunk staged in LDS, the steps across chunks on the workspace in place;
+ * the step is one function, and the sorted sequence -- unique, (key, row) being a total order -- is the same.
+ * _bwd, ONE launch: g[1]; every element of dz_all [Bt][D], dmu and dlogvar [Bl][D] (all dense) is written:
+ *   dz_all = g lambda_sw (2 / (L Bt)) sum_l G[l][i] Theta[l][d] (l ascending, fp64 accumulation, fp32 store)
+ *   dmu = g (coef_kl / Bl) mu, dlogvar = g (coef_kl / Bl) (-1/2)(1 - exp(logvar)).
+ * There is no gradient to prior or t.  lambda_sw == 0 gives an exactly zero dz_all.
+ * Every sum is fp64 in a fixed order, there are no atomics: results are bitwise reproducible and do not depend on the
+ * grid or on where the keys sit.  Refused before any launch: a NULL pointer, Bt outside 1..2^20, L outside 1..4096, D
+ * outside 1..2048, Bl outside 1..2^24, L * Bt above 2^26 when G is asked for, a negative or non-finite lambda_sw, a
+ * non-finite coef_kl, a row stride below D, a workspace that is too small. */
+int itcv_sw_lds_rows(void);
+size_t itcv_sw_workspace(int Bt, int L, int D);
+int itcv_sw_kl_fwd(const float* z_all, size_t ldz, const float* prior, size_t ldp, const float* t, const float* mu,
+                   const float* logvar, float* out, float* terms, double* per, double* Theta, double* G, int Bl, int Bt,
+                   int L, int D, double lambda_sw, double coef_kl, void* ws, size_t ws_bytes, void* stream);
+int itcv_sw_kl_bwd(const float* g, const float* mu, const float* logvar, const double* G, const double* Theta,
+                   float* dz_all, float* dmu, float* dlogvar, int Bl, int Bt, int L, int D, double lambda_sw,
+                   double coef_kl, void* stream);
 /* The latent op of Ada-GVAE / Ada-ML-VAE (Locatello et al. 2020; disentanglement_lib's `weak` module: GroupVAEBase with
  * aggregate_argmax) with its gradient (csrc/ada.hip).  mu, logvar, eps [2B][D] fp32 with unit column stride and row strides
  * ld_mu, ld_logvar, ld_eps >= D (mu and logvar may be the halves of one [2B][2D] tensor); rows b and B + b are a pair

@@ -36,6 +36,7 @@ ProfScope::~ProfScope() {
 }
 thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
 Options g_opt;
+extern int g_sw_lds_rows, g_sw_max_blocks;   // sw.hip
 }
 
 extern "C" {
@@ -63,6 +64,16 @@ int itcv_set_option(const char* name, int value) {
     itcv::g_opt.planes_mfma_waves = value;
     return 0;
   }
+  if (!strcmp(name, "sw_lds_rows")) {
+    if (value < 0 || value > 4096) return itcv::fail("%s: sw_lds_rows takes 0..4096 (got %lld)", "itcv_set_option", value);
+    itcv::g_sw_lds_rows = value;
+    return 0;
+  }
+  if (!strcmp(name, "sw_max_blocks")) {
+    if (value < 0 || value > 1024) return itcv::fail("%s: sw_max_blocks takes 0..1024 (got %lld)", "itcv_set_option", value);
+    itcv::g_sw_max_blocks = value;
+    return 0;
+  }
   return itcv::fail("%s: unknown option", "itcv_set_option");
 }
 int itcv_get_option(const char* name) {
@@ -70,6 +81,8 @@ int itcv_get_option(const char* name) {
   if (name && !strcmp(name, "band_persist_blocks")) return itcv::g_opt.band_persist_blocks;
   if (name && !strcmp(name, "wgrad_m16")) return itcv::g_opt.wgrad_m16;
   if (name && !strcmp(name, "planes_mfma_waves")) return itcv::g_opt.planes_mfma_waves;
+  if (name && !strcmp(name, "sw_lds_rows")) return itcv::g_sw_lds_rows;
+  if (name && !strcmp(name, "sw_max_blocks")) return itcv::g_sw_max_blocks;
   return -1;
 }
 const char* itcv_last_error(void) { return itcv::g_err; }

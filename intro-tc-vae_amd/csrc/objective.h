@@ -1,11 +1,11 @@
-// What the objective kernels share: dip.hip, mmd.hip, ada.hip, joint.hip, sup.hip, iwae.hip and vamp.hip include this
-// header, and nothing else does.  Device side: the ordered block sum of their finish kernels, the mean KL of the local
-// rows (dip, mmd) and the fp64 reparameterised sample, its KL term and their gradient (ada, joint; vamp the sample).  Host
+// What the objective kernels share: dip.hip, mmd.hip, sw.hip, ada.hip, joint.hip, sup.hip, iwae.hip and vamp.hip include
+// this header, and nothing else does.  Device side: the ordered block sum of their finish kernels, the mean KL of the local
+// rows (dip, mmd, sw) and the fp64 reparameterised sample, its KL term and their gradient (ada, joint; vamp the sample).  Host
 // side: the capped row grid.  The host's finite test and the refusals that every entry point words alike are in common.h:
 // nothing ties them to objectives.
 //
 // None of these files may contract a multiply and an add into a fused multiply-add -- that is what keeps their bits --
-// but they say so in different places: six at file scope, iwae.hip inside its fp64 bodies only.  So EVERY arithmetic
+// but they say so in different places: seven at file scope, iwae.hip inside its fp64 bodies only.  So EVERY arithmetic
 // helper here carries `#pragma clang fp contract(off)` in its own body and the header has no file-scope pragma: a helper
 // gives the same bits wherever it is included, and the header changes nothing of the code around it.
 //

@@ -29,10 +29,12 @@ F32 = torch.float32
 def set_option(name, value):
     """Launch-shape options of the library (include/itcv_hip.h: itcv_set_option): 'band_m16' (0/1),
     'band_persist_blocks' (0 = one tile per block, else the persistent kernel's block count), 'wgrad_m16' (0 / 1 =
-    32x32x16 / 16x16x32 products in the planes weight gradient), 'planes_mfma_waves' (4 / 8).  Validated by the library."""
+    32x32x16 / 16x16x32 products in the planes weight gradient), 'planes_mfma_waves' (4 / 8), and the two test options of
+    the sliced-Wasserstein kernels, 'sw_lds_rows' and 'sw_max_blocks' (0 = the default).  Validated by the library."""
     call("itcv_set_option", name.encode(), int(value))
     _up2_fold_route.cache_clear()      # the one cached host decision that reads an option ('band_m16')
     lib.forget("itcv_conv2d_dgrad_up2_supported")
+    lib.forget("itcv_sw_workspace")    # 'sw_lds_rows' / 'sw_max_blocks'
 
 
 def get_option(name):
@@ -1562,6 +1564,80 @@ class MmdKlFn(Function):
         call("itcv_mmd_kl_bwd", ptr(_f32c(g)), ptr(z_all), ptr(prior), ptr(mu), ptr(logvar), ptr(Wt), ptr(rs), ptr(dz),
              ptr(dmu), ptr(dlv), Bl, Bt, P, D, lambda_mmd, coef_kl, stream())
         return dz, None, dmu, dlv, None, None, None, None
+
+
+def _sw_forward(z_all, prior, t, mu, logvar, lambda_sw, coef_kl, keep):
+    """itcv_sw_kl_fwd.  z_all / prior [Bt, D] are read in place when their columns have unit stride (the row stride goes to
+    the kernel); t [L, D], mu / logvar [Bl, D] (None, None: no KL, ``coef_kl`` 0) are made dense.  ``keep``: also G
+    [L, Bt].  Returns (mu, logvar, out, terms [3], per [L] fp64, Theta [L, D] fp64, G or None)."""
+    abi.need_device(z_all, prior, t, mu, logvar)
+    z_all, ldz = _rows_f32(z_all, "z_all")
+    prior, ldp = _rows_f32(prior, "prior")
+    if prior.shape != z_all.shape:
+        raise ValueError(f"z_all and prior must share one [Bt, D] shape: the sliced distance pairs sorted samples of equal "
+                         f"counts (got {tuple(z_all.shape)}, {tuple(prior.shape)})")
+    Bt, D = z_all.shape
+    if t.dim() != 2 or t.shape[1] != D:
+        raise ValueError(f"the directions t must be [L, D] with the D of z_all (got {tuple(t.shape)}, D = {D})")
+    t, L, Bl = _f32c(t), t.shape[0], 1
+    if mu is not None:
+        if mu.dim() != 2 or mu.shape != logvar.shape or mu.shape[1] != D:
+            raise ValueError(f"mu / logvar must share one [Bl, D] shape with the D of z_all (got {tuple(mu.shape)}, "
+                             f"{tuple(logvar.shape)}, D = {D})")
+        mu, logvar, Bl = _f32c(mu), _f32c(logvar), mu.shape[0]
+    dev = z_all.device
+    out, terms = _loss_terms(3, dev)
+    per = torch.empty((L,), dtype=torch.float64, device=dev)
+    Theta = torch.empty((L, D), dtype=torch.float64, device=dev)
+    G = torch.empty((L, Bt), dtype=torch.float64, device=dev) if keep else None
+    nws = lib.itcv_sw_workspace(Bt, L, D)
+    ws = _ws(nws, dev)
+    call("itcv_sw_kl_fwd", z_all.data_ptr(), ldz, prior.data_ptr(), ldp, ptr(t), ptr(mu), ptr(logvar), ptr(out), ptr(terms),
+         ptr(per), ptr(Theta), ptr(G), Bl, Bt, L, D, float(lambda_sw), float(coef_kl), ptr(ws), nws, stream())
+    return mu, logvar, out, terms, per, Theta, G
+
+
+def sw_kl_forward(z_all, prior, t, mu, logvar, lambda_sw, coef_kl):
+    """itcv_sw_kl_fwd on z_all / prior [Bt, D], the directions t [L, D] and this rank's mu / logvar [Bl, D].  Returns (out,
+    terms [3], per [L] fp64, Theta [L, D] fp64, G [L, Bt] fp64).  No gradient: ``SwKlFn`` is the differentiable form."""
+    return _sw_forward(z_all, prior, t, mu, logvar, lambda_sw, coef_kl, True)[2:]
+
+
+def sw_distance(a, b, t):
+    """(SW^2 as an fp32 device scalar, per [L] fp64) of the sliced-Wasserstein distance between the rows of a and b [N, D]
+    over the directions t [L, D]: the forward-only form of itcv_sw_kl_fwd (no KL, no G; nothing of size L x N is
+    written).  No gradient."""
+    with torch.no_grad():
+        _, _, out, _, per, _, _ = _sw_forward(a, b, t, None, None, 1.0, 0.0, False)
+    return out, per
+
+
+class SwKlFn(Function):
+    """coef_kl * mean KL of this rank's rows + lambda_sw * the sliced-Wasserstein distance SW^2 between the sampled latents
+    of the whole global batch and as many draws from the prior over the directions ``t`` (include/itcv_hip.h:
+    itcv_sw_kl_fwd): two launches forward, one backward.  Second output: (mean KL, SW^2, max_l SW_l^2) [3], no gradient.
+    ``prior`` and ``t`` are constants.  Kept for the backward: mu, logvar, Theta [L, D] and the scattered differences G
+    [L, Bt], both fp64."""
+
+    @staticmethod
+    def forward(ctx, z_all, prior, t, mu, logvar, lambda_sw, coef_kl):
+        mu, logvar, out, terms, _, Theta, G = _sw_forward(z_all, prior, t, mu, logvar, lambda_sw, coef_kl, True)
+        ctx.save_for_backward(mu, logvar, Theta, G)
+        ctx.cfg = (float(lambda_sw), float(coef_kl))
+        ctx.mark_non_differentiable(terms)
+        return out, terms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_terms):
+        mu, logvar, Theta, G = ctx.saved_tensors
+        lambda_sw, coef_kl = ctx.cfg
+        (L, Bt), D, Bl = G.shape, Theta.shape[1], mu.shape[0]
+        dz = torch.empty((Bt, D), dtype=F32, device=G.device)
+        dmu, dlv = torch.empty_like(mu), torch.empty_like(logvar)
+        call("itcv_sw_kl_bwd", ptr(_f32c(g)), ptr(mu), ptr(logvar), ptr(G), ptr(Theta), ptr(dz), ptr(dmu), ptr(dlv), Bl, Bt, L,
+             D, lambda_sw, coef_kl, stream())
+        return dz, None, None, dmu, dlv, None, None
 
 
 # ------------------------------------------------------------------ FactorVAE: permutation + discriminator

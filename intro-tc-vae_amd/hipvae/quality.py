@@ -1,10 +1,13 @@
-"""Sample quality on the device: how good, and how varied, are the images a model generates?  Four families of scores of
-generated ("fake") against real feature rows, all from the kernels of csrc/quality.hip (rules: include/itcv_hip.h):
+"""Sample quality on the device: how good, and how varied, are the images a model generates?  Five families of scores of
+generated ("fake") against real feature rows, from the kernels of csrc/quality.hip (rules: include/itcv_hip.h):
 
 * ``frechet_distance``: the Frechet distance of the two Gaussians fitted to the features (Heusel et al. 2017);
 * ``kernel_distance``: the unbiased MMD^2 under the cubic polynomial kernel (KID, Binkowski et al. 2018);
 * ``prdc``: precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020), the `prdc`
-  package's definitions over k-th-neighbour radii.
+  package's definitions over k-th-neighbour radii;
+* ``sliced_wasserstein_distance``: the sliced-Wasserstein distance over random directions (Deshpande et al. 2018), from
+  the kernels of csrc/sw.hip; ``compute_sliced_wasserstein`` over the same features, or between encoder samples and
+  the prior.
 
 The features are pluggable.  The default is the model's own encoder mean, so the records are ``frechet`` and ``kid`` over
 THAT feature map: they rank models that share an encoder architecture and are NOT comparable with a published FID, which
@@ -252,6 +255,90 @@ def compute_sample_quality(source, model, num_real=10000, num_fake=None, feature
     if "prdc" in scores:
         out.update(prdc(real, fake, nearest_k))
     out["features"] = dict(real=real, fake=fake)
+    out["indices"] = indices
+    return out
+
+
+# ---- the sliced-Wasserstein distance ----------------------------------------------------------------------------------
+def sliced_wasserstein_directions(num_projections, dim, seed=0):
+    """fp32 ``[num_projections, dim]`` N(0, I) draws from a private CPU ``torch.Generator`` seeded by ``seed`` (the kernel
+    normalises the rows): torch's global generators are untouched."""
+    gen = torch.Generator().manual_seed(int(seed))
+    return torch.randn((int(num_projections), int(dim)), generator=gen)
+
+
+def sliced_wasserstein_distance(real, fake, num_projections=1024, seed=0):
+    """``dict(swd, sw2, sw2_std, per)`` of the sliced-Wasserstein distance (Deshpande et al. 2018; csrc/sw.hip) between
+    the fp32 device rows ``real [N, D]`` and ``fake [N, D]`` -- equal counts -- over ``num_projections`` random
+    directions: ``sw2`` the mean over the directions of the squared 1-D Wasserstein-2 distances ``per`` (an fp64 device
+    tensor), ``swd`` its square root, ``sw2_std`` the standard error of that mean over the directions (ddof = 1; 0.0 for
+    one direction).  The directions are ``sliced_wasserstein_directions(num_projections, D, seed)``: the same seed gives
+    the same bits.  One read-back."""
+    if real.dim() != 2 or fake.shape != real.shape:
+        raise ValueError(f"sliced_wasserstein_distance: real and fake must share one [N, D] shape: the distance pairs sorted "
+                         f"samples of equal counts (got {tuple(real.shape)}, {tuple(fake.shape)})")
+    L = int(num_projections)
+    if not 1 <= L <= 4096:
+        raise ValueError(f"sliced_wasserstein_distance: num_projections must lie in 1..4096 (got {num_projections!r})")
+    t = sliced_wasserstein_directions(L, real.shape[1], seed).to(real.device)
+    _, per = HF.sw_distance(real, fake, t)
+    sw2 = per.sum() / L                                  # the kernel's own fold is fp32 once stored: this one stays fp64
+    se = per.std(unbiased=True) / L ** 0.5 if L > 1 else per.new_zeros(())
+    sw2, se = torch.stack([sw2, se]).tolist()            # the one read-back
+    if not np.isfinite(sw2):
+        raise ValueError("quality: the features contain non-finite values")
+    return dict(swd=float(np.sqrt(sw2)), sw2=sw2, sw2_std=se, per=per)
+
+
+def compute_sliced_wasserstein(source, model, num=10000, space="feature", prior=None, num_projections=1024, feature="encoder",
+                               batch_size=64, seed=0, indices=None, gmm_params=None):
+    """The sliced-Wasserstein distance of ``model`` on ``source``: ``sliced_wasserstein_distance``'s dict plus ``indices``
+    and, for a fitted or given prior, ``gmm`` / ``prior`` as in ``compute_sample_quality``.
+
+    ``space="feature"``: the features of ``num`` real images (``indices``, or ``inference.draw_indices``) against those
+    of as many decoded prior samples -- the usual companion of Frechet / KID, over the same pluggable feature map
+    (``real_features`` / ``generated_features``).  ``space="latent"``: as many samples of the encoder z = mu +
+    eps exp(logvar / 2), eps from a private CPU generator, against as many prior samples: q(z) against p(z) read
+    directly, without fitting a density first.  ``prior``: None or ``"normal"`` (N(0, I)), ``"gmm"`` (a mixture fitted to
+    the real images' latents, ``fit_gmm(latents, **gmm_params)``), a ``GaussianMixture`` or a ``VampPrior``."""
+    from . import density
+    if space not in ("feature", "latent"):
+        raise ValueError(f'compute_sliced_wasserstein: space must be "feature" or "latent" (got {space!r})')
+    if prior is not None and not isinstance(prior, (density.GaussianMixture, density.VampPrior)) \
+            and prior not in ("normal", "gmm"):
+        raise ValueError('compute_sliced_wasserstein: prior must be None, "normal", "gmm", a GaussianMixture or a VampPrior '
+                         f"(got {prior!r})")
+    if indices is None:
+        indices = draw_indices(len(source), num, seed)
+    indices = np.asarray(indices, dtype=np.int64)
+    n, out = len(indices), {}
+    if isinstance(prior, str) and prior == "gmm":
+        prior = density.fit_gmm(real_features(source, model, indices, batch_size), **{"seed": seed, **(gmm_params or {})})
+    if isinstance(prior, density.GaussianMixture):
+        out["gmm"] = prior
+    elif isinstance(prior, density.VampPrior):
+        out["prior"] = prior
+    else:
+        prior = None
+    if space == "feature":
+        real = real_features(source, model, indices, batch_size, feature)
+        fake = generated_features(model, n, batch_size, seed, feature, prior)
+    else:
+        gen = torch.Generator().manual_seed(int(seed))
+
+        def sample(x):
+            mu, logvar = model.encode(x)[:2]
+            return mu + torch.randn(mu.shape, generator=gen).to(mu.device) * torch.exp(0.5 * logvar)
+
+        real = real_features(source, model, indices, batch_size, sample)
+        if prior is None:
+            fake = torch.randn((n, real.shape[1]), generator=gen).to(real.device)
+        elif isinstance(prior, density.VampPrior):
+            fake = density.vamp_sample(prior, n, seed)
+        else:
+            fake = density.gmm_sample(prior, n, seed)
+        fake = fake.to(torch.float32)
+    out.update(sliced_wasserstein_distance(real, fake, num_projections, seed))
     out["indices"] = indices
     return out
 

@@ -273,6 +273,53 @@ def mmd_regularizer(z, prior, lambda_mmd, kernel="imq", bandwidth=None, with_ter
     return mmd_kl_loss(z, zd, zd, prior, 0.0, lambda_mmd, kernel, bandwidth, with_terms=with_terms)
 
 
+def sw_kl_loss(z, mu, logvar, prior, theta, beta, lambda_sw, z_all=None, prior_all=None, with_terms=False):
+    """The KL hook of the sliced-Wasserstein autoencoder (Kolouri et al. 2018; not in the reference):
+    beta * kl_divergence(logvar, mu, "mean") + lambda_sw * SW^2(z, prior) with
+
+        SW^2 = (1 / L) sum_l (1 / B) sum_i (sort(z theta_l)_i - sort(prior theta_l)_i)^2,   theta_l = t_l / |t_l|
+
+    between the sampled latents ``z`` [B, D] and as many draws ``prior`` [B, D] from N(0, I), over the L directions given
+    as the rows of ``theta`` [L, D] (N(0, I) draws; they are normalised by the kernel).  Neither ``prior`` nor ``theta``
+    receives a gradient.  The order of z's projections is the stable one (ties by row index).  Two launches forward, one
+    backward, fp64 throughout, bitwise reproducible.  ``z_all`` / ``prior_all``: the data-parallel extension -- the
+    samples and prior draws of the whole global batch (given together); the distance is then that of the global batch,
+    the KL that of this rank's ``mu`` / ``logvar``, and the local ``z`` / ``prior`` are not read.  ``with_terms``: also
+    return the device vector (mean KL, SW^2, max_l SW_l^2), no gradient."""
+    if (z_all is None) != (prior_all is None):
+        raise ValueError("z_all and prior_all are given together")
+    if z_all is None:
+        z_all, prior_all = z, prior
+    D = z_all.shape[-1]
+    if z_all.dim() != 2 or prior_all.shape != z_all.shape or theta.dim() != 2 or theta.shape[1] != D \
+            or mu.shape != logvar.shape or mu.dim() != 2 or mu.shape[1] != D:
+        raise ValueError(f"z and prior must share one [B, D] shape, theta [L, D], mu and logvar [Bl, D] its D (got "
+                         f"{tuple(z_all.shape)}, {tuple(prior_all.shape)}, {tuple(theta.shape)}, {tuple(mu.shape)}, "
+                         f"{tuple(logvar.shape)})")
+    lambda_sw, beta = float(lambda_sw), float(beta)
+    if not (lambda_sw >= 0.0 and math.isfinite(lambda_sw)) or not math.isfinite(beta):
+        raise ValueError(f"lambda_sw must be a finite number >= 0 and beta finite (got {lambda_sw!r}, {beta!r})")
+    out, terms = HF.SwKlFn.apply(z_all, prior_all.detach(), theta.detach(), mu, logvar, lambda_sw, beta)
+    return (out, terms) if with_terms else out
+
+
+def sw_regularizer(z, prior, theta, lambda_sw, with_terms=False):
+    """``sw_kl_loss`` without its KL term (beta = 0): lambda_sw * SW^2(z, prior) alone.  There is no ``mu`` / ``logvar``
+    to read: ``z`` stands in for both, and with beta = 0 their values do not reach the result."""
+    zd = z.detach()
+    return sw_kl_loss(z, zd, zd, prior, theta, 0.0, lambda_sw, with_terms=with_terms)
+
+
+def sliced_wasserstein(a, b, theta):
+    """(SW^2 as a device scalar, the per-direction SW_l^2 [L] in fp64) between the rows of ``a`` and ``b`` [N, D] (equal
+    counts) over the directions ``theta`` [L, D]: the forward of ``sw_kl_loss`` alone, no gradient, nothing of size
+    L x N written."""
+    if a.dim() != 2 or b.shape != a.shape or theta.dim() != 2 or theta.shape[1] != a.shape[1]:
+        raise ValueError(f"a and b must share one [N, D] shape and theta [L, D] its D (got {tuple(a.shape)}, "
+                         f"{tuple(b.shape)}, {tuple(theta.shape)})")
+    return HF.sw_distance(a, b, theta)
+
+
 ADA_AVERAGINGS = HF.ADA_AVERAGINGS
 
 

@@ -14,6 +14,8 @@ from .semi import S2VAESolver, S2TCSolver, S2DIPSolver, S2FactorSolver
 from .iwae import IWAESolver
 # the learned mixture prior: imported by name too (``from solvers import VampSolver``)
 from .vamp import VampSolver
+# the sliced-Wasserstein autoencoder, the sibling of the MMD pair: imported by name too (``from solvers import SWAESolver``)
+from .swae import SWAESolver, IntroSWAESolver
 
 __all__ = ["VAESolver", "IntroSolver", "TCSovler", "IntroTCSovler", "DIPSolver", "IntroDIPSolver", "MMDSolver",
            "IntroMMDSolver", "FactorSolver", "AdaGVAESolver", "JointVAESolver", "AnnealedVAESolver"]
