@@ -834,6 +834,9 @@ int itcv_aggregate_logdensity(const float* z, const float* mu, const float* logv
  *   _hist:   counts[d][bins * off[k] + b * fsize[k] + f] (off = prefix sums of fsize; itcv_disent_counts_elems uint32,
  *            fsum = off[K]) and the factor marginals vcount[off[k] + f]; both are cleared by the call.  Integer sums:
  *            bitwise reproducible.
+ *   _hist_tiling: host only, no GPU work: the launch plan _hist makes for (D, K, fsize, bins), as out[21] ints:
+ *            [0] columns per block (a power of two, 1..64), [1] column tiles, [2] factor groups ng, [3] LDS bytes of a
+ *            block, [4 .. 4 + ng] the first factor of every group and then K, zeros behind.  Refuses what _hist refuses.
  *   _mi:     mi[D][K] = max(0, sum_{c>0} (c/N)(log c - log r_b - log s_f + log N)) in nats (r, s: row / column sums of the
  *            pair's table) and h[K] = sum_{s>0} -(s/N) log(s/N), in fp64. */
 size_t itcv_disent_minmax_workspace(int N, int D);
@@ -844,6 +847,7 @@ int itcv_disent_bins(const float* mu, size_t ld, int N, int D, const float* mn, 
 size_t itcv_disent_counts_elems(int D, int fsum, int bins);
 int itcv_disent_hist(const float* mu, size_t ld, const int* v, int N, int D, int K, const int* fsize, int bins,
                      const float* mn, const float* mx, unsigned* counts, unsigned* vcount, int* flags, void* stream);
+int itcv_disent_hist_tiling(int D, int K, const int* fsize, int bins, int* out);
 int itcv_disent_mi(const unsigned* counts, const unsigned* vcount, int N, int D, int K, const int* fsize, int bins,
                    double* mi, double* h, void* stream);
 

@@ -339,6 +339,17 @@ int itcv_disent_hist(const float* mu, size_t ld, const int* v, int N, int D, int
   return 0;
 }
 
+int itcv_disent_hist_tiling(int D, int K, const int* fsize, int bins, int* out) {
+  ITCV_REQUIRE(fsize && out && D >= 1, "itcv_disent_hist_tiling");
+  HistPlan pl;
+  int tc;
+  size_t lds;
+  if (int e = hist_plan("itcv_disent_hist_tiling", D, K, fsize, bins, &pl, &tc, &lds)) return e;
+  out[0] = tc, out[1] = cdiv(D, tc), out[2] = pl.ng, out[3] = (int)lds;
+  for (int g = 0; g <= kSegMaxK; ++g) out[4 + g] = g <= pl.ng ? pl.gk[g] : 0;
+  return 0;
+}
+
 int itcv_disent_mi(const unsigned* counts, const unsigned* vcount, int N, int D, int K, const int* fsize, int bins,
                    double* mi, double* h, void* stream) {
   ITCV_REQUIRE(counts && vcount && fsize && mi && h && N >= 1 && N <= kDisMaxN && D >= 1, "itcv_disent_mi");

@@ -2614,6 +2614,16 @@ def disent_hist(mu, factors, factor_sizes, mn, mx, bins, flags):
     return counts, vcount
 
 
+def disent_hist_tiling(D, factor_sizes, bins):
+    """The launch plan ``disent_hist`` makes for these sizes, asked of the library's own planner without any GPU work: a
+    dict of ``tc`` (columns per block), ``column_tiles``, ``groups`` (the first factor of every factor group) and
+    ``lds_bytes``.  Raises what ``disent_hist`` raises for sizes outside the supported range."""
+    sizes = [int(s) for s in factor_sizes]
+    out = (ctypes.c_int * 21)()
+    call("itcv_disent_hist_tiling", int(D), len(sizes), (ctypes.c_int * max(len(sizes), 1))(*sizes), int(bins), out)
+    return dict(tc=out[0], column_tiles=out[1], groups=list(out[4:4 + out[2]]), lds_bytes=out[3])
+
+
 def disent_mi(counts, vcount, N, D, factor_sizes, bins):
     """(MI[D, K], H[K]) in fp64 from the integer tables of ``disent_hist``."""
     sizes = [int(s) for s in factor_sizes]

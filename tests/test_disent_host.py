@@ -1,7 +1,9 @@
 """CPU-only checks of the device-side disentanglement scores: the new entry points are declared, bound and exported
 alike (and refuse what lies outside their range before any launch), ``FactorSampler`` indexes and draws as documented,
 and a numpy fp64 restatement of the scores' rule -- written here, shared with tests/test_hip_disent.py -- reproduces the
-results recorded from the unmodified reference (tests/golden/disent.npz)."""
+results recorded from the unmodified reference (tests/golden/disent.npz).  The histogram's launch plan is restated too
+(``ref_hist_tiling``) and held to the library's own planner (``itcv_disent_hist_tiling``, no GPU work) on the table of
+tiers the GPU tests launch (``HIST_TIERS``), on the earlier tests' shapes and over a random sweep."""
 import ctypes
 import os
 import re
@@ -81,6 +83,87 @@ def ref_all(x, v, sizes, bins):
     joint, marg = ref_counts(b, np.asarray(v), sizes, bins)
     mi, h = ref_mi(joint, marg, len(b))
     return b, joint, marg, mi, h
+
+
+# ---- the histogram's launch plan (hist_plan of csrc/disent.hip), restated --------------------------------------------
+def ref_hist_tiling(D, sizes, bins):
+    """A block's table, (tc * bins + 1) * gsum words, must fit 64 KiB: consecutive factors are grouped greedily against the
+    words one column needs, then the column tile is halved from 64 while it is wider than needed or does not fit."""
+    cap = 16384 // (bins + 1)
+    groups, gs, gmax = [0], 0, 0
+    for k, s in enumerate(sizes):
+        if gs and gs + s > cap:
+            groups.append(k)
+            gs = 0
+        gs += s
+        gmax = max(gmax, gs)
+    t = 64
+    while t > 1 and (t // 2 >= D or (t * bins + 1) * gmax * 4 > 65536):
+        t //= 2
+    return dict(tc=t, column_tiles=-(-D // t), groups=groups, lds_bytes=(t * bins + 1) * gmax * 4)
+
+
+# name: (D, factor sizes, bins, columns per block, column tiles, width of the last tile, factor groups, LDS bytes).
+# The tiers tests/test_hip_disent.py launches at N = 1037; "large_n" is its N = 262 445 case.
+HIST_TIERS = {
+    "tc64": (70, (6, 6, 2, 3, 3), 10, 64, 2, 6, [0], 51280),
+    "tc32": (70, (6, 6, 2, 3, 3), 20, 32, 3, 6, [0], 51280),
+    "tc4_dsprites": (10, (3, 6, 40, 32, 32), 20, 4, 3, 2, [0], 36612),
+    "tc2": (5, (100, 100), 32, 2, 3, 1, [0], 52000),
+    "tc2_groups": (5, (250, 250, 250), 32, 2, 3, 1, [0, 1, 2], 65000),
+    "tc1_wide": (3, (200, 200), 32, 1, 3, 1, [0], 52800),
+    "large_n": (5, (3, 7), 20, 8, 1, 5, [0], 6440),
+}
+# the shapes of the tests that came with the kernels: (D, factor sizes, bins, columns per block, factor groups)
+HIST_EARLIER = [
+    (10, (6, 6, 2, 3, 3, 40, 40), 10, 16, 1), (10, (6, 6, 2, 3, 3, 40, 40), 20, 8, 1), (9, (6, 6, 2, 3, 3, 40, 40), 20, 8, 1),
+    (1, (3,), 10, 1, 1), (1, (2,), 1, 1, 1), (1, (2,), 2, 1, 1), (1, (2,), 32, 1, 1), (2, (2, 1), 10, 2, 1),
+    (129, (2, 3, 256, 5, 1, 7, 4, 9, 2, 6, 3, 8, 2, 5, 4, 3), 32, 1, 1), (3, (256,) * 16, 32, 1, 16), (10, (4, 5), 10, 16, 1),
+    (10, (4, 5), 20, 16, 1)]
+
+
+@pytest.mark.parametrize("name", sorted(HIST_TIERS))
+def test_hist_tiling_query_restatement_and_case_table_agree(name):
+    from hipvae import functional as HF
+    D, sizes, bins, tc, tiles, last, groups, lds = HIST_TIERS[name]
+    want = dict(tc=tc, column_tiles=tiles, groups=groups, lds_bytes=lds)
+    assert ref_hist_tiling(D, sizes, bins) == want
+    assert HF.disent_hist_tiling(D, sizes, bins) == want
+    assert D - (tiles - 1) * tc == last and lds <= 65536
+
+
+def test_hist_tiling_on_the_earlier_shapes_and_over_a_sweep():
+    from hipvae import functional as HF
+    for D, sizes, bins, tc, ng in HIST_EARLIER:
+        got = HF.disent_hist_tiling(D, sizes, bins)
+        assert got == ref_hist_tiling(D, sizes, bins), (D, sizes, bins)
+        assert (got["tc"], len(got["groups"])) == (tc, ng), (D, sizes, bins, got)
+    # what the earlier shapes never launched (2 is reached by the N = 1 edge case alone, with one row)
+    assert sorted({t[3] for t in HIST_EARLIER}) == [1, 2, 8, 16]
+    assert sorted({t[3] for t in HIST_TIERS.values()}) == [1, 2, 4, 8, 32, 64]
+    rs = np.random.RandomState(0)
+    for _ in range(300):
+        D, bins, K = int(rs.randint(1, 200)), int(rs.randint(1, 33)), int(rs.randint(1, 17))
+        sizes = [int(s) for s in rs.randint(1, 257, size=K)]
+        got = HF.disent_hist_tiling(D, sizes, bins)
+        assert got == ref_hist_tiling(D, sizes, bins), (D, sizes, bins)
+        # more than one group leaves room for two columns at the most: a group is closed only when the next factor would
+        # pass 16384 // (bins + 1) words, so the largest group holds more than half of that
+        assert got["lds_bytes"] <= 65536 and (len(got["groups"]) == 1 or got["tc"] <= 2)
+
+
+def test_hist_tiling_query_refuses_what_the_histogram_refuses():
+    from hipvae import abi
+    from hipvae import functional as HF
+    out = (ctypes.c_int * 21)()
+    for K, sizes, bins, msg in [(2, (4, 5), 33, "bins = 33"), (2, (4, 257), 10, "size 257"), (17, (2,) * 17, 10, "K = 17")]:
+        assert abi.lib.itcv_disent_hist_tiling(8, K, _sizes(*sizes), bins, out) != 0
+        assert abi.last_error().startswith("itcv_disent_hist_tiling") and msg in abi.last_error(), abi.last_error()
+    assert abi.lib.itcv_disent_hist_tiling(0, 2, _sizes(4, 5), 10, out) != 0
+    assert abi.lib.itcv_disent_hist_tiling(8, 2, None, 10, out) != 0 and abi.lib.itcv_disent_hist_tiling(8, 2, _sizes(4, 5), 10, None) != 0
+    with pytest.raises(RuntimeError, match="bins = 0"):
+        HF.disent_hist_tiling(8, (4, 5), 0)
+    assert "itcv_disent_hist_tiling" in abi.SIGNATURES and abi.ABI_VERSION == 4
 
 
 # ---- boundary ------------------------------------------------------------------------------------------------------

@@ -12,8 +12,14 @@ carries a 10x margin:
 Everything else is exact: predictions, S, SAP, the vote tables, the classifier and both accuracies.  Exactness of the
 predictions between two solves of the same problem needs the decision values to be away from a tie by more than the
 solves can differ: both lie within sqrt(2) * gtol of the unique optimum (F is 1-strongly convex), so decision values
-differ by at most 2 * 1.5e-10 * (1 + max|x|) = 3e-10 * (1 + max|x|); the fixture keeps every gap above 1e-7."""
+differ by at most 2 * 1.5e-10 * (1 + max|x|) = 3e-10 * (1 + max|x|); the fixture keeps every gap above 1e-7.
+
+The generated cases of the GPU tests whose exactness rests on a property of the data are built here and held to it on the
+CPU: the 19-class SAP case converges and keeps every test decision 1e-6 from a tie (100 x what a theta error of 1e-9
+moves a decision at |x| <= 10), the wide SAP case converges, and the copied columns of the FactorVAE tie cases have
+bitwise-equal variances and ratios while every other arg-min stays 1e-6 (relative) clear of the runner-up."""
 import ctypes
+import functools
 import os
 import re
 
@@ -202,7 +208,102 @@ def ref_sap_continuous(x_train, y_train):
     return S
 
 
+# ---- the cases of tests/test_hip_extra_scores.py that need a condition checked on the host ---------------------------
+MANY_GAP_MIN = 1e-6            # 100 x what a theta error of 1e-9 moves a decision with |x| <= 10
+MANY_SEED, WIDE_SEED = 5, 0      # of seeds 0..7 the one with the widest gap (1.6e-5; the narrowest, seed 3, has 1.2e-6)
+
+
+@functools.lru_cache(maxsize=None)
+def sap_many_classes_case(seed=MANY_SEED):
+    """More problems than the fit kernel has waves: a factor of size 21 whose classes 0 and 7 are absent (19 problems: waves
+    0, 1, 2 solve three each, the others two) and a binary factor; 700 train and 300 test rows, D = 2, the latents shifted
+    by their labels."""
+    rs = np.random.RandomState(seed)
+    n, sizes = 1000, [21, 2]
+    present = np.array([c for c in range(21) if c not in (0, 7)])
+    y = np.stack([present[rs.randint(19, size=n)], rs.randint(2, size=n)], 1).astype(np.int32)
+    x = 0.7 * rs.randn(n, 2)
+    x[:, 0] += 0.35 * y[:, 0]
+    x[:, 1] += 1.2 * y[:, 1]
+    x = x.astype(np.float32)
+    theta, gnorm, iters, cvalid, ok = ref_sap_fit(x[:700], y[:700], sizes)
+    pred, gap = ref_sap_predict(theta, cvalid, x[700:], sizes)
+    return dict(sizes=sizes, x_train=x[:700], y_train=y[:700], x_test=x[700:], y_test=y[700:], theta=theta, gnorm=gnorm,
+                iters=iters, cvalid=cvalid, ok=ok, pred=pred, gap=gap)
+
+
+@functools.lru_cache(maxsize=None)
+def sap_wide_case(seed=WIDE_SEED):
+    """N = 130, D = 70, one factor of 3 classes: two 64-column tiles of the copy kernel (the second 6 wide, and without the
+    label part), three 64-row tiles (the last of 2 rows), 70 x 3 problems."""
+    rs = np.random.RandomState(seed)
+    y = rs.randint(3, size=(130, 1)).astype(np.int32)
+    x = (0.7 * rs.randn(130, 70) + y * rs.uniform(-1.5, 1.5, size=70)).astype(np.float32)
+    theta, gnorm, iters, cvalid, ok = ref_sap_fit(x, y, [3])
+    return dict(sizes=[3], x=x, y=y, theta=theta, gnorm=gnorm, cvalid=cvalid, ok=ok)
+
+
+FVAE_TIES = {(5, 6, 69): 5, (69, 70): 69, (6, 69): 6}       # the columns that are copies of one another: who takes the vote
+
+
+@functools.lru_cache(maxsize=None)
+def fvae_tie_case(cols):
+    """D = 131, 41 train and 9 eval groups of L = 3 rows; the columns ``cols`` are copies of cols[0] in all three inputs, and
+    their group rows are shrunk so that they hold the smallest ratio of most groups.  Lane l of the vote kernel holds the
+    columns l, l + 64, l + 128: (5, 69) tie inside a lane, (5, 6) and (69, 70) across lanes with the smaller index in the
+    lower lane, (6, 69) across lanes with the LARGER index in the lower lane."""
+    rs = np.random.RandomState(13)
+    D, K, L = 131, 3, 3
+    mv = rs.randn(67, D).astype(np.float32) * rs.uniform(0.5, 2.0, size=D).astype(np.float32)
+    mt, me = rs.randn(41 * L, D).astype(np.float32), rs.randn(9 * L, D).astype(np.float32)
+    for a in (mt, me):
+        a[:, cols[0]] *= np.float32(0.01)
+    for a in (mv, mt, me):
+        for c in cols[1:]:
+            a[:, c] = a[:, cols[0]]
+    return dict(L=L, K=K, mu_var=mv, mu_train=mt, mu_eval=me, fidx_train=rs.randint(K, size=41),
+                fidx_eval=rs.randint(K, size=9))
+
+
 # ---- the tests -------------------------------------------------------------------------------------------------------
+def test_many_classes_case_converges_and_keeps_its_decisions_off_a_tie():
+    c = sap_many_classes_case()
+    cnt = np.bincount(c["y_train"][:, 0], minlength=21)
+    assert (cnt > 0).sum() == 19 and cnt[0] == 0 and cnt[7] == 0 and (np.bincount(c["y_train"][:, 1]) > 0).all()
+    assert c["cvalid"].tolist() == [int(k not in (0, 7)) for k in range(21)] + [1, 1]
+    assert c["ok"] and c["gnorm"].max() <= 1e-10 and np.abs(c["x_test"]).max() <= 10.0
+    solved = c["iters"] > 0
+    assert solved.sum() == 2 * (19 + 1) and not c["theta"][~solved].any()
+    print("smallest decision gap", c["gap"], "newton steps at the most", c["iters"].max())
+    assert c["gap"] >= MANY_GAP_MIN
+    assert len(set(c["pred"][0, 0])) > 3                              # the informative latent tells classes apart
+
+
+def test_wide_case_converges():
+    c = sap_wide_case()
+    assert c["ok"] and c["gnorm"].max() <= 1e-10 and c["cvalid"].tolist() == [1, 1, 1]
+    assert (np.abs(c["theta"]).max(axis=(1, 2)) > 0).all()            # all 70 columns are fitted
+
+
+@pytest.mark.parametrize("cols", sorted(FVAE_TIES), ids=lambda c: "-".join(map(str, c)))
+def test_fvae_tie_case_ties_exactly_and_the_first_copy_takes_the_votes(cols):
+    c = fvae_tie_case(cols)
+    gvar = ref_gvar(c["mu_var"])
+    assert all(gvar[k] == gvar[cols[0]] for k in cols)                # the same bits: the ratios tie exactly
+    winner = FVAE_TIES[cols]
+    assert winner == min(cols)
+    for part in ("train", "eval"):
+        ratio, _ = ref_group_ratios(c[f"mu_{part}"], c["L"], gvar, 0.05)
+        assert all(np.array_equal(ratio[:, k], ratio[:, winner]) for k in cols)
+        votes = ref_votes(c[f"mu_{part}"], c["L"], gvar, 0.05, c[f"fidx_{part}"], c["K"])
+        taken = int(votes[winner].sum())
+        print(cols, part, "groups won by the copies", taken, "of", len(c[f"fidx_{part}"]))
+        assert 2 * taken > len(c[f"fidx_{part}"]) and not any(votes[k].any() for k in cols if k != winner)
+        # away from the planted tie, no arg-min is close enough for a last-bit difference of gvar (1e-13) to move it
+        rest = np.sort(np.delete(ratio, [k for k in cols if k != winner], axis=1), axis=1)
+        assert ((rest[:, 1] - rest[:, 0]) / rest[:, 1]).min() > 1e-6
+
+
 @pytest.fixture(scope="module")
 def golden():
     g = np.load(os.path.join(GOLDEN, "extra_scores.npz"))

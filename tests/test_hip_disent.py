@@ -4,14 +4,34 @@ restatement of tests/test_disent_host.py and the results recorded from the unmod
 Bounds: integer tables and bin numbers are compared EXACTLY.  MI and H: 1e-10 absolute -- a pair's table has at most
 32 x 256 non-zero cells, each term is a few ulp (2.2e-16) of an O(10) logarithm times c/N <= 1, and the weights c/N sum
 to 1, so the sum's error stays near 1e-14 for any order of summation and below 32 * 256 * 10 * 4 ulp ~ 1e-11 in the
-worst case.  Scores (a mean of differences / quotients of those): 1e-9."""
+worst case.  Scores (a mean of differences / quotients of those): 1e-9.
+
+What each shape launches (the histogram's plan is asked of the library through ``HF.disent_hist_tiling`` and restated in
+tests/test_disent_host.py, which holds HIST_TIERS to these figures on the CPU; tc = columns per block, rp = 256 / tc rows
+per step of a block, a row slice is 512 rows):
+
+  case            N        D    factor sizes          bins  tc  column tiles      groups  LDS bytes  row slices
+  tc64            1037     70   6 6 2 3 3             10    64  2, the last 6     1       51 280     3, the last 13 rows
+  tc32            1037     70   6 6 2 3 3             20    32  3, the last 6     1       51 280     3
+  tc4_dsprites    1037     10   3 6 40 32 32          20    4   3, the last 2     1       36 612     3
+  tc2             1037     5    100 100               32    2   3, the last 1     1       52 000     3
+  tc2_groups      1037     5    250 250 250           32    2   3, the last 1     3       65 000     3
+  tc1_wide        1037     3    200 200               32    1   3                 1       52 800     3
+  large_n         262 445  5    3 7                   20    8   1 (5 of 8 used)   1       6 440      513, the last 301 rows
+  (earlier tests: tc 16 and 8 on the fixture, 2 on a single row, 1 everywhere else, 16 groups at tc 1)
+
+1037 is a multiple of no 4 * rp, so every tier's last step of a slice is ragged.  large_n also doubles the min-max slices
+to 512 rows (513 partials for the fold) and sends the binning kernel's capped grid of 4096 blocks on its second trip.
+Largest errors on the MI355X over the seven cases: |MI - ref| 2.2e-16, |H - ref| 1.8e-15, MIG and modularity below 3e-16;
+every integer table, marginal and bin number equal, every repeated call bit for bit."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from test_disent_host import GOLDEN, ref_all, ref_bins, ref_mig, ref_modularity
+from test_disent_host import GOLDEN, HIST_TIERS, ref_all, ref_bins, ref_mig, ref_modularity
+from test_hip_extra_scores import strided
 
 pytestmark = pytest.mark.gpu
 
@@ -150,6 +170,68 @@ def test_factor_groups_when_one_table_exceeds_the_lds_budget():
     v = np.stack([rs.randint(s, size=N) for s in sizes], 1).astype(np.int32)
     x = (v[:, :D] / 256.0 + 0.1 * rs.randn(N, D)).astype(np.float32)
     check_against_restatement(G(x), G(v), sizes, 32, x)
+
+
+# ---- every tier of the histogram's launch plan, and the large-N trips ------------------------------------------------
+def planted_case(N, D, sizes, seed):
+    """Latents that depend on the factors (no flat tables), as the right part of a wider NaN-padded tensor."""
+    rs = np.random.RandomState(seed)
+    v = np.stack([rs.randint(s, size=N) for s in sizes], 1).astype(np.int32)
+    W = rs.randn(len(sizes), D) * (rs.rand(len(sizes), D) < 0.5)
+    x = ((v / np.array(sizes, dtype=np.float64)) @ W + 0.2 * rs.randn(N, D)).astype(np.float32)
+    return x, v
+
+
+def check_tier(name, x, v):
+    """The plan is the one the case is named for; then bins, tables, marginals (exact), MI, H, MIG and modularity of the
+    strided input against the restatement, every call made twice and compared bit for bit."""
+    from hipvae import disentangle as DS
+    from hipvae import functional as HF
+    D, sizes, bins, tc, tiles, last, groups, lds = HIST_TIERS[name]
+    assert x.shape[1] == D and HF.disent_hist_tiling(D, sizes, bins) == dict(tc=tc, column_tiles=tiles, groups=groups,
+                                                                              lds_bytes=lds)
+    sizes = list(sizes)
+    mu, vv = strided(x), G(v)
+    dmi, dh, mi, h = check_against_restatement(mu, vv, sizes, bins, x)
+    got = DS.scores(mu, vv, sizes, mig_bins=bins, modularity_bins=bins)
+    want_mig, want_mod = ref_mig(mi, h), ref_modularity(mi)
+    print(name, "mig", got["mig"], want_mig, "modularity", got["modularity"], want_mod)
+    assert np.isfinite([want_mig, want_mod]).all()
+    assert close(got["mig"], want_mig, SCORE_TOL) and close(got["modularity"], want_mod, SCORE_TOL)
+    dj, dm = DS.factor_counts(mu, vv, sizes, bins)
+    first = torch.cat([t.reshape(-1) for t in dj + dm]).clone()
+    dj, dm = DS.factor_counts(mu, vv, sizes, bins)
+    assert torch.equal(first, torch.cat([t.reshape(-1) for t in dj + dm]))
+    mi2, h2 = DS.mutual_info(mu, vv, sizes, bins)
+    assert torch.equal(dmi, mi2) and torch.equal(dh, h2)
+    assert torch.equal(DS.discretize(mu, bins), DS.discretize(mu, bins))
+    assert DS.scores(mu, vv, sizes, mig_bins=bins, modularity_bins=bins) == got
+
+
+@pytest.mark.parametrize("name", ["tc64", "tc32", "tc4_dsprites", "tc2", "tc2_groups", "tc1_wide"])
+def test_histogram_column_tile_tiers(name):
+    """N = 1037: three row slices, the last of 13 rows, a multiple of no 4 * (256 / tc).  tc2_groups is the only way factor
+    groups and tc > 1 combine: a second group is opened only when the largest group holds more than half of the words one
+    column may use, which leaves room for two columns at the most (the host tests sweep that)."""
+    D, sizes = HIST_TIERS[name][:2]
+    x, v = planted_case(1037, D, sizes, seed=21 + D)
+    check_tier(name, x, v)
+
+
+def test_large_n_doubled_minmax_slices_second_bins_trip_and_513_row_slices():
+    """N = 262 144 + 301: the min-max slices double to 512 rows (513 partials, the last of 301 rows), the binning kernel's
+    capped grid takes a second trip (N D = 1 312 225 > 4096 * 256) and the histogram runs 513 row slices at tc = 8.  The
+    extremes of columns 0 and 3 sit in row 0 and in the last 301 rows: a dropped slice moves the range."""
+    from hipvae import abi
+    N, (D, sizes) = 262144 + 301, HIST_TIERS["large_n"][:2]
+    assert abi.lib.itcv_disent_minmax_workspace(N, D) == 2 * 513 * D * 4 and N - 512 * 512 == 301
+    assert N * D > 4096 * 256 and -(-N // 512) == 513
+    x, v = planted_case(N, D, sizes, seed=5)
+    x[0, 0], x[N - 7, 0] = 12.0, -11.5
+    x[N - 300, 3], x[0, 3] = 12.5, -13.25
+    for c, (lo, hi) in ((0, (N - 7, 0)), (3, (0, N - 300))):
+        assert int(x[:, c].argmin()) == lo and int(x[:, c].argmax()) == hi
+    check_tier("large_n", x, v)
 
 
 def test_refusals(golden):

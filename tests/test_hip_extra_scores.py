@@ -5,15 +5,38 @@ Bounds: vote tables, classifiers, accuracies, class masks, predictions, counts, 
 fixtures keep every arg-min / arg-max away from a tie, see the host tests).  gvar: 1e-13 relative (a two-pass fp64
 variance of 200 O(1) values; each of the two sums carries at most 200 ulp = 4.4e-14 in any order).  theta: 1e-9 absolute
 -- the device and the restatement both stop within sqrt(2) * gtol = 1.5e-10 of the unique optimum, and rounding of the
-sums (<= 1e-13 here) is far below that.  Continuous variant: 1e-12 (ratios of fp64 sums of 601 O(1) terms)."""
+sums (<= 1e-13 here) is far below that.  Continuous variant: 1e-12 (ratios of fp64 sums of 601 O(1) terms).
+
+The planted ties are the exception to "away from a tie": there the two sides are EQUAL bits (copies of a column, decisions
+that are small integers), so the tie rule itself decides, and the host tests assert the equality.
+
+What each later shape launches (conditions on the data are asserted in tests/test_extra_scores_host.py):
+
+  test                                  shape                                   path
+  vote ... exact_tie [5-6-69]           D 131, L 3, 41 + 9 groups               first minimum of a lane (5 before 69), butterfly 5 | 6
+                     [69-70]                                                    butterfly, the smaller index in the lower lane
+                     [6-69]                                                     butterfly, the LARGER index in the lower lane
+  classifier_second_trip                D 300, K 130, tables by hand            a thread's second trip (D > 256), first of two equal
+                                                                                maxima, all-zero rows, K > 4
+  variances_with_empty_row_slots        N 2 and 31, D 131                       30 and 1 of the 32 row slots empty
+  votes_shortest_group ...              M 5; L 2 and 197; D 70                  a short second block; L - 1 = 1; L past 64, odd
+  sap_more_problems_than_waves          N 700, D 2, 19 of 21 classes + binary   waves 0, 1, 2 solve 3 problems, the others 2
+  sap_wide_and_ragged_copy_tiles        N 130, D 70, 3 classes                  copy kernel 3 x 2 tiles: a 2-row tile, a 6-column tile,
+                                                                                the blocks that skip the labels; 210 problems
+  sap_score_tie_rules                   300 rows, D 2, sizes 4 4 3 by hand      ties of 2 and of 3 decisions, class 0 absent, dec == 0.0,
+                                                                                dec < 0, dec > 0; a second block of test rows
+
+Largest errors on the MI355X in these tests: gvar 7.7e-16 relative (0 at N = 2 and 31), theta 1.0e-15 (19 + 1 problems;
+final gradient 3.2e-14, 6 Newton steps) and 3.3e-16 (the wide case; 1.0e-15, 4 steps); everything else is exact."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from test_extra_scores_host import (GOLDEN, ref_factor_vae, ref_gvar, ref_sap, ref_sap_continuous, ref_sap_fit,
-                                    ref_sap_matrix, ref_sap_predict, ref_votes)
+from test_extra_scores_host import (FVAE_TIES, GOLDEN, MANY_GAP_MIN, fvae_tie_case, offsets, ref_factor_vae, ref_gvar,
+                                    ref_sap, ref_sap_continuous, ref_sap_fit, ref_sap_matrix, ref_sap_predict, ref_votes,
+                                    sap_many_classes_case, sap_wide_case)
 
 pytestmark = pytest.mark.gpu
 
@@ -134,6 +157,98 @@ def test_fvae_all_inactive_and_refusals(golden):
     assert DS.factor_vae_score(mv, mt, ft, me, fe, 5, 4) == tuple(float(v) for v in g["fv_acc5"])
 
 
+@pytest.mark.parametrize("cols", sorted(FVAE_TIES), ids=lambda c: "-".join(map(str, c)))
+def test_fvae_vote_goes_to_the_smallest_index_of_an_exact_tie(cols):
+    """Copies of a column have bitwise-equal variances and ratios (asserted on the host): the vote goes to the smallest
+    index, inside a lane (5 before 69) and in the butterfly, whichever of the two lanes holds the larger index."""
+    from hipvae import disentangle as DS
+    from hipvae import functional as HF
+    c, winner = fvae_tie_case(cols), FVAE_TIES[cols]
+    L, K, ft, fe = c["L"], c["K"], c["fidx_train"], c["fidx_eval"]
+    want = ref_factor_vae(c["mu_var"], c["mu_train"], ft, c["mu_eval"], fe, L, K)
+    mv, mt, me = strided(c["mu_var"]), strided(c["mu_train"]), strided(c["mu_eval"])
+    got = DS.factor_vae_votes(mv, mt, ft, me, fe, L, K)
+    gv = got["gvar"].cpu().numpy()
+    print("max relative |gvar - ref|", np.max(np.abs(gv - want["gvar"]) / want["gvar"]))
+    assert (np.abs(gv - want["gvar"]) <= 1e-13 * want["gvar"]).all() and all(gv[k] == gv[winner] for k in cols)
+    for part in ("train", "eval"):
+        votes = got[f"votes_{part}"].cpu().numpy()
+        assert np.array_equal(votes, want[f"votes_{part}"])
+        assert 2 * votes[winner].sum() > votes.sum() and not any(votes[k].any() for k in cols if k != winner)
+    assert np.array_equal(got["classifier"].cpu().numpy(), want["classifier"])
+    assert (got["train_accuracy"], got["eval_accuracy"], got["num_active"]) == \
+        (want["train_accuracy"], want["eval_accuracy"], want["num_active"])
+    again = DS.factor_vae_votes(mv, mt, ft, me, fe, L, K)
+    assert all(torch.equal(got[k], again[k]) for k in ("gvar", "votes_train", "votes_eval", "classifier"))
+    # the entry point alone, handed the restatement's variances
+    flags = HF.extra_flags(dev())
+    votes = HF.fvae_votes(mt, L, G(want["gvar"]), 0.05, ft, K, flags)
+    assert np.array_equal(votes.cpu().numpy(), want["votes_train"]) and flags.tolist() == [0, 0, 0]
+
+
+def test_fvae_classifier_second_trip_tied_maxima_and_empty_rows():
+    """D = 300 (the second trip of the block's 256 threads), K = 130, tables written by the test: a single maximum in most
+    rows, two equal maxima in every 10th (the first k wins), no vote at all in every 17th other (class 0)."""
+    from hipvae import functional as HF
+    D, K = 300, 130
+    rs = np.random.RandomState(2)
+    vt = rs.randint(0, 3, size=(D, K)).astype(np.int64)
+    ve = rs.randint(0, 4, size=(D, K)).astype(np.int64)
+    want_cls, want_ht = np.zeros(D, dtype=np.int32), 0
+    for d in range(D):
+        k1 = (7 * d + 3) % K
+        if d % 10 == 0:
+            k1 = min(k1, K - 41)
+            vt[d, k1] = vt[d, k1 + 40] = 5 + d % 4                  # two equal maxima: the first one
+        elif d % 17 == 0:
+            vt[d], k1 = 0, 0                                          # nobody voted for this dimension
+        else:
+            vt[d, k1] = 3 + d % 4
+        want_cls[d] = k1
+        want_ht += int(vt[d, k1])
+    want_he = int(ve[np.arange(D), want_cls].sum())
+    Mt, Me = int(vt.sum()), int(ve.sum())
+    gvar = np.ones(D)
+    gvar[::7] = 1e-4                                                  # sqrt = 0.01 < 0.05: inactive, counted out of res[2]
+    assert np.array_equal(want_cls, np.argmax(vt, axis=1)) and len(set(want_cls)) > 100
+    runs = [HF.fvae_classify(G(vt), G(ve), Mt, Me, G(gvar), 0.05) for _ in range(2)]
+    cls, res = runs[0]
+    assert torch.equal(cls, runs[1][0]) and torch.equal(res, runs[1][1])
+    assert np.array_equal(cls.cpu().numpy(), want_cls)
+    assert res.tolist() == [float(want_ht) / float(Mt), float(want_he) / float(Me), float(D - len(range(0, D, 7)))]
+
+
+@pytest.mark.parametrize("N", [2, 31])
+def test_fvae_variances_with_empty_row_slots(N):
+    """Fewer rows than the 32 row slots of the variance kernel: the empty slots add exact zeros."""
+    from hipvae import functional as HF
+    rs = np.random.RandomState(40 + N)
+    x = (rs.randn(N, 131) * rs.uniform(0.5, 2.0, size=131)).astype(np.float32)
+    want = ref_gvar(x)
+    flags = HF.extra_flags(dev())
+    got = HF.fvae_gvar(strided(x), flags)
+    assert torch.equal(got, HF.fvae_gvar(strided(x), flags)) and flags.tolist() == [0, 0, 0]
+    print("N", N, "max relative |gvar - ref|", np.max(np.abs(got.cpu().numpy() - want) / want))
+    assert (want > 0).all() and (np.abs(got.cpu().numpy() - want) <= 1e-13 * want).all()
+
+
+@pytest.mark.parametrize("L", [2, 197])
+def test_fvae_votes_shortest_group_and_one_past_the_wave(L):
+    """M = 5 groups (a second, short block) of L = 2 and of L = 197 rows, D = 70; the variances are handed over, so both
+    sides divide by the same bits and add the rows in the same order: exact."""
+    from hipvae import functional as HF
+    rs = np.random.RandomState(L)
+    M, D, K = 5, 70, 4
+    mu = (rs.randn(M * L, D) * rs.uniform(0.2, 2.0, size=(M, 1, D)).repeat(L, 1).reshape(M * L, D)).astype(np.float32)
+    gvar, fidx = rs.uniform(0.5, 2.0, size=D), rs.randint(K, size=M)
+    gvar[::9] = 1e-4                                                  # inactive dimensions take no vote
+    want = ref_votes(mu, L, gvar, 0.05, fidx, K)
+    flags = HF.extra_flags(dev())
+    runs = [HF.fvae_votes(strided(mu), L, G(gvar), 0.05, fidx, K, flags) for _ in range(2)]
+    assert torch.equal(runs[0], runs[1]) and flags.tolist() == [0, 0, 0]
+    assert np.array_equal(runs[0].cpu().numpy(), want) and want.sum() == M and not want[::9].any()
+
+
 # ---- SAP ---------------------------------------------------------------------------------------------------------------
 def check_fit(x, y, sizes, want_theta, want_cvalid, **kw):
     from hipvae import disentangle as DS
@@ -236,6 +351,87 @@ def test_sap_rows_past_the_lds_limit_are_streamed():
     inside = DS.fit_sap_classifiers(xtr[:N - 37], ytr[:N - 37], sizes)
     want = ref_sap_fit(x[:N - 37], y[:N - 37], sizes)
     assert np.abs(inside[0].cpu().numpy() - want[0]).max() <= THETA_TOL and float(inside[1].max()) <= GTOL
+
+
+def test_sap_more_problems_than_waves():
+    """19 present classes of 21 and a binary factor: the 8 waves of a (latent, factor) block are dealt three problems (waves
+    0, 1, 2) or two; every slot of the big factor is either solved or one of the two absent classes."""
+    from hipvae import disentangle as DS
+    from hipvae import functional as HF
+    c = sap_many_classes_case()
+    assert c["ok"] and c["gap"] >= MANY_GAP_MIN and int(c["cvalid"][:21].sum()) == 19 > 2 * (512 // 64)
+    xtr, ytr, xte, yte = strided(c["x_train"]), G(c["y_train"]), strided(c["x_test"]), G(c["y_test"])
+    first = check_fit(xtr, ytr, c["sizes"], c["theta"], c["cvalid"])
+    assert all(torch.equal(a, b) for a, b in zip(first, DS.fit_sap_classifiers(xtr, ytr, c["sizes"])))      # bitwise
+    theta, _, iters, cvalid = first
+    th, it = theta.cpu().numpy(), iters.cpu().numpy()
+    for slot in (0, 7, 21):                                           # the absent classes, the binary factor's first class
+        assert not th[:, slot].any() and not it[:, slot].any()
+    assert (it[:, [k for k in range(23) if k not in (0, 7, 21)]] > 0).all()
+    flags = HF.extra_flags(dev())
+    runs = [HF.sap_svc_score(xte, yte, c["sizes"], cvalid, theta, flags, with_pred=True) for _ in range(2)]
+    assert all(torch.equal(a, b) for a, b in zip(*runs)) and flags.tolist() == [0, 0, 0]
+    want_S, want_correct = ref_sap_matrix(c["pred"], c["y_test"])
+    assert np.array_equal(runs[0][1].cpu().numpy(), c["pred"]) and np.array_equal(runs[0][0].cpu().numpy(), want_correct)
+    S = DS.sap_score_matrix(xtr, ytr, xte, yte, c["sizes"])
+    assert np.array_equal(S.cpu().numpy(), want_S) and DS.sap_score(xtr, ytr, xte, yte, c["sizes"]) == ref_sap(want_S)
+
+
+def test_sap_wide_and_ragged_copy_tiles():
+    """N = 130, D = 70: the copy kernel runs 3 x 2 tiles (the last row tile 2 rows, the second column tile 6 columns and no
+    label part).  A column's problems read that column alone, so a dense 8-column slice of the same data -- one column
+    tile, other row stride -- must give the same bits, on either side of the tile edge."""
+    from hipvae import disentangle as DS
+    c = sap_wide_case()
+    assert c["ok"] and c["x"].shape == (130, 70)
+    x, y = strided(c["x"]), G(c["y"])
+    first = check_fit(x, y, c["sizes"], c["theta"], c["cvalid"])
+    assert all(torch.equal(a, b) for a, b in zip(first, DS.fit_sap_classifiers(x, y, c["sizes"])))
+    for lo in (0, 60, 62):
+        part = DS.fit_sap_classifiers(G(np.ascontiguousarray(c["x"][:, lo:lo + 8])), y, c["sizes"])
+        assert all(torch.equal(a[lo:lo + 8], b) for a, b in zip(first[:3], part)) and torch.equal(first[3], part[3])
+
+
+def test_sap_score_tie_rules():
+    """Hand-written classifiers whose decisions are small integers and quarters, exact in fp64.  Three or more present
+    classes: ascending and strict, so a tie goes to the smallest present class (also when class 0 is absent); two present
+    classes: the last one only on a decision > 0, the first one on 0.0 and below.  The slots of absent classes and of a
+    binary factor's first class hold values that would win if they were read."""
+    from hipvae import functional as HF
+    sizes, present = [4, 4, 3], [[0, 2, 3], [1, 2, 3], [0, 2]]
+    off = offsets(sizes)
+    cvalid = np.zeros(off[-1], dtype=np.int32)
+    theta = np.full((2, off[-1], 2), 1000.0)
+    for j, V in enumerate(present):
+        cvalid[off[j] + np.array(V)] = 1
+    # latent 0.  factor 0: dec = (x, 1, 1); factor 1: three equal classifiers; factor 2: dec = x - 1
+    theta[0, [0, 2, 3]] = [(1, 0), (0, 1), (0, 1)]
+    theta[0, [5, 6, 7]] = [(0.5, 0.25)] * 3
+    theta[0, 10] = (1, -1)
+    # latent 1.  factor 0: dec = (0, -x, x); factor 1: dec = (x, x, 1); factor 2: dec = -2 x
+    theta[1, [0, 2, 3]] = [(0, 0), (-1, 0), (1, 0)]
+    theta[1, [5, 6, 7]] = [(1, 0), (1, 0), (0, 1)]
+    theta[1, 10] = (-2, 0)
+    x = np.array([[0, 0], [1, 1], [2, -1], [-1, 2], [3, -2]], dtype=np.float32)
+    y = np.array([[2, 1, 0], [0, 1, 2], [3, 3, 2], [2, 1, 0], [0, 3, 2]], dtype=np.int32)
+    want_pred = np.array([[[2, 0, 0, 2, 0],      # x = 0: classes 2 and 3 tie at 1; x = 1: all three tie; x = -1: 2 and 3 tie
+                           [1, 1, 1, 1, 1],      # all decisions equal, class 0 absent
+                           [0, 0, 2, 0, 2]],     # x = 0: -1; x = 1: exactly 0.0; x = 2: +1; x = -1: -2; x = 3: +2
+                          [[0, 3, 2, 3, 2],      # x = 0: all three tie at 0
+                           [3, 1, 3, 1, 3],      # x = 1: all three tie at 1; x = 2: classes 1 and 2 tie at 2
+                           [0, 0, 2, 0, 2]]],    # x = 0: exactly 0.0; x = 2: -4; x = -1: +2
+                         dtype=np.int32)
+    want_correct = np.array([[4, 3, 4], [0, 4, 4]], dtype=np.int64)
+    assert np.array_equal(ref_sap_predict(theta, cvalid, x, sizes)[0], want_pred)
+    assert np.array_equal(ref_sap_matrix(want_pred, y)[1], want_correct)
+    reps = 60                                                         # 300 rows: a second, short block of test rows
+    xs, ys = strided(np.tile(x, (reps, 1))), G(np.tile(y, (reps, 1)))
+    flags = HF.extra_flags(dev())
+    runs = [HF.sap_svc_score(xs, ys, sizes, G(cvalid), G(theta), flags, with_pred=True) for _ in range(2)]
+    assert all(torch.equal(a, b) for a, b in zip(*runs)) and flags.tolist() == [0, 0, 0]
+    correct, pred = runs[0]
+    assert np.array_equal(pred.cpu().numpy(), np.tile(want_pred, (1, 1, reps)))
+    assert np.array_equal(correct.cpu().numpy(), reps * want_correct)
 
 
 def test_sap_continuous_factors(golden):
