@@ -40,7 +40,19 @@ const char* itcv_last_error(void);
  *   "sw_lds_rows"          0 (default: 4096): rows of itcv_sw_kl_fwd whose sort keys sit in LDS, above that in the workspace;
  *                          range 0..4096 (bit-identical: a test option that forces the workspace path at any Bt)
  *   "sw_max_blocks"        0 (default: 256): the grid cap of itcv_sw_kl_fwd's first launch; range 0..1024 (bit-identical)
+ *   "stream_nt"            ITCV_STREAM_NT_DEFAULT (default): mask of ITCV_STREAM_NT_* bits below, one per kernel family; a set
+ *                          bit makes the family's once-used streams non-temporal loads / stores (bit-identical: a cache
+ *                          policy changes no value).  Any value >= 0 is taken; bits outside ITCV_STREAM_NT_ALL are dropped
+ *                          (itcv_get_option reads back the kept bits).
  * itcv_set_option returns non-zero for an unknown name or a value out of range; itcv_get_option returns -1 for an unknown name. */
+#define ITCV_STREAM_NT_BN_APPLY 0x1    /* x, dy, skip loads of the BatchNorm backward apply pass (last use) */
+#define ITCV_STREAM_NT_WGRAD_SLABS 0x2 /* fp32 slab stores of a deferred planes weight gradient (read by the fold, far later) */
+#define ITCV_STREAM_NT_FOLD 0x4        /* slab loads of the deferred weight-gradient fold, itcv_wgrad_reduce_many (last use) */
+#define ITCV_STREAM_NT_WGRAD_OPS 0x8   /* reserved: operand loads of the weight gradient; no kernel reads this bit */
+#define ITCV_STREAM_NT_OPTIM 0x10      /* reserved: optimiser streams; measured, no gain, no kernel reads this bit */
+#define ITCV_STREAM_NT_BN_FWD 0x20     /* conv-output loads of the BatchNorm forward apply pass (next read: the backward) */
+#define ITCV_STREAM_NT_ALL (ITCV_STREAM_NT_BN_APPLY | ITCV_STREAM_NT_WGRAD_SLABS | ITCV_STREAM_NT_FOLD | ITCV_STREAM_NT_WGRAD_OPS | ITCV_STREAM_NT_OPTIM | ITCV_STREAM_NT_BN_FWD)
+#define ITCV_STREAM_NT_DEFAULT (ITCV_STREAM_NT_BN_APPLY | ITCV_STREAM_NT_WGRAD_SLABS | ITCV_STREAM_NT_FOLD | ITCV_STREAM_NT_BN_FWD)
 int itcv_set_option(const char* name, int value);
 int itcv_get_option(const char* name);
 

@@ -36,6 +36,7 @@ ProfScope::~ProfScope() {
 }
 thread_local hipEvent_t g_prof_start = nullptr, g_prof_stop = nullptr;
 Options g_opt;
+int g_stream_nt = ITCV_STREAM_NT_DEFAULT;
 extern int g_sw_lds_rows, g_sw_max_blocks;   // sw.hip
 }
 
@@ -64,6 +65,11 @@ int itcv_set_option(const char* name, int value) {
     itcv::g_opt.planes_mfma_waves = value;
     return 0;
   }
+  if (!strcmp(name, "stream_nt")) {
+    if (value < 0) return itcv::fail("%s: stream_nt takes a mask of ITCV_STREAM_NT_* bits (got %lld)", "itcv_set_option", value);
+    itcv::g_stream_nt = value & ITCV_STREAM_NT_ALL;
+    return 0;
+  }
   if (!strcmp(name, "sw_lds_rows")) {
     if (value < 0 || value > 4096) return itcv::fail("%s: sw_lds_rows takes 0..4096 (got %lld)", "itcv_set_option", value);
     itcv::g_sw_lds_rows = value;
@@ -81,6 +87,7 @@ int itcv_get_option(const char* name) {
   if (name && !strcmp(name, "band_persist_blocks")) return itcv::g_opt.band_persist_blocks;
   if (name && !strcmp(name, "wgrad_m16")) return itcv::g_opt.wgrad_m16;
   if (name && !strcmp(name, "planes_mfma_waves")) return itcv::g_opt.planes_mfma_waves;
+  if (name && !strcmp(name, "stream_nt")) return itcv::g_stream_nt;
   if (name && !strcmp(name, "sw_lds_rows")) return itcv::g_sw_lds_rows;
   if (name && !strcmp(name, "sw_max_blocks")) return itcv::g_sw_max_blocks;
   return -1;

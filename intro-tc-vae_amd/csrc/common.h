@@ -115,6 +115,53 @@ __device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, uint32_t byt
 }
 constexpr uint32_t kOOB = 0xFFFFFFFFu;
 
+// ---- stream policy (option "stream_nt", include/itcv_hip.h: one ITCV_STREAM_NT_* bit per kernel family) ----------------
+// A tensor a kernel reads for the last time, or writes for a reader more than a cache's worth of traffic away, is loaded /
+// stored non-temporally (`nt` on the instruction): it moves at the same rate and is not kept in front of the lines the
+// next kernel asks for.  Hand-offs (the next kernel reads the bytes) always stay plain.  NT is a template argument
+// reached through pick<2>(stream_nt(bit)); a policy bit changes no value, so both forms are bitwise equal (tests).
+extern int g_stream_nt;   // abi.hip
+inline int stream_nt(int bit) { return (g_stream_nt & bit) ? 1 : 0; }
+typedef float f32x4n __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ float4 ld4(const float* p) {
+  if constexpr (NT) {
+    const f32x4n v = __builtin_nontemporal_load(reinterpret_cast<const f32x4n*>(p));
+    return make_float4(v.x, v.y, v.z, v.w);
+  } else {
+    return *reinterpret_cast<const float4*>(p);
+  }
+}
+template <bool NT>
+__device__ __forceinline__ float2 ld2(const float* p) {
+  typedef float f32x2n __attribute__((ext_vector_type(2)));
+  if constexpr (NT) {
+    const f32x2n v = __builtin_nontemporal_load(reinterpret_cast<const f32x2n*>(p));
+    return make_float2(v.x, v.y);
+  } else {
+    return *reinterpret_cast<const float2*>(p);
+  }
+}
+template <bool NT>
+__device__ __forceinline__ float ld1(const float* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(p);
+  else return *p;
+}
+template <bool NT>
+__device__ __forceinline__ void st4(float* p, const float4& v) {
+  if constexpr (NT) {
+    const f32x4n t = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(t, reinterpret_cast<f32x4n*>(p));
+  } else {
+    *reinterpret_cast<float4*>(p) = v;
+  }
+}
+template <bool NT>
+__device__ __forceinline__ void st1(float* p, float v) {
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+
 // init + p[0] + p[stride] + ... (n terms, ascending: a fixed order, bitwise reproducible) with the loads of 8 terms in
 // flight -- a plain `for (k) s += p[k*stride]` is one exposed memory round trip per term.
 template <typename T>

@@ -1493,6 +1493,7 @@ struct WgradArgsP {
   size_t xplane, dyplane;   // chunks per plane
   const ScaleRec* xscale;   // fp16 planes: scale records of x and dy (the slabs are multiplied by 1 / (Sx * Sdy))
   const ScaleRec* dyscale;
+  int nt_slabs;             // ITCV_STREAM_NT_WGRAD_SLABS on a deferred call: the slab stores are non-temporal (see the epilogues)
 #ifdef ITCV_DIAG
   int debug;                // diagnostic only (ITCV_ABLATE & 64): block 0 reports main-loop shader cycles / steps in slab[0..1]
 #endif
@@ -1726,25 +1727,33 @@ __global__ __launch_bounds__(512 + 64 * NLW) void conv_wgrad_bf16p_kernel(WgradA
       }
     }
     // slab[split][tap][co][ci]: lane (G, i16) holds rows 4G .. 4G+3 and column i16 of every 16 x 16 block
+    // Deferred calls (the fold reads the slabs at the end of the backward, gigabytes of traffic later) store them
+    // non-temporally: a kernel-uniform run-time switch around the two store loops, not a template argument -- the kernel
+    // has 160 instantiations and the policy touches nothing in front of the epilogue.
     const float oscale = F16 ? inv_scale_of(a.xscale) * inv_scale_of(a.dyscale) : 1.f;
+    auto store_slabs = [&](auto nt_c) {
+      constexpr bool NT = decltype(nt_c)::value != 0;
 #pragma unroll
-    for (int j = 0; j < TNw; ++j)
+      for (int j = 0; j < TNw; ++j)
 #pragma unroll
-      for (int bj = 0; bj < 2; ++bj) {
-        const int ci = ci0 + 32 * (wn * TNw + j) + 16 * bj + i16;
-        if (ci >= a.Ci) continue;
+        for (int bj = 0; bj < 2; ++bj) {
+          const int ci = ci0 + 32 * (wn * TNw + j) + 16 * bj + i16;
+          if (ci >= a.Ci) continue;
 #pragma unroll
-        for (int tp = 0; tp < 3; ++tp) {
-          float* out = a.slab + ((size_t)((split * KH + kh) * 9 + dhi * 3 + tp) * a.Co) * a.Ci + ci;
+          for (int tp = 0; tp < 3; ++tp) {
+            float* out = a.slab + ((size_t)((split * KH + kh) * 9 + dhi * 3 + tp) * a.Co) * a.Ci + ci;
 #pragma unroll
-          for (int bi = 0; bi < 2; ++bi)
+            for (int bi = 0; bi < 2; ++bi)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int co = co0 + 32 * wm + 16 * bi + 4 * G + r;
-              if (co < a.Co) out[(size_t)co * a.Ci] = F16 ? acc[tp][j][bi][bj][r] * oscale : acc[tp][j][bi][bj][r];
-            }
+              for (int r = 0; r < 4; ++r) {
+                const int co = co0 + 32 * wm + 16 * bi + 4 * G + r;
+                if (co < a.Co) st1<NT>(out + (size_t)co * a.Ci, F16 ? acc[tp][j][bi][bj][r] * oscale : acc[tp][j][bi][bj][r]);
+              }
+          }
         }
-      }
+    };
+    if (a.nt_slabs) store_slabs(std::integral_constant<int, 1>{});
+    else store_slabs(std::integral_constant<int, 0>{});
     return;
   }
   f32x16 acc[3][TNw];
@@ -1853,20 +1862,25 @@ __global__ __launch_bounds__(512 + 64 * NLW) void conv_wgrad_bf16p_kernel(WgradA
   }
   // slab[split][tap][co][ci]
   const float oscale = F16 ? inv_scale_of(a.xscale) * inv_scale_of(a.dyscale) : 1.f;   // exact: powers of two
+  auto store_slabs = [&](auto nt_c) {
+    constexpr bool NT = decltype(nt_c)::value != 0;
 #pragma unroll
-  for (int j = 0; j < TNw; ++j) {
-    const int ci = ci0 + 32 * (wn * TNw + j) + l31;
-    if (ci >= a.Ci) continue;
+    for (int j = 0; j < TNw; ++j) {
+      const int ci = ci0 + 32 * (wn * TNw + j) + l31;
+      if (ci >= a.Ci) continue;
 #pragma unroll
-    for (int tp = 0; tp < 3; ++tp) {
-      float* out = a.slab + ((size_t)((split * KH + kh) * 9 + dhi * 3 + tp) * a.Co) * a.Ci + ci;
+      for (int tp = 0; tp < 3; ++tp) {
+        float* out = a.slab + ((size_t)((split * KH + kh) * 9 + dhi * 3 + tp) * a.Co) * a.Ci + ci;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + 32 * wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (co < a.Co) out[(size_t)co * a.Ci] = F16 ? acc[tp][j][r] * oscale : acc[tp][j][r];
+        for (int r = 0; r < 16; ++r) {
+          const int co = co0 + 32 * wm + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          if (co < a.Co) st1<NT>(out + (size_t)co * a.Ci, F16 ? acc[tp][j][r] * oscale : acc[tp][j][r]);
+        }
       }
     }
-  }
+  };
+  if (a.nt_slabs) store_slabs(std::integral_constant<int, 1>{});
+  else store_slabs(std::integral_constant<int, 0>{});
 }
 
 // ---- 5x5 weight gradients with a 3-channel side (stem 3 -> 64, predict 64 -> 3), bf16x3, matrix cores ----------
@@ -1980,6 +1994,8 @@ __global__ __launch_bounds__(256) void conv_wgrad5_planes_kernel(const float* __
 
 // dw (+)= sum_jobs slab: element e = (m = cs*5 + dw, dh, cb); stem: dW[cb][cs][dh][dw], predict: dW[cs][cb][dh][dw]
 // (16 threads per element walk the jobs, folded in a fixed order through LDS)
+// (plain loads: the slabs were written by the launch in front of this one -- a hand-off.  Non-temporal loads cost this
+// kernel 42 %, 8.7 -> 12.3 us per launch in the c2 step, and were taken out: DESIGN section 6, round 9)
 __global__ __launch_bounds__(256) void wgrad5_reduce(const float* __restrict__ slab, float* __restrict__ dwt, int CS,
                                                     int njobs, int stem, int accumulate) {
   __shared__ float part[16][17];
@@ -2029,6 +2045,9 @@ static_assert(sizeof(WgReduceDesc) == 80, "WgReduceDesc layout is part of the AB
 // 144-byte run of dw.  The first form of this fold (64 elements x 9 taps per block, the four waves taking quarters of the
 // slice range, exchange through LDS) had a few KB in flight per block and idle phases around its barriers: ~2 TB/s whatever
 // the tiling (tools/reduce_bench.py).
+// NT (ITCV_STREAM_NT_FOLD, the deferred fold wgrad_p_reduce_many), here and in the fine form: the slab loads are
+// non-temporal (each slab byte is read once, a whole backward after it was written); the dw read-modify-write stays plain.
+template <bool NT>
 __device__ __forceinline__ void wgrad_reduce_tile(const WgReduceDesc& d, int tile) {
   const int e = (tile * 256 + (int)threadIdx.x) * 4;
   if (e >= d.coci) return;                                   // Co * Ci % 4 == 0 (Ci % 32 == 0)
@@ -2062,7 +2081,7 @@ __device__ __forceinline__ void wgrad_reduce_tile(const WgReduceDesc& d, int til
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
-        for (int tp = 0; tp < 9; ++tp) v[u][tp] = *reinterpret_cast<const float4*>(p + (size_t)(sl + u) * stride + (size_t)tp * plane);
+        for (int tp = 0; tp < 9; ++tp) v[u][tp] = ld4<NT>(p + (size_t)(sl + u) * stride + (size_t)tp * plane);
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -2072,7 +2091,7 @@ __device__ __forceinline__ void wgrad_reduce_tile(const WgReduceDesc& d, int til
     if (sl < d.splits[k]) {
       float4 v[9];
 #pragma unroll
-      for (int tp = 0; tp < 9; ++tp) v[tp] = *reinterpret_cast<const float4*>(p + (size_t)sl * stride + (size_t)tp * plane);
+      for (int tp = 0; tp < 9; ++tp) v[tp] = ld4<NT>(p + (size_t)sl * stride + (size_t)tp * plane);
 #pragma unroll
       for (int tp = 0; tp < 9; ++tp) acc[tp] += v[tp].x, acc[9 + tp] += v[tp].y, acc[18 + tp] += v[tp].z, acc[27 + tp] += v[tp].w;
     }
@@ -2105,13 +2124,13 @@ constexpr int kWgFineElems = 16 * kWgFineTiles, kWgFineOut = 9 * kWgFineElems;
 constexpr int kWgPartFloats = 16 * kWgFineOut;   // 36 KB of LDS
 static_assert(kWgFineElems == 64 && kWgFineOut <= 3 * 256, "lane mapping of wgrad_reduce_tile_fine");
 
-template <int U>   // acc += slices sl .. sl + U - 1, in that order, all their loads issued first
+template <int U, bool NT>   // acc += slices sl .. sl + U - 1, in that order, all their loads issued first
 __device__ __forceinline__ void wgrad_fine_add(float (&acc)[36], const float* p, int sl, size_t stride, size_t plane) {
   float4 v[U][9];
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
-    for (int tp = 0; tp < 9; ++tp) v[u][tp] = *reinterpret_cast<const float4*>(p + (size_t)(sl + u) * stride + (size_t)tp * plane);
+    for (int tp = 0; tp < 9; ++tp) v[u][tp] = ld4<NT>(p + (size_t)(sl + u) * stride + (size_t)tp * plane);
 #pragma unroll
   for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -2119,6 +2138,7 @@ __device__ __forceinline__ void wgrad_fine_add(float (&acc)[36], const float* p,
       acc[tp] += v[u][tp].x, acc[9 + tp] += v[u][tp].y, acc[18 + tp] += v[u][tp].z, acc[27 + tp] += v[u][tp].w;
 }
 
+template <bool NT>
 __device__ __forceinline__ void wgrad_reduce_tile_fine(const WgReduceDesc& d, int item, float* part /* [16][64][9] */) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, el4 = lane & 15, sg = wave * 4 + (lane >> 4);
   const int e0 = item * kWgFineElems, e = e0 + el4 * 4;      // Co * Ci % 4 == 0
@@ -2141,9 +2161,9 @@ __device__ __forceinline__ void wgrad_reduce_tile_fine(const WgReduceDesc& d, in
     if (live) {
       const float* p = d.slab[k] + e;
       int sl = s0;
-      for (; sl + 4 <= s1; sl += 4) wgrad_fine_add<4>(acc, p, sl, stride, plane);
-      if (sl + 2 <= s1) wgrad_fine_add<2>(acc, p, sl, stride, plane), sl += 2;
-      if (sl < s1) wgrad_fine_add<1>(acc, p, sl, stride, plane);
+      for (; sl + 4 <= s1; sl += 4) wgrad_fine_add<4, NT>(acc, p, sl, stride, plane);
+      if (sl + 2 <= s1) wgrad_fine_add<2, NT>(acc, p, sl, stride, plane), sl += 2;
+      if (sl < s1) wgrad_fine_add<1, NT>(acc, p, sl, stride, plane);
     }
     if (k) __syncthreads();
     float4* pw = reinterpret_cast<float4*>(part + sg * kWgFineOut + el4 * 36);
@@ -2174,13 +2194,14 @@ static inline bool wgrad_reduce_fine(const int* splits, int nsrc) {
 }
 static inline int wgrad_reduce_blocks(int coci, bool fine) { return fine ? cdiv(coci, 16) : cdiv(coci, 1024); }
 
+// (the single-layer fold reads slabs the launch in front of it wrote, a hand-off: plain loads, as in wgrad5_reduce)
 __global__ __launch_bounds__(256) void wgrad_p_reduce(const float* __restrict__ slab, float* __restrict__ dw, int CoCi,
                                                      int splits, int accumulate, int fine) {
   __shared__ __attribute__((aligned(16))) float part[kWgPartFloats];
   WgReduceDesc d;
   d.slab[0] = slab, d.dw = dw, d.splits[0] = splits, d.nsrc = 1, d.coci = CoCi, d.accumulate = accumulate;
-  if (fine) wgrad_reduce_tile_fine(d, blockIdx.x, part);   // grid: one block per kWgFineTiles tile numbers
-  else wgrad_reduce_tile(d, blockIdx.x);
+  if (fine) wgrad_reduce_tile_fine<false>(d, blockIdx.x, part);   // grid: one block per kWgFineTiles tile numbers
+  else wgrad_reduce_tile<false>(d, blockIdx.x);
 }
 
 // The same reduce for MANY layers in one launch (a backward pass's weight gradients, folded when the pass is over): a
@@ -2196,6 +2217,7 @@ constexpr int kWgMaxDesc = 96;
 __device__ __forceinline__ int wgrad_desc_items(const WgReduceDesc& d) {
   return d.fine ? (d.nblocks + kWgFineTiles - 1) / kWgFineTiles : d.nblocks;
 }
+template <bool NT>
 __global__ __launch_bounds__(256) void wgrad_p_reduce_many(const WgReduceDesc* __restrict__ tab, int n) {
   __shared__ __attribute__((aligned(16))) float part[kWgPartFloats];
   __shared__ WgReduceDesc s_desc[kWgMaxDesc];
@@ -2232,10 +2254,10 @@ __global__ __launch_bounds__(256) void wgrad_p_reduce_many(const WgReduceDesc* _
     while (s_first[r + 1] <= w) ++r;
     const WgReduceDesc& d = s_desc[s_ord[r]];
     if (d.fine) {
-      wgrad_reduce_tile_fine(d, w - s_first[r], part);
+      wgrad_reduce_tile_fine<NT>(d, w - s_first[r], part);
       __syncthreads();                                // `part` is reused by the next item
     } else {
-      wgrad_reduce_tile(d, w - s_first[r]);
+      wgrad_reduce_tile<NT>(d, w - s_first[r]);
     }
   }
 }
@@ -3130,6 +3152,8 @@ int itcv_conv2d_wgrad_bf16p(const void* xplanes, const void* dyplanes, float* dw
   a.dyplane = (size_t)B * (Co / 8) * H * W;
   a.xscale = f16 ? reinterpret_cast<const ScaleRec*>(a.xp + 2 * a.xplane) : nullptr;
   a.dyscale = f16 ? reinterpret_cast<const ScaleRec*>(a.dyp + 2 * a.dyplane) : nullptr;
+  // a direct call's slabs are a hand-off to the reduce launched right behind it: plain stores
+  a.nt_slabs = accumulate == 2 ? stream_nt(ITCV_STREAM_NT_WGRAD_SLABS) : 0;
 #ifdef ITCV_DIAG
   a.debug = (diag_ablate() & 64) ? 1 : 0;
 #endif
@@ -3183,7 +3207,10 @@ int itcv_wgrad_reduce_many(const void* dev_table, int n, int total_blocks, void*
   if (n > kWgMaxDesc) return fail("%s: at most %d descriptors per table (itcv_wgrad_reduce_max_descs)", "itcv_wgrad_reduce_many", kWgMaxDesc);
   // total_blocks (the table's tile count) bounds the number of work items from above; the kernel counts the items itself
   const int grid = total_blocks < 2048 ? total_blocks : 2048;
-  hipLaunchKernelGGL(wgrad_p_reduce_many, dim3(grid), dim3(256), 0, S(stream), static_cast<const WgReduceDesc*>(dev_table), n);
+  pick<2>(stream_nt(ITCV_STREAM_NT_FOLD), [&](auto nt_c) {
+    hipLaunchKernelGGL(wgrad_p_reduce_many<(decltype(nt_c)::value != 0)>, dim3(grid), dim3(256), 0, S(stream),
+                       static_cast<const WgReduceDesc*>(dev_table), n);
+  });
   ITCV_CHECK_LAUNCH("itcv_wgrad_reduce_many");
   return 0;
 }

@@ -241,7 +241,8 @@ __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? 
 
 // ------------------------------------------------------------------ forward apply
 // y = pool(lrelu(gamma*(x-mean)*rstd + beta (+skip)))
-template <int POOL>
+// NT (ITCV_STREAM_NT_BN_FWD): x, the conv output, is next read by the backward -- a non-temporal load.
+template <int POOL, bool NT>
 __global__ void bn_act_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                   const float* __restrict__ rstd, const float* __restrict__ gamma,
                                   const float* __restrict__ beta, const float* __restrict__ skip,
@@ -255,7 +256,7 @@ __global__ void bn_act_fwd_kernel(const float* __restrict__ x, const float* __re
       const uint32_t pl = fdiv((uint32_t)i, HW, hw_shift);
       const int c = c_mask >= 0 ? (int)(pl & (uint32_t)c_mask) : (int)(pl % (uint32_t)C);
       const float sc = gamma[c] * rstd[c], sh = beta[c] - mean[c] * sc;
-      float4 v = *reinterpret_cast<const float4*>(x + i);
+      float4 v = ld4<NT>(x + i);
       v.x = v.x * sc + sh, v.y = v.y * sc + sh, v.z = v.z * sc + sh, v.w = v.w * sc + sh;
       if (skip) {
         const float4 k = *reinterpret_cast<const float4*>(skip + i);
@@ -272,8 +273,8 @@ __global__ void bn_act_fwd_kernel(const float* __restrict__ x, const float* __re
       const int c = c_mask >= 0 ? (int)(bc & (uint32_t)c_mask) : (int)(bc % (uint32_t)C);
       const float sc = gamma[c] * rstd[c], sh = beta[c] - mean[c] * sc;
       const size_t src = (size_t)bc * HW + (size_t)(2 * ho) * W + 2 * wo;
-      const float2 a = *reinterpret_cast<const float2*>(x + src);
-      const float2 b = *reinterpret_cast<const float2*>(x + src + W);
+      const float2 a = ld2<NT>(x + src);
+      const float2 b = ld2<NT>(x + src + W);
       float v0 = a.x * sc + sh, v1 = a.y * sc + sh, v2 = b.x * sc + sh, v3 = b.y * sc + sh;
       if (skip) {
         const float2 ka = *reinterpret_cast<const float2*>(skip + src);
@@ -331,7 +332,8 @@ __device__ __forceinline__ void store_planes_wave(u32x4* __restrict__ planes, si
 }
 
 // F16: the planes are fp16 hi / lo of the output with scale 1 (activations are O(1); common.h), record behind plane 1.
-template <int POOL, int NS, bool STATS, bool F16 = false>
+// NT: as in bn_act_fwd_kernel (the loads of x only; skip, the fp32 output and the planes are hand-offs).
+template <int POOL, int NS, bool STATS, bool F16, bool NT>
 __global__ __launch_bounds__(256) void bn_act_fwd_planes_kernel(
     const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ rstd,
     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ skip,
@@ -404,7 +406,7 @@ __global__ __launch_bounds__(256) void bn_act_fwd_planes_kernel(
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = c8 * 8 + j;
-      if (POOL == 0) xin[POOL ? 0 : j] = *reinterpret_cast<const float4*>(x + ((size_t)b * C + c) * HW + (size_t)pp * 4);
+      if (POOL == 0) xin[POOL ? 0 : j] = ld4<NT>(x + ((size_t)b * C + c) * HW + (size_t)pp * 4);
       p_ga[j] = gamma[c], p_be[j] = beta[c];
       p_mu[j] = STATS ? s_mean[(bc8 - g0) * 8 + j] : mean[c], p_rs[j] = STATS ? s_rstd[(bc8 - g0) * 8 + j] : rstd[c];
     }
@@ -428,8 +430,8 @@ __global__ __launch_bounds__(256) void bn_act_fwd_planes_kernel(
       } else {
         const uint32_t ho = (pp * 2) / Wo, wo = pp * 2 - ho * Wo;
         const size_t src = bc * HW + (size_t)(2 * ho) * W + 2 * wo;
-        const float4 a = *reinterpret_cast<const float4*>(x + src);
-        const float4 bb = *reinterpret_cast<const float4*>(x + src + W);
+        const float4 a = ld4<NT>(x + src);
+        const float4 bb = ld4<NT>(x + src + W);
         float v0 = a.x * sc + sh, v1 = a.y * sc + sh, v2 = bb.x * sc + sh, v3 = bb.y * sc + sh;
         float w0 = a.z * sc + sh, w1 = a.w * sc + sh, w2 = bb.z * sc + sh, w3 = bb.w * sc + sh;
         if (skip) {
@@ -543,17 +545,18 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __
 // ---- vectorised (float4) backward kernels: W % 4 == 0, tensors < 2^31 elements ------------------
 
 // upstream gradient of the 4 consecutive pixels (h, w..w+3) of plane bc (see upstream<MODE>)
-template <int MODE>
+// (NT: the apply passes read dy for the last time; the reduce passes in front of them keep the plain loads)
+template <int MODE, bool NT = false>
 __device__ __forceinline__ float4 upstream4(const float* __restrict__ dy, uint32_t bc, uint32_t h, uint32_t w,
                                             uint32_t H, uint32_t W) {
-  if (MODE == 0) return *reinterpret_cast<const float4*>(dy + (size_t)bc * H * W + h * W + w);
+  if (MODE == 0) return ld4<NT>(dy + (size_t)bc * H * W + h * W + w);
   if (MODE == 1) {
-    const float2 d = *reinterpret_cast<const float2*>(dy + (size_t)bc * (H / 2) * (W / 2) + (h >> 1) * (W / 2) + (w >> 1));
+    const float2 d = ld2<NT>(dy + (size_t)bc * (H / 2) * (W / 2) + (h >> 1) * (W / 2) + (w >> 1));
     return make_float4(0.25f * d.x, 0.25f * d.x, 0.25f * d.y, 0.25f * d.y);
   }
   const float* p = dy + (size_t)bc * (4 * H * W) + (size_t)(2 * h) * (2 * W) + 2 * w;
-  const float4 a0 = *reinterpret_cast<const float4*>(p), a1 = *reinterpret_cast<const float4*>(p + 4);
-  const float4 b0 = *reinterpret_cast<const float4*>(p + 2 * W), b1 = *reinterpret_cast<const float4*>(p + 2 * W + 4);
+  const float4 a0 = ld4<NT>(p), a1 = ld4<NT>(p + 4);
+  const float4 b0 = ld4<NT>(p + 2 * W), b1 = ld4<NT>(p + 2 * W + 4);
   return make_float4((a0.x + a0.y) + (b0.x + b0.y), (a0.z + a0.w) + (b0.z + b0.w), (a1.x + a1.y) + (b1.x + b1.y),
                      (a1.z + a1.w) + (b1.z + b1.w));
 }
@@ -693,7 +696,8 @@ __global__ __launch_bounds__(kRedThreads) void bn_bwd_partial_v4(
   }
 }
 
-template <int MODE>
+// NT (ITCV_STREAM_NT_BN_APPLY): x, dy and skip are read for the last time -- non-temporal loads; dx / dskip are hand-offs.
+template <int MODE, bool NT>
 __global__ void bn_bwd_apply_v4(const float* __restrict__ x, const float* __restrict__ dy,
                                 const float* __restrict__ mean, const float* __restrict__ rstd,
                                 const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -708,12 +712,12 @@ __global__ void bn_bwd_apply_v4(const float* __restrict__ x, const float* __rest
     const uint32_t c = c_mask >= 0 ? (bc & (uint32_t)c_mask) : (bc % (uint32_t)C);
     const float mu = mean[c], rs = rstd[c], ga = gamma[c], be = beta[c];
     const float m1 = (float)(dsums[c] / count), m2 = (float)(dsums[C + c] / count), gr = ga * rs;
-    const float4 xv = *reinterpret_cast<const float4*>(x + i);
-    float4 g = upstream4<MODE>(dy, bc, h, w, H, W);
+    const float4 xv = ld4<NT>(x + i);
+    float4 g = upstream4<MODE, NT>(dy, bc, h, w, H, W);
     const float xh0 = (xv.x - mu) * rs, xh1 = (xv.y - mu) * rs, xh2 = (xv.z - mu) * rs, xh3 = (xv.w - mu) * rs;
     float u0 = xh0 * ga + be, u1 = xh1 * ga + be, u2 = xh2 * ga + be, u3 = xh3 * ga + be;
     if (skip) {
-      const float4 k = *reinterpret_cast<const float4*>(skip + i);
+      const float4 k = ld4<NT>(skip + i);
       u0 += k.x, u1 += k.y, u2 += k.z, u3 += k.w;
     }
     if (!(u0 > 0.f)) g.x *= slope;
@@ -742,7 +746,8 @@ struct BnBwdSumsIn {
 // F16: dx goes out as fp16 hi / lo planes of S dx.  S is the same in every block of every group of the call: each block
 // takes the maxima U, V of the partial pass's mx arrays (see bn_bwd_partial_v4) and maps the bound U (2 + V) just under
 // 2^15; block 0 of group 0 records {S, 1/S} behind plane 1.
-template <int MODE, int NS, bool SUMS, bool F16 = false>
+// NT: as in bn_bwd_apply_v4 (the float4 loads of x, dy and skip; the planes and dx / dskip are hand-offs).
+template <int MODE, int NS, bool SUMS, bool F16, bool NT>
 __global__ __launch_bounds__(256) void bn_bwd_apply_planes(
     const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean,
     const float* __restrict__ rstd, const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -853,14 +858,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_planes(
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
         const uint32_t c = c8 * 8 + j0 + jj, bc = b * C + c;
-        xv4[jj] = *reinterpret_cast<const float4*>(x + bc * HW + hw);
-        g4[jj] = upstream4<MODE>(dy, bc, h, w, H, W);
+        xv4[jj] = ld4<NT>(x + bc * HW + hw);
+        g4[jj] = upstream4<MODE, NT>(dy, bc, h, w, H, W);
         pm[jj][0] = mean[c], pm[jj][1] = rstd[c], pm[jj][2] = gamma[c], pm[jj][3] = beta[c];
         if (!SUMS) ds4[jj][0] = dsums[c], ds4[jj][1] = dsums[C + c];
       }
       if (skip) {
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) k4[jj] = *reinterpret_cast<const float4*>(skip + (b * C + c8 * 8 + j0 + jj) * HW + hw);
+        for (int jj = 0; jj < 4; ++jj) k4[jj] = ld4<NT>(skip + (b * C + c8 * 8 + j0 + jj) * HW + hw);
       } else {
 #pragma unroll
         for (int jj = 0; jj < 4; ++jj) k4[jj] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1104,10 +1109,13 @@ static int bn_fwd_apply_launch(const BnPlan& p, const float* x, const float* mea
     pick<2>(pool ? 1 : 0, [&](auto pool_c) {
       pick<3>(bn_fmt(ns), [&](auto fmt_c) {
         pick<2>(fold.part ? 1 : 0, [&](auto stats_c) {
-          constexpr int POOL = decltype(pool_c)::value, FMT = decltype(fmt_c)::value;
-          constexpr bool STATS = decltype(stats_c)::value != 0;
-          launch_timed((bn_act_fwd_planes_kernel<POOL, FMT == 1 ? 3 : 2, STATS, FMT == 2>), p.agrid, dim3(256), 0, st, x, mean,
-                       rstd, gamma, beta, skip, y, static_cast<u32x4*>(planes), B, C, H, W, slope, fold, p.pstride, p.grp);
+          pick<2>(stream_nt(ITCV_STREAM_NT_BN_FWD), [&](auto nt_c) {
+            constexpr int POOL = decltype(pool_c)::value, FMT = decltype(fmt_c)::value;
+            constexpr bool STATS = decltype(stats_c)::value != 0, NT = decltype(nt_c)::value != 0;
+            launch_timed((bn_act_fwd_planes_kernel<POOL, FMT == 1 ? 3 : 2, STATS, FMT == 2, NT>), p.agrid, dim3(256), 0, st, x,
+                         mean, rstd, gamma, beta, skip, y, static_cast<u32x4*>(planes), B, C, H, W, slope, fold, p.pstride,
+                         p.grp);
+          });
         });
       });
     });
@@ -1118,8 +1126,11 @@ static int bn_fwd_apply_launch(const BnPlan& p, const float* x, const float* mea
   else ITCV_REQUIRE((H * W) % 4 == 0, "itcv_bn_act_fwd(H*W % 4)");
   const size_t nout = pool ? (size_t)B * C * (H / 2) * (W / 2) : (size_t)B * C * H * W;
   pick<2>(pool ? 1 : 0, [&](auto pool_c) {
-    hipLaunchKernelGGL(bn_act_fwd_kernel<decltype(pool_c)::value>, p.agrid, dim3(256), 0, st, x, mean, rstd, gamma, beta, skip,
-                       y, C, H, W, nout, slope, ilog2_exact(H * W), ilog2_exact(C) >= 0 ? C - 1 : -1);
+    pick<2>(stream_nt(ITCV_STREAM_NT_BN_FWD), [&](auto nt_c) {
+      hipLaunchKernelGGL((bn_act_fwd_kernel<decltype(pool_c)::value, decltype(nt_c)::value != 0>), p.agrid, dim3(256), 0, st, x,
+                         mean, rstd, gamma, beta, skip, y, C, H, W, nout, slope, ilog2_exact(H * W),
+                         ilog2_exact(C) >= 0 ? C - 1 : -1);
+    });
   });
   ITCV_CHECK_LAUNCH("itcv_bn_act_fwd");
   return 0;
@@ -1184,11 +1195,13 @@ static int bn_bwd_apply_launch(const BnPlan& p, const float* x, const float* dy,
     pick<3>(p.mode, [&](auto mode_c) {
       pick<3>(bn_fmt(ns), [&](auto fmt_c) {
         pick<2>(fold.part ? 1 : 0, [&](auto sums_c) {
-          constexpr int MODE = decltype(mode_c)::value, FMT = decltype(fmt_c)::value;
-          constexpr bool SUMS = decltype(sums_c)::value != 0;
-          launch_timed((bn_bwd_apply_planes<MODE, FMT == 1 ? 3 : 2, SUMS, FMT == 2>), p.agrid, dim3(256), 0, st, x, dy, mean,
-                       rstd, gamma, beta, skip, SUMS ? static_cast<const double*>(nullptr) : dsums, count, dx, dskip,
-                       static_cast<u32x4*>(dx_planes), B, C, H, W, slope, wsh, fold, p.pstride, p.grp, mx, p.nmx);
+          pick<2>(stream_nt(ITCV_STREAM_NT_BN_APPLY), [&](auto nt_c) {
+            constexpr int MODE = decltype(mode_c)::value, FMT = decltype(fmt_c)::value;
+            constexpr bool SUMS = decltype(sums_c)::value != 0, NT = decltype(nt_c)::value != 0;
+            launch_timed((bn_bwd_apply_planes<MODE, FMT == 1 ? 3 : 2, SUMS, FMT == 2, NT>), p.agrid, dim3(256), 0, st, x, dy,
+                         mean, rstd, gamma, beta, skip, SUMS ? static_cast<const double*>(nullptr) : dsums, count, dx, dskip,
+                         static_cast<u32x4*>(dx_planes), B, C, H, W, slope, wsh, fold, p.pstride, p.grp, mx, p.nmx);
+          });
         });
       });
     });
@@ -1199,9 +1212,11 @@ static int bn_bwd_apply_launch(const BnPlan& p, const float* x, const float* dy,
   pick<3>(p.mode, [&](auto mode_c) {
     constexpr int MODE = decltype(mode_c)::value;
     if (p.vec)
-      hipLaunchKernelGGL(bn_bwd_apply_v4<MODE>, p.agrid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, skip, dsums, count,
-                         dx, dskip, C, H, W, (uint32_t)(n / 4), slope, wsh, ilog2_exact(H * W),
-                         ilog2_exact(C) >= 0 ? C - 1 : -1);
+      pick<2>(stream_nt(ITCV_STREAM_NT_BN_APPLY), [&](auto nt_c) {
+        hipLaunchKernelGGL((bn_bwd_apply_v4<MODE, decltype(nt_c)::value != 0>), p.agrid, dim3(256), 0, st, x, dy, mean, rstd,
+                           gamma, beta, skip, dsums, count, dx, dskip, C, H, W, (uint32_t)(n / 4), slope, wsh,
+                           ilog2_exact(H * W), ilog2_exact(C) >= 0 ? C - 1 : -1);
+      });
     else
       hipLaunchKernelGGL(bn_bwd_apply_kernel<MODE>, p.agrid, dim3(256), 0, st, x, dy, mean, rstd, gamma, beta, skip, dsums,
                          count, dx, dskip, C, H, W, n, slope);

@@ -96,6 +96,9 @@ BN_PATHS = tuple(n.title().replace("_", "") for n in sorted(_bn, key=_bn.get))  
 LOSS_TYPES = {n.lower(): v for n, v in _defs("ITCV_LOSS_").items()}
 OPT_MAXIMIZE, OPT_NESTEROV, OPT_AMSGRAD, OPT_DECOUPLED_WD, OPT_CENTERED = (_defs("ITCV_OPT_")[n] for n in (
     "MAXIMIZE", "NESTEROV", "AMSGRAD", "DECOUPLED_WD", "CENTERED"))
+# option 'stream_nt': family name -> bit ("BN_APPLY", "WGRAD_SLABS", "FOLD", "WGRAD_OPS", "OPTIM", "BN_FWD"), plus the two
+# masks "ALL" and "DEFAULT" (the value the library starts with)
+STREAM_NT = _defs("ITCV_STREAM_NT_")
 
 
 def build(verbose=False):

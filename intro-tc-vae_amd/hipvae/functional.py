@@ -29,8 +29,10 @@ F32 = torch.float32
 def set_option(name, value):
     """Launch-shape options of the library (include/itcv_hip.h: itcv_set_option): 'band_m16' (0/1),
     'band_persist_blocks' (0 = one tile per block, else the persistent kernel's block count), 'wgrad_m16' (0 / 1 =
-    32x32x16 / 16x16x32 products in the planes weight gradient), 'planes_mfma_waves' (4 / 8), and the two test options of
-    the sliced-Wasserstein kernels, 'sw_lds_rows' and 'sw_max_blocks' (0 = the default).  Validated by the library."""
+    32x32x16 / 16x16x32 products in the planes weight gradient), 'planes_mfma_waves' (4 / 8), 'stream_nt' (a mask of
+    abi.STREAM_NT bits: which kernel families stream their once-used tensors non-temporally; bit-identical), and the two
+    test options of the sliced-Wasserstein kernels, 'sw_lds_rows' and 'sw_max_blocks' (0 = the default).  Validated by
+    the library."""
     call("itcv_set_option", name.encode(), int(value))
     _up2_fold_route.cache_clear()      # the one cached host decision that reads an option ('band_m16')
     lib.forget("itcv_conv2d_dgrad_up2_supported")
